@@ -1,22 +1,30 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the MI355X-native quadrotor race environment (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant e2e|indi] [--envs 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant e2e|indi] [--envs 65536] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one env.step() of the whole batch (residual MLPs -> Euler integration -> reward / gate logic ->
 auto-reset -> gate-frame observation for every env).  Workload at N=1 = BASELINE.json configs[1] as specified in
 SURVEY.md 8(d): 65 536 envs, Bebop E2E + NNDroneModel residual MLPs + training disturbance ranges, gates_ahead = 1,
-7-gate zigzag track, random U(-1,1) actions PRE-GENERATED on the device [K][N][4] (torch Philox, seed = rank);
-every step's obs / reward / done go to a full rollout buffer [K][N][...] (what PPO's collect phase stores), so each
+7-gate zigzag track, random U(-1,1) actions PRE-GENERATED on the device [C][N][4] (torch Philox, seed = rank);
+every step's obs / reward / done go to a rollout buffer [C][N][...] (what PPO's collect phase stores), so each
 step writes fresh HBM.  Inputs are resident in HBM before the timed region.
 
-Two ways to run those K steps through the C ABI are timed, both producing bit-identical outputs:
-  * `value`: qr_step_many -- ONE fused rollout kernel for the K steps (env state stays in registers between steps);
-  * `per_step_launch`: qr_step_launches -- K step kernels, one per env.step() (closed-loop calling pattern).
-Timing: the K-step region is repeated back-to-back R times inside ONE barrier + synchronize bracket, R chosen (the
-same on every rank) so that the bracket holds >= 20 ms of work; `ms_per_step` = bracket / (R K); the whole bracket is
-measured `--repeats` times (median reported, all values listed).  `steps` stays K.
+A plain run measures the headline only: reset, W warm-up steps, then EXACTLY K timed steps through qr_step_many (the fused
+rollout kernel, env state in registers between steps) inside ONE barrier + synchronize bracket; `ms_per_step` = bracket / K and
+`value` = env-steps/s of that bracket (maximum over ranks).  The K steps are issued as back-to-back launches of at most C steps,
+C = min(K, the steps whose buffers fit in ROLLOUT_CHUNK_BYTES) -- one launch up to 555 steps at 65 536 E2E envs -- so that any K
+runs in bounded memory; a launch of C steps reuses the [C][N][...] buffers and the C pre-generated actions.
+`--dump-outputs DIR` writes what the last timed step returned (obs, reward, done, truncated; float32) as DIR/<name>.npy.
+
+`--full` adds everything else, measured after the headline on the same env (the rest of this docstring):
+Two ways to run C-step regions through the C ABI are timed, both producing bit-identical outputs:
+  * `fused_repeated`: qr_step_many -- ONE fused rollout kernel for the C steps (env state stays in registers between steps);
+  * `per_step_launch`: qr_step_launches -- C step kernels, one per env.step() (closed-loop calling pattern).
+Timing: the C-step region is repeated back-to-back R times inside ONE barrier + synchronize bracket, R chosen (the
+same on every rank) so that the bracket holds >= 20 ms of work; `ms_per_step` = bracket / (R C); the whole bracket is
+measured `--repeats` times (median reported, all values listed).
 
 Roofline objects (every `frac` is against the roof that binds that kernel, and can be recomputed from `profiles/`):
   * fused rollout kernel (the dominant kernel of `value`): bound "hbm" on the bytes THAT kernel moves (action in, obs / reward /
@@ -52,6 +60,9 @@ BYTES_PER_ENV_STEP = {"e2e": lambda ga: 189 + 4 * (20 + 4 * ga), "indi": lambda 
 # obs / reward / done / trunc out: E2E 16 + 4*(20+4G) + 6 = 118 B, INDI 16 + 4*(13+4G) + 6 = 90 B at G=1 (PMC: 121.5 / 92.3 B)
 FUSED_BYTES_PER_ENV_STEP = {"e2e": lambda ga: 16 + 4 * (20 + 4 * ga) + 6, "indi": lambda ga: 16 + 4 * (13 + 4 * ga) + 6}
 MIN_TIMED_MS = 20.0
+# rollout buffers + actions of one fused launch: bounds the memory of any --steps (at 65 536 E2E envs: 555 steps per launch)
+ROLLOUT_CHUNK_BYTES = 4 << 30
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files of all ranks together
 # Numbers in the line that were NOT measured by this run: PMC counter figures collected by the builder with rocprofv3 (separate
 # --pmc passes) and committed under profiles/.  They are labelled with the file and the commit that added it.
 PMC_TRAFFIC_FILE = ("profiles", "r06_pmc_traffic.json")     # tools/run_pmc.sh: FETCH_SIZE / WRITE_SIZE passes, keyed by kernel symbol
@@ -79,6 +90,11 @@ def parse(argv=None):
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the indi / ppo / predecessor / host-path objects")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: repeated-bracket and per-kernel roofline figures, per-step and "
+                         "closed-loop paths, the other variant, PPO / config-5 legs, parity, CPU baselines, exchange / config 4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -230,6 +246,72 @@ def graph_of_launches(rt, fn, batch):
     except Exception:  # pragma: no cover
         torch.cuda.synchronize()
         return fn, 1
+
+
+def chunk_steps(n, L, K, W):
+    """Steps per fused launch: all of max(K, W) when their rollout buffers + actions fit in ROLLOUT_CHUNK_BYTES, fewer otherwise."""
+    per_step = n * (4 * L + 4 + 1 + 1 + 16)   # obs f32, reward f32, done u8, trunc u8; action f32 x 4
+    return int(max(1, min(max(K, W, 1), ROLLOUT_CHUNK_BYTES // per_step)))
+
+
+def timed_steps(rt, env, n, K, W, keep_outputs=False):
+    """THE headline measurement: reset, W warm-up steps, then exactly K timed steps of the fused rollout path inside one barrier +
+    synchronize bracket, both as back-to-back qr_step_many launches of at most C steps.  Returns the headline figures (time = maximum
+    over ranks) and, as host arrays, what the last timed step returned."""
+    import torch
+
+    L, dev = env.state_len, env.device
+    C = chunk_steps(n, L, K, W)
+    gen = torch.Generator(device=dev).manual_seed(rt.rank)  # torch Philox, seed = rank
+    actions = torch.rand((C, n, 4), device=dev, generator=gen) * 2 - 1
+    out = (torch.empty((C, n, L), dtype=torch.float32, device=dev), torch.empty((C, n), dtype=torch.float32, device=dev),
+           torch.empty((C, n), dtype=torch.uint8, device=dev), torch.empty((C, n), dtype=torch.uint8, device=dev))
+
+    def steps(k):   # k steps as ceil(k / C) launches; returns the buffer row of the last step
+        left, last = k, None
+        while left > 0:
+            c = min(C, left)
+            env.rollout_device(actions[:c], tuple(t[:c] for t in out))
+            left, last = left - c, c - 1
+        return last
+
+    timing_knob = hasattr(env, "set_timing")
+    if timing_knob:
+        env.set_timing(False)   # no hipEvent pair around the launches
+    env.reset_device()
+    steps(W)
+    rt.barrier()
+    t0 = time.perf_counter()
+    last = steps(K)
+    rt.barrier()
+    local_s = time.perf_counter() - t0
+    if timing_knob:
+        env.set_timing(True)
+    timed_s = rt.max_over_ranks(local_s)
+    outputs = None
+    if keep_outputs:
+        outputs = {name: t[last].cpu().numpy() for name, t in zip(("obs", "reward", "done", "truncated"), out)}
+    del actions, out
+    return {"value": n * rt.world * K / timed_s, "ms_per_step": timed_s * 1e3 / K, "local_ms_per_step": local_s * 1e3 / K,
+            "steps_per_launch": C, "launches": -(-K // C), "outputs": outputs}
+
+
+def dump_outputs(d, outputs, rt):
+    """--dump-outputs: one DIR/<name>.npy (float32) per output of the last timed step, rows = envs (suffix _rank<r> when world > 1).
+    Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of env rows is written, with its row numbers in env_index.npy (float64)."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in outputs.items()}
+    n = len(arrs["reward"])
+    row_bytes = sum(a[:1].nbytes for a in arrs.values())
+    budget = DUMP_LIMIT_BYTES // rt.world - 4096 * (len(arrs) + 1)    # headroom for the .npy headers
+    if n * row_bytes > budget:
+        m = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(20261016).choice(n, size=m, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    suffix = "" if rt.world == 1 else "_rank%d" % rt.rank
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + suffix + ".npy"), a)
 
 
 def _load_json(*path):
@@ -626,34 +708,35 @@ def _short(x, n=160):
 def headline(result):
     """The ONE line the driver parses: the contract's fields plus a FLAT `roofline` object that carries every fraction quoted in
     DESIGN.md section 5 (fused kernel on its own bytes, the vector-flop view, SURVEY 8(d)'s yardstick, the per-step kernel, the
-    closed loop with as-issued and useful flop) and the provenance of anything not measured by this run.  Everything else stays in
-    the full object (stderr + gpurun_out/bench_full_*.json).  Kept under 4 KB."""
+    closed loop with as-issued and useful flop) and the provenance of anything not measured by this run -- those under --full only.
+    Everything else stays in the full object (--full: stderr + bench_out/bench_full_*.json).  Kept under 4 KB."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "value_kernel_only", "launch")
     h = {k: result[k] for k in keep if k in result}
     c = result["config"]
     h["config"] = {"workload": _short(c["workload"], 220), "envs_per_gpu": c["envs_per_gpu"], "variant": c["variant"],
                    "gates_ahead": c["gates_ahead"], "obs_len": c["obs_len"]}
-    r = result.get("roofline", {})
-    flat = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "steps_per_launch", "launch_us",
-                                  "launch_us_hipevent", "launch_us_bracket", "timing_consistent", "us_per_step", "bytes_per_env_step",
-                                  "frac_on_8d_bytes", "traffic_commit")}
-    flat["frac_on_8d_bytes_is"] = "throughput yardstick of BASELINE.md section 4 (SURVEY 8(d) bytes / this kernel's time), NOT traffic: the state stays in registers"
-    flat["traffic_source"] = PMC_SOURCES["traffic"]
-    v = r.get("valu") or {}
-    flat["valu_frac"], flat["valu_flop_per_env_step"], flat["valu_flop_source"] = v.get("frac"), v.get("flop_per_env_step"), PMC_SOURCES["flop"]
-    ps = result.get("per_step_launch") or {}
-    pr = ps.get("roofline") or {}
-    flat.update({"per_step_kernel": pr.get("kernel"), "per_step_kernel_us": pr.get("kernel_us"), "per_step_frac": pr.get("frac"),
-                 "per_step_bytes_per_launch": pr.get("bytes_per_launch"), "per_step_traffic": pr.get("traffic"),
-                 "per_step_timing_consistent": pr.get("timing_consistent"),
-                 "per_step_value": ps.get("value")})
-    cl = result.get("closed_loop") or {}
-    cr = cl.get("roofline") or {}
-    flat.update({"closed_loop_us_per_step": cl.get("kernel_us_per_step"), "closed_loop_value": cl.get("value"),
-                 "closed_loop_mfma_frac_as_issued": cr.get("frac"), "closed_loop_mfma_frac_useful": cr.get("frac_useful"),
-                 "closed_loop_flop_as_issued": cr.get("flop_per_env_step"), "closed_loop_flop_useful": cr.get("flop_useful_per_env_step")})
-    h["roofline"] = flat
+    r = result.get("roofline")
+    if r:
+        flat = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "steps_per_launch", "launch_us",
+                                      "launch_us_hipevent", "launch_us_bracket", "timing_consistent", "us_per_step", "bytes_per_env_step",
+                                      "frac_on_8d_bytes", "traffic_commit")}
+        flat["frac_on_8d_bytes_is"] = "throughput yardstick of BASELINE.md section 4 (SURVEY 8(d) bytes / this kernel's time), NOT traffic: the state stays in registers"
+        flat["traffic_source"] = PMC_SOURCES["traffic"]
+        v = r.get("valu") or {}
+        flat["valu_frac"], flat["valu_flop_per_env_step"], flat["valu_flop_source"] = v.get("frac"), v.get("flop_per_env_step"), PMC_SOURCES["flop"]
+        ps = result.get("per_step_launch") or {}
+        pr = ps.get("roofline") or {}
+        flat.update({"per_step_kernel": pr.get("kernel"), "per_step_kernel_us": pr.get("kernel_us"), "per_step_frac": pr.get("frac"),
+                     "per_step_bytes_per_launch": pr.get("bytes_per_launch"), "per_step_traffic": pr.get("traffic"),
+                     "per_step_timing_consistent": pr.get("timing_consistent"),
+                     "per_step_value": ps.get("value")})
+        cl = result.get("closed_loop") or {}
+        cr = cl.get("roofline") or {}
+        flat.update({"closed_loop_us_per_step": cl.get("kernel_us_per_step"), "closed_loop_value": cl.get("value"),
+                     "closed_loop_mfma_frac_as_issued": cr.get("frac"), "closed_loop_mfma_frac_useful": cr.get("frac_useful"),
+                     "closed_loop_flop_as_issued": cr.get("flop_per_env_step"), "closed_loop_flop_useful": cr.get("flop_useful_per_env_step")})
+        h["roofline"] = flat
     cb = result.get("cpu_baseline")
     if cb:
         h["cpu_baseline"] = {k: _short(cb.get(k), 200) for k in ("value", "unit", "cores", "kind", "sample", "value_1core", "host_cores",
@@ -691,7 +774,8 @@ def headline(result):
             if k == "config4":
                 h[k]["exchange_ms"] = result[k]["exchange"]["ms"]
                 h[k]["exchange_GBps_in_per_gpu"] = result[k]["exchange"]["GBps_in_per_gpu"]
-    h["full_object"] = result.get("_full_path")
+    if "_full_path" in result:
+        h["full_object"] = result["_full_path"]
     # stay under 4 KB whatever the run produced (eight ranks add per-rank lists): shed explanatory strings first, then optional objects
     shed = [("roofline", "frac_on_8d_bytes_is"), ("roofline", "valu_flop_source"), ("ppo", "config5_what"), ("ppo", "update_launch"), ("ppo", "dtype"),
             ("cpu_baseline", "sample"), ("config", "workload"), ("roofline", "traffic_source"), ("parity", None), ("other_variant", None),
@@ -716,28 +800,43 @@ def run(args, rt, env_factory=make_env, closed_loop=True):
     """The measurement proper (also driven with a CPU stand-in over gloo by tests/test_bench_gloo.py)."""
     n, K, W, ga = args.envs, args.steps, args.warmup, args.gates_ahead
     env = env_factory(args.variant, n, ga, rt.env_id_base(n), 0, None if args.no_residual else "default")
-    m = measure_env(rt, env, args.variant, n, K, W, ga, args.repeats, closed_loop=closed_loop)
-    (out, _) = m.pop("_buffers")
     L = env.state_len
+    hl = timed_steps(rt, env, n, K, W, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hl["outputs"], rt)
+    C = hl["steps_per_launch"]
     result = {
         "metric": "env-steps/sec at N=%d envs per GPU (Quadcopter3DGates.step, " % n
                   + ("E2E + residual MLPs" if args.variant == "e2e" else "INDI inner loop") + ")",
-        "value": m.pop("value"), "unit": "env-steps/s", "n_gpus": rt.world, "steps": K, "warmup": W,
-        "ms_per_step": m.pop("ms_per_step"), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "value": hl["value"], "unit": "env-steps/s", "n_gpus": rt.world, "steps": K, "warmup": W,
+        "ms_per_step": hl["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": workload_text(args.variant, n, ga), "envs_per_gpu": n, "variant": args.variant, "gates_ahead": ga,
                    "obs_len": L, "sharding": f"{rt.world} independent shard(s), env_id_base = rank*N"},
         "path": "qr_step_many (fused K-step rollout kernel)",
+        "launch": "%d stream launch(es) of <= %d steps in one bracket" % (hl["launches"], C),
     }
+    local = {"kernel": env.rollout_kernel_name() if hasattr(env, "rollout_kernel_name") else None}
+    if not args.full:
+        result["rccl"] = rccl_report(rt, hl["local_ms_per_step"], local)
+        return result
+
+    # --- --full: everything beyond the headline, on C-step regions (= the headline's launches) -------------------------------
+    m = measure_env(rt, env, args.variant, n, C, min(W, C), ga, args.repeats, closed_loop=closed_loop)
+    (out, _) = m.pop("_buffers")
+    result["fused_repeated"] = {k: m.pop(k) for k in ("value", "ms_per_step", "repeats", "launches_per_bracket", "timed_ms_per_bracket",
+                                                     "all_ms_per_step", "launch")}
+    result["fused_repeated"]["steps_per_launch"] = C
     result.update(m)
-    local = {"kernel": (m.get("roofline") or {}).get("kernel"), "kernel_us_per_step": (m.get("roofline") or {}).get("us_per_step")}
+    local["kernel_us_per_step"] = (m.get("roofline") or {}).get("us_per_step")
     if rt.use_cuda:
         import torch
         prop = torch.cuda.get_device_properties(rt.device)
         local["clock_mhz_max"] = getattr(prop, "clock_rate", 0) / 1e3 or None
         local["device"] = prop.name
-    result["rccl"] = rccl_report(rt, float(np.median(m["all_ms_per_step"])), local)
+    result["rccl"] = rccl_report(rt, hl["local_ms_per_step"], local)
     result["provenance"] = PMC_SOURCES
+    K, W = C, min(W, C)
 
     # --- rollout-boundary exchange: RCCL all-gather of [obs | reward | done] of this run's shard ------------------------
     if rt.collectives and not args.no_exchange:
@@ -873,6 +972,8 @@ def main(argv=None):
     os.environ.setdefault("OMP_WAIT_POLICY", "passive")   # the CPU baseline's OpenMP workers sleep between regions instead of spinning
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, argv))
     factory = _standin_factory()
@@ -882,11 +983,11 @@ def main(argv=None):
         result["data"] = "cpu-standin (test only)"
     else:
         result = run(args, rt)
-    if rt.rank == 0:
-        # the full object: a file next to the profiles scratch (pulled back by gpurun) and stderr; stdout gets ONE compact line, last
+    if rt.rank == 0 and args.full:
+        # the full object: a file under bench_out/ (git-ignored) and stderr; stdout gets ONE compact line, last
         full_path = None
         try:
-            d = os.path.join(ROOT, "gpurun_out")
+            d = os.path.join(ROOT, "bench_out")
             os.makedirs(d, exist_ok=True)
             full_path = os.path.join(d, "bench_full_n%d_%s_k%d.json" % (rt.world, args.variant, args.steps))
             json.dump(result, open(full_path, "w"), indent=1)
@@ -894,6 +995,7 @@ def main(argv=None):
             full_path = None
         result["_full_path"] = None if full_path is None else os.path.relpath(full_path, ROOT)
         print(json.dumps({k: v for k, v in result.items() if k != "_full_path"}), file=sys.stderr, flush=True)
+    if rt.rank == 0:
         print(json.dumps(headline(result)), flush=True)
     rt.finish()
 

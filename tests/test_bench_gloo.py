@@ -22,6 +22,7 @@ class CpuBenchEnv:
     """The device API bench.measure_env() uses, on the CPU oracle."""
 
     created = []
+    steps_run = 0
 
     def __init__(self, variant, n, ga, env_id_base, seed=0, residual=None):
         import parity as P
@@ -43,6 +44,7 @@ class CpuBenchEnv:
         import time
 
         K = actions.shape[0]
+        CpuBenchEnv.steps_run += K
         if out is None:
             out = (torch.empty((K, self.num_envs, self.state_len)), torch.empty((K, self.num_envs)),
                    torch.empty((K, self.num_envs), dtype=torch.uint8), torch.empty((K, self.num_envs), dtype=torch.uint8))
@@ -82,14 +84,15 @@ def _worker(rank, world, port, tmp):
     import bench
 
     args = bench.parse(["--gpus", str(world), "--steps", "6", "--warmup", "2", "--envs", "64", "--repeats", "2",
-                        "--no-cpu-baseline", "--no-parity", "--variant", "indi"])
+                        "--no-cpu-baseline", "--no-parity", "--variant", "indi", "--full"])
     rt = bench.Runtime(rank, 0, world, torch.device("cpu"), use_cuda=False)
     assert rt.env_id_base(64) == rank * 64
     res = bench.run(args, rt, env_factory=CpuBenchEnv, closed_loop=False)
     # every env this rank built is keyed by rank * n (main shard and the config-4 shard)
     assert CpuBenchEnv.created and all(base == rank * n for (_, n, base) in CpuBenchEnv.created), CpuBenchEnv.created
     # same repeat count and same (max-reduced) time on every rank
-    probe = torch.tensor([res["launches_per_bracket"], res["ms_per_step"]], dtype=torch.float64)
+    probe = torch.tensor([res["fused_repeated"]["launches_per_bracket"], res["fused_repeated"]["ms_per_step"], res["ms_per_step"]],
+                         dtype=torch.float64)
     both = [torch.empty_like(probe) for _ in range(world)]
     dist.all_gather(both, probe)
     assert torch.equal(both[0], both[1])
@@ -97,7 +100,7 @@ def _worker(rank, world, port, tmp):
         json.dumps(res)  # serialisable
         assert res["n_gpus"] == world and res["steps"] == 6 and res["scaling"] == "weak"
         assert abs(res["value"] - 64 * world * 6 / (res["ms_per_step"] * 1e-3 * 6)) < 1e-6 * res["value"]
-        assert res["timed_ms_per_bracket"] >= 0.9 * bench.MIN_TIMED_MS
+        assert res["fused_repeated"]["timed_ms_per_bracket"] >= 0.9 * bench.MIN_TIMED_MS
         ex = res["exchange"]   # obs f32 + reward f32 + done u8, gathered into [world][K][n][...] receive buffers
         assert ex["gathered_shape"] == [world, 6, 64, 17] and ex["bytes_per_rank"] == 6 * 64 * (17 * 4 + 4 + 1)
         assert ex["gathered_bytes"] == world * ex["bytes_per_rank"]
@@ -150,7 +153,7 @@ def test_bench_gpus2_without_a_launcher_spawns_two_ranks():
     """`python bench.py --gpus 2` launched PLAINLY (no torchrun around it, WORLD_SIZE unset) must start its two
     ranks itself -- it used to run one rank and print n_gpus 1.  CPU ranks over gloo stand in for the GPUs."""
     r = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--envs", "64", "--repeats", "2", "--no-cpu-baseline", "--no-parity",
-                    "--variant", "indi", "--no-extras"])
+                    "--variant", "indi", "--no-extras", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["rccl"]["rccl_world_size"] == 2 and line["rccl"]["backend"] == "gloo"
@@ -176,3 +179,73 @@ def test_timed_region_fills_the_bracket():
     rt = bench.Runtime(0, 0, 1, torch.device("cpu"), use_cuda=False)
     per, ts, R = bench.timed_region(rt, lambda: time.sleep(0.001), repeats=2, min_ms=20.0)
     assert R >= 10 and 0.0009 < per < 0.003 and len(ts) == 2
+
+
+def _plain_run(argv, monkeypatch=None, **consts):
+    import bench
+
+    for k, v in consts.items():
+        monkeypatch.setattr(bench, k, v)
+    CpuBenchEnv.steps_run = 0
+    args = bench.parse(argv)
+    rt = bench.Runtime(0, 0, 1, torch.device("cpu"), use_cuda=False)
+    return bench.run(args, rt, env_factory=CpuBenchEnv, closed_loop=False), CpuBenchEnv.steps_run
+
+
+def test_plain_run_times_exactly_the_requested_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) steps the env W + K times and nothing else; --dump-outputs writes what the last timed step returned
+    (float32), the same files on a second run with the same arguments."""
+    import bench
+
+    argv = ["--steps", "7", "--warmup", "3", "--envs", "64", "--variant", "indi"]
+    res, ran = _plain_run(argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert ran == 3 + 7
+    assert res["steps"] == 7 and res["warmup"] == 3 and res["ms_per_step"] > 0
+    assert abs(res["value"] - 64 * 7 / (res["ms_per_step"] * 1e-3 * 7)) < 1e-6 * res["value"]
+    for k in ("roofline", "per_step_launch", "closed_loop", "fused_repeated", "parity", "cpu_baseline", "exchange"):
+        assert k not in res, k
+    h = bench.headline(res)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in h, k
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("obs", "reward", "done", "truncated")}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in got)
+    assert all(a.dtype == np.float32 and a.shape[0] == 64 for a in got.values()) and got["obs"].shape == (64, 13 + 4)
+    # the same env driven by hand: reset, the 3 warm-up actions, the 7 timed ones (one pool of max(K, W) actions, seed = rank)
+    acts = torch.rand((7, 64, 4), generator=torch.Generator().manual_seed(0)) * 2 - 1
+    ref = CpuBenchEnv("indi", 64, 1, 0)
+    ref.reset_device()
+    ref.rollout_device(acts[:3])
+    o, r, d, t = ref.rollout_device(acts[:7])
+    np.testing.assert_array_equal(got["obs"], o[-1].numpy())
+    np.testing.assert_array_equal(got["reward"], r[-1].numpy())
+    np.testing.assert_array_equal(got["done"], d[-1].numpy().astype(np.float32))
+    np.testing.assert_array_equal(got["truncated"], t[-1].numpy().astype(np.float32))
+    _plain_run(argv + ["--dump-outputs", str(tmp_path / "b")])
+    for k, a in got.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / (k + ".npy")))
+
+
+def test_plain_run_splits_long_runs_into_bounded_launches(tmp_path, monkeypatch):
+    """More steps than ROLLOUT_CHUNK_BYTES holds: the K timed steps run as ceil(K / C) launches of <= C steps, still exactly K."""
+    import bench
+
+    per_step = 64 * (4 * 17 + 4 + 1 + 1 + 16)
+    res, ran = _plain_run(["--steps", "11", "--warmup", "5", "--envs", "64", "--variant", "indi"], monkeypatch,
+                          ROLLOUT_CHUNK_BYTES=4 * per_step)
+    assert ran == 5 + 11 and res["steps"] == 11
+    assert bench.chunk_steps(64, 17, 11, 5) == 4 and res["launch"].startswith("3 stream launch(es) of <= 4 steps")
+
+
+def test_dump_outputs_samples_rows_beyond_the_size_limit(tmp_path, monkeypatch):
+    """Beyond DUMP_LIMIT_BYTES: a fixed, seeded sample of env rows (the same on every run) with its row numbers, within the limit."""
+    limit = 40000 + 5 * 4096
+    for d in ("a", "b"):
+        _plain_run(["--steps", "2", "--warmup", "0", "--envs", "512", "--variant", "indi", "--dump-outputs", str(tmp_path / d)],
+                   monkeypatch, DUMP_LIMIT_BYTES=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["done.npy", "env_index.npy", "obs.npy", "reward.npy", "truncated.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < 512 and np.all(np.diff(idx) > 0)
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -418,7 +418,7 @@ def test_bench_collectives_over_rccl_on_one_rank():
     env = dict(os.environ, QR_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
-           "--envs", "32768", "--repeats", "2", "--no-cpu-baseline", "--no-parity"]
+           "--envs", "32768", "--repeats", "2", "--no-cpu-baseline", "--no-parity", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -428,7 +428,7 @@ def test_bench_collectives_over_rccl_on_one_rank():
     assert j["rccl"]["rccl_world_size"] == 1 and j["rccl"]["backend"] == "nccl" and j["rccl"]["rccl_version"][0].isdigit()
     assert len(j["rccl"]["per_rank_ms_per_step"]) == 1
     assert j["exchange"]["ms"] > 0 and j["config4"]["envs_per_gpu"] == 32768 and j["config4"]["exchange_ms"] > 0
-    # the full object goes to stderr (and to gpurun_out/bench_full_*.json)
+    # the full object goes to stderr (and to bench_out/bench_full_*.json)
     full = json.loads([ln for ln in r.stderr.splitlines() if ln.startswith("{")][-1])
     ex = full["exchange"]
     assert ex["gathered_shape"][:2] == [1, ex["steps"]] and ex["gathered_bytes"] == ex["bytes_per_rank"]
