@@ -53,10 +53,12 @@ class ActorCritic(nn.Module):
     def value(self, obs):
         return self.vf(obs).squeeze(-1)
 
-    def log_prob_entropy(self, obs, actions):
-        mean = self.pi(obs)
+    def log_prob_from_mean(self, mean, actions):
         std = self.log_std.exp()
-        lp = (-0.5 * ((actions - mean) / std) ** 2 - self.log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+        return (-0.5 * ((actions - mean) / std) ** 2 - self.log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+
+    def log_prob_entropy(self, obs, actions):
+        lp = self.log_prob_from_mean(self.pi(obs), actions)
         ent = (0.5 + 0.5 * math.log(2 * math.pi) + self.log_std).sum().expand(obs.shape[0])
         return lp, ent
 
@@ -420,6 +422,13 @@ class PPO:
         if self._updater is not None:   # values on the matrix cores too; GAE and episode statistics follow in train()
             self.buf_val.copy_(value(self.buf_obs.view(T * N, -1)).view(T, N))
             self.last_val = value(last_obs)
+            if self.policy_forward == "f32class" and self._updater.precision != "f32":
+                # f32-class collect + f16-operand update: the update's forward (the f16 operand images) gives means up to ~7e-4 away
+                # from the collect kernel's, an offset of z dmu / sigma in every log-ratio.  Store the OLD log-probs from the update's
+                # own forward, so that the ratio is 1 at the first minibatch (as the torch-update branch below does for its network).
+                # The f16-operand collect kernel and the f32-class pair already agree with their updates: no recompute there.
+                mean = self._updater.forward(0, self.buf_obs.view(T * N, -1))
+                self.buf_lp.copy_(self.policy.log_prob_from_mean(mean, self.buf_act.view(T * N, 4)).view(T, N))
             self._stats_pending = True
             return
         self.buf_val.copy_(value(self.buf_obs.view(T * N, -1)).view(T, N))
