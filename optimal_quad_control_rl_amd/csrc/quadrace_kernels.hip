@@ -125,10 +125,17 @@ __device__ __forceinline__ void obs_tile_flush(const float* __restrict__ tile, f
     constexpr int kVec = 16 * L;  // float4 elements in the block (64*L floats; 64*L*4 bytes is a multiple of 16)
     const float4* t4 = reinterpret_cast<const float4*>(tile);
     float4* g4 = reinterpret_cast<float4*>(obs_out + wave_first_env * L);
+    // Every round runs with the caller's whole EXEC mask: when L % 4 != 0 the last round has 16 (L % 4) elements, and the lanes past
+    // them store the last element once more (the same 16 bytes to the same address) instead of being masked off.  A lane-masked last
+    // round made the register allocator place live-range copies (restores of registers it had borrowed for the store addresses) inside
+    // that masked block, whose EXEC was never widened again before the caller's region ended: the restores reached 16 lanes only.  In
+    // the closed-loop policy kernel at L = 25 and 29 the clobbered registers were LDS addresses of the output layer's weight operands
+    // (v_mov_b32 v247, v56 / v249, v57 under `s_and_b64 exec, exec, ...`), so every full wave computed wrong action means.
 #pragma unroll
     for (int t = 0; t < (kVec + 63) / 64; ++t) {
         const int e = t * 64 + lane;
-        if ((t + 1) * 64 <= kVec || e < kVec) stream_store(g4 + e, t4[e]);
+        const int ec = (t + 1) * 64 <= kVec || e < kVec ? e : kVec - 1;
+        stream_store(g4 + ec, t4[ec]);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -28,7 +28,7 @@ def test_policy_matches_reference_nn_forward():
     assert np.abs(out - d["mean"]).mean() < 1e-3
 
 
-@pytest.mark.parametrize("L", [13, 17, 20, 24, 36])
+@pytest.mark.parametrize("L", [13, 17, 20, 24, 36, 21, 25, 28, 29, 32])
 @pytest.mark.parametrize("n", [1, 63, 64, 1000, 65536])
 def test_policy_matches_torch(L, n):
     from optimal_quad_control_rl_amd.policy import MfmaPolicy
@@ -77,7 +77,7 @@ def test_f32class_policy_matches_reference_nn_forward_at_float32_level():
     assert e16 > 50 * e_ref                     # the two kernels really are different arithmetic
 
 
-@pytest.mark.parametrize("L", [13, 17, 20, 24, 36])
+@pytest.mark.parametrize("L", [13, 17, 20, 24, 36, 21, 25, 28, 29, 32])
 @pytest.mark.parametrize("n", [1, 63, 1000, 65536])
 def test_f32class_policy_matches_float64_torch(L, n):
     """... for every observation length, ragged and full launches, large inputs (rates up to 1000 rad/s) and a non-trivial output head:
@@ -117,15 +117,15 @@ def test_policy_errors():
     assert L.qr_policy_destroy(h) == 0
 
 
-def _make(variant, n, seed=5):
+def _make(variant, n, seed=5, gates_ahead=1):
     from optimal_quad_control_rl_amd import (Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES,
                                              square_track, zigzag_track)
 
     if variant == "e2e":
-        env = Quadcopter3DGates(n, *zigzag_track(), gates_ahead=1, seed=seed, infos_mode="none")
+        env = Quadcopter3DGates(n, *zigzag_track(), gates_ahead=gates_ahead, seed=seed, infos_mode="none")
         env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
     else:
-        env = Quadcopter3DGatesINDI(n, *square_track(), gates_ahead=1, seed=seed, infos_mode="none")
+        env = Quadcopter3DGatesINDI(n, *square_track(), gates_ahead=gates_ahead, seed=seed, infos_mode="none")
     env.max_steps = 30  # auto-resets inside the window
     env.reset_device()
     return env
@@ -148,9 +148,26 @@ def _policy_for(env, gain=20.0):
 def test_closed_loop_rollout_equals_policy_plus_step_launches(variant, n, precision):
     """deterministic closed-loop rollout kernel == K x [policy kernel, clip, step kernel], bit for bit -- with the f16-operand forward
     and (round 6, QR_ROLLOUT_F32CLASS) with the reference-precision forward inside the kernel."""
+    _closed_loop_equals_launches(variant, n, precision, gates_ahead=1)
+
+
+_GATES_AHEAD = [(v, g) for v in ("e2e", "indi") for g in range(5)]
+
+
+@pytest.mark.parametrize("variant,gates_ahead", _GATES_AHEAD, ids=["%s-L%d" % (v, (20 if v == "e2e" else 13) + 4 * g) for v, g in _GATES_AHEAD])
+@pytest.mark.parametrize("precision", ["f16-operands", "f32"])
+def test_closed_loop_rollout_equals_launches_at_every_gates_ahead(variant, gates_ahead, precision):
+    """The same bit-for-bit identity for all 20 instantiations of the closed-loop kernel (variant x gates_ahead 0..4, i.e. every
+    observation length, x both forwards) on one ragged size; with tests/test_gpu_exact_forward.py (the policy kernel bit-exact at every
+    length) it pins the policy inside every rollout kernel."""
+    _closed_loop_equals_launches(variant, 1000, precision, gates_ahead)
+
+
+def _closed_loop_equals_launches(variant, n, precision, gates_ahead):
     K = 48
-    net, pol = _policy_for(_make(variant, 8))
-    a, b = _make(variant, n), _make(variant, n)
+    net, pol = _policy_for(_make(variant, 8, gates_ahead=gates_ahead))
+    a, b = _make(variant, n, gates_ahead=gates_ahead), _make(variant, n, gates_ahead=gates_ahead)
+    assert a.state_len == (20 if variant == "e2e" else 13) + 4 * gates_ahead
     obs, act, logp, rew, done, trunc, last = a.rollout_policy_device(pol, K, torch.zeros(4), deterministic=True, precision=precision)
     o = b.states_tensor.clone()
     for k in range(K):

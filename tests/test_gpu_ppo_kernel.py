@@ -74,7 +74,11 @@ def _flat_ref_grads(ref):
 
 @pytest.mark.parametrize("L,B,clip", [(17, 1024, 0.2), (17, 1024, 50.0), (24, 512, 0.2), (36, 256, 50.0), (13, 64, 0.2),
                                       (17, 16384, 0.2), (24, 32768, 50.0), (17, 6400, 0.2),    # 6400: 100 groups -> 25 chunks (no XCD mapping)
-                                      (24, 5000, 0.2), (24, 5000, 50.0), (13, 100, 50.0)])      # 5000 = the reference's batch_size (R:792): 78 groups + 8 rows
+                                      (24, 5000, 0.2), (24, 5000, 50.0), (13, 100, 50.0),       # 5000 = the reference's batch_size (R:792): 78 groups + 8 rows
+                                      # the other observation lengths: 20 = E2E with gates_ahead 0 (the reference class's default), 32 = kIn 33,
+                                      # the bias column alone in a third f16 K-step and in a second 32-wide tile column (DenseMap's last)
+                                      (20, 1000, 0.2), (21, 16384, 50.0), (25, 2048, 0.2), (28, 5000, 50.0), (29, 2048, 50.0),
+                                      (32, 4096, 0.2), (32, 4096, 50.0)])
 @pytest.mark.parametrize("partial", ["bf16", "f32"])
 def test_gradient_matches_autograd(L, B, clip, partial):
     """Two references: (1) autograd through the same networks with f16-rounded GEMM operands -- what the kernels compute,
@@ -93,7 +97,7 @@ def test_gradient_matches_autograd(L, B, clip, partial):
     g = up.grad(obs, act, old_lp, adv, ret, idx, clip, vf_coef, ent_coef, stats=True)
     ref = ref.double()
     obs64, act64, old_lp64, adv64, ret64 = (t.double() for t in (obs, act, old_lp, adv, ret))
-    loss, pg, vl, ratio = _torch_loss(ref, obs64, act64, old_lp64, adv64, ret64, idx, clip, vf_coef, ent_coef, f16_operands=True)
+    loss, pg, vl, ratio16 = _torch_loss(ref, obs64, act64, old_lp64, adv64, ret64, idx, clip, vf_coef, ent_coef, f16_operands=True)
     loss.backward()
     refs16 = _flat_ref_grads(ref)
     for p in ref.parameters():
@@ -122,6 +126,12 @@ def test_gradient_matches_autograd(L, B, clip, partial):
     assert np.allclose(g[off:].cpu().numpy(), st, rtol=1e-6, atol=1e-6)
     assert abs(st[0] / B - float(pg)) < 5e-3 * max(1.0, abs(float(pg)))
     assert abs(st[1] / B - float(vl)) < 5e-3 * max(1.0, abs(float(vl)))
+    kl = float(((ratio - 1) - ratio.log()).mean())
+    assert abs(st[2] / B - kl) < 5e-3 * max(1.0, abs(kl))   # the approx-KL sum (SB3's target-KL stop reads it alone)
+    # ... and against the ratios of the same f16 operands (float64): what is left is the float32 evaluation of (r - 1) - log r
+    kl16 = float(((ratio16 - 1) - ratio16.log()).sum())
+    print("KL sum %.6e vs f16-operand float64 %.6e: relative %.2e" % (st[2], kl16, abs(st[2] / kl16 - 1)))
+    assert abs(float(st[2]) - kl16) <= 1e-3 * abs(kl16)
     clipped = float(((ratio - 1).abs() > clip).float().sum())
     assert abs(st[3] - clipped) <= max(3.0, 0.02 * B)      # f16 forward moves a few ratios across the clip edge
     if clip < 1:
@@ -452,6 +462,13 @@ def test_f32class_gradient_matches_float64_autograd(L, B, clip):
     st = up.stats.cpu().numpy()
     assert np.allclose(g[n:].cpu().numpy(), st, rtol=1e-6, atol=1e-6)
     assert abs(st[0] / B - float(pg)) < 1e-5 * max(1.0, abs(float(pg))) and abs(st[1] / B - float(vl)) < 1e-5 * max(1.0, abs(float(vl)))
+    # the approx-KL sum against float64, and the clipped count exactly -- except rows within float32 noise of the clip edge
+    kl64 = float(((ratio - 1) - ratio.log()).sum())
+    edge = int(((ratio - 1).abs() - clip).abs().lt(1e-5).sum())
+    clipped64 = int(((ratio - 1).abs() > clip).sum())
+    print("KL sum %.6e vs float64 %.6e (relative %.2e); clipped %d vs %d (%d rows on the edge)" % (st[2], kl64, abs(st[2] / kl64 - 1), st[3], clipped64, edge))
+    assert abs(float(st[2]) - kl64) <= 1e-5 * abs(kl64)
+    assert abs(int(st[3]) - clipped64) <= edge
     up.close()
 
 
