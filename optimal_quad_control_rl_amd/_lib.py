@@ -96,7 +96,7 @@ SIGNATURES = {
 }
 
 
-ADDED_IN_ROUND_5 = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr_policy_forward_f32class", "qr_ppo_grad_f32class")   # (and round 6)
+OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr_policy_forward_f32class", "qr_ppo_grad_f32class")   # added in rounds 5-6: a QR_PROBE_LIB build of older sources may lack them
 
 
 class QuadraceError(RuntimeError):
@@ -123,7 +123,7 @@ def load(build_if_missing=True):
         raise RuntimeError(f"{_build.LIB} is missing: run `python -m optimal_quad_control_rl_amd.build`")
     L = C.CDLL(_build.LIB)
     for name, (rt, at) in SIGNATURES.items():
-        if name in ADDED_IN_ROUND_5 and not hasattr(L, name) and os.environ.get("QR_PROBE_LIB"):
+        if name in OPTIONAL_SYMBOLS and not hasattr(L, name) and os.environ.get("QR_PROBE_LIB"):
             continue   # a forensic build of an older source tree (tools/isa_patch.py): ABI 3 is additive, the older library lacks the entry
         fn = getattr(L, name)  # AttributeError here = ABI drift between header and library
         fn.restype, fn.argtypes = rt, at

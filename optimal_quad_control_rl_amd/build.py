@@ -15,11 +15,10 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libquadrace.so")
 SOURCES = ["quadrace_kernels.hip", "quadrace_kernels_mlp.hip", "quadrace_abi.hip", "quadrace_policy.hip", "quadrace_ppo.hip", "quadrace_ppo_f32.hip",
            "quad3d.hip"]
-HEADERS = ["quadrace_device.hpp", "quadrace_policy.hpp", os.path.join("..", "..", "include", "quadrace.h"),
-           os.path.join("..", "..", "include", "quad3d.h"), "quadrace_kernels.hip"]   # (quadrace_kernels_mlp.hip includes quadrace_kernels.hip)
-# quadrace_kernels_mlp.hip = the two fused E2E + residual-MLP rollout kernels, without the SLP vectoriser: at two waves per SIMD a
-# packed-f32 instruction costs 1.3 x a scalar one and the register moves that feed it come on top (1 Mi envs: 40.5 -> 42.3 G
-# env-steps/s, profiles/r05_slp_ab.txt); every other kernel keeps the vectoriser (INDI at 65 536 envs loses 8 % without it)
+HEADERS = ["quadrace_device.hpp", "quadrace_policy.hpp", "quadrace_env_kernels.hpp", "quadrace_launch.hpp",
+           os.path.join("..", "..", "include", "quadrace.h"), os.path.join("..", "..", "include", "quad3d.h")]
+# quadrace_kernels_mlp.hip = the launcher, and with it the instantiations, of the two fused E2E + residual-MLP rollout kernels: compiled
+# without the SLP vectoriser (reasons and measurements at the top of that file); every other kernel keeps it
 PER_SOURCE_FLAGS = {"quadrace_kernels_mlp.hip": ["-fno-slp-vectorize"]}
 # -ffp-contract=off: FMAs are written explicitly (fmaf) in the kernels, so the arithmetic is fixed by the source and
 # the per-step kernel and the fused rollout kernel produce bit-identical trajectories.

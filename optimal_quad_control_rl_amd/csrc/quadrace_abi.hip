@@ -10,31 +10,7 @@
 #include <vector>
 
 #include "../../include/quadrace.h"
-#include "quadrace_device.hpp"
-#include "quadrace_policy.hpp"
-
-namespace qr {
-hipError_t launch_step(int variant, const Params& P, const float* actions, float* obs, float* rew, uint8_t* done,
-                       uint8_t* trunc, hipStream_t st);
-const char* rollout_kernel_name(int variant, const Params& P, int form);
-hipError_t launch_rollout(int variant, const Params& P, int form, int K, const float* actions, float* obs, float* rew,
-                          uint8_t* done, uint8_t* trunc, hipStream_t st);
-hipError_t launch_rollout_policy(int variant, const Params& P, const PolicyArgs& A, int K, float* obs, float* act,
-                                 float* logp, float* rew, uint8_t* done, uint8_t* trunc, float* last_obs,
-                                 hipStream_t st);
-const half8* policy_weights(const qr_policy* p);
-const half8* policy_weights_lo(const qr_policy* p);
-int policy_obs_len(const qr_policy* p);
-int policy_device(const qr_policy* p);
-hipError_t launch_reset(int variant, const Params& P, const uint8_t* mask, float* obs, hipStream_t st);
-hipError_t launch_observe(int variant, const Params& P, float* obs, hipStream_t st);
-hipError_t launch_clear_episode(const Params& P, hipStream_t st);
-hipError_t launch_residual_probe(const Params& P, float* out, hipStream_t st);
-hipError_t launch_get_state(int variant, const Params& P, float* world, float* dist, int32_t* target, int32_t* steps,
-                            uint32_t* episode, hipStream_t st);
-hipError_t launch_set_state(int variant, const Params& P, const float* world, const float* dist,
-                            const int32_t* target, const int32_t* steps, const uint32_t* episode, hipStream_t st);
-}  // namespace qr
+#include "quadrace_launch.hpp"
 
 struct qr_env {
     qr_config cfg{};

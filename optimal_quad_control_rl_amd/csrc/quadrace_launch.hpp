@@ -1,0 +1,130 @@
+// quadrace_launch.hpp -- the host side every translation unit of libquadrace.so shares: the run-time -> compile-time dispatch of
+// (variant, gates_ahead) and of the observation length, the launch of a kernel with dynamic LDS, and the prototypes of the functions
+// that are defined in one unit and called from another.  Host code, but included by files that are compiled for both sides: everything
+// here is a template, `inline`, or a declaration (nothing is visible outside the library: -fvisibility=hidden, exports.map).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <type_traits>
+
+#include "../../include/quadrace.h"
+#include "quadrace_device.hpp"
+#include "quadrace_policy.hpp"
+
+namespace qr {
+
+inline dim3 grid_for(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
+
+// ---------------------------------------------------------------------------------------------------
+// compile-time dispatch: keeps every observation index static (registers, no scratch).  `f` is a generic lambda that receives the
+// value(s) as std::integral_constant; the legal values are listed here and nowhere else.
+// ---------------------------------------------------------------------------------------------------
+// gates_ahead -> f(integral_constant<int, GA>); hipErrorInvalidValue for a value outside 0..4
+template <typename F>
+hipError_t dispatch_ga(int gates_ahead, F&& f) {
+#ifdef QR_GA_ONLY  // developer builds (ISA inspection, tools/phase_probe.py): instantiate one gates_ahead value only
+    if (gates_ahead != QR_GA_ONLY) return hipErrorInvalidValue;
+    return f(std::integral_constant<int, QR_GA_ONLY>{});
+#else
+    switch (gates_ahead) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return hipErrorInvalidValue;
+    }
+#endif
+}
+// (variant, gates_ahead) -> f(integral_constant<int, V>, integral_constant<int, GA>)
+template <typename F>
+hipError_t dispatch_vg(int variant, int gates_ahead, F&& f) {
+    return dispatch_ga(gates_ahead, [&](auto ga) {
+        return variant == kE2E ? f(std::integral_constant<int, kE2E>{}, ga) : f(std::integral_constant<int, kINDI>{}, ga);
+    });
+}
+// observation length -> f(integral_constant<int, L>): every length the two env variants can produce (gates_ahead 0..4).  The caller
+// supplies what an illegal length yields: `invalid()` runs only then (it may record an error message).
+template <typename F, typename Invalid>
+auto dispatch_L(int L, F&& f, Invalid&& invalid) -> decltype(invalid()) {
+    switch (L) {
+        case 13: return f(std::integral_constant<int, 13>{});
+        case 17: return f(std::integral_constant<int, 17>{});
+        case 21: return f(std::integral_constant<int, 21>{});
+        case 25: return f(std::integral_constant<int, 25>{});
+        case 29: return f(std::integral_constant<int, 29>{});
+        case 20: return f(std::integral_constant<int, 20>{});
+        case 24: return f(std::integral_constant<int, 24>{});
+        case 28: return f(std::integral_constant<int, 28>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 36: return f(std::integral_constant<int, 36>{});
+        default: return invalid();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// kernels with dynamic LDS.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel, and one process may
+// drive handles on several GPUs (include/quadrace.h): the mask of the device ordinals a kernel has been configured on lives HERE, one
+// per kernel (per instantiation of configure_dynamic_lds), so a launch site can neither forget it nor share it between two kernels.
+// ---------------------------------------------------------------------------------------------------
+inline hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes, unsigned long long& done_mask) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64 && ((done_mask >> dev) & 1ull)) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && dev >= 0 && dev < 64) done_mask |= 1ull << dev;
+    return e;
+}
+// the limit of `Kernel` on the CURRENT device (idempotent; not a stream operation, so it may run before a graph capture)
+template <auto Kernel>
+hipError_t configure_dynamic_lds(size_t bytes) {
+    static unsigned long long configured = 0;   // per device ordinal
+    return ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), bytes, configured);
+}
+template <auto Kernel, typename... Args>
+hipError_t launch_dynamic_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    if (hipError_t e = configure_dynamic_lds<Kernel>(lds)) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// defined in one translation unit, called from another
+// ---------------------------------------------------------------------------------------------------
+// quadrace_abi.hip
+int set_last_error(int code, const std::string& msg);
+
+// quadrace_kernels.hip
+hipError_t launch_step(int variant, const Params& P, const float* actions, float* obs, float* rew, uint8_t* done,
+                       uint8_t* trunc, hipStream_t st);
+const char* rollout_kernel_name(int variant, const Params& P, int form);
+hipError_t launch_rollout(int variant, const Params& P, int form, int K, const float* actions, float* obs, float* rew,
+                          uint8_t* done, uint8_t* trunc, hipStream_t st);
+hipError_t launch_rollout_policy(int variant, const Params& P, const PolicyArgs& A, int K, float* obs, float* act,
+                                 float* logp, float* rew, uint8_t* done, uint8_t* trunc, float* last_obs,
+                                 hipStream_t st);
+hipError_t launch_reset(int variant, const Params& P, const uint8_t* mask, float* obs, hipStream_t st);
+hipError_t launch_observe(int variant, const Params& P, float* obs, hipStream_t st);
+hipError_t launch_clear_episode(const Params& P, hipStream_t st);
+hipError_t launch_residual_probe(const Params& P, float* out, hipStream_t st);
+hipError_t launch_get_state(int variant, const Params& P, float* world, float* dist, int32_t* target, int32_t* steps,
+                            uint32_t* episode, hipStream_t st);
+hipError_t launch_set_state(int variant, const Params& P, const float* world, const float* dist,
+                            const int32_t* target, const int32_t* steps, const uint32_t* episode, hipStream_t st);
+
+// quadrace_kernels_mlp.hip: the two fused E2E + residual-MLP rollout kernels (one workgroup per CU / lean form)
+hipError_t launch_rollout_mlp(bool lean, const Params& P, int K, const float4* a4, float* obs, float* rew, uint8_t* done,
+                              uint8_t* trunc, hipStream_t st);
+
+// quadrace_policy.hip
+hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);
+hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st);
+const half8* policy_weights(const qr_policy* p);   // accessors for the closed-loop rollout entry point in quadrace_abi.hip
+const half8* policy_weights_lo(const qr_policy* p);
+int policy_obs_len(const qr_policy* p);
+int policy_device(const qr_policy* p);
+
+}  // namespace qr

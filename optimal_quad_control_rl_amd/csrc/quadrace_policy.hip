@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/quadrace.h"
-#include "quadrace_policy.hpp"
+#include "quadrace_launch.hpp"
 
 namespace qr {
 
@@ -48,30 +48,12 @@ policy_kernel(const half8* __restrict__ weights, int n, const float* __restrict_
     if (i < n) mean_out[i] = make_float4(mean[0], mean[1], mean[2], mean[3]);
 }
 
-template <int L>
-hipError_t launch_policy_L(const half8* w, int n, const float* obs, float* mean, hipStream_t st) {
-    const size_t lds = (size_t)PolicyDims<L>::kTotalHalf8 * 16;
-    static unsigned long long configured = 0;   // per device ordinal
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(policy_kernel<L>), lds, configured)) return e;
-    hipLaunchKernelGGL(policy_kernel<L>, dim3((n + kPolBlock - 1) / kPolBlock), dim3(kPolBlock), lds, st, w, n, obs,
-                       reinterpret_cast<float4*>(mean));
-    return hipGetLastError();
-}
-
 hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st) {
-    switch (L) {  // every observation length the two env variants can produce (gates_ahead 0..4)
-        case 13: return launch_policy_L<13>(w, n, obs, mean, st);
-        case 17: return launch_policy_L<17>(w, n, obs, mean, st);
-        case 21: return launch_policy_L<21>(w, n, obs, mean, st);
-        case 25: return launch_policy_L<25>(w, n, obs, mean, st);
-        case 29: return launch_policy_L<29>(w, n, obs, mean, st);
-        case 20: return launch_policy_L<20>(w, n, obs, mean, st);
-        case 24: return launch_policy_L<24>(w, n, obs, mean, st);
-        case 28: return launch_policy_L<28>(w, n, obs, mean, st);
-        case 32: return launch_policy_L<32>(w, n, obs, mean, st);
-        case 36: return launch_policy_L<36>(w, n, obs, mean, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_L(L, [&](auto Lc) {
+        constexpr int kL = decltype(Lc)::value;
+        return launch_dynamic_lds<policy_kernel<kL>>(dim3((n + kPolBlock - 1) / kPolBlock), dim3(kPolBlock),
+                                                     (size_t)PolicyDims<kL>::kTotalHalf8 * 16, st, w, n, obs, reinterpret_cast<float4*>(mean));
+    }, [] { return hipErrorInvalidValue; });
 }
 
 template <int L>
@@ -95,30 +77,13 @@ policy_f32class_kernel(const half8* __restrict__ w0, const half8* __restrict__ w
     if (i < n) mean_out[i] = make_float4(mean[0], mean[1], mean[2], mean[3]);
 }
 
-template <int L>
-hipError_t launch_policy_f32class_L(const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st) {
-    const size_t lds = (size_t)PolicyDims<L>::kTotalHalf8 * 16;
-    static unsigned long long configured = 0;   // per device ordinal
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(policy_f32class_kernel<L>), lds, configured)) return e;
-    hipLaunchKernelGGL(policy_f32class_kernel<L>, dim3((n + kPolBlock - 1) / kPolBlock), dim3(kPolBlock), lds, st, w0, w1, n, obs,
-                       reinterpret_cast<float4*>(mean));
-    return hipGetLastError();
-}
-
 hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st) {
-    switch (L) {
-        case 13: return launch_policy_f32class_L<13>(w0, w1, n, obs, mean, st);
-        case 17: return launch_policy_f32class_L<17>(w0, w1, n, obs, mean, st);
-        case 21: return launch_policy_f32class_L<21>(w0, w1, n, obs, mean, st);
-        case 25: return launch_policy_f32class_L<25>(w0, w1, n, obs, mean, st);
-        case 29: return launch_policy_f32class_L<29>(w0, w1, n, obs, mean, st);
-        case 20: return launch_policy_f32class_L<20>(w0, w1, n, obs, mean, st);
-        case 24: return launch_policy_f32class_L<24>(w0, w1, n, obs, mean, st);
-        case 28: return launch_policy_f32class_L<28>(w0, w1, n, obs, mean, st);
-        case 32: return launch_policy_f32class_L<32>(w0, w1, n, obs, mean, st);
-        case 36: return launch_policy_f32class_L<36>(w0, w1, n, obs, mean, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_L(L, [&](auto Lc) {
+        constexpr int kL = decltype(Lc)::value;
+        return launch_dynamic_lds<policy_f32class_kernel<kL>>(dim3((n + kPolBlock - 1) / kPolBlock), dim3(kPolBlock),
+                                                              (size_t)PolicyDims<kL>::kTotalHalf8 * 16, st, w0, w1, n, obs,
+                                                              reinterpret_cast<float4*>(mean));
+    }, [] { return hipErrorInvalidValue; });
 }
 
 }  // namespace qr
@@ -132,9 +97,6 @@ struct qr_policy {
     bool has_weights = false;
 };
 
-namespace qr {
-int set_last_error(int code, const std::string& msg);  // quadrace_abi.hip
-}
 namespace {
 int pfail(int code, const std::string& m) { return qr::set_last_error(code, m); }
 inline int rho(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -154,10 +116,8 @@ const char* qr_policy_last_error(void) { return qr_last_error(); }  // same thre
 int qr_policy_create(int32_t obs_len, int32_t device, qr_policy** out) {
     if (!out) return pfail(QR_E_INVALID, "qr_policy_create: null output");
     *out = nullptr;
-    static const int ok[] = {13, 17, 21, 25, 29, 20, 24, 28, 32, 36};
-    bool found = false;
-    for (int v : ok) found |= (v == obs_len);
-    if (!found) return pfail(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs");
+    if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
+        return pfail(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return pfail(QR_E_NO_DEVICE, "qr_policy_create: no HIP device visible (no CPU fallback)");

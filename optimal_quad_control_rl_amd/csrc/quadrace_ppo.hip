@@ -35,7 +35,7 @@
 #include <type_traits>
 
 #include "../../include/quadrace.h"
-#include "quadrace_policy.hpp"
+#include "quadrace_launch.hpp"
 
 namespace qr {
 
@@ -1632,8 +1632,6 @@ struct qr_ppo {
 };
 
 namespace qr {
-int set_last_error(int code, const std::string& msg);  // quadrace_abi.hip
-hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);  // quadrace_policy.hip
 const half8* ppo_policy_image(const qr_ppo* p) { return p ? p->d_images : nullptr; }
 // what quadrace_ppo_f32.hip needs of a handle
 int ppo_handle_info(const qr_ppo* p, int* L, int* device, int* max_B, int* num_params) {
@@ -1689,11 +1687,10 @@ struct PpoOps {
     // dynamic-LDS limit of the gradient kernel on the CURRENT device (idempotent; not a stream operation, so it also runs
     // before a graph capture instead of inside it)
     static int configure(qr_ppo* p) {
-        static unsigned long long configured_f = 0, configured_fb = 0;   // per device ordinal
         if (p->partial_bf16) {
-            PPO_HIP(qr::ensure_dynamic_lds(reinterpret_cast<const void*>(qr::ppo_grad_kernel<L, __bf16>), kLdsFused, configured_fb));
+            PPO_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16>>(kLdsFused)));
         } else {
-            PPO_HIP(qr::ensure_dynamic_lds(reinterpret_cast<const void*>(qr::ppo_grad_kernel<L, float>), kLdsFused, configured_f));
+            PPO_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float>>(kLdsFused)));
         }
         return QR_OK;
     }
@@ -1739,20 +1736,8 @@ struct PpoOps {
 };
 
 template <typename F>
-int dispatch_L(int L, F&& f) {
-    switch (L) {
-        case 13: return f(std::integral_constant<int, 13>());
-        case 17: return f(std::integral_constant<int, 17>());
-        case 21: return f(std::integral_constant<int, 21>());
-        case 25: return f(std::integral_constant<int, 25>());
-        case 29: return f(std::integral_constant<int, 29>());
-        case 20: return f(std::integral_constant<int, 20>());
-        case 24: return f(std::integral_constant<int, 24>());
-        case 28: return f(std::integral_constant<int, 28>());
-        case 32: return f(std::integral_constant<int, 32>());
-        case 36: return f(std::integral_constant<int, 36>());
-        default: return ppofail(QR_E_INVALID, "obs_len must be an observation length of the race envs");
-    }
+int dispatch_L(int L, F&& f) {   // qr::dispatch_L with this file's failure: the message goes to qr_last_error()
+    return qr::dispatch_L(L, f, [] { return ppofail(QR_E_INVALID, "obs_len must be an observation length of the race envs"); });
 }
 
 int fill_batch(qr_ppo* p, qr::PpoBatch& b, const float* theta, const float* obs, const float* act, const float* old_logp,

@@ -235,7 +235,7 @@ def store_data_hazards(lines):
     return bad
 
 
-def _code_objects(path):
+def code_objects(path):
     """Every AMDGPU ELF embedded in a host object / shared library (the .hip_fatbin bundles), or the file itself if it is one."""
     data = open(path, "rb").read()
     found, pos = [], 0
@@ -261,7 +261,7 @@ def lint_library(path, stats=None):
     bundler layout, a truncated section table) raises instead of being reported clean.  `stats` (a dict) receives the counts."""
     bad = []
     objdump = os.path.join(llvm_bin(), "llvm-objdump")
-    blobs = _code_objects(path)
+    blobs = code_objects(path)
     n_sym = n_ins = n_pk = 0
     for blob in blobs:
         with tempfile.NamedTemporaryFile(suffix=".co") as f:

@@ -1,4 +1,4 @@
-"""Plain NumPy restatement of the closed-loop rollout's action noise (qr_rollout_policy, csrc/quadrace_kernels.hip
+"""Plain NumPy restatement of the closed-loop rollout's action noise (qr_rollout_policy, csrc/quadrace_env_kernels.hpp
 rollout_policy_kernel), written from the spec and not from the kernel's arithmetic:
 
   counter = (gid lo, gid hi, step lo, step hi)    gid = env_id_base + i, step = first_step + k (64-bit values)

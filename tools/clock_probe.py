@@ -23,7 +23,6 @@ tag = os.environ.get("QR_PROBE_TAG", "")
 dbg = os.path.join(B.PKG, "_dbg", "libquadrace_clk%s.so" % tag)   # travels with the snapshot when built in the container
 os.makedirs(os.path.dirname(dbg), exist_ok=True)
 CSRC = os.environ.get("QR_PROBE_CSRC", B.CSRC)   # A/B against another checkout of the sources (same box, same call)
-deps = [os.path.join(CSRC, h) for h in B.HEADERS]
 flags = ["-DQR_CLOCK_PROBE", *extra]
 if not (os.environ.get("QR_PROBE_NOBUILD") == "1" and os.path.exists(dbg)):   # the product's own pipeline (assembly rewrite + lint), stale objects only
     B.CSRC = CSRC

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Hand-patch the ISA of ONE kernel of quadrace_kernels.hip and link a library from it -- the experiment behind DESIGN's account of
+"""Hand-patch the ISA of ONE kernel that quadrace_kernels.hip instantiates (the kernels of csrc/quadrace_env_kernels.hpp except the two
+fused E2E + residual-MLP rollout kernels, which belong to quadrace_kernels_mlp.hip) and link a library from it -- the experiment behind DESIGN's account of
 the two-waves-per-SIMD corruption: insert wait states (or anything else) at a named place of a failing build WITHOUT letting the
 compiler re-schedule or re-allocate anything else.
 
@@ -13,7 +14,9 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fvisibility=hidden", "-fPIC"]
-OTHERS = ["quadrace_abi.hip", "quadrace_policy.hip", "quadrace_ppo.hip", "quad3d.hip"]
+sys.path.insert(0, ROOT)
+from optimal_quad_control_rl_amd import build as B
+OTHERS = [s for s in B.SOURCES if s != "quadrace_kernels.hip"]
 
 
 def run(cmd, **kw):
@@ -35,7 +38,7 @@ def main():
     for s in OTHERS:
         o = os.path.join(out, s.replace(".hip", ".o")); objs.append(o)
         if not os.path.exists(o):
-            run(["/opt/rocm/bin/hipcc", *flags, *extra, "-c", os.path.join(csrc, s), "-o", o])
+            run(["/opt/rocm/bin/hipcc", *flags, *B.PER_SOURCE_FLAGS.get(s, []), *extra, "-c", os.path.join(csrc, s), "-o", o])
     dev_s = os.path.join(out, "quadrace_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
     host_s = os.path.join(out, "quadrace_kernels-host-x86_64-unknown-linux-gnu.s")
     if not os.path.exists(dev_s):

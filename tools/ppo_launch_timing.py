@@ -11,7 +11,7 @@ from optimal_quad_control_rl_amd import build as B
 extra = os.environ.get("QR_TICK_EXTRA_FLAGS", "").split()
 dbg = os.path.join(ROOT, "optimal_quad_control_rl_amd", "_dbg", "libquadrace_dbg_nodrain%s.so" % ("_x" if extra else ""))
 os.makedirs(os.path.dirname(dbg), exist_ok=True)
-srcs = [os.path.join(B.CSRC, s) for s in B.SOURCES]
+srcs = [os.path.join(B.CSRC, s) for s in B.SOURCES + B.HEADERS]
 if "--build-only" in sys.argv or not os.path.exists(dbg) or os.path.getmtime(dbg) < max(os.path.getmtime(f) for f in srcs):
     B.build_native(extra_flags=("-DQR_PHASE_TIMING", "-DQR_PHASE_TIMING_NODRAIN", *extra), out=dbg, drop_flags=("-mllvm", "-amdgpu-mfma-vgpr-form"))
 if "--build-only" in sys.argv:

@@ -10,7 +10,7 @@ nodrain = os.environ.get("QR_TICK_NODRAIN") == "1"
 extra = os.environ.get("QR_TICK_EXTRA_FLAGS", "").split()
 dbg = os.path.join(ROOT, "optimal_quad_control_rl_amd", "_dbg", "libquadrace_dbg%s%s.so" % ("_nodrain" if nodrain else "", "_x" if extra else ""))   # travels with the snapshot (git-ignored)
 os.makedirs(os.path.dirname(dbg), exist_ok=True)
-srcs = [os.path.join(B.CSRC, s) for s in B.SOURCES]
+srcs = [os.path.join(B.CSRC, s) for s in B.SOURCES + B.HEADERS]
 if "--build-only" in sys.argv or not os.path.exists(dbg) or os.path.getmtime(dbg) < max(os.path.getmtime(f) for f in srcs):
     B.build_native(extra_flags=("-DQR_PHASE_TIMING", *(["-DQR_PHASE_TIMING_NODRAIN"] if nodrain else []), *extra), out=dbg, drop_flags=("-mllvm", "-amdgpu-mfma-vgpr-form"))
 if "--build-only" in sys.argv:
