@@ -520,6 +520,24 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
         stash_ok = true;
     }
     if constexpr (V == kE2E) disturbance_obs_values(P, e.d, e.od);   // constant within an episode: refreshed by the resets below
+    if constexpr (kMlp && !kLean) {
+        // Every load of the state has returned before the step loop starts.  Left alone, the last of them (dB, read by the dynamics
+        // on every step and redefined by the reset path) could still be in flight at the loop entry, and the compiler, unable to
+        // prove otherwise, waited for it INSIDE the loop: loads and stores share vmcnt, so with the previous step's observation,
+        // reward and done stores outstanding the only wait it can emit is vmcnt(0) -- once per step, the wave's whole store queue
+        // drained before the dynamics went on (a lone wave per SIMD has nothing to cover that).  Reading the values through an
+        // empty asm here puts the one wait behind the stash fill, which still runs in the shadow of the HBM loads; what is left is the
+        // chunk top's vmcnt(0) for the prefetched actions, once per chunk (tests/test_step_loop_waits.py).  rollout_fast_kernel (no
+        // MLPs) keeps its per-step wait: without it that kernel measured 4 % SLOWER (1.516 -> 1.585 us per step at 65 536 envs, medians
+        // of three alternating runs, profiles/r07_store_drain.txt; not analysed further).
+#pragma unroll
+        for (int q = 0; q < S; ++q) asm volatile("" : "+v"(e.s[q]));
+        if constexpr (V == kE2E) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) asm volatile("" : "+v"(e.d[q]));
+        }
+        asm volatile("" : "+v"(e.target), "+v"(e.episode), "+v"(e.steps));
+    }
     uint32_t* who = nullptr;
     float4* pool = nullptr;
     if constexpr (kLean) {
