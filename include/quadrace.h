@@ -49,7 +49,8 @@ extern "C" {
 /* libquadrace.so is built with -fvisibility=hidden: only what this header declares is exported */
 #pragma GCC visibility push(default)
 
-#define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5) */
+#define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
+                             qr_evaluate_policy (round 8) */
 
 enum {
     QR_OK = 0,
@@ -215,6 +216,34 @@ int qr_rollout_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const f
                       uint64_t first_step, int32_t deterministic, float* obs_out_dev, float* act_out_dev,
                       float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
                       float* last_obs_dev, void* stream);
+
+/* Closed-loop EVALUATION of a policy: K steps of  obs -> policy -> env.step(clip(mean, -1, 1))  in ONE kernel that stores nothing per
+ * step and keeps the lap / crash accounting in registers -- what a user of the reference does after training (deterministic flight,
+ * gate-passage and lap times FP:261-289, crash rate R:4487-4519).  The env state afterwards is the state after K closed-loop steps,
+ * bit-identical to qr_rollout_policy(..., QR_ROLLOUT_DETERMINISTIC) with the same K.
+ * rec_dev [N][QR_EVAL_REC_INTS] int32 (16-byte aligned), all times in STEPS (seconds = steps * dt):
+ *   [0] gate passes counted   [1] crashes (done && !trunc)   [2] time-limit ends (trunc)   [3] passes since this env's last (re)start
+ *   [4] step index of its last lap boundary or (re)start     [5] steps evaluated so far (cumulative over calls)
+ *   [6..13] sum of lap durations, lap 1..QR_EVAL_MAX_LAPS since a (re)start   [14..21] number of laps counted, lap 1..8   [22], [23] 0
+ * Per step: [5] += 1; a PASS is a step that does not end the episode and after which the target gate differs from the one before it
+ * (a pass on a finishing step is not counted); on a pass [0] += 1, [3] += 1 and, when [3] is a multiple of gates_per_lap, lap number
+ * j = [3] / gates_per_lap is complete: if j <= 8, [5 + j] += [5] - [4] and [13 + j] += 1; then [4] = [5].  On done: [1] or [2] += 1,
+ * [3] = 0, [4] = [5].  Lap 1 therefore runs from the (re)start, laps 2.. are flying laps.
+ * recf_dev [N][QR_EVAL_REC_FLOATS] float32 (16-byte aligned; may be NULL) = {return of the running episode, sum of the finished
+ * episodes' returns, sum of their squares, 0}: sequential float32 adds in step order (the finished episodes number [1] + [2]).
+ * Both records are READ at the start of the call and written at its end: zero them for a fresh evaluation, pass them again to
+ * continue one (K = 2000 in one call equals 1200 then 800); pass the SAME gates_per_lap when continuing: the running lap's position is
+ * re-derived from [3] with the value of the current call.  gates_per_lap is an argument because a track may list its gates more
+ * than once (square_track(): 8 rows, a lap is 4 passes).
+ * flags: 0 or QR_ROLLOUT_F32CLASS.  QR_E_INVALID: NULL or misaligned record, num_steps < 1, gates_per_lap < 1, another flag, policy
+ * obs_len != env obs_len, a track with fewer than two gates (a pass cannot move the target).  QR_E_STATE: pause / pause_if_collision
+ * set (evaluation is defined for the default mode), a policy without weights.  A registered terminal-observation buffer is not written.
+ * qr_last_step_many_ms() reports this launch too. */
+#define QR_EVAL_REC_INTS 24
+#define QR_EVAL_MAX_LAPS 8
+#define QR_EVAL_REC_FLOATS 4
+int qr_evaluate_policy(qr_env* env, qr_policy* policy, int32_t num_steps, int32_t gates_per_lap, int32_t flags,
+                       int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* ---- PPO minibatch update on the matrix cores (replaces SB3's PPO.train inner loop, R:783-795 / R:820) -------------
  * Networks: policy obs -> 120 -> 120 -> 120 -> 4 and value obs -> 120 -> 120 -> 120 -> 1 (ReLU), log_std[4].

@@ -7,7 +7,8 @@ for gfx950 behind a C ABI (include/quadrace.h -> libquadrace.so); this package i
 from .tracks import TRAIN_DISTURBANCE_RANGES, square_track, zigzag_track  # noqa: F401
 
 __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square_track", "TRAIN_DISTURBANCE_RANGES",
-           "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor"]
+           "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
+           "evaluate_policy", "summarize_eval"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -23,6 +24,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import sb3
 
         return getattr(sb3, name)
+    if name in ("evaluate_policy", "summarize_eval"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
+        from . import evaluation
+
+        return getattr(evaluation, name)
     if name == "ShardedRaceEnv":
         from . import sharded
 

@@ -532,6 +532,37 @@ int qr_rollout_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_
     return QR_OK;
 }
 
+int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_per_lap, int32_t flags, int32_t* rec_dev,
+                       float* recf_dev, void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    if (!policy) return fail(QR_E_INVALID, "qr_evaluate_policy: null policy handle");
+    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy: rec_dev is required");
+    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy: the record buffers must be 16-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy: num_steps must be >= 1");
+    if (gates_per_lap < 1) return fail(QR_E_INVALID, "qr_evaluate_policy: gates_per_lap must be >= 1");
+    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy: `flags` takes QR_ROLLOUT_F32CLASS or 0");
+    if (e->num_gates < 2)
+        return fail(QR_E_INVALID, "qr_evaluate_policy: the track has one gate: a pass cannot move the target, so passes cannot be counted");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, "qr_evaluate_policy: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy: policy obs_len != env obs_len");
+    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy: policy on another GPU");
+    const qr::half8* w = qr::policy_weights(policy);
+    if (!w) return fail(QR_E_STATE, "qr_evaluate_policy: the policy has no weights");
+    qr::PolicyArgs A{};   // no sampling: only the weight images are read
+    A.weights = w;
+    A.weights_lo = qr::policy_weights_lo(policy);
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    A.deterministic = 1;
+    hipStream_t st = (hipStream_t)stream;
+    const bool ev = want_events(e, st);
+    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
+    QR_HIP(qr::launch_eval_policy(e->cfg.variant, e->P, A, K, gates_per_lap, rec_dev, recf_dev, st));
+    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
+    e->timing_valid = ev;
+    return QR_OK;
+}
+
 int qr_observe(qr_env* e, float* obs_out_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
     if (!obs_out_dev) return fail(QR_E_INVALID, "qr_observe: null output");

@@ -119,6 +119,10 @@ hipError_t launch_set_state(int variant, const Params& P, const float* world, co
 hipError_t launch_rollout_mlp(bool lean, const Params& P, int K, const float4* a4, float* obs, float* rew, uint8_t* done,
                               uint8_t* trunc, hipStream_t st);
 
+// quadrace_eval.hip: the closed-loop evaluation kernel (qr_evaluate_policy)
+hipError_t launch_eval_policy(int variant, const Params& P, const PolicyArgs& A, int K, int gates_per_lap, int32_t* rec, float* recf,
+                              hipStream_t st);
+
 // quadrace_policy.hip
 hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);
 hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st);

@@ -633,6 +633,22 @@ class Quadcopter3DGates(_Base):
         self._last_obs = self._obs
         return obs, act, logp, rew, done, trunc, self._obs
 
+    def evaluate_device(self, policy, num_steps, gates_per_lap, rec, recf=None, precision="f16-operands"):
+        """Closed-loop deterministic evaluation in ONE kernel (qr_evaluate_policy): K x [obs -> MFMA policy -> env.step(clip(mean))]
+        with the lap / crash accounting on the device and nothing stored per step.  `rec` int32 CUDA tensor [N, 24] and `recf`
+        float32 [N, 4] (optional) are read at the start and written at the end: zero them for a fresh evaluation, pass them again
+        to continue one (record layout: include/quadrace.h; summary: evaluation.summarize_eval).  Returns (rec, recf)."""
+        if precision not in ("f16-operands", "f32"):
+            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        n = self.num_envs
+        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
+        if recf is not None:
+            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        _lib.check(self._L.qr_evaluate_policy(self._h, policy._h, int(num_steps), int(gates_per_lap), 2 if precision == "f32" else 0,
+                                              _ptr(rec), _ptr(recf), self._stream()))
+        self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
+        return rec, recf
+
     def profile_rollout(self, actions, out):
         """Like rollout_device but every step kernel is bracketed by its own hipEvent pair on the launch stream.
         Returns (mean single-kernel duration in ms, whole-region ms).  Blocks."""

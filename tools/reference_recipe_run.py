@@ -29,6 +29,8 @@ ap.add_argument("--precision", default="f16-operands", help="f16-operands (hand-
                 "the reference's precision end to end) | f32-collect (f32-class collect kernel + the f16-operand update kernels)")
 ap.add_argument("--stop-when-reached", action="store_true", help="end the run at the first evaluation that reaches the reference's level (lap-target, <= 0.1 crashes / 12 s): "
                 "answers 'does this seed reach it' at a fraction of the 1.03e9 steps; the result says so (stopped_when_reached)")
+ap.add_argument("--device-eval", action="store_true", help="evaluate with the on-device evaluator (evaluate_policy -> qr_evaluate_policy: two launches, gate passes "
+                "detected from the target gate) instead of the per-step loop below; opt-in, because committed profiles quote the loop's numbers")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 
@@ -79,6 +81,17 @@ def evaluate():
     return dict(flying_lap=fl, first_lap=laps[1] if float(lap_cnt[1]) > 0 else None, gates_per_12s=float(gates12.mean()),
                 crashes_per_12s=float(crashes12.mean()), laps_counted=lap_cnt[1:].tolist())
 
+
+def evaluate_on_device():
+    """the same protocol through evaluate_policy: 1 200-step window for the rates, 2 000 steps for the lap times"""
+    from optimal_quad_control_rl_amd import evaluate_policy
+    r = evaluate_policy(model, ev, n_eval_steps=2000, window_steps=1200, gates_per_lap=G, seed=99)
+    return dict(flying_lap=r["total"]["flying_lap_seconds"], first_lap=r["total"]["first_lap_seconds"], gates_per_12s=r["window"]["gates_per_window"],
+                crashes_per_12s=r["window"]["crashes_per_window"], laps_counted=[float(c) for c in r["total"]["laps_counted"][:6]], evaluator="device")
+
+
+if a.device_eval:
+    evaluate = evaluate_on_device
 
 ckpt = os.path.join(tempfile.mkdtemp(prefix="refrecipe_"), "ckpt")
 TIMESTEPS = model.n_steps * env.num_envs * 10                                   # R:818: a checkpoint every 10 policy rollouts

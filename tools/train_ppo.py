@@ -36,6 +36,8 @@ ap.add_argument("--eval-final", action="store_true", help="evaluate the FINAL po
 ap.add_argument("--save", default="", help="save an SB3-shaped checkpoint (optimal_quad_control_rl_amd.sb3 format) of the final model here")
 ap.add_argument("--curve", type=int, default=0, help="evaluate the current policy every this many rollouts (training clock stopped)")
 ap.add_argument("--lap-target", type=float, default=2.6, help="flying lap (s) that counts as the reference's level for --curve")
+ap.add_argument("--device-eval", action="store_true", help="evaluate with the on-device evaluator (evaluate_policy -> qr_evaluate_policy: two launches, gate passes "
+                "detected from the target gate) instead of the per-step loop below; opt-in, because committed profiles quote the loop's numbers")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 
@@ -106,6 +108,21 @@ def evaluate(m):
                 eval_lap_seconds={f"lap{i}": laps[i] for i in range(1, 7)}, eval_laps_counted=lap_cnt[1:].tolist(),
                 eval_flying_lap_seconds=float(lap_sum[2:].sum() / lap_cnt[2:].sum().clamp(min=1)))
 
+
+def evaluate_on_device(m):
+    """the same protocol and keys through evaluate_policy: 1 200-step window for the rates, 2 000 steps for the lap times"""
+    from optimal_quad_control_rl_amd import evaluate_policy
+    r = evaluate_policy(m, ev, n_eval_steps=2000, window_steps=1200, gates_per_lap=G, seed=99)
+    w, t = r["window"], r["total"]
+    g12 = max(w["gates_per_window"], 1e-9)
+    return dict(eval_gates_per_12s=w["gates_per_window"], eval_crashes_per_12s=w["crashes_per_window"], eval_seconds_per_gate=1200 * dt / g12,
+                eval_seconds_per_lap_4gates=4 * 1200 * dt / g12,
+                eval_lap_seconds={f"lap{i}": (t["lap_seconds"][i - 1] or 0.0) for i in range(1, 7)}, eval_laps_counted=[float(c) for c in t["laps_counted"][:6]],
+                eval_flying_lap_seconds=t["flying_lap_seconds"] or 0.0, eval_mean_reward=t["mean_reward"], evaluator="device")
+
+
+if a.device_eval:
+    evaluate = evaluate_on_device
 
 best = {"gates": -1.0, "state": None}
 def keep_best(m):
