@@ -50,7 +50,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 #define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
-                             qr_evaluate_policy (round 8) */
+                             qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9) */
 
 enum {
     QR_OK = 0,
@@ -244,6 +244,30 @@ int qr_rollout_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const f
 #define QR_EVAL_REC_FLOATS 4
 int qr_evaluate_policy(qr_env* env, qr_policy* policy, int32_t num_steps, int32_t gates_per_lap, int32_t flags,
                        int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Closed-loop FLIGHT RECORDER: the K steps of qr_rollout_policy (same policy forward, same action noise keyed by (noise_seed, global env id,
+ * first_step + t), same env arithmetic and reset stream: the env state afterwards is bit-identical to qr_rollout_policy with the same
+ * arguments) in ONE kernel whose whole per-step output is one packed float32 row per env -- what a user of the reference logs to plot a
+ * flight (I:666-695: world_states, the commanded actions and step_counts * dt per step).  No observation, log-prob, reward, done or
+ * truncation arrays are written, and no terminal-observation rows.
+ * rows_dev [num_steps][rec_envs][R] float32, contiguous, 16-byte aligned, R = qr_record_row_len() = S + QR_RECORD_EXTRA (S = 16 E2E / 13 INDI):
+ *   [0, S)      world state BEFORE the step: what qr_get_state would return, the state the action was computed from
+ *   [S, S + 4)  the command the env received: clip(action, -1, 1)
+ *   [S + 4]     reward of the step
+ *   [S + 5]     how the step ended: 0.0 running, 1.0 crash (done && !trunc), 2.0 time limit (trunc) -- the split of qr_evaluate_policy's [1], [2]
+ *   [S + 6]     target gate index before the step, as a float
+ *   [S + 7]     the env's step count before the step, as a float (exact below 2^24): 0.0 marks the first row of an episode; time = value * dt
+ * A row pairs a state with the command applied IN that state.  rec_envs = M, 1 <= M <= N: rows are written for envs [0, M) only, all N envs
+ * still fly (the env state afterwards does not depend on M), memory beyond [num_steps][M][R] is never written.  The rows of a full wave
+ * (64 consecutive envs below M) leave the chip as one contiguous block of 64 R floats per step.
+ * flags: QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS, as in qr_rollout_policy; log_std: host float[4].
+ * QR_E_INVALID: NULL policy, log_std or rows_dev, misaligned rows_dev, num_steps < 1, rec_envs outside 1..N, another flag bit, policy
+ * obs_len != env obs_len, policy on another GPU.  QR_E_STATE: pause / pause_if_collision set, a policy without weights.  A failed call
+ * launches nothing.  A registered terminal-observation buffer is not written.  qr_last_step_many_ms() reports this launch too. */
+#define QR_RECORD_EXTRA 8
+int qr_record_row_len(const qr_env* env);   /* S + QR_RECORD_EXTRA */
+int qr_record_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const float* log_std, uint64_t noise_seed,
+                     uint64_t first_step, int32_t flags, int32_t rec_envs, float* rows_dev, void* stream);
 
 /* ---- PPO minibatch update on the matrix cores (replaces SB3's PPO.train inner loop, R:783-795 / R:820) -------------
  * Networks: policy obs -> 120 -> 120 -> 120 -> 4 and value obs -> 120 -> 120 -> 120 -> 1 (ReLU), log_std[4].

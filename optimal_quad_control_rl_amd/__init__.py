@@ -8,7 +8,7 @@ from .tracks import TRAIN_DISTURBANCE_RANGES, square_track, zigzag_track  # noqa
 
 __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square_track", "TRAIN_DISTURBANCE_RANGES",
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
-           "evaluate_policy", "summarize_eval"]
+           "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -28,6 +28,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import evaluation
 
         return getattr(evaluation, name)
+    if name in ("record_policy", "FlightRecord"):  # on-device flight recorder: the trajectory a policy flew (qr_record_policy)
+        from . import recording
+
+        return getattr(recording, name)
     if name == "ShardedRaceEnv":
         from . import sharded
 

@@ -61,6 +61,8 @@ SIGNATURES = {
     "qr_rollout_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
     "qr_evaluate_policy": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "qr_record_row_len": (C.c_int, [_vp]),
+    "qr_record_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp]),
     "qr_profile_steps": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _f32p, _f32p]),
     "qr_ppo_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qr_ppo_create_ex": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
@@ -97,7 +99,16 @@ SIGNATURES = {
 }
 
 
-OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr_policy_forward_f32class", "qr_ppo_grad_f32class", "qr_evaluate_policy")   # added in rounds 5-8: a QR_PROBE_LIB build of older sources may lack them
+OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr_policy_forward_f32class", "qr_ppo_grad_f32class", "qr_evaluate_policy",
+                    "qr_record_policy", "qr_record_row_len")   # added in rounds 5-9: a QR_PROBE_LIB build of older sources may lack them
+
+
+def require(L, name):
+    """The optional entry point `name` of the loaded library, or a QuadraceError that names it (an older library loaded under QR_PROBE_LIB)."""
+    try:
+        return getattr(L, name)
+    except AttributeError:
+        raise QuadraceError(QR_E_STATE, "the loaded libquadrace.so does not export %s (built from older sources): rebuild it" % name) from None
 
 
 class QuadraceError(RuntimeError):

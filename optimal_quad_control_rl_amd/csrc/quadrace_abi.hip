@@ -563,6 +563,44 @@ int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_pe
     return QR_OK;
 }
 
+int qr_record_row_len(const qr_env* e) { return e ? e->S + QR_RECORD_EXTRA : QR_E_INVALID; }
+
+int qr_record_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                     int32_t flags, int32_t rec_envs, float* rows_dev, void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    if (!policy) return fail(QR_E_INVALID, "qr_record_policy: null policy handle");
+    if (!log_std) return fail(QR_E_INVALID, "qr_record_policy: log_std is required");
+    if (!rows_dev) return fail(QR_E_INVALID, "qr_record_policy: rows_dev is required");
+    if ((uintptr_t)rows_dev & 15) return fail(QR_E_INVALID, "qr_record_policy: rows_dev must be 16-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, "qr_record_policy: num_steps must be >= 1");
+    if (rec_envs < 1 || rec_envs > e->cfg.num_envs) return fail(QR_E_INVALID, "qr_record_policy: rec_envs must be in 1..num_envs");
+    if (flags & ~(QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return fail(QR_E_INVALID, "qr_record_policy: `flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, "qr_record_policy: pause / pause_if_collision envs are evaluation modes; use qr_step");
+    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_record_policy: policy obs_len != env obs_len");
+    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_record_policy: policy on another GPU");
+    const qr::half8* w = qr::policy_weights(policy);
+    if (!w) return fail(QR_E_STATE, "qr_record_policy: the policy has no weights");
+    qr::PolicyArgs A{};   // the sampling arguments of qr_rollout_policy (same noise stream); no log-prob is computed
+    A.weights = w;
+    A.weights_lo = qr::policy_weights_lo(policy);
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    for (int c = 0; c < 4; ++c) A.std[c] = expf(log_std[c]);
+    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;   // domain separation from the reset stream: see qr_rollout_policy
+    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
+    A.step_lo = (uint32_t)first_step;
+    A.step_hi = (uint32_t)(first_step >> 32);
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool ev = want_events(e, st);
+    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
+    QR_HIP(qr::launch_record_policy(e->cfg.variant, e->P, A, K, rec_envs, rows_dev, st));
+    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
+    e->timing_valid = ev;
+    return QR_OK;
+}
+
 int qr_observe(qr_env* e, float* obs_out_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
     if (!obs_out_dev) return fail(QR_E_INVALID, "qr_observe: null output");

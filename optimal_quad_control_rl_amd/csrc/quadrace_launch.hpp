@@ -123,6 +123,9 @@ hipError_t launch_rollout_mlp(bool lean, const Params& P, int K, const float4* a
 hipError_t launch_eval_policy(int variant, const Params& P, const PolicyArgs& A, int K, int gates_per_lap, int32_t* rec, float* recf,
                               hipStream_t st);
 
+// quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
+hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
+
 // quadrace_policy.hip
 hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);
 hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st);

@@ -649,6 +649,33 @@ class Quadcopter3DGates(_Base):
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return rec, recf
 
+    RECORD_EXTRA = 8   # QR_RECORD_EXTRA of include/quadrace.h
+
+    def record_policy_device(self, policy, num_steps, log_std, noise_seed=0, first_step=0, deterministic=True, rec_envs=None, out=None,
+                             precision="f16-operands"):
+        """The flight recorder (qr_record_policy): the closed loop of rollout_policy_device in ONE kernel whose only per-step output is
+        one packed row per env.  Returns the float32 device tensor [K, M, R], M = rec_envs (None: every env; all envs fly either way),
+        R = STATE_LEN + 8: columns [0, S) the world state BEFORE the step (what get_state_tensors would give), [S, S + 4) the command
+        the env received (clip(action, -1, 1)), then reward, end code (0 running / 1 crash / 2 time limit), target gate before the
+        step, step count before the step (time = steps * dt).  recording.FlightRecord gives the columns names.  `out`: a tensor of
+        that shape to write into.  Same noise stream and env state afterwards as rollout_policy_device with the same arguments."""
+        if precision not in ("f16-operands", "f32"):
+            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        fn = _lib.require(self._L, "qr_record_policy")
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        m = n if rec_envs is None else int(rec_envs)
+        r = self.STATE_LEN + self.RECORD_EXTRA
+        if out is None:
+            out = torch.empty((max(K, 0), min(max(m, 0), n), r), dtype=torch.float32, device=dev)
+        else:
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (K, m, r), (out.dtype, out.shape)
+        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
+                                  dtype=np.float32).reshape(4)
+        _lib.check(fn(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
+                      int(bool(deterministic)) | (2 if precision == "f32" else 0), m, _ptr(out), self._stream()))
+        self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
+        return out
+
     def profile_rollout(self, actions, out):
         """Like rollout_device but every step kernel is bracketed by its own hipEvent pair on the launch stream.
         Returns (mean single-kernel duration in ms, whole-region ms).  Blocks."""
