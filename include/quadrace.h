@@ -50,7 +50,8 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 #define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
-                             qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9) */
+                             qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
+                             qr_policy_bank_* / qr_evaluate_policy_bank (round 10) */
 
 enum {
     QR_OK = 0,
@@ -244,6 +245,36 @@ int qr_rollout_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const f
 #define QR_EVAL_REC_FLOATS 4
 int qr_evaluate_policy(qr_env* env, qr_policy* policy, int32_t num_steps, int32_t gates_per_lap, int32_t flags,
                        int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Evaluation of a BANK of policies in one launch, on shared random numbers: what a user holds after a run is many policies (a checkpoint
+ * every few rollouts, several seeds), and "which one do I keep?" is one call instead of one qr_evaluate_policy per policy.
+ * A bank owns two contiguous device arrays [capacity][image] (the f16 images and the low pieces); qr_policy_bank_set fills slot
+ * `slot` in [0, capacity) from the argument layout of qr_policy_set_weights, and the slot's two images are bit-identical to what a
+ * qr_policy given the same arrays holds.  It synchronises the device first, like qr_policy_set_weights.
+ * qr_evaluate_policy_bank flies slot p, p in [0, num_policies), on envs [p E, (p + 1) E) of the handle, E = envs_per_policy: a 256-env
+ * workgroup stages the image of ITS policy.  Records have the layout and semantics of qr_evaluate_policy: rec_dev [N][QR_EVAL_REC_INTS],
+ * recf_dev [N][QR_EVAL_REC_FLOATS] (may be NULL), N = num_policies * E, rows [p E, (p + 1) E) belong to policy p; both are read at the start
+ * and written at the end, so a call can be continued.  The env state afterwards is the state after num_steps closed-loop steps.
+ * GROUP-LOCAL RESET STREAM: inside THIS call an env that ends its episode draws its restart from the Philox stream of env id
+ * env_id_base + (i mod E) instead of env_id_base + i (same key, episode counter and block index).  Env j of every group therefore draws
+ * the same restart for the same episode number, and group p flies exactly what an E-env handle with the same seed, env_id_base and
+ * start state flies under qr_evaluate_policy with the same weights.  This is a property of this call alone: every other entry point on
+ * the same handle (qr_reset, qr_step, qr_step_many, qr_rollout_policy, qr_evaluate_policy, qr_record_policy) keeps resetting with the
+ * handle's ordinary ids, so qr_reset gives the groups DIFFERENT starts; copy one group's state onto the others (qr_get_state /
+ * qr_set_state) for common starts.
+ * Refused before anything is launched (qr_last_error / qr_policy_last_error set): everything qr_evaluate_policy refuses; QR_E_INVALID:
+ * NULL bank, num_policies < 1 or > capacity, envs_per_policy < 256 or not a multiple of 256, num_policies * envs_per_policy !=
+ * qr_num_envs(env), bank obs_len or device differing from the env's; QR_E_STATE: a slot in [0, num_policies) that was never set.
+ * qr_last_step_many_ms() reports this launch too. */
+typedef struct qr_policy_bank qr_policy_bank;
+int qr_policy_bank_create(int32_t obs_len, int32_t device, int32_t capacity, qr_policy_bank** out);
+int qr_policy_bank_destroy(qr_policy_bank* bank);
+int qr_policy_bank_capacity(const qr_policy_bank* bank);
+int qr_policy_bank_set(qr_policy_bank* bank, int32_t slot, const float* w1, const float* b1, const float* w2, const float* b2,
+                       const float* w3, const float* b3, const float* w4, const float* b4);
+int qr_evaluate_policy_bank(qr_env* env, qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy,
+                            int32_t num_steps, int32_t gates_per_lap, int32_t flags,
+                            int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* Closed-loop FLIGHT RECORDER: the K steps of qr_rollout_policy (same policy forward, same action noise keyed by (noise_seed, global env id,
  * first_step + t), same env arithmetic and reset stream: the env state afterwards is bit-identical to qr_rollout_policy with the same

@@ -563,6 +563,40 @@ int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_pe
     return QR_OK;
 }
 
+// The refusals come first and in full: nothing is enqueued (no event, no launch) unless every argument is valid.
+int qr_evaluate_policy_bank(qr_env* e, qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy, int32_t K,
+                            int32_t gates_per_lap, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    if (!bank) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: null bank handle");
+    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: rec_dev is required");
+    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: the record buffers must be 16-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_steps must be >= 1");
+    if (gates_per_lap < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: gates_per_lap must be >= 1");
+    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: `flags` takes QR_ROLLOUT_F32CLASS or 0");
+    if (e->num_gates < 2)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: the track has one gate: a pass cannot move the target, so passes cannot be counted");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, "qr_evaluate_policy_bank: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (qr::bank_obs_len(bank) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank obs_len != env obs_len");
+    if (qr::bank_device(bank) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank on another GPU");
+    if (num_policies < 1 || num_policies > qr::bank_capacity(bank))
+        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_policies must be in 1..capacity");
+    if (envs_per_policy < qr::kBlock || envs_per_policy % qr::kBlock != 0)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: envs_per_policy must be a multiple of 256, at least 256 (one workgroup serves one policy)");
+    if ((int64_t)num_policies * envs_per_policy != (int64_t)e->cfg.num_envs)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_policies * envs_per_policy must equal the env count of the handle");
+    const int unset = qr::bank_first_unset(bank, num_policies);
+    if (unset >= 0) return fail(QR_E_STATE, "qr_evaluate_policy_bank: slot " + std::to_string(unset) + " of the bank has no weights");
+    hipStream_t st = (hipStream_t)stream;
+    const bool ev = want_events(e, st);
+    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
+    QR_HIP(qr::launch_eval_policy_bank(e->cfg.variant, e->P, qr::bank_weights(bank), qr::bank_weights_lo(bank), (flags & QR_ROLLOUT_F32CLASS) != 0,
+                                       num_policies, envs_per_policy, K, gates_per_lap, rec_dev, recf_dev, st));
+    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
+    e->timing_valid = ev;
+    return QR_OK;
+}
+
 int qr_record_row_len(const qr_env* e) { return e ? e->S + QR_RECORD_EXTRA : QR_E_INVALID; }
 
 int qr_record_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step,

@@ -123,6 +123,10 @@ hipError_t launch_rollout_mlp(bool lean, const Params& P, int K, const float4* a
 hipError_t launch_eval_policy(int variant, const Params& P, const PolicyArgs& A, int K, int gates_per_lap, int32_t* rec, float* recf,
                               hipStream_t st);
 
+// quadrace_eval_bank.hip: the same for a bank of policies (qr_evaluate_policy_bank): workgroup b flies image b / (envs_per_policy / kBlock)
+hipError_t launch_eval_policy_bank(int variant, const Params& P, const half8* bank, const half8* bank_lo, bool f32class, int num_policies,
+                                   int envs_per_policy, int K, int gates_per_lap, int32_t* rec, float* recf, hipStream_t st);
+
 // quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
 hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
 
@@ -133,5 +137,11 @@ const half8* policy_weights(const qr_policy* p);   // accessors for the closed-l
 const half8* policy_weights_lo(const qr_policy* p);
 int policy_obs_len(const qr_policy* p);
 int policy_device(const qr_policy* p);
+const half8* bank_weights(const qr_policy_bank* b);   // the same for a bank of policies (qr_evaluate_policy_bank)
+const half8* bank_weights_lo(const qr_policy_bank* b);
+int bank_obs_len(const qr_policy_bank* b);
+int bank_device(const qr_policy_bank* b);
+int bank_capacity(const qr_policy_bank* b);
+int bank_first_unset(const qr_policy_bank* b, int num_policies);
 
 }  // namespace qr

@@ -97,6 +97,17 @@ struct qr_policy {
     bool has_weights = false;
 };
 
+// A bank of policies for qr_evaluate_policy_bank: two contiguous device arrays [capacity][total_half8] half8 (the f16 images and the
+// low pieces), slot s at element s * total_half8, each slot bit-identical to the two images of a qr_policy given the same arrays.
+struct qr_policy_bank {
+    int L = 0, device = 0, capacity = 0;
+    int steps1 = 0;
+    size_t total_half8 = 0;
+    qr::half8* d_weights = nullptr;
+    qr::half8* d_weights_lo = nullptr;
+    std::vector<uint8_t> is_set;   // per slot: qr_policy_bank_set has succeeded
+};
+
 namespace {
 int pfail(int code, const std::string& m) { return qr::set_last_error(code, m); }
 inline int rho(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -107,7 +118,79 @@ const half8* policy_weights(const qr_policy* p) { return (p && p->has_weights) ?
 const half8* policy_weights_lo(const qr_policy* p) { return (p && p->has_weights) ? p->d_weights_lo : nullptr; }
 int policy_obs_len(const qr_policy* p) { return p ? p->L : -1; }
 int policy_device(const qr_policy* p) { return p ? p->device : -1; }
+// the same for a bank (qr_evaluate_policy_bank in quadrace_abi.hip)
+const half8* bank_weights(const qr_policy_bank* b) { return b ? b->d_weights : nullptr; }
+const half8* bank_weights_lo(const qr_policy_bank* b) { return b ? b->d_weights_lo : nullptr; }
+int bank_obs_len(const qr_policy_bank* b) { return b ? b->L : -1; }
+int bank_device(const qr_policy_bank* b) { return b ? b->device : -1; }
+int bank_capacity(const qr_policy_bank* b) { return b ? b->capacity : -1; }
+int bank_first_unset(const qr_policy_bank* b, int num_policies) {   // first slot of [0, num_policies) never set, or -1
+    for (int s = 0; s < num_policies && s < b->capacity; ++s)
+        if (!b->is_set[(size_t)s]) return s;
+    return -1;
+}
 }  // namespace qr
+
+namespace {
+// The two packed images of one network (PolicyDims<L> layout, total_half8 half8 each) from torch.nn.Linear arrays, w[out][in], b[out]:
+// what qr_policy_set_weights uploads, and what a slot of a qr_policy_bank holds.  Returns the number of half8 elements written.
+size_t pack_policy_images(int L, int steps1, size_t total_half8, const float* w1, const float* b1, const float* w2, const float* b2,
+                          const float* w3, const float* b3, const float* w4, const float* b4, std::vector<__half>& img,
+                          std::vector<__half>& img_lo) {
+    const int H = qr::kPolHidden, BU = qr::kPolBiasUnit;
+    img.assign(total_half8 * 8, __float2half(0.0f));
+    img_lo.assign(total_half8 * 8, __float2half(0.0f));
+    // every packed value as two f16 pieces: W0 = f16(w) (the f16-operand image), W1 = f16(w - W0) (exact difference in f32; the image
+    // of the low pieces for the f32-class forward).  A weight beyond the f16 range saturates in W0 and W1 carries the rest.
+    auto put = [&](size_t idx, float w) {
+        float c = w;
+        if (c > 65504.0f) c = 65504.0f;
+        if (c < -65504.0f) c = -65504.0f;
+        const __half h0 = __float2half(c);
+        img[idx] = __float2half(w);   // (unchanged behaviour of the f16 image: inf beyond the range, as before)
+        float r = w - __half2float(h0);
+        if (r > 65504.0f) r = 65504.0f;
+        if (r < -65504.0f) r = -65504.0f;
+        img_lo[idx] = (w == w) ? __float2half(r) : __float2half(0.0f);
+    };
+    // padded weight accessors incl. the bias column and the constant-1 unit
+    auto W1 = [&](int row, int k) -> float {  // row < 128, k < 16*steps1 ; input k == L is the constant 1
+        if (row < H) return k < L ? w1[row * L + k] : (k == L ? b1[row] : 0.0f);
+        return (row == BU && k == L) ? 1.0f : 0.0f;
+    };
+    auto WH = [&](const float* w, const float* b, int row, int hid) -> float {  // hidden layers: in = hidden units
+        if (row < H) return hid < H ? w[row * H + hid] : (hid == BU ? b[row] : 0.0f);
+        return (row == BU && hid == BU) ? 1.0f : 0.0f;
+    };
+    auto W4 = [&](int row, int hid) -> float {  // 4 output rows in a 32-row tile
+        if (row < 4) return hid < H ? w4[row * H + hid] : (hid == BU ? b4[row] : 0.0f);
+        return 0.0f;
+    };
+    size_t e = 0;  // half8 element index
+    for (int t = 0; t < 4; ++t)
+        for (int s = 0; s < steps1; ++s)
+            for (int l = 0; l < 64; ++l, ++e)
+                for (int j = 0; j < 8; ++j) put(e * 8 + j, W1(32 * t + (l & 31), 16 * s + 8 * (l >> 5) + j));
+    for (int layer = 0; layer < 2; ++layer) {
+        const float* w = layer == 0 ? w2 : w3;
+        const float* b = layer == 0 ? b2 : b3;
+        for (int t = 0; t < 4; ++t)
+            for (int sp = 0; sp < 8; ++sp)
+                for (int l = 0; l < 64; ++l, ++e)
+                    for (int j = 0; j < 8; ++j) {
+                        const int hid = 32 * (sp >> 1) + rho(8 * (sp & 1) + j, l >> 5);
+                        put(e * 8 + j, WH(w, b, 32 * t + (l & 31), hid));
+                    }
+    }
+    for (int sp = 0; sp < 8; ++sp)
+        for (int l = 0; l < 64; ++l, ++e)
+            for (int j = 0; j < 8; ++j) {
+                const int hid = 32 * (sp >> 1) + rho(8 * (sp & 1) + j, l >> 5);
+                put(e * 8 + j, W4(l & 31, hid));
+            }
+    return e;
+}
+}  // namespace
 
 extern "C" {
 
@@ -153,57 +236,8 @@ int qr_policy_set_weights(qr_policy* p, const float* w1, const float* b1, const 
                           const float* w3, const float* b3, const float* w4, const float* b4) {
     if (!p || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4)
         return pfail(QR_E_INVALID, "qr_policy_set_weights: null argument");
-    const int L = p->L, H = qr::kPolHidden, HP = qr::kPolHiddenPad, BU = qr::kPolBiasUnit;
-    std::vector<__half> img(p->total_half8 * 8, __float2half(0.0f)), img_lo(p->total_half8 * 8, __float2half(0.0f));
-    // every packed value as two f16 pieces: W0 = f16(w) (the f16-operand image), W1 = f16(w - W0) (exact difference in f32; the image
-    // of the low pieces for the f32-class forward).  A weight beyond the f16 range saturates in W0 and W1 carries the rest.
-    auto put = [&](size_t idx, float w) {
-        float c = w;
-        if (c > 65504.0f) c = 65504.0f;
-        if (c < -65504.0f) c = -65504.0f;
-        const __half h0 = __float2half(c);
-        img[idx] = __float2half(w);   // (unchanged behaviour of the f16 image: inf beyond the range, as before)
-        float r = w - __half2float(h0);
-        if (r > 65504.0f) r = 65504.0f;
-        if (r < -65504.0f) r = -65504.0f;
-        img_lo[idx] = (w == w) ? __float2half(r) : __float2half(0.0f);
-    };
-    // padded weight accessors incl. the bias column and the constant-1 unit
-    auto W1 = [&](int row, int k) -> float {  // row < 128, k < 16*steps1 ; input k == L is the constant 1
-        if (row < H) return k < L ? w1[row * L + k] : (k == L ? b1[row] : 0.0f);
-        return (row == BU && k == L) ? 1.0f : 0.0f;
-    };
-    auto WH = [&](const float* w, const float* b, int row, int hid) -> float {  // hidden layers: in = hidden units
-        if (row < H) return hid < H ? w[row * H + hid] : (hid == BU ? b[row] : 0.0f);
-        return (row == BU && hid == BU) ? 1.0f : 0.0f;
-    };
-    auto W4 = [&](int row, int hid) -> float {  // 4 output rows in a 32-row tile
-        if (row < 4) return hid < H ? w4[row * H + hid] : (hid == BU ? b4[row] : 0.0f);
-        return 0.0f;
-    };
-    size_t e = 0;  // half8 element index
-    for (int t = 0; t < 4; ++t)
-        for (int s = 0; s < p->steps1; ++s)
-            for (int l = 0; l < 64; ++l, ++e)
-                for (int j = 0; j < 8; ++j) put(e * 8 + j, W1(32 * t + (l & 31), 16 * s + 8 * (l >> 5) + j));
-    for (int layer = 0; layer < 2; ++layer) {
-        const float* w = layer == 0 ? w2 : w3;
-        const float* b = layer == 0 ? b2 : b3;
-        for (int t = 0; t < 4; ++t)
-            for (int sp = 0; sp < 8; ++sp)
-                for (int l = 0; l < 64; ++l, ++e)
-                    for (int j = 0; j < 8; ++j) {
-                        const int hid = 32 * (sp >> 1) + rho(8 * (sp & 1) + j, l >> 5);
-                        put(e * 8 + j, WH(w, b, 32 * t + (l & 31), hid));
-                    }
-    }
-    for (int sp = 0; sp < 8; ++sp)
-        for (int l = 0; l < 64; ++l, ++e)
-            for (int j = 0; j < 8; ++j) {
-                const int hid = 32 * (sp >> 1) + rho(8 * (sp & 1) + j, l >> 5);
-                put(e * 8 + j, W4(l & 31, hid));
-            }
-    (void)HP;
+    std::vector<__half> img, img_lo;
+    const size_t e = pack_policy_images(p->L, p->steps1, p->total_half8, w1, b1, w2, b2, w3, b3, w4, b4, img, img_lo);
     if (e != p->total_half8) return pfail(QR_E_STATE, "qr_policy_set_weights: internal packing size mismatch");
     if (hipSetDevice(p->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
     if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");
@@ -227,6 +261,66 @@ int qr_policy_forward_f32class(qr_policy* p, int32_t n, const float* obs_dev, fl
     if (!p->has_weights) return pfail(QR_E_STATE, "qr_policy_forward_f32class: qr_policy_set_weights has not been called");
     hipError_t e = qr::launch_policy_f32class(p->L, p->d_weights, p->d_weights_lo, n, obs_dev, mean_out_dev, (hipStream_t)stream);
     if (e != hipSuccess) return pfail(QR_E_HIP, std::string("qr_policy_forward_f32class: ") + hipGetErrorString(e));
+    return QR_OK;
+}
+
+// ---- bank of policies (qr_evaluate_policy_bank) ----
+int qr_policy_bank_create(int32_t obs_len, int32_t device, int32_t capacity, qr_policy_bank** out) {
+    if (!out) return pfail(QR_E_INVALID, "qr_policy_bank_create: null output");
+    *out = nullptr;
+    if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
+        return pfail(QR_E_INVALID, "qr_policy_bank_create: obs_len must be an observation length of the race envs");
+    if (capacity < 1) return pfail(QR_E_INVALID, "qr_policy_bank_create: capacity must be >= 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return pfail(QR_E_NO_DEVICE, "qr_policy_bank_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return pfail(QR_E_INVALID, "qr_policy_bank_create: bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return pfail(QR_E_HIP, "qr_policy_bank_create: hipSetDevice failed");
+    qr_policy_bank* b = new qr_policy_bank();
+    b->L = obs_len;
+    b->device = device;
+    b->capacity = capacity;
+    b->steps1 = (obs_len + 1 + 15) / 16;
+    b->total_half8 = (size_t)4 * b->steps1 * 64 + 2 * 4 * 8 * 64 + 8 * 64;
+    b->is_set.assign((size_t)capacity, 0);
+    const size_t bytes = (size_t)capacity * b->total_half8 * 16;
+    if (hipMalloc((void**)&b->d_weights, bytes) != hipSuccess || hipMalloc((void**)&b->d_weights_lo, bytes) != hipSuccess) {
+        if (b->d_weights) (void)hipFree(b->d_weights);
+        delete b;
+        return pfail(QR_E_HIP, "qr_policy_bank_create: hipMalloc failed");
+    }
+    *out = b;
+    return QR_OK;
+}
+
+int qr_policy_bank_destroy(qr_policy_bank* b) {
+    if (!b) return QR_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    if (b->d_weights) (void)hipFree(b->d_weights);
+    if (b->d_weights_lo) (void)hipFree(b->d_weights_lo);
+    delete b;
+    return QR_OK;
+}
+
+int qr_policy_bank_capacity(const qr_policy_bank* b) { return b ? b->capacity : pfail(QR_E_INVALID, "qr_policy_bank_capacity: null bank"); }
+
+int qr_policy_bank_set(qr_policy_bank* b, int32_t slot, const float* w1, const float* b1, const float* w2, const float* b2,
+                       const float* w3, const float* b3, const float* w4, const float* b4) {
+    if (!b || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) return pfail(QR_E_INVALID, "qr_policy_bank_set: null argument");
+    if (slot < 0 || slot >= b->capacity) return pfail(QR_E_INVALID, "qr_policy_bank_set: slot must be in [0, capacity)");
+    std::vector<__half> img, img_lo;
+    const size_t e = pack_policy_images(b->L, b->steps1, b->total_half8, w1, b1, w2, b2, w3, b3, w4, b4, img, img_lo);
+    if (e != b->total_half8) return pfail(QR_E_STATE, "qr_policy_bank_set: internal packing size mismatch");
+    if (hipSetDevice(b->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");   // a launch may still read the slot
+    const size_t off = (size_t)slot * b->total_half8;
+    if (hipMemcpy(b->d_weights + off, img.data(), img.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_weights_lo + off, img_lo.data(), img_lo.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess) {
+        b->is_set[(size_t)slot] = 0;
+        return pfail(QR_E_HIP, "qr_policy_bank_set: upload failed");
+    }
+    b->is_set[(size_t)slot] = 1;
     return QR_OK;
 }
 

@@ -8,6 +8,13 @@ detection and the lap accounting stay on the device, one 24-int record (+ one 4-
     r = evaluate_policy(model, eval_env, n_eval_steps=2000, window_steps=1200, seed=99)
     r["window"]["crashes_per_window"], r["total"]["first_lap_seconds"], r["total"]["flying_lap_seconds"]
 
+Many policies -- the checkpoints of a run, the seeds of a sweep -- are evaluated `env.num_envs // envs_per_policy` at a time in ONE launch
+(`qr_evaluate_policy_bank`, csrc/quadrace_eval_bank.hip), every one of them on the same starts, disturbances and restarts:
+
+    from optimal_quad_control_rl_amd import evaluate_policies, rank_policies
+    results = evaluate_policies(["run/model_10.zip", "run/model_20.zip", model], eval_env, envs_per_policy=256, seed=0)
+    best = rank_policies(results)[0]
+
 All times inside the records are integer step counts; seconds appear only here (steps x env.dt).
 """
 import math
@@ -110,3 +117,110 @@ def evaluate_policy(model, env, n_eval_steps=2000, window_steps=1200, gates_per_
         torch.cuda.current_stream(core.device).synchronize()
         policy.close()
     return {"window": window, "total": total}
+
+
+def plan_policy_batches(num_policies, slots):
+    """How evaluate_policies spreads `num_policies` policies over launches of `slots` policies each: a list of batches, each a list of
+    exactly `slots` policy indices.  The last batch is padded by repeating its last policy (a launch always flies every group of the
+    env); `kept` = how many leading slots of the batch are real.  Returns [(indices, kept), ...]; pure arithmetic, no device."""
+    num_policies, slots = int(num_policies), int(slots)
+    if num_policies < 1:
+        raise ValueError("need at least one policy")
+    if slots < 1:
+        raise ValueError("the env holds no complete group: num_envs < envs_per_policy")
+    plan = []
+    for first in range(0, num_policies, slots):
+        real = list(range(first, min(first + slots, num_policies)))
+        plan.append((real + [real[-1]] * (slots - len(real)), len(real)))
+    return plan
+
+
+def _as_actor(entry):
+    """(torch actor, model or None) of one entry of evaluate_policies: a checkpoint path written by `model.save`, an SB3-shaped PPO,
+    a native trainer, or a bare torch actor (Linear, ReLU, ..., Linear)."""
+    import os
+
+    import torch
+
+    if isinstance(entry, (str, os.PathLike)):
+        from .sb3 import PPO
+
+        entry = PPO.load(os.fspath(entry))   # needs no env
+    if isinstance(entry, torch.nn.Module) and not hasattr(entry, "pi") and not hasattr(entry, "net"):
+        return entry, None
+    return _actor(entry), entry
+
+
+def evaluate_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, window_steps=1200, gates_per_lap=None, precision=None, seed=0):
+    """evaluate_policy for a LIST of policies, `env.num_envs // envs_per_policy` of them per launch (qr_evaluate_policy_bank): policy p
+    of a batch flies envs [p E, (p + 1) E) of `env`.  Every batch starts from `seed(seed); reset_device(); share_starts(E)` and the
+    kernel keys restarts by the env's index within its group, so ALL policies -- within a batch and across batches -- see bit-identical
+    starts, disturbances and restarts for as long as their own flying allows, the ones an E-env handle sees under
+    evaluate_policy(..., seed=seed).  Entries: a checkpoint path written by `model.save` (loaded with PPO.load), an SB3-shaped PPO, a
+    native trainer, or a torch actor.  envs_per_policy: a multiple of 256; env.num_envs must be a multiple of it.  precision: None =
+    "f32" if any model collects in f32, else "f16-operands" (one launch has one precision).  Returns one {"window", "total"} dict per
+    policy, in order, each what evaluate_policy returns for that policy on an E-env handle."""
+    import torch
+
+    from .policy import MfmaPolicyBank
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    E, n = int(envs_per_policy), core.num_envs
+    if E < 256 or E % 256 != 0:
+        raise ValueError("envs_per_policy must be a multiple of 256 (one workgroup serves one policy)")
+    if n % E != 0:
+        raise ValueError("env.num_envs must be a multiple of envs_per_policy")
+    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
+    if not 1 <= window_steps <= n_eval_steps:
+        raise ValueError("need 1 <= window_steps <= n_eval_steps")
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for _, m in actors)
+        precision = "f32" if f32 else "f16-operands"
+    gpl = default_gates_per_lap(core) if gates_per_lap is None else int(gates_per_lap)
+    slots = n // E
+    results = [None] * len(actors)
+    bank = MfmaPolicyBank(core.state_len, slots, core.device.index)
+    try:
+        for indices, kept in plan_policy_batches(len(actors), slots):
+            for slot, idx in enumerate(indices):
+                bank.load_torch(slot, actors[idx][0])
+            core.seed(seed)
+            core.reset_device()
+            core.share_starts(E)
+            rec = torch.zeros((n, REC_INTS), dtype=torch.int32, device=core.device)
+            recf = torch.zeros((n, REC_FLOATS), dtype=torch.float32, device=core.device)
+            core.evaluate_bank_device(bank, slots, E, window_steps, gpl, rec, recf, precision=precision)
+            windows = []
+            for slot in range(kept):
+                w = summarize_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt, gpl)
+                w["crashes_per_window"], w["gates_per_window"] = w["crashes_per_env"], w["gates_per_env"]
+                windows.append(w)
+            if n_eval_steps > window_steps:
+                core.evaluate_bank_device(bank, slots, E, n_eval_steps - window_steps, gpl, rec, recf, precision=precision)
+            for slot in range(kept):
+                total = summarize_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt, gpl)
+                results[indices[slot]] = {"window": windows[slot], "total": total}
+    finally:
+        torch.cuda.current_stream(core.device).synchronize()
+        bank.close()
+    return results
+
+
+def rank_policies(results, max_crashes_per_window=0.1):
+    """Indices of `results` (evaluate_policies / evaluate_policy dicts), best first.  First the policies that crash at most
+    `max_crashes_per_window` times per env and window AND have a flying lap, by flying-lap time (ties: fewer crashes, then the
+    index); then everything else -- no flying lap, or over the crash bound -- by crash rate (ties: the index).  0.1 crashes per 12 s
+    window is the band the project states for a policy worth keeping."""
+    def crashes(r):
+        return float(r["window"]["crashes_per_window"])
+
+    def fly(r):
+        return r["total"]["flying_lap_seconds"]
+
+    good = [i for i, r in enumerate(results) if fly(r) is not None and crashes(r) <= max_crashes_per_window]
+    rest = [i for i in range(len(results)) if i not in set(good)]
+    good.sort(key=lambda i: (fly(results[i]), crashes(results[i]), i))
+    rest.sort(key=lambda i: (crashes(results[i]), i))
+    return good + rest

@@ -649,6 +649,39 @@ class Quadcopter3DGates(_Base):
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return rec, recf
 
+    def evaluate_bank_device(self, bank, num_policies, envs_per_policy, num_steps, gates_per_lap, rec, recf=None, precision="f16-operands"):
+        """A bank of policies in ONE kernel (qr_evaluate_policy_bank): slot p of `bank` (policy.MfmaPolicyBank), p < num_policies, flies
+        envs [p E, (p + 1) E), E = envs_per_policy (a multiple of 256; num_policies * E == num_envs), with the evaluator's accounting.
+        Records as in evaluate_device: rows [p E, (p + 1) E) of `rec` [N, 24] / `recf` [N, 4] belong to policy p.  Inside this call an env
+        that ends its episode restarts from the reset stream of its index WITHIN its group, so groups that start equal (share_starts)
+        see the same starts, disturbances and restarts; every other call on this env resets with the ordinary ids.  Returns (rec, recf)."""
+        if precision not in ("f16-operands", "f32"):
+            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        fn = _lib.require(self._L, "qr_evaluate_policy_bank")
+        n = self.num_envs
+        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
+        if recf is not None:
+            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        _lib.check(fn(self._h, bank._h, int(num_policies), int(envs_per_policy), int(num_steps), int(gates_per_lap),
+                      2 if precision == "f32" else 0, _ptr(rec), _ptr(recf), self._stream()))
+        self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
+        return rec, recf
+
+    def share_starts(self, envs_per_policy):
+        """Copy the full state (world, disturbances, target, steps, episode) of envs [0, E) onto every following group of E envs
+        (E = envs_per_policy divides num_envs).  After `seed(s); reset_device(); share_starts(E)` every group is bit-equal to an E-env
+        handle after `seed(s); reset_device()`: the common starts evaluate_bank_device's group-local reset stream continues from."""
+        e, n = int(envs_per_policy), self.num_envs
+        if e < 1 or n % e != 0:
+            raise ValueError("envs_per_policy must divide num_envs")
+        reps = n // e
+        if reps > 1:
+            world, dist, target, steps, episode = self.get_state_tensors()
+            tile = lambda t: None if t is None else t[:e].repeat((reps,) + (1,) * (t.dim() - 1)).contiguous()
+            self.set_state_tensors(tile(world), tile(dist), tile(target), tile(steps), tile(episode))
+        self.update_states()
+        return self
+
     RECORD_EXTRA = 8   # QR_RECORD_EXTRA of include/quadrace.h
 
     def record_policy_device(self, policy, num_steps, log_std, noise_seed=0, first_step=0, deterministic=True, rec_envs=None, out=None,

@@ -1,0 +1,360 @@
+"""GPU: the bank evaluator (qr_evaluate_policy_bank, eval_policy_bank_kernel<V, GA, kF32>) against the single-policy evaluator
+(qr_evaluate_policy), which tests/test_gpu_evaluate.py already pins to tests/eval_spec.py.  Slot p of a bank launch on P x E envs must
+equal an E-env twin handle (same seed, track, limits, disturbance ranges) flown by evaluate_device with the same weights in an
+MfmaPolicy: integer records equal, float records bit-equal, the five state tensors bit-equal.  No tolerance anywhere.  Non-vacuity is
+asserted on the twins' own data (eval_spec.nonvacuous_*), so a comparison of nothing with nothing fails instead of passing."""
+import ctypes as C
+import statistics
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import eval_spec as S
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -77777.0
+SC = S.SCENARIO
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _env(variant, n, gates_ahead, seed=SC["seed"], track=None, max_steps=SC["max_steps"]):
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES
+
+    trk = S.scenario_track() if track is None else track
+    if variant == "e2e":
+        env = Quadcopter3DGates(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")   # residual MLPs: the default
+        env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    else:
+        env = Quadcopter3DGatesINDI(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")
+    env.max_steps = max_steps
+    env.reset_device()
+    return env
+
+
+def _constant_layers(obs_len, action):
+    """zero weights and an output bias: the action does not depend on the observation"""
+    z = np.zeros
+    return [(z((120, obs_len), np.float32), z(120, np.float32)), (z((120, 120), np.float32), z(120, np.float32)),
+            (z((120, 120), np.float32), z(120, np.float32)), (z((4, 120), np.float32), np.asarray(action, np.float32))]
+
+
+def _closed_loop_layers(obs_len, action, seed=3, gain=5.0):
+    """seeded random weights around `action`: every action depends on the observation the kernel fed to its forward"""
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    torch.manual_seed(seed)
+    net = ActorCritic(obs_len, 4)
+    with torch.no_grad():
+        net.pi[-1].weight.mul_(gain)
+        net.pi[-1].bias.copy_(torch.as_tensor(action, dtype=torch.float32))
+    return [(m.weight.detach().clone(), m.bias.detach().clone()) for m in net.pi if isinstance(m, torch.nn.Linear)]
+
+
+def _four_policies(variant, obs_len):
+    """slot 0: the scenario's constant action; 1: seeded closed loop around it; 2: another constant action; 3: another seeded closed loop"""
+    act = np.asarray(SC[variant + "_action"], np.float32)
+    other = act * np.float32(0.75) + np.asarray([0.02, -0.01, 0.01, 0.03], np.float32)
+    return [_constant_layers(obs_len, act), _closed_loop_layers(obs_len, act, seed=3), _constant_layers(obs_len, other),
+            _closed_loop_layers(obs_len, other, seed=4)]
+
+
+def _records(env):
+    return (torch.zeros((env.num_envs, S.REC_INTS), dtype=torch.int32, device=env.device),
+            torch.zeros((env.num_envs, S.REC_FLOATS), dtype=torch.float32, device=env.device))
+
+
+def _bank(obs_len, layer_sets, capacity=None):
+    from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
+
+    bank = MfmaPolicyBank(obs_len, capacity or len(layer_sets))
+    for slot, layers in enumerate(layer_sets):
+        bank.set_weights(slot, layers)
+    return bank
+
+
+def _slot_equals(env_state, twin, lo, hi, what):
+    for name, x, y in zip(("world", "disturbances", "target", "steps", "episode"), env_state, twin.get_state_tensors()):
+        assert x is None or torch.equal(x[lo:hi], y), (what, name)
+
+
+_CASES = [(v, g, e, p) for v in ("e2e", "indi") for g in (0, 1) for e in (256, 1024) for p in ("f16-operands", "f32")]
+
+
+@pytest.mark.parametrize("variant,gates_ahead,E,precision", _CASES, ids=["%s-ga%d-E%d-%s" % c for c in _CASES])
+def test_every_slot_equals_a_standalone_evaluation(variant, gates_ahead, E, precision):
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+
+    K, gpl, P = SC["steps"], SC[variant + "_gates_per_lap"], 4
+    env = _env(variant, P * E, gates_ahead)
+    env.share_starts(E)
+    sets = _four_policies(variant, env.state_len)
+    bank = _bank(env.state_len, sets)
+    start = env.get_state_tensors()
+    rec, recf = _records(env)
+    env.evaluate_bank_device(bank, P, E, K, gpl, rec, recf, precision=precision)
+    assert bool((rec[:, 22:] == 0).all()) and bool((recf[:, 3] == 0).all()) and bool((rec[:, 5] == K).all())
+    after = env.get_state_tensors()
+    obs_after = env.states_tensor.clone()
+    passes = []
+    for p in range(P):
+        twin = _env(variant, E, gates_ahead)
+        _slot_equals(start, twin, p * E, (p + 1) * E, "share_starts, slot %d" % p)     # every group starts as an E-env handle does
+        pol = MfmaPolicy(twin.state_len).set_weights(sets[p])
+        trec, trecf = _records(twin)
+        twin.evaluate_device(pol, K, gpl, trec, trecf, precision=precision)
+        srec = trec.cpu().numpy()
+        if p == 0:
+            nv = S.nonvacuous_e2e(srec) if variant == "e2e" else S.nonvacuous_indi(srec)
+            print(variant, gates_ahead, E, precision, nv)
+            assert nv["ok"], nv
+        passes.append(int(srec[:, 0].sum()))
+        lo, hi = p * E, (p + 1) * E
+        assert torch.equal(rec[lo:hi], trec), ("integer records", p, int((rec[lo:hi] != trec).any(dim=1).sum()))
+        assert torch.equal(recf[lo:hi].view(torch.int32), trecf.view(torch.int32)), ("float records", p)
+        _slot_equals(after, twin, lo, hi, "slot %d" % p)
+        assert torch.equal(obs_after[lo:hi], twin.states_tensor), ("observation buffer", p)   # the wrapper refreshed its buffer
+        twin.close(); pol.close()
+    print("gate passes per slot", passes)
+    assert len(set(passes)) >= 2, passes                       # the policies do fly differently
+    env.close(); bank.close()
+
+
+@pytest.mark.parametrize("variant", ["e2e", "indi"])
+@pytest.mark.parametrize("precision", ["f16-operands", "f32"])
+def test_equal_weights_fly_equal_flights(variant, precision):
+    """Common random numbers: two slots with the same weights are bit-identical, restarts included."""
+    K, gpl, P, E = SC["steps"], SC[variant + "_gates_per_lap"], 4, 512
+    env = _env(variant, P * E, 1)
+    env.share_starts(E)
+    sets = _four_policies(variant, env.state_len)
+    bank = _bank(env.state_len, [sets[0], sets[1], sets[0], sets[1]])
+    rec, recf = _records(env)
+    env.evaluate_bank_device(bank, P, E, K, gpl, rec, recf, precision=precision)
+    st = env.get_state_tensors()
+    for a, b in ((0, 2), (1, 3)):
+        ra, rb = rec[a * E:(a + 1) * E], rec[b * E:(b + 1) * E]
+        ends = int(ra[:, 1].sum() + ra[:, 2].sum())
+        print(variant, precision, "slots", a, b, "crashes", int(ra[:, 1].sum()), "time-limit ends", int(ra[:, 2].sum()))
+        assert ends > 0                                         # the groups did restart: the reset stream is part of the comparison
+        assert torch.equal(ra, rb)
+        assert torch.equal(recf[a * E:(a + 1) * E].view(torch.int32), recf[b * E:(b + 1) * E].view(torch.int32))
+        for x in st:
+            assert x is None or torch.equal(x[a * E:(a + 1) * E], x[b * E:(b + 1) * E])
+    assert not torch.equal(rec[0:E], rec[E:2 * E])             # different weights: different flights
+    env.close(); bank.close()
+
+
+@pytest.mark.parametrize("variant", ["e2e", "indi"])
+def test_one_bank_call_equals_two_with_the_records_carried_over(variant):
+    gpl, P, E = SC[variant + "_gates_per_lap"], 4, 256
+    a, b = _env(variant, P * E, 1), _env(variant, P * E, 1)
+    a.share_starts(E); b.share_starts(E)
+    bank = _bank(a.state_len, _four_policies(variant, a.state_len))
+    ra, rfa = _records(a)
+    rb, rfb = _records(b)
+    a.evaluate_bank_device(bank, P, E, 600, gpl, ra, rfa)
+    b.evaluate_bank_device(bank, P, E, 250, gpl, rb, rfb)
+    first = rb.clone()
+    b.evaluate_bank_device(bank, P, E, 350, gpl, rb, rfb)
+    assert bool((first[:, 5] == 250).all()) and int(ra[:, 14:22].sum()) > int(first[:, 14:22].sum()) > 0
+    assert torch.equal(ra, rb) and torch.equal(rfa.view(torch.int32), rfb.view(torch.int32))
+    for x, y in zip(a.get_state_tensors(), b.get_state_tensors()):
+        assert x is None or torch.equal(x, y)
+    a.close(); b.close(); bank.close()
+
+
+def test_bank_refusals_launch_nothing():
+    from optimal_quad_control_rl_amd import _lib
+    from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
+
+    P, E, K = 2, 256, 8
+    n = P * E
+    env = _env("indi", n, 1)
+    L = env._L
+    sets = _four_policies("indi", env.state_len)
+    bank = _bank(env.state_len, sets[:3], capacity=4)           # slots 0..2 set, slot 3 never set
+    assert L.qr_policy_bank_capacity(bank._h) == 4
+    rec = torch.full((n, S.REC_INTS), 7, dtype=torch.int32, device=env.device)
+    recf = torch.full((n, S.REC_FLOATS), SENTINEL, dtype=torch.float32, device=env.device)
+    before = env.get_state_tensors()
+
+    def call(e=env, b=bank, p=P, epp=E, k=K, gpl=2, flags=0, r=rec, rf=recf):
+        return L.qr_evaluate_policy_bank(e._h, b._h if b is not None else None, p, epp, k, gpl, flags, _ptr(r), _ptr(rf), e._stream())
+
+    def refused(code, **kw):
+        rc = call(**kw)
+        assert rc == code, (list(kw.keys()), rc, L.qr_last_error())
+        assert len(L.qr_last_error()) > 0 and L.qr_policy_last_error() == L.qr_last_error()
+        torch.cuda.synchronize()
+        assert bool((rec == 7).all()) and bool((recf == SENTINEL).all())
+        for x, y in zip(before, env.get_state_tensors()):
+            assert x is None or torch.equal(x, y)
+
+    # everything qr_evaluate_policy refuses
+    refused(_lib.QR_E_INVALID, r=None)
+    refused(_lib.QR_E_INVALID, k=0)
+    refused(_lib.QR_E_INVALID, k=-3)
+    refused(_lib.QR_E_INVALID, gpl=0)
+    refused(_lib.QR_E_INVALID, flags=1)
+    refused(_lib.QR_E_INVALID, flags=4)
+    refused(_lib.QR_E_INVALID, flags=2 | 8)
+    refused(_lib.QR_E_INVALID, b=None)
+    big = torch.full((n * S.REC_INTS + 4,), 7, dtype=torch.int32, device=env.device)
+    bigf = torch.full((n * S.REC_FLOATS + 4,), SENTINEL, dtype=torch.float32, device=env.device)
+    refused(_lib.QR_E_INVALID, r=big[1:])
+    refused(_lib.QR_E_INVALID, rf=bigf[2:])
+    assert bool((big == 7).all()) and bool((bigf == SENTINEL).all())
+    env.pause = True
+    refused(_lib.QR_E_STATE)
+    env.pause = False
+    env.pause_if_collision = True
+    refused(_lib.QR_E_STATE)
+    env.pause_if_collision = False
+    # the bank's own refusals
+    refused(_lib.QR_E_INVALID, p=0)
+    refused(_lib.QR_E_INVALID, p=-1)
+    refused(_lib.QR_E_INVALID, p=5, epp=256)                    # > capacity
+    refused(_lib.QR_E_INVALID, epp=0)
+    refused(_lib.QR_E_INVALID, epp=128, p=4)                    # < 256 (4 x 128 == n)
+    refused(_lib.QR_E_INVALID, epp=384)                         # not a multiple of 256
+    refused(_lib.QR_E_INVALID, p=1, epp=256)                    # P E != n
+    refused(_lib.QR_E_INVALID, p=3, epp=256)
+    refused(_lib.QR_E_INVALID, p=1, epp=1024)
+    other_len = MfmaPolicyBank(env.state_len + 4, 2)
+    refused(_lib.QR_E_INVALID, b=other_len)
+    other_len.close()
+    # a slot in [0, num_policies) that was never set: 4 x 256 on a 1024-env handle, slot 3 unset
+    env4 = _env("indi", 4 * 256, 1)
+    before4 = env4.get_state_tensors()
+    rec4 = torch.full((4 * 256, S.REC_INTS), 7, dtype=torch.int32, device=env.device)
+    rc = call(e=env4, p=4, epp=256, r=rec4, rf=None)
+    assert rc == _lib.QR_E_STATE and b"slot 3" in L.qr_last_error(), (rc, L.qr_last_error())
+    torch.cuda.synchronize()
+    assert bool((rec4 == 7).all())
+    for x, y in zip(before4, env4.get_state_tensors()):
+        assert x is None or torch.equal(x, y)
+    empty = MfmaPolicyBank(env.state_len, 2)
+    refused(_lib.QR_E_STATE, b=empty)
+    empty.close()
+    # bank_set refuses a slot outside [0, capacity)
+    with pytest.raises(_lib.QuadraceError):
+        bank.set_weights(4, sets[0])
+    with pytest.raises(_lib.QuadraceError):
+        bank.set_weights(-1, sets[0])
+    # a track with one gate: a pass cannot move the target
+    gp, gy, sp = S.scenario_track()
+    one = _env("indi", n, 1, track=(gp[:1], gy[:1], sp))
+    rc = call(e=one)
+    assert rc == _lib.QR_E_INVALID and b"one gate" in L.qr_last_error()
+    torch.cuda.synchronize()
+    assert bool((rec == 7).all()) and bool((recf == SENTINEL).all())
+    one.close()
+    # ... and a valid call runs, reports its time, and leaves a registered terminal-observation buffer alone
+    env.max_steps = 5
+    tb = torch.full((K, n, env.state_len), SENTINEL, device=env.device)
+    env.set_terminal_obs_buffer(tb)
+    rec.zero_(); recf.zero_()
+    assert call(flags=2) == _lib.QR_OK and call(rf=None) == _lib.QR_OK
+    torch.cuda.synchronize()
+    assert bool((tb == SENTINEL).all())
+    assert bool((rec[:, 5] == 2 * K).all()) and int(rec[:, 2].sum()) >= n
+    assert env.last_rollout_ms() > 0.0           # qr_last_step_many_ms reports the launch
+    env.close(); env4.close(); bank.close()
+
+
+def test_python_evaluate_policies_equals_per_policy_evaluation(tmp_path):
+    """A list longer than one batch (6 policies, 4 slots: the second batch is padded), mixing a saved checkpoint path, a PPO object and
+    bare actors, equals evaluate_policy on E-env twins with the same seed, dict for dict."""
+    from optimal_quad_control_rl_amd import (PPO, Quadcopter3DGates, TRAIN_DISTURBANCE_RANGES, VecMonitor, evaluate_policies, evaluate_policy,
+                                             rank_policies, square_track)
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    trk = square_track()
+    train = VecMonitor(Quadcopter3DGates(256, *trk, gates_ahead=1, seed=1))
+    train.venv.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    model = PPO("MlpPolicy", train, policy_kwargs=dict(activation_fn=torch.nn.ReLU, net_arch=[dict(pi=[120] * 3, vf=[120] * 3)], log_std_init=0),
+                n_steps=8, batch_size=256, n_epochs=1, seed=3)
+    with torch.no_grad():
+        model._net.pi[-1].bias.copy_(torch.tensor([0.25, 0.2, 0.25, 0.2]))   # untrained, but not falling straight down
+    path = model.save(str(tmp_path / "ckpt_a"))
+    with torch.no_grad():                                                     # the live model moves on after the checkpoint
+        model._net.pi[-1].bias.copy_(torch.tensor([0.3, 0.3, 0.3, 0.3]))
+
+    def actor(seed, bias):
+        torch.manual_seed(seed)
+        net = ActorCritic(train.venv.state_len, 4)
+        with torch.no_grad():
+            net.pi[-1].bias.copy_(torch.tensor(bias))
+        return net.pi
+
+    entries = [path, model, actor(5, [0.2, 0.25, 0.2, 0.25]), actor(6, [0.35, 0.3, 0.35, 0.3]), path, actor(7, [0.1, 0.1, 0.1, 0.1])]
+    E, K, W, seed = 256, 600, 250, 99
+    ev = VecMonitor(_env("e2e", 4 * E, 1, seed=1, track=trk))
+    res = evaluate_policies(entries, ev, envs_per_policy=E, n_eval_steps=K, window_steps=W, seed=seed)
+    assert len(res) == len(entries)
+    twin = _env("e2e", E, 1, seed=1, track=trk)
+    for i, entry in enumerate(entries):
+        if isinstance(entry, str):
+            m = PPO.load(entry)
+        elif isinstance(entry, torch.nn.Module):
+            m = types.SimpleNamespace(_net=types.SimpleNamespace(pi=entry))
+        else:
+            m = entry
+        want = evaluate_policy(m, twin, n_eval_steps=K, window_steps=W, seed=seed, precision="f16-operands")
+        print(i, res[i]["window"]["crashes_per_window"], res[i]["total"]["first_lap_seconds"], res[i]["total"]["flying_lap_seconds"])
+        assert want["total"]["steps"] == K and want["window"]["steps"] == W and want["total"]["envs"] == E
+        assert res[i] == want, i
+    assert res[0] == res[4] and res[0] != res[1]                 # the same checkpoint twice, in different batches; the model moved on
+    assert sum(r["total"]["episodes"] for r in res) > 0
+    order = rank_policies(res)
+    assert sorted(order) == list(range(len(entries)))
+    ev.venv.close(); twin.close(); train.venv.close()
+
+
+def test_bank_not_slower_than_the_single_evaluator():
+    """The per-step work of a bank workgroup is the single evaluator's; only the once-per-launch staging differs.  Protocol of
+    test_not_slower_than_the_rollout_kernel: N = 65 536, K = 2 000, E2E + residual MLPs + training disturbances, square track; the bank
+    holds 256 copies of one seeded network (E = 256), so both launches fly the same network from the same seeded start; alternating
+    launches, one warm-up pair, median of 5, times from qr_last_step_many_ms.  f16 operands: bank <= 1.03 x single (3 % = the
+    run-to-run spread DESIGN section 5 states for these kernels).  precision="f32": the ratio is printed WITHOUT a bound (the low-piece
+    images of 256 policies no longer share cache lines; nobody has measured what that costs)."""
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, TRAIN_DISTURBANCE_RANGES, square_track
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    n, K, E = 65536, 2000, 256
+    P = n // E
+    env = Quadcopter3DGates(n, *square_track(), gates_ahead=1, infos_mode="none", seed=99)
+    env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    env.max_steps = 10 ** 6
+    torch.manual_seed(0)
+    pi = ActorCritic(env.state_len, 4).pi
+    pol = MfmaPolicy(env.state_len).load_torch(pi)
+    layers = [(m.weight, m.bias) for m in pi if isinstance(m, torch.nn.Linear)]
+    bank = _bank(env.state_len, [layers] * P)
+    rec, recf = _records(env)
+    medians = {}
+    for precision in ("f16-operands", "f32"):
+        t_bank, t_single = [], []
+        for rep in range(6):
+            env.seed(99); env.reset_device(); rec.zero_(); recf.zero_()
+            env.evaluate_bank_device(bank, P, E, K, 4, rec, recf, precision=precision)
+            ms_b = env.last_rollout_ms()
+            env.seed(99); env.reset_device(); rec.zero_(); recf.zero_()
+            env.evaluate_device(pol, K, 4, rec, recf, precision=precision)
+            ms_s = env.last_rollout_ms()
+            if rep:
+                t_bank.append(ms_b * 1e3 / K); t_single.append(ms_s * 1e3 / K)
+        mb, ms = statistics.median(t_bank), statistics.median(t_single)
+        medians[precision] = (mb, ms)
+        print("%s: qr_evaluate_policy_bank %s -> median %.4f us/step; qr_evaluate_policy %s -> median %.4f us/step; ratio %.4f"
+              % (precision, ["%.4f" % t for t in t_bank], mb, ["%.4f" % t for t in t_single], ms, mb / ms))
+    env.close(); pol.close(); bank.close()
+    mb, ms = medians["f16-operands"]
+    assert mb <= 1.03 * ms, (mb, ms, mb / ms)
