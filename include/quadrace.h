@@ -51,7 +51,8 @@ extern "C" {
 
 #define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
                              qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
-                             qr_policy_bank_* / qr_evaluate_policy_bank (round 10) */
+                             qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
+                             qr_condition_bank_* / qr_evaluate_policy_grid (round 11) */
 
 enum {
     QR_OK = 0,
@@ -275,6 +276,48 @@ int qr_policy_bank_set(qr_policy_bank* bank, int32_t slot, const float* w1, cons
 int qr_evaluate_policy_bank(qr_env* env, qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy,
                             int32_t num_steps, int32_t gates_per_lap, int32_t flags,
                             int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Evaluation of a GRID of policies x flight CONDITIONS in one launch: "how does this policy hold up when the conditions are not the ones
+ * it trained under?" (other disturbance ranges or scale, another track or start, another time limit) is one call instead of one
+ * reconfigured handle per condition, and every cell draws the same random numbers.
+ * A condition is what qr_set_track + qr_set_disturbance + the max_steps of qr_set_limits configure on a handle, plus the lap length
+ * gates_per_lap.  A condition bank owns one device array [capacity][image]; qr_condition_bank_set fills slot `slot` in [0, capacity)
+ * from HOST arrays with the argument layout of those setters: gate_pos [num_gates][3], gate_yaw [num_gates], start_pos [3], dist_ranges
+ * [6][2] (lo, hi) or NULL, dist_scale.  The slot's image is a header of the per-condition scalars (num_gates, max_steps, gates_per_lap,
+ * the observation scaling of the disturbances) followed by [reset table | gate rows], byte for byte what a handle of the bank's variant
+ * holds after the three setters with the same values: the handle and the bank build it with the same host functions.  dist_ranges NULL
+ * stands for a handle on which qr_set_disturbance was never called (all-zero ranges, scale 1; dist_scale is ignored); for the INDI
+ * variant, which has no disturbances, it must be NULL.  qr_condition_bank_set synchronises the device first, like the setters.
+ * QR_E_INVALID: NULL bank or track array, slot outside [0, capacity), num_gates outside 2..QR_MAX_GATES (the evaluators need two gates),
+ * gates_per_lap < 1, dist_ranges given for INDI.
+ * qr_evaluate_policy_grid: group g in [0, num_groups) = envs [g E, (g + 1) E) of the handle, E = envs_per_group, flies slot
+ * policy_of_group[g] of `policies` under slot condition_of_group[g] of `conditions` (two HOST int32 arrays of num_groups entries, any
+ * order, repeats allowed).  A 256-env workgroup stages the weight image of ITS policy and the table image of ITS condition; num_gates,
+ * max_steps, the observation scaling and gates_per_lap are the condition's.  The residual weights, dt, pause flags and gates_ahead stay
+ * the handle's, and the handle's own track / disturbance / max_steps configuration is not used by this call.  Records have the layout
+ * and the continue-a-call behaviour of qr_evaluate_policy (rows [g E, (g + 1) E) belong to group g); restarts use the GROUP-LOCAL RESET
+ * STREAM of qr_evaluate_policy_bank (env id env_id_base + (i mod E)).
+ * CONTRACT: group g flies bit for bit (records and the env state afterwards) what an E-env handle flies under qr_evaluate_policy with
+ * the weights of policy policy_of_group[g] and that condition's gates_per_lap, when that handle has been configured by qr_set_track,
+ * qr_set_disturbance (not called where the condition's dist_ranges is NULL) and qr_set_limits with the values of condition
+ * condition_of_group[g], has the same seed, env_id_base, variant, gates_ahead, residual weights and dt, and starts from the same state.
+ * Every cell of a policies x conditions grid therefore sees the same uniform draws; only the condition's own scaling of them differs.
+ * The two maps are validated on the host -- no index reaches the device unchecked -- and copied to a device array the handle owns; a
+ * map that differs from the previous call's is copied after a device synchronisation (an earlier launch may still read the array).
+ * Refused before anything is launched or copied (qr_last_error set, records and state untouched): everything qr_evaluate_policy_bank
+ * refuses, with envs_per_group in the role of envs_per_policy (num_groups < 1, num_groups * envs_per_group != qr_num_envs(env), ...);
+ * QR_E_INVALID: NULL condition bank or map array, an index outside its bank's capacity, a condition bank of another variant or device;
+ * QR_E_STATE: a referenced slot of either bank that was never set, or a new map while `stream` is being captured.
+ * qr_last_step_many_ms() reports this launch too. */
+typedef struct qr_condition_bank qr_condition_bank;
+int qr_condition_bank_create(int32_t variant, int32_t device, int32_t capacity, qr_condition_bank** out);
+int qr_condition_bank_destroy(qr_condition_bank* bank);
+int qr_condition_bank_capacity(const qr_condition_bank* bank);
+int qr_condition_bank_set(qr_condition_bank* bank, int32_t slot, const float* gate_pos, const float* gate_yaw, int32_t num_gates,
+                          const float* start_pos, const float* dist_ranges, float dist_scale, int32_t max_steps, int32_t gates_per_lap);
+int qr_evaluate_policy_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups,
+                            int32_t envs_per_group, const int32_t* policy_of_group, const int32_t* condition_of_group,
+                            int32_t num_steps, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* Closed-loop FLIGHT RECORDER: the K steps of qr_rollout_policy (same policy forward, same action noise keyed by (noise_seed, global env id,
  * first_step + t), same env arithmetic and reset stream: the env state afterwards is bit-identical to qr_rollout_policy with the same

@@ -8,7 +8,8 @@ from .tracks import TRAIN_DISTURBANCE_RANGES, square_track, zigzag_track  # noqa
 
 __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square_track", "TRAIN_DISTURBANCE_RANGES",
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
-           "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank"]
+           "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
+           "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -24,7 +25,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import sb3
 
         return getattr(sb3, name)
-    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
+    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
         from . import evaluation
 
         return getattr(evaluation, name)
@@ -32,6 +33,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import recording
 
         return getattr(recording, name)
+    if name in ("Condition", "ConditionBank", "disturbance_sweep"):  # flight conditions of the grid evaluator (qr_condition_bank_*)
+        from . import conditions
+
+        return getattr(conditions, name)
     if name == "MfmaPolicyBank":  # a bank of policies for one-launch evaluation (qr_policy_bank_*, qr_evaluate_policy_bank)
         from . import policy
 

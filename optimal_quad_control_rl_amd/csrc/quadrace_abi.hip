@@ -41,20 +41,35 @@ struct qr_env {
         qr::Params P{};
     } sg;
     hipStream_t capture_stream = nullptr;
+    // qr_evaluate_policy_grid: the device copy of the last group map, [group_map_cap] (policy, condition), and its host mirror
+    int2* d_group_map = nullptr;
+    int group_map_cap = 0;
+    std::vector<int32_t> group_map_host;
+};
+
+// A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
+// [CondHeader | reset table | gate rows], built by the functions that build a handle's tables (condition_obs_scale,
+// gate_relative_table, build_condition_image below).
+struct qr_condition_bank {
+    int variant = 0, device = 0, capacity = 0;
+    float* d_slots = nullptr;
+    std::vector<uint8_t> is_set;   // per slot: qr_condition_bank_set has succeeded
 };
 
 namespace {
 
-// observation scaling of the constant disturbances (R:414-448): if min == max the range becomes (min-1, max+1)
-void update_obs_scale(qr_env* e) {
+// observation scaling of the constant disturbances (R:414-448): if min == max the range becomes (min-1, max+1).  Shared by the
+// handle (Params::obs_lo / obs_inv) and the header of a condition image.
+void condition_obs_scale(const float* dist_lo, const float* dist_hi, float* obs_lo, float* obs_inv) {
     static const int col[4] = {0, 1, 2, 5};
     for (int c = 0; c < 4; ++c) {
-        float lo = e->dist_lo[col[c]], hi = e->dist_hi[col[c]];
+        float lo = dist_lo[col[c]], hi = dist_hi[col[c]];
         if (lo == hi) { lo -= 1.0f; hi += 1.0f; }
-        e->P.obs_lo[c] = lo;
-        e->P.obs_inv[c] = 1.0f / (hi - lo);
+        obs_lo[c] = lo;
+        obs_inv[c] = 1.0f / (hi - lo);
     }
 }
+void update_obs_scale(qr_env* e) { condition_obs_scale(e->dist_lo, e->dist_hi, e->P.obs_lo, e->P.obs_inv); }
 
 thread_local std::string g_err;
 
@@ -80,43 +95,66 @@ namespace {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-int upload_tables(qr_env* e) {
-    const int gate_floats = e->num_gates * qr::kGateStride;
-    // device image: [MLP table | reset table | gate rows]
-    std::vector<float> host(qr::kOffGatesImage + gate_floats, 0.0f);
-    std::memcpy(host.data(), e->mlp_table, sizeof(e->mlp_table));
+// gate i expressed in the frame of gate i-1, looped track (R:307-319), float32 like the reference: pos_rel [G][3], yaw_rel [G]
+void gate_relative_table(const float* gate_pos, const float* gate_yaw, int G, float* pos_rel, float* yaw_rel) {
+    for (int i = 0; i < G; ++i) {
+        const int j = (i + G - 1) % G;
+        const float dx = gate_pos[3 * i + 0] - gate_pos[3 * j + 0];
+        const float dy = gate_pos[3 * i + 1] - gate_pos[3 * j + 1];
+        const float c = cosf(gate_yaw[j]), s = sinf(gate_yaw[j]);
+        volatile float cx = c * dx, sy = s * dy, sx = -s * dx, cy = c * dy;  // no host FMA contraction
+        pos_rel[3 * i + 0] = cx + sy;
+        pos_rel[3 * i + 1] = sx + cy;
+        pos_rel[3 * i + 2] = gate_pos[3 * i + 2] - gate_pos[3 * j + 2];
+        yaw_rel[i] = gate_yaw[i] - gate_yaw[j];
+    }
+}
+
+// The condition-dependent part of the device table image, [reset table | gate rows]: img[0 .. kResetTableFloats + G * kGateStride),
+// zero-filled by the caller.  What a handle holds from kOffResetImage on, and what a slot of a qr_condition_bank holds behind its header.
+void build_condition_image(int variant, const float* start, const float* dist_lo, const float* dist_hi, float dist_scale, int G,
+                           const float* gate_pos, const float* gate_yaw, const float* gate_pos_rel, const float* gate_yaw_rel, float* img) {
     // reset table rows (lo, hi - lo, add, mul): value = ((lo + (hi-lo)*u) + add) * mul   (R:455-489 / I:270-296)
-    float* R = host.data() + qr::kOffResetImage;
+    float* R = img;
     auto row = [&](int t, float lo, float hi, float add, float mul) {
         volatile float span = hi - lo;  // float32 subtraction, like the oracle / the reference's ranges
         R[4 * t + 0] = lo; R[4 * t + 1] = span; R[4 * t + 2] = add; R[4 * t + 3] = mul;
     };
     const float pi9 = 0.3490658503988659f, pi = 3.141592653589793f;
-    for (int t = 0; t < 3; ++t) row(t, -0.5f, 0.5f, e->start[t], 1.0f);
+    for (int t = 0; t < 3; ++t) row(t, -0.5f, 0.5f, start[t], 1.0f);
     for (int t = 3; t < 6; ++t) row(t, -0.5f, 0.5f, 0.0f, 1.0f);
     row(6, -pi9, pi9, 0.0f, 1.0f);
     row(7, -pi9, pi9, 0.0f, 1.0f);
     row(8, -pi, pi, 0.0f, 1.0f);
     for (int t = 9; t < 12; ++t) row(t, -0.1f, 0.1f, 0.0f, 1.0f);
-    if (e->cfg.variant == QR_VARIANT_E2E) {
+    if (variant == QR_VARIANT_E2E) {
         for (int t = 12; t < 16; ++t) row(t, -1.0f, 1.0f, 0.0f, 1.0f);
-        for (int k = 0; k < 6; ++k) row(16 + k, e->dist_lo[k], e->dist_hi[k], 0.0f, e->dist_scale);
+        for (int k = 0; k < 6; ++k) row(16 + k, dist_lo[k], dist_hi[k], 0.0f, dist_scale);
     } else {
         row(12, -0.1f, 0.1f, 0.0f, 1.0f);
     }
-    for (int g = 0; g < e->num_gates; ++g) {
-        float* grow = host.data() + qr::kOffGatesImage + g * qr::kGateStride;
-        grow[0] = e->gate_pos[3 * g + 0];
-        grow[1] = e->gate_pos[3 * g + 1];
-        grow[2] = e->gate_pos[3 * g + 2];
-        grow[3] = e->gate_yaw[g];
-        grow[4] = cosf(e->gate_yaw[g]);  // the reference evaluates np.cos/np.sin on the f32 yaw every step (R:372-375,528)
-        grow[5] = sinf(e->gate_yaw[g]);
-        grow[8] = e->gate_pos_rel[3 * g + 0];
-        grow[9] = e->gate_pos_rel[3 * g + 1];
-        grow[10] = e->gate_pos_rel[3 * g + 2];
-        grow[11] = e->gate_yaw_rel[g];
+    for (int g = 0; g < G; ++g) {
+        float* grow = img + qr::kResetTableFloats + g * qr::kGateStride;
+        grow[0] = gate_pos[3 * g + 0];
+        grow[1] = gate_pos[3 * g + 1];
+        grow[2] = gate_pos[3 * g + 2];
+        grow[3] = gate_yaw[g];
+        grow[4] = cosf(gate_yaw[g]);  // the reference evaluates np.cos/np.sin on the f32 yaw every step (R:372-375,528)
+        grow[5] = sinf(gate_yaw[g]);
+        grow[8] = gate_pos_rel[3 * g + 0];
+        grow[9] = gate_pos_rel[3 * g + 1];
+        grow[10] = gate_pos_rel[3 * g + 2];
+        grow[11] = gate_yaw_rel[g];
     }
+}
+
+int upload_tables(qr_env* e) {
+    const int gate_floats = e->num_gates * qr::kGateStride;
+    // device image: [MLP table | reset table | gate rows]
+    std::vector<float> host(qr::kOffGatesImage + gate_floats, 0.0f);
+    std::memcpy(host.data(), e->mlp_table, sizeof(e->mlp_table));
+    build_condition_image(e->cfg.variant, e->start, e->dist_lo, e->dist_hi, e->dist_scale, e->num_gates, e->gate_pos.data(), e->gate_yaw.data(),
+                          e->gate_pos_rel.data(), e->gate_yaw_rel.data(), host.data() + qr::kOffResetImage);
     QR_HIP(hipDeviceSynchronize());  // configuration setters are rare: do not race kernels still reading the table
     QR_HIP(hipMemcpy(e->d_tables, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     return QR_OK;
@@ -236,6 +274,7 @@ int qr_destroy(qr_env* e) {
     if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
     if (e->slab) (void)hipFree(e->slab);
     if (e->d_tables) (void)hipFree(e->d_tables);
+    if (e->d_group_map) (void)hipFree(e->d_group_map);
     delete e;
     return QR_OK;
 }
@@ -253,18 +292,7 @@ int qr_set_track(qr_env* e, const float* gate_pos, const float* gate_yaw, int32_
     e->gate_yaw.assign(gate_yaw, gate_yaw + G);
     e->gate_pos_rel.assign(3 * G, 0.0f);
     e->gate_yaw_rel.assign(G, 0.0f);
-    // gate i expressed in the frame of gate i-1, looped track (R:307-319), float32 like the reference
-    for (int i = 0; i < G; ++i) {
-        const int j = (i + G - 1) % G;
-        const float dx = gate_pos[3 * i + 0] - gate_pos[3 * j + 0];
-        const float dy = gate_pos[3 * i + 1] - gate_pos[3 * j + 1];
-        const float c = cosf(gate_yaw[j]), s = sinf(gate_yaw[j]);
-        volatile float cx = c * dx, sy = s * dy, sx = -s * dx, cy = c * dy;  // no host FMA contraction
-        e->gate_pos_rel[3 * i + 0] = cx + sy;
-        e->gate_pos_rel[3 * i + 1] = sx + cy;
-        e->gate_pos_rel[3 * i + 2] = gate_pos[3 * i + 2] - gate_pos[3 * j + 2];
-        e->gate_yaw_rel[i] = gate_yaw[i] - gate_yaw[j];
-    }
+    gate_relative_table(gate_pos, gate_yaw, G, e->gate_pos_rel.data(), e->gate_yaw_rel.data());
     for (int k = 0; k < 3; ++k) e->start[k] = start_pos[k];
     e->P.num_gates = G;
     e->has_track = true;
@@ -592,6 +620,157 @@ int qr_evaluate_policy_bank(qr_env* e, qr_policy_bank* bank, int32_t num_policie
     if (ev) QR_HIP(hipEventRecord(e->ev0, st));
     QR_HIP(qr::launch_eval_policy_bank(e->cfg.variant, e->P, qr::bank_weights(bank), qr::bank_weights_lo(bank), (flags & QR_ROLLOUT_F32CLASS) != 0,
                                        num_policies, envs_per_policy, K, gates_per_lap, rec_dev, recf_dev, st));
+    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
+    e->timing_valid = ev;
+    return QR_OK;
+}
+
+// ---- bank of flight conditions (qr_evaluate_policy_grid) ----
+int qr_condition_bank_create(int32_t variant, int32_t device, int32_t capacity, qr_condition_bank** out) {
+    if (!out) return fail(QR_E_INVALID, "qr_condition_bank_create: null output");
+    *out = nullptr;
+    if (variant != QR_VARIANT_E2E && variant != QR_VARIANT_INDI) return fail(QR_E_INVALID, "qr_condition_bank_create: unknown variant");
+    if (capacity < 1) return fail(QR_E_INVALID, "qr_condition_bank_create: capacity must be >= 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(QR_E_NO_DEVICE, "qr_condition_bank_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(QR_E_INVALID, "qr_condition_bank_create: bad device ordinal");
+    QR_HIP(hipSetDevice(device));
+    qr_condition_bank* b = new qr_condition_bank();
+    b->variant = variant;
+    b->device = device;
+    b->capacity = capacity;
+    b->is_set.assign((size_t)capacity, 0);
+    const size_t bytes = (size_t)capacity * qr::kCondSlotFloats * sizeof(float);
+    if (hipMalloc((void**)&b->d_slots, bytes) != hipSuccess) {
+        delete b;
+        return fail(QR_E_HIP, "qr_condition_bank_create: hipMalloc failed");
+    }
+    (void)hipMemset(b->d_slots, 0, bytes);
+    *out = b;
+    return QR_OK;
+}
+
+int qr_condition_bank_destroy(qr_condition_bank* b) {
+    if (!b) return QR_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    if (b->d_slots) (void)hipFree(b->d_slots);
+    delete b;
+    return QR_OK;
+}
+
+int qr_condition_bank_capacity(const qr_condition_bank* b) { return b ? b->capacity : fail(QR_E_INVALID, "qr_condition_bank_capacity: null bank"); }
+
+int qr_condition_bank_set(qr_condition_bank* b, int32_t slot, const float* gate_pos, const float* gate_yaw, int32_t G, const float* start_pos,
+                          const float* dist_ranges, float dist_scale, int32_t max_steps, int32_t gates_per_lap) {
+    if (!b) return fail(QR_E_INVALID, "qr_condition_bank_set: null bank");
+    if (!gate_pos || !gate_yaw || !start_pos) return fail(QR_E_INVALID, "qr_condition_bank_set: null track argument");
+    if (slot < 0 || slot >= b->capacity) return fail(QR_E_INVALID, "qr_condition_bank_set: slot must be in [0, capacity)");
+    if (G < 2 || G > QR_MAX_GATES) return fail(QR_E_INVALID, "qr_condition_bank_set: num_gates must be in 2..QR_MAX_GATES (the evaluators need two gates)");
+    if (gates_per_lap < 1) return fail(QR_E_INVALID, "qr_condition_bank_set: gates_per_lap must be >= 1");
+    if (dist_ranges && b->variant != QR_VARIANT_E2E)
+        return fail(QR_E_INVALID, "qr_condition_bank_set: dist_ranges must be NULL for the INDI variant (it has no disturbances)");
+    // NULL ranges = a handle on which qr_set_disturbance was never called: all-zero ranges, scale 1
+    float dist_lo[6] = {}, dist_hi[6] = {};
+    if (dist_ranges)
+        for (int k = 0; k < 6; ++k) {
+            dist_lo[k] = dist_ranges[2 * k + 0];
+            dist_hi[k] = dist_ranges[2 * k + 1];
+        }
+    else
+        dist_scale = 1.0f;
+    std::vector<float> host(qr::kCondSlotFloats, 0.0f);
+    qr::CondHeader h{};
+    h.num_gates = G;
+    h.max_steps = max_steps;
+    h.gates_per_lap = gates_per_lap;
+    condition_obs_scale(dist_lo, dist_hi, h.obs_lo, h.obs_inv);
+    std::memcpy(host.data(), &h, sizeof(h));
+    std::vector<float> pos_rel(3 * (size_t)G), yaw_rel((size_t)G);
+    gate_relative_table(gate_pos, gate_yaw, G, pos_rel.data(), yaw_rel.data());
+    build_condition_image(b->variant, start_pos, dist_lo, dist_hi, dist_scale, G, gate_pos, gate_yaw, pos_rel.data(), yaw_rel.data(),
+                          host.data() + qr::kCondHeaderFloats);
+    QR_HIP(hipSetDevice(b->device));
+    QR_HIP(hipDeviceSynchronize());   // a launch may still read the slot
+    if (hipMemcpy(b->d_slots + (size_t)slot * qr::kCondSlotFloats, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        b->is_set[(size_t)slot] = 0;
+        return fail(QR_E_HIP, "qr_condition_bank_set: upload failed");
+    }
+    b->is_set[(size_t)slot] = 1;
+    return QR_OK;
+}
+
+// The refusals come first and in full: nothing is enqueued or copied unless every argument is valid, and no index reaches the device
+// that has not been checked against its bank here.
+int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups, int32_t envs_per_group,
+                            const int32_t* policy_of_group, const int32_t* condition_of_group, int32_t K, int32_t flags, int32_t* rec_dev,
+                            float* recf_dev, void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    if (!policies) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: null policy bank handle");
+    if (!conditions) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: null condition bank handle");
+    if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the two group maps are required");
+    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: rec_dev is required");
+    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the record buffers must be 16-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_steps must be >= 1");
+    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: `flags` takes QR_ROLLOUT_F32CLASS or 0");
+    if (e->num_gates < 2)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the track has one gate: a pass cannot move the target, so passes cannot be counted");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, "qr_evaluate_policy_grid: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (qr::bank_obs_len(policies) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: bank obs_len != env obs_len");
+    if (qr::bank_device(policies) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: policy bank on another GPU");
+    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank of another variant");
+    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank on another GPU");
+    if (num_groups < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_groups must be >= 1");
+    if (envs_per_group < qr::kBlock || envs_per_group % qr::kBlock != 0)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: envs_per_group must be a multiple of 256, at least 256 (one workgroup serves one group)");
+    if ((int64_t)num_groups * envs_per_group != (int64_t)e->cfg.num_envs)
+        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_groups * envs_per_group must equal the env count of the handle");
+    const int pcap = qr::bank_capacity(policies);
+    for (int g = 0; g < num_groups; ++g) {
+        const int p = policy_of_group[g], c = condition_of_group[g];
+        if (p < 0 || p >= pcap)
+            return fail(QR_E_INVALID, "qr_evaluate_policy_grid: policy_of_group[" + std::to_string(g) + "] is outside the policy bank");
+        if (c < 0 || c >= conditions->capacity)
+            return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
+    }
+    for (int g = 0; g < num_groups; ++g) {
+        if (!qr::bank_slot_set(policies, policy_of_group[g]))
+            return fail(QR_E_STATE, "qr_evaluate_policy_grid: slot " + std::to_string(policy_of_group[g]) + " of the policy bank has no weights");
+        if (!conditions->is_set[(size_t)condition_of_group[g]])
+            return fail(QR_E_STATE, "qr_evaluate_policy_grid: slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // the group map: interleaved (policy, condition) per group, in a device array of the handle.  An equal map is already there;
+    // another one is copied after a device synchronisation, like the tables (an earlier launch may still read the array), which a
+    // stream under capture does not allow.
+    std::vector<int32_t> map(2 * (size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g) {
+        map[2 * (size_t)g + 0] = policy_of_group[g];
+        map[2 * (size_t)g + 1] = condition_of_group[g];
+    }
+    if (!e->d_group_map || map != e->group_map_host) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+            return fail(QR_E_STATE, "qr_evaluate_policy_grid: a new group map is uploaded after a device synchronisation, which a stream under "
+                                    "capture does not allow; call once with this map outside the capture");
+        QR_HIP(hipDeviceSynchronize());
+        e->group_map_host.clear();   // nothing valid on the device until the copy below has succeeded
+        if (num_groups > e->group_map_cap) {
+            if (e->d_group_map) (void)hipFree(e->d_group_map);
+            e->d_group_map = nullptr;
+            e->group_map_cap = 0;
+            QR_HIP(hipMalloc((void**)&e->d_group_map, sizeof(int2) * (size_t)num_groups));
+            e->group_map_cap = num_groups;
+        }
+        QR_HIP(hipMemcpy(e->d_group_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        e->group_map_host = map;
+    }
+    const bool ev = want_events(e, st);
+    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
+    QR_HIP(qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
+                                       e->d_group_map, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
     if (ev) QR_HIP(hipEventRecord(e->ev1, st));
     e->timing_valid = ev;
     return QR_OK;

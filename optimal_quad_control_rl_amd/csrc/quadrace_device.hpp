@@ -62,6 +62,16 @@ static_assert(kOffB2 + 4 <= kMlpTableFloats && kMlpTableFloats % 16 == 0, "MLP t
 constexpr int kResetTableFloats = 96;
 constexpr int kOffResetImage = kMlpTableFloats;
 constexpr int kOffGatesImage = kMlpTableFloats + kResetTableFloats;
+// Condition image (one slot of a qr_condition_bank, read by eval_policy_grid_kernel): [header (16 dwords) | reset table | gate rows],
+// the last two byte for byte the handle's table image from kOffResetImage on; a slot is kCondSlotFloats floats, 16-byte aligned.
+struct CondHeader {
+    int num_gates, max_steps, gates_per_lap, pad0;
+    float obs_lo[4], obs_inv[4];   // Params::obs_lo / obs_inv of a handle under the condition's disturbance ranges
+    int pad1[4];
+};
+constexpr int kCondHeaderFloats = 16;
+constexpr int kCondSlotFloats = kCondHeaderFloats + kResetTableFloats + kMaxGates * kGateStride;
+static_assert(sizeof(CondHeader) == 4 * kCondHeaderFloats && kCondSlotFloats % 4 == 0, "condition image layout");
 
 struct Params {
     // planar state in HBM (structure of float4 arrays, plane stride = n_stride elements)

@@ -127,6 +127,11 @@ hipError_t launch_eval_policy(int variant, const Params& P, const PolicyArgs& A,
 hipError_t launch_eval_policy_bank(int variant, const Params& P, const half8* bank, const half8* bank_lo, bool f32class, int num_policies,
                                    int envs_per_policy, int K, int gates_per_lap, int32_t* rec, float* recf, hipStream_t st);
 
+// quadrace_eval_grid.hip: a grid of policies x flight conditions (qr_evaluate_policy_grid): the workgroups of group g = b / (envs_per_group /
+// kBlock) fly policy map[g].x under condition map[g].y; conds = slot 0 of [capacity][kCondSlotFloats]
+hipError_t launch_eval_policy_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const int2* map,
+                                   bool f32class, int num_groups, int envs_per_group, int K, int32_t* rec, float* recf, hipStream_t st);
+
 // quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
 hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
 
@@ -143,5 +148,6 @@ int bank_obs_len(const qr_policy_bank* b);
 int bank_device(const qr_policy_bank* b);
 int bank_capacity(const qr_policy_bank* b);
 int bank_first_unset(const qr_policy_bank* b, int num_policies);
+bool bank_slot_set(const qr_policy_bank* b, int slot);   // slot in [0, capacity) and filled (qr_evaluate_policy_grid)
 
 }  // namespace qr

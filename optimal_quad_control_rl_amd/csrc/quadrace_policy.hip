@@ -129,6 +129,7 @@ int bank_first_unset(const qr_policy_bank* b, int num_policies) {   // first slo
         if (!b->is_set[(size_t)s]) return s;
     return -1;
 }
+bool bank_slot_set(const qr_policy_bank* b, int slot) { return b && slot >= 0 && slot < b->capacity && b->is_set[(size_t)slot]; }
 }  // namespace qr
 
 namespace {

@@ -15,6 +15,15 @@ Many policies -- the checkpoints of a run, the seeds of a sweep -- are evaluated
     results = evaluate_policies(["run/model_10.zip", "run/model_20.zip", model], eval_env, envs_per_policy=256, seed=0)
     best = rank_policies(results)[0]
 
+A policy under conditions it did not train under -- other disturbance scales or ranges, another track, another time limit -- is a GRID
+of policies x conditions, flown `env.num_envs // envs_per_cell` cells per launch on the same random numbers (`qr_evaluate_policy_grid`,
+csrc/quadrace_eval_grid.hip):
+
+    from optimal_quad_control_rl_amd import evaluate_grid, disturbance_sweep
+    conds = disturbance_sweep(eval_env, [0, 0.5, 1, 2, 3])
+    results = evaluate_grid([model], conds, eval_env, envs_per_cell=256, seed=0)      # results[p][c]
+    rows = robustness_table(results, [c.name for c in conds])
+
 All times inside the records are integer step counts; seconds appear only here (steps x env.dt).
 """
 import math
@@ -206,6 +215,97 @@ def evaluate_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, win
         torch.cuda.current_stream(core.device).synchronize()
         bank.close()
     return results
+
+
+def plan_grid_batches(num_policies, num_conditions, slots):
+    """How evaluate_grid spreads the num_policies x num_conditions cells over launches of `slots` groups each: cells in row-major
+    order (policy-major: cell k = (k // num_conditions, k % num_conditions)), each batch a list of exactly `slots` (policy,
+    condition) pairs.  The last batch is padded by repeating its last cell (a launch always flies every group of the env); `kept` =
+    how many leading groups of the batch are real.  Returns [(cells, kept), ...]; pure arithmetic, no device."""
+    num_policies, num_conditions, slots = int(num_policies), int(num_conditions), int(slots)
+    if num_policies < 1 or num_conditions < 1:
+        raise ValueError("need at least one policy and one condition")
+    if slots < 1:
+        raise ValueError("the env holds no complete group: num_envs < envs_per_cell")
+    total = num_policies * num_conditions
+    plan = []
+    for first in range(0, total, slots):
+        real = [(k // num_conditions, k % num_conditions) for k in range(first, min(first + slots, total))]
+        plan.append((real + [real[-1]] * (slots - len(real)), len(real)))
+    return plan
+
+
+def evaluate_grid(policies, conditions, env, envs_per_cell=256, n_eval_steps=2000, window_steps=1200, precision=None, seed=0):
+    """evaluate_policy for every cell of `policies` x `conditions` (conditions.Condition), `env.num_envs // envs_per_cell` cells per
+    launch (qr_evaluate_policy_grid): each group of E = envs_per_cell envs flies one policy under one condition -- the condition's
+    track, start, disturbance ranges and scale, max_steps and gates_per_lap; `env`'s residual weights, dt and gates_ahead.  Every
+    batch starts from `env.condition_starts(..., seed=seed)` and the kernel keys restarts by the env's index within its group, so
+    all cells see the same uniform draws (only the condition's own scaling of them differs), and cell (p, c) is what an E-env
+    handle configured with condition c sees under evaluate_policy(policies[p], ..., seed=seed).  Entries of `policies` and
+    `precision`: as evaluate_policies.  Returns results[p][c], each a {"window", "total"} dict.  `env` keeps its own configuration."""
+    import torch
+
+    from .conditions import ConditionBank
+    from .policy import MfmaPolicyBank
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    E, n = int(envs_per_cell), core.num_envs
+    if E < 256 or E % 256 != 0:
+        raise ValueError("envs_per_cell must be a multiple of 256 (one workgroup serves one cell)")
+    if n % E != 0:
+        raise ValueError("env.num_envs must be a multiple of envs_per_cell")
+    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
+    if not 1 <= window_steps <= n_eval_steps:
+        raise ValueError("need 1 <= window_steps <= n_eval_steps")
+    conditions = list(conditions)
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for _, m in actors)
+        precision = "f32" if f32 else "f16-operands"
+    slots = n // E
+    results = [[None] * len(conditions) for _ in actors]
+    pbank = MfmaPolicyBank(core.state_len, len(actors), core.device.index)
+    cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
+    try:
+        for p, (actor, _) in enumerate(actors):
+            pbank.load_torch(p, actor)
+        for c, cond in enumerate(conditions):
+            cbank.set(c, cond)
+        for cells, kept in plan_grid_batches(len(actors), len(conditions), slots):
+            pol, cog = [p for p, _ in cells], [c for _, c in cells]
+            core.condition_starts(conditions, cog, E, seed=seed)
+            rec = torch.zeros((n, REC_INTS), dtype=torch.int32, device=core.device)
+            recf = torch.zeros((n, REC_FLOATS), dtype=torch.float32, device=core.device)
+            core.evaluate_grid_device(pbank, cbank, pol, cog, E, window_steps, rec, recf, precision=precision)
+            windows = []
+            for g in range(kept):
+                w = summarize_eval(rec[g * E:(g + 1) * E], recf[g * E:(g + 1) * E], core.dt, conditions[cog[g]].gates_per_lap)
+                w["crashes_per_window"], w["gates_per_window"] = w["crashes_per_env"], w["gates_per_env"]
+                windows.append(w)
+            if n_eval_steps > window_steps:
+                core.evaluate_grid_device(pbank, cbank, pol, cog, E, n_eval_steps - window_steps, rec, recf, precision=precision)
+            for g in range(kept):
+                total = summarize_eval(rec[g * E:(g + 1) * E], recf[g * E:(g + 1) * E], core.dt, conditions[cog[g]].gates_per_lap)
+                results[pol[g]][cog[g]] = {"window": windows[g], "total": total}
+    finally:
+        torch.cuda.current_stream(core.device).synchronize()
+        pbank.close()
+        cbank.close()
+    return results
+
+
+def robustness_table(results, names):
+    """evaluate_grid's results[p][c] as one table per policy: a list (per policy) of rows (condition name, crashes per window,
+    flying-lap seconds or None, gates per window), in the order of `names` (one name per condition)."""
+    names = list(names)
+    tables = []
+    for per_policy in results:
+        if len(per_policy) != len(names):
+            raise ValueError("one name per condition is needed")
+        tables.append([(name, float(r["window"]["crashes_per_window"]), r["total"]["flying_lap_seconds"], float(r["window"]["gates_per_window"]))
+                       for name, r in zip(names, per_policy)])
+    return tables
 
 
 def rank_policies(results, max_crashes_per_window=0.1):

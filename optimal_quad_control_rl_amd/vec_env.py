@@ -505,7 +505,8 @@ class Quadcopter3DGates(_Base):
 
     def seed(self, seed=None):
         """Upstream seed() is a no-op (R:600-601); here it keys the in-kernel Philox reset stream."""
-        _lib.check(self._L.qr_seed(self._h, int(0 if seed is None else seed)))
+        self._seed = int(0 if seed is None else seed)   # condition_starts reseeds with it
+        _lib.check(self._L.qr_seed(self._h, self._seed))
         return [seed] * self.num_envs
 
     def get_attr(self, attr_name, indices=None):
@@ -680,6 +681,115 @@ class Quadcopter3DGates(_Base):
             tile = lambda t: None if t is None else t[:e].repeat((reps,) + (1,) * (t.dim() - 1)).contiguous()
             self.set_state_tensors(tile(world), tile(dist), tile(target), tile(steps), tile(episode))
         self.update_states()
+        return self
+
+    def evaluate_grid_device(self, policy_bank, condition_bank, policy_of_group, condition_of_group, envs_per_group, num_steps, rec, recf=None,
+                             precision="f16-operands"):
+        """A grid of policies x flight conditions in ONE kernel (qr_evaluate_policy_grid): group g = envs [g E, (g + 1) E), E =
+        envs_per_group (a multiple of 256; len(policy_of_group) * E == num_envs), flies slot policy_of_group[g] of `policy_bank`
+        (policy.MfmaPolicyBank) under slot condition_of_group[g] of `condition_bank` (conditions.ConditionBank): track, start,
+        disturbance ranges and scale, max_steps and gates_per_lap are the condition's; residual weights, dt and gates_ahead this
+        env's.  Records as in evaluate_device, rows [g E, (g + 1) E) belong to group g; restarts use the group-local reset stream of
+        evaluate_bank_device, so groups that start equal draw the same random numbers and every group flies what an E-env handle
+        configured with its condition flies (condition_starts gives those starts).  Afterwards the env's observation buffer holds,
+        for every group, the observation a handle under the group's condition has of the state the call left (one reconfigure +
+        observe per distinct condition of the map, then the env's own configuration again).  Returns (rec, recf)."""
+        if precision not in ("f16-operands", "f32"):
+            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        fn = _lib.require(self._L, "qr_evaluate_policy_grid")
+        n = self.num_envs
+        pol = np.ascontiguousarray(policy_of_group, dtype=np.int32).reshape(-1)
+        cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
+        if pol.shape != cond.shape:
+            raise ValueError("policy_of_group and condition_of_group must have one entry per group each")
+        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
+        if recf is not None:
+            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy_bank._h, condition_bank._h, int(pol.shape[0]), int(envs_per_group), pol.ctypes.data_as(i32p),
+                      cond.ctypes.data_as(i32p), int(num_steps), 2 if precision == "f32" else 0, _ptr(rec), _ptr(recf), self._stream()))
+        # the kernel stores no observation: refresh the env's own buffer from the state it left, every group as ITS condition observes it
+        self._observe_under(condition_bank.conditions, cond, int(envs_per_group))
+        return rec, recf
+
+    def _under_each_condition(self, conditions, condition_of_group, fn):
+        """fn(c) with the HANDLE configured as conditions[c] (track, start, disturbances, max_steps), once per distinct entry of
+        condition_of_group in ascending order; the handle's own configuration is restored afterwards, also when fn raises."""
+        own = (self.gate_pos, self.gate_yaw, self.start_pos, np.array(self._disturbance_ranges), self._disturbance_scale, self._max_steps)
+        try:
+            for c in sorted(set(int(c) for c in condition_of_group)):
+                cond = conditions[c]
+                if cond is None:
+                    raise ValueError("condition slot %d was never set" % c)
+                if cond.disturbance_ranges is not None and self.VARIANT != QR_VARIANT_E2E:
+                    raise ValueError("an INDI env has no disturbances: the condition's disturbance_ranges must be None")
+                # ranges None on an E2E env = the state of a handle whose disturbances were never set: zero ranges, scale 1
+                ranges = np.zeros((6, 2), dtype=np.float32) if cond.disturbance_ranges is None else cond.disturbance_ranges
+                scale = 1 if cond.disturbance_ranges is None else cond.disturbance_scale
+                self._configure(cond.gate_pos, cond.gate_yaw, cond.start_pos, ranges, scale, cond.max_steps)
+                fn(c)
+        finally:
+            self._configure(*own)
+
+    def _observe_under(self, conditions, condition_of_group, envs_per_group):
+        """The env's own observation buffer <- the observation of the current state, rows of group g as a handle configured with
+        conditions[condition_of_group[g]] observes them (gate rows and disturbance scaling are the condition's)."""
+        e = int(envs_per_group)
+        cog = [int(c) for c in condition_of_group]
+        tmp = torch.empty_like(self._obs)
+
+        def observe(c):
+            _lib.check(self._L.qr_observe(self._h, _ptr(tmp), self._stream()))
+            for g, cg in enumerate(cog):
+                if cg == c:
+                    self._obs[g * e:(g + 1) * e].copy_(tmp[g * e:(g + 1) * e])
+
+        self._under_each_condition(conditions, cog, observe)
+        torch.cuda.current_stream(self.device).synchronize()   # tmp is freed on return
+        self._last_obs = self._obs
+
+    def _configure(self, gate_pos, gate_yaw, start_pos, disturbance_ranges, disturbance_scale, max_steps):
+        """Track, start, disturbances and max_steps of the HANDLE (qr_set_track, qr_set_disturbance, qr_set_limits) and the attributes
+        that mirror them.  disturbance_ranges None leaves the disturbances alone."""
+        self.gate_pos = np.array(gate_pos, dtype=np.float32).reshape(-1, 3)
+        self.gate_yaw = np.array(gate_yaw, dtype=np.float32).reshape(-1)
+        self.start_pos = np.array(start_pos, dtype=np.float32).reshape(3)
+        self.num_gates = int(self.gate_pos.shape[0])
+        _lib.check(self._L.qr_set_track(self._h, _f32p(self.gate_pos), _f32p(self.gate_yaw), self.num_gates, _f32p(self.start_pos)))
+        self.gate_pos_rel = np.zeros((self.num_gates, 3), dtype=np.float32)
+        self.gate_yaw_rel = np.zeros(self.num_gates, dtype=np.float32)
+        _lib.check(self._L.qr_get_track_tables(self._h, _f32p(self.gate_pos_rel), _f32p(self.gate_yaw_rel)))
+        if disturbance_ranges is not None and self.VARIANT == QR_VARIANT_E2E:
+            self._disturbance_ranges = np.array(disturbance_ranges)
+            self._disturbance_scale = disturbance_scale
+            self._push_disturbance()
+        self.max_steps = max_steps
+
+    def condition_starts(self, conditions, condition_of_group, envs_per_group, seed=None):
+        """Give every group g of E = envs_per_group envs the start an E-env handle configured with conditions[condition_of_group[g]]
+        gets from `seed(s); reset_device()` (s = `seed`, default: the seed this env was last seeded with): per distinct condition the
+        handle takes the condition's track, start, disturbances and max_steps, is seeded and reset, and rows [0, E) of its state are
+        kept; then the env's own configuration is restored and the assembled state set.  Groups under the same condition start
+        bit-equal; groups under conditions that differ in the disturbance scale only differ in `disturbances` only.  A few N-env
+        resets; the episode counters and step counts are those of a fresh reset."""
+        e, n = int(envs_per_group), self.num_envs
+        cog = [int(c) for c in condition_of_group]
+        if e < 1 or len(cog) * e != n:
+            raise ValueError("len(condition_of_group) * envs_per_group must equal num_envs")
+        if any(c < 0 or c >= len(conditions) for c in cog):
+            raise ValueError("condition_of_group holds an index outside `conditions`")
+        s = self._seed if seed is None else int(seed)
+        starts = {}
+
+        def start(c):
+            self.seed(s)
+            self.reset_device()
+            starts[c] = [None if t is None else t[:e].clone() for t in self.get_state_tensors()]
+
+        self._under_each_condition(conditions, cog, start)
+        parts = list(zip(*[starts[c] for c in cog]))
+        self.set_state_tensors(*[None if p[0] is None else torch.cat(p).contiguous() for p in parts])
+        self._observe_under(conditions, cog, e)
         return self
 
     RECORD_EXTRA = 8   # QR_RECORD_EXTRA of include/quadrace.h
