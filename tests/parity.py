@@ -56,6 +56,98 @@ def obs_err(a, b, world=None):
     return err / scale
 
 
+E2E, INDI = 0, 1
+KNIFE_EDGE = 1e-5   # a `done` flag may differ between two float32 implementations only this close to a termination threshold
+
+
+def knife_edge_margin(variant, s, a, d, blob, gate_row, dt=0.01):
+    """Distance of ONE env's step from the nearest termination threshold (R:528-550), from the pre-step state: new state by the
+    oracle's free functions (float32, the reference's expression), then the smallest of |proj_old|, |proj_new| (plane crossing),
+    ||p_new - g|_axis - 0.5| (gate window), |z_new| (ground), 10 - |x|, 10 - |y|, 1000 - |rates| (bounds).  A `done` flag that
+    differs between two float32 implementations must sit within rounding noise of one of them."""
+    from oracle import oracle as O
+
+    s = np.asarray(s, np.float32)[None]
+    a = np.asarray(a, np.float32)[None]
+    if variant == E2E:
+        de = np.asarray(d, np.float32)[None].copy()
+        if blob is not None:
+            thrust, moment = O.residual(blob, s)
+            de[:, 0:3] += moment
+            de[:, 5] += thrust[:, 0]
+        ds = O.f_e2e(s, a, de)
+    else:
+        ds = O.f_indi(s, a)
+    nw = (s.astype(np.float64) + dt * ds.astype(np.float64))[0]
+    gx, gy, gz, yaw = (float(v) for v in gate_row)
+    c, sn = np.cos(yaw), np.sin(yaw)
+    proj_old = (float(s[0, 0]) - gx) * c + (float(s[0, 1]) - gy) * sn
+    proj_new = (nw[0] - gx) * c + (nw[1] - gy) * sn
+    m = [abs(proj_old), abs(proj_new), abs(nw[2]), 10.0 - abs(nw[0]), 10.0 - abs(nw[1])]
+    m += [abs(abs(nw[k] - g) - 0.5) for k, g in ((0, gx), (1, gy), (2, gz))]
+    m += [1000.0 - abs(nw[k]) for k in (9, 10, 11)]
+    return min(abs(x) for x in m)
+
+
+def assert_knife_edges(variant, mism, world, actions, dist, blob, track, target, where=""):
+    """Every env flagged in `mism` (its `done` differs between two implementations) must step from (world, dist, target) -- the
+    ORACLE's pre-step state -- to within KNIFE_EDGE of a termination threshold.  Returns the number of such envs."""
+    gate_pos, gate_yaw = np.asarray(track[0], np.float32), np.asarray(track[1], np.float32)
+    G = len(gate_yaw)
+    for i in np.nonzero(mism)[0]:
+        g = int(target[i]) % G
+        margin = knife_edge_margin(variant, world[i], actions[i], dist[i] if variant == E2E else None, blob if variant == E2E else None,
+                                   (*gate_pos[g], gate_yaw[g]))
+        assert margin < KNIFE_EDGE, f"{where} env {i}: done differs with margin {margin:.3e} (target gate {g})"
+    return int(np.count_nonzero(mism))
+
+
+def ring_track(G):
+    """A G-gate track for the table edges (G up to the ABI's 32): gates on a circle of radius 6 m, gate g at angle a = 2 pi g / G,
+    position (6 cos a, 6 sin a, -1.5 + 0.3 sin 3a), yaw a + pi/2 (the normal is the counter-clockwise tangent: yaw reaches +-pi and
+    beyond); start position (6, -1, -1.5), one metre before gate 0."""
+    a = 2.0 * np.pi * np.arange(G) / G
+    gate_pos = np.stack([6.0 * np.cos(a), 6.0 * np.sin(a), -1.5 + 0.3 * np.sin(3.0 * a)], axis=1).astype(np.float32)
+    gate_yaw = (a + np.pi / 2).astype(np.float32)
+    return gate_pos, gate_yaw, np.array([6.0, -1.0, -1.5], np.float32)
+
+
+def ring_straddle_states(track, n, state_len, seed=0):
+    """Env i just before its target gate i % G (the target index is decoupled from the lane index): 0.03 m before the gate plane,
+    a seeded offset uniform in +-0.3 m along the gate's in-plane horizontal axis and along z (inside the 0.5 m window whatever the
+    gate's yaw), 6 m/s along the gate normal, attitude / rates / motor state zero, step count zero.  One 10 ms step moves the env
+    0.06 m along the normal: it passes its gate mid-window whatever the action, the residual model or the disturbance, because an
+    Euler step's new position depends on the old velocity only.  The disturbances (E2E) are seeded draws inside TRAIN_DIST_RANGES, so
+    that their observation columns carry values.  Returns (world[n, state_len], dist[n, 6], target[n], steps[n])."""
+    gate_pos, gate_yaw, _ = track
+    G = len(gate_yaw)
+    rng = np.random.default_rng(seed)
+    target = (np.arange(n) % G).astype(np.int32)
+    yaw = gate_yaw[target].astype(np.float64)
+    normal = np.stack([np.cos(yaw), np.sin(yaw)], axis=1)
+    across = np.stack([-np.sin(yaw), np.cos(yaw)], axis=1)
+    off = rng.uniform(-0.3, 0.3, size=(n, 2))
+    world = np.zeros((n, state_len), np.float64)
+    world[:, 0:2] = gate_pos[target, 0:2] - 0.03 * normal + off[:, :1] * across
+    world[:, 2] = gate_pos[target, 2] + off[:, 1]
+    world[:, 3:5] = 6.0 * normal
+    dist = rng.uniform(TRAIN_DIST_RANGES[:, 0], TRAIN_DIST_RANGES[:, 1], size=(n, 6))
+    return world.astype(np.float32), dist.astype(np.float32), target, np.zeros(n, np.int32)
+
+
+def ring_pass_census(track, target0, target1, done, reward):
+    """What the straddle states did in one step, from the ORACLE's results: per-gate pass counts and the number of G-1 -> 0 wraps.
+    Asserts that every env passed its gate without terminating, that every gate index was passed and that the wrap occurred."""
+    G = len(track[1])
+    assert not done.any(), f"{int(done.sum())} straddle envs terminated"
+    np.testing.assert_array_equal(target1, (target0 + 1) % G)
+    assert (reward > 5.0).all(), "a clean pass pays 10 - 10 * distance"
+    passes = np.bincount(target0, minlength=G)
+    wraps = int(((target0 == G - 1) & (target1 == 0)).sum())
+    assert (passes > 0).all() and wraps > 0, (passes, wraps)
+    return passes, wraps
+
+
 class TrajectoryReport:
     def __init__(self):
         self.max_state = 0.0

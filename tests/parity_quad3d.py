@@ -19,6 +19,44 @@ TOL32_STEP_STATE = 2e-6
 TOL32_STEP_REWARD = 2e-5
 TOL32_FREE_RUN = 1e-4      # ~90 open-loop steps; the k_pv * v_y moment coupling makes the attitude diverge e-fold per ~0.2 s
 
+# A `done` flag may differ between two implementations only this close to a termination threshold (knife_edge_margin_q3).
+#   gates (float32): the race env's figure (tests/parity.py KNIFE_EDGE), same arithmetic, same 0.5 m window and plane test.
+#   hover (float64): two implementations that pass the state check agree on every new state component to TOL64_STEP * max(1, |x|).
+#   The largest threshold a component is compared with is the 10 m position bound, so a component next to ANY threshold differs
+#   by at most 10 * TOL64_STEP; the goal test compares norms of three components, which differ by at most sqrt(3) times that:
+#   1.8 * 10 * TOL64_STEP, rounded up to 20 * TOL64_STEP = 2e-11.
+KNIFE_EDGE_32 = 1e-5
+KNIFE_EDGE_64 = 20 * TOL64_STEP
+
+
+def knife_edge_margin_q3(kind, s, a, gate_row=None, dt=0.01, pos_thr=0.3, vel_thr=0.3, ang_thr=10 * np.pi / 180, rat_thr=10 * np.pi / 180):
+    """Distance of ONE env's step from the nearest termination threshold of its env (oracle/quad3d_oracle.c), from the pre-step
+    state `s` and action `a`; new state by the oracle's free function (oracle.quad3d.f_func) in the env's own precision.
+      hover (hover_step_one): goal = |pos| < pos_thr and |vel| < vel_thr and every |angle| < ang_thr and every |rate| < rat_thr;
+        out of bounds = |x|, |y|, |z| > 10 or |phi|, |theta| > pi -- all on the NEW state.  Margin: the smallest distance of any of
+        those quantities from its threshold.
+      gates (gates_step_one), gate_row = (gx, gy, gz, yaw) of the env's target gate: plane crossing proj_old < 0 < proj_new and
+        the 0.5 m window on every axis of p_new - gate.  Ground and bounds are tested on the PRE-step state there, which a
+        teacher-forced comparison injects bit for bit, so they cannot differ and are left out; the time limit is an integer.
+    The bound a margin is held to is KNIFE_EDGE_64 / KNIFE_EDGE_32 (derivation above)."""
+    from oracle import quad3d as q3
+
+    if kind == "hover":
+        s = np.asarray(s, np.float64)[None]
+        ns = (s + dt * q3.f_func(s, np.asarray(a, np.float32)[None]))[0]
+        m = [abs(np.linalg.norm(ns[0:3]) - pos_thr), abs(np.linalg.norm(ns[3:6]) - vel_thr)]
+        m += [abs(abs(ns[k]) - ang_thr) for k in (6, 7, 8)] + [abs(abs(ns[k]) - rat_thr) for k in (9, 10, 11)]
+        m += [abs(abs(ns[k]) - 10.0) for k in (0, 1, 2)] + [abs(abs(ns[k]) - np.pi) for k in (6, 7)]
+        return min(m)
+    s = np.asarray(s, np.float32)[None]
+    ds = q3.f_func(s, np.asarray(a, np.float32)[None])
+    ns = (s.astype(np.float64) + dt * ds.astype(np.float64))[0]
+    gx, gy, gz, yaw = (float(v) for v in gate_row)
+    c, sn = np.cos(yaw), np.sin(yaw)
+    proj_old = (float(s[0, 0]) - gx) * c + (float(s[0, 1]) - gy) * sn
+    proj_new = (ns[0] - gx) * c + (ns[1] - gy) * sn
+    return min([abs(proj_old), abs(proj_new)] + [abs(abs(ns[k] - g) - 0.5) for k, g in ((0, gx), (1, gy), (2, gz))])
+
 
 def gates_track():
     d = load("q3_gates")

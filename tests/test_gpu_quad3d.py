@@ -86,7 +86,9 @@ def test_reset_bit_exact_vs_oracle(kind):
 
 @pytest.mark.parametrize("kind", ["hover", "gates"])
 def test_lockstep_vs_oracle_through_resets(kind):
-    """Teacher-forced lock-step, N = 4096, random actions, max_steps = 30 so every env is auto-reset in the window."""
+    """Teacher-forced lock-step, N = 4096, random actions, max_steps = 30 so every env is auto-reset in the window.  A differing
+    `done` is accepted only with the proof that the step sits on a termination threshold (parity_quad3d.knife_edge_margin_q3:
+    < 1e-5 for the float32 gates env, < 20 * TOL64_STEP for the float64 hover env); at most 8 in the whole run."""
     n, K = 4096, 45
     trk = pq.gates_track()
     g, o = ProductImpl(kind, n, trk, seed=7), oracle(kind, n, trk, seed=7)
@@ -95,17 +97,23 @@ def test_lockstep_vs_oracle_through_resets(kind):
     g.reset(); o.reset()
     tol_s, tol_r = (pq.TOL64_STEP, pq.TOL64_STEP) if kind == "hover" else (pq.TOL32_STEP_STATE, pq.TOL32_STEP_REWARD)
     rng = np.random.default_rng(3)
-    total_done = 0
+    total_done, mismatches = 0, 0
+    edge = pq.KNIFE_EDGE_64 if kind == "hover" else pq.KNIFE_EDGE_32
     desync = np.zeros(n, bool)   # envs whose reset streams diverged after a knife-edge done mismatch
     for k in range(K):
         g.set_state(o.states, o.target, o.steps)
+        s_pre, t_pre = o.states.copy(), o.target.copy()
         a = rng.uniform(-1, 1, size=(n, 4)).astype(np.float32)
         if k % 2:
             a = (0.2 * a).astype(np.float32)
         sg, rg, dg, tg = g.step(a)
         so, ro, do, to = o.step(a)
         mism = dg != do
-        assert mism.sum() <= 1, f"step {k}: {mism.sum()} done mismatches"
+        for i in np.nonzero(mism)[0]:
+            row = None if kind == "hover" else (*trk[0][t_pre[i]], trk[1][t_pre[i]])
+            margin = pq.knife_edge_margin_q3(kind, s_pre[i], a[i], row)
+            assert margin < edge, f"step {k} env {i}: done differs with margin {margin:.3e}"
+        mismatches += int(mism.sum())
         ok = ~mism
         np.testing.assert_array_equal(tg[ok], to[ok])
         assert np.abs(rg[ok].astype(np.float64) - ro[ok]).max() <= tol_r
@@ -119,7 +127,7 @@ def test_lockstep_vs_oracle_through_resets(kind):
         np.testing.assert_array_equal(tgt[ok], o.target[ok])
         np.testing.assert_array_equal(steps[ok], o.steps[ok])
         total_done += int(do.sum())
-    assert total_done >= n
+    assert total_done >= n and mismatches <= 8, (total_done, mismatches)
 
 
 # ---- size-independent properties at BASELINE size ----------------------------------------------------------------------

@@ -115,8 +115,17 @@ _CASES = [(v, g, n, p, st) for v in ("e2e", "indi") for g in (0, 1) for n in (40
 @pytest.mark.parametrize("variant,gates_ahead,n,precision,stochastic", _CASES,
                          ids=["%s-ga%d-n%d-%s-%s" % (c[0], c[1], c[2], c[3], "stoch" if c[4] else "det") for c in _CASES])
 def test_rows_equal_the_rollout_kernel(variant, gates_ahead, n, precision, stochastic):
-    K = K_WIN
-    r, a = _env(variant, n, gates_ahead), _env(variant, n, gates_ahead)
+    _rows_equal_the_rollout_kernel(variant, gates_ahead, n, precision, stochastic)
+
+
+def _rows_equal_the_rollout_kernel(variant, gates_ahead, n, precision, stochastic, K=K_WIN, track=None, prepare=None, max_steps=None,
+                                   nonvacuous=_assert_window_is_not_vacuous):
+    """`track`, `prepare(env)`, `max_steps`, `K`: another track, start, time limit and window than the scenario's
+    (tests/test_gpu_table_edges.py); `nonvacuous(rows, s, final_target, what)` asserts that the window holds what the caller needs.
+    Returns the rows and the final targets."""
+    r, a = _env(variant, n, gates_ahead, track=track, max_steps=max_steps), _env(variant, n, gates_ahead, track=track, max_steps=max_steps)
+    if prepare is not None:
+        prepare(r); prepare(a)
     pol = _policy(r.state_len, SC[variant + "_action"])
     s, mode = r.STATE_LEN, _mode(stochastic)
     assert r._L.qr_record_row_len(r._h) == s + 8
@@ -125,7 +134,8 @@ def test_rows_equal_the_rollout_kernel(variant, gates_ahead, n, precision, stoch
     assert tuple(rows.shape) == (K, n, s + 8) and rows.dtype == torch.float32
     obs, act, logp, rew, done, trunc, _ = a.rollout_policy_device(pol, K, precision=precision, **mode)
     c = _cols(rows, s)
-    _assert_window_is_not_vacuous(rows, s, r.get_state_tensors()[2], "%s ga%d n%d %s %s" % (variant, gates_ahead, n, precision, stochastic))
+    final_target = r.get_state_tensors()[2]
+    nonvacuous(rows, s, final_target, "%s ga%d n%d %s %s" % (variant, gates_ahead, n, precision, stochastic))
     _equal_bits(c["command"], act.clamp(-1.0, 1.0), "command = clip(action)")
     if stochastic:
         assert int((act.abs() > 1.0).sum()) > 0                       # the clip is exercised: rows hold the command, not the sample
@@ -138,6 +148,7 @@ def test_rows_equal_the_rollout_kernel(variant, gates_ahead, n, precision, stoch
     assert torch.equal(c["target"][0], target0.float()) and torch.equal(c["steps"][0], steps0.float())
     assert torch.equal(r.states_tensor, a.states_tensor)                # the wrapper refreshed its observation buffer
     r.close(); a.close(); pol.close()
+    return rows, final_target
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -57,15 +57,17 @@ def test_residual_and_body_velocity_match_reference_rows_directly(PA, residual_b
 def test_full_size_lockstep_through_resets_vs_oracle(PA, OA, variant, residual_blob):
     """BASELINE size N = 65 536, 64 teacher-forced steps through auto-resets (max_steps = 40 truncates every env once;
     random actions crash many more): dones / targets / step counts exact, freshly reset lanes bit-exact, integrated lanes
-    within the one-step tolerance."""
+    within the one-step tolerance.  Every env whose `done` differs is shown to sit < 1e-5 from a termination threshold
+    (parity.knife_edge_margin, from the oracle's pre-step state), and the whole run may hold at most 8 of them."""
     n, K = 65536, 64
-    g, o = _pair(PA, OA, variant, n, "zigzag" if variant == E2E else "square", 1, residual_blob, seed=21)
+    tname = "zigzag" if variant == E2E else "square"
+    g, o = _pair(PA, OA, variant, n, tname, 1, residual_blob, seed=21)
     o.env.set_threads(16)
     g.env.max_steps = 40
     o.env.set_limits(40, 0.01)
     g.reset(); o.reset()
     rng = np.random.default_rng(31)
-    tot_done, worst_state, worst_obs = 0, 0.0, 0.0
+    tot_done, mismatches, worst_state, worst_obs = 0, 0, 0.0, 0.0
     for k in range(K):
         wo, do, to, so = o.get_state()
         g.set_state(wo, do if variant == E2E else None, to, so)
@@ -76,7 +78,7 @@ def test_full_size_lockstep_through_resets_vs_oracle(PA, OA, variant, residual_b
         og, rg, dng, trg = g.step(a)
         oo, ro, dno, tro = o.step(a)
         mism = dng != dno
-        assert mism.sum() <= 4, f"step {k}: {mism.sum()} done mismatches"   # knife-edge threshold cases only
+        mismatches += P.assert_knife_edges(variant, mism, wo, a, do, residual_blob, P.tracks()[tname], to, where=f"step {k}")
         ok = ~mism
         wg, dg, tg, sg = g.get_state()
         wo2, do2, to2, so2 = o.get_state()
@@ -93,7 +95,7 @@ def test_full_size_lockstep_through_resets_vs_oracle(PA, OA, variant, residual_b
         worst_obs = max(worst_obs, float(P.obs_err(og[ok], oo[ok], wo2[ok]).max()))
         tot_done += int(dno.sum())
     assert worst_state < P.TOL_STEP_STATE and worst_obs < P.TOL_STEP_OBS, (worst_state, worst_obs)
-    assert tot_done >= n
+    assert tot_done >= n and mismatches <= 8, (tot_done, mismatches)
 
 
 @pytest.mark.parametrize("variant", [E2E, INDI])

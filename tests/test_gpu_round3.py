@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import parity as P
+from parity import knife_edge_margin   # moved to tests/parity.py; test_gpu_round5 imports it from here
 
 pytestmark = pytest.mark.gpu
 
@@ -31,35 +32,6 @@ def OA():
     from oracle_adapter import OracleAdapter
 
     return OracleAdapter
-
-
-def knife_edge_margin(variant, s, a, d, blob, gate_row, dt=0.01):
-    """Distance of ONE env's step from the nearest termination threshold (R:528-550), from the pre-step state: new state by the
-    oracle's free functions (float32, the reference's expression), then the smallest of |proj_old|, |proj_new| (plane crossing),
-    ||p_new - g|_axis - 0.5| (gate window), |z_new| (ground), 10 - |x|, 10 - |y|, 1000 - |rates| (bounds).  A `done` flag that
-    differs between two float32 implementations must sit within rounding noise of one of them."""
-    from oracle import oracle as O
-
-    s = np.asarray(s, np.float32)[None]
-    a = np.asarray(a, np.float32)[None]
-    if variant == E2E:
-        de = np.asarray(d, np.float32)[None].copy()
-        if blob is not None:
-            thrust, moment = O.residual(blob, s)
-            de[:, 0:3] += moment
-            de[:, 5] += thrust[:, 0]
-        ds = O.f_e2e(s, a, de)
-    else:
-        ds = O.f_indi(s, a)
-    nw = (s.astype(np.float64) + dt * ds.astype(np.float64))[0]
-    gx, gy, gz, yaw = (float(v) for v in gate_row)
-    c, sn = np.cos(yaw), np.sin(yaw)
-    proj_old = (float(s[0, 0]) - gx) * c + (float(s[0, 1]) - gy) * sn
-    proj_new = (nw[0] - gx) * c + (nw[1] - gy) * sn
-    m = [abs(proj_old), abs(proj_new), abs(nw[2]), 10.0 - abs(nw[0]), 10.0 - abs(nw[1])]
-    m += [abs(abs(nw[k] - g) - 0.5) for k, g in ((0, gx), (1, gy), (2, gz))]
-    m += [1000.0 - abs(nw[k]) for k in (9, 10, 11)]
-    return min(abs(x) for x in m)
 
 
 @pytest.mark.parametrize("variant,tname,ga", [(E2E, "zigzag", 0), (E2E, "zigzag", 2), (E2E, "square", 0), (E2E, "square", 2),

@@ -57,14 +57,15 @@ def test_reset_bit_exact_vs_oracle(PA, OA, variant, residual_blob):
 
 @pytest.mark.parametrize("variant,tname,ga", [(E2E, "zigzag", 1), (E2E, "square", 2), (INDI, "square", 1), (INDI, "zigzag", 0)])
 def test_lockstep_vs_oracle(PA, OA, variant, tname, ga, residual_blob):
-    """Teacher-forced lock-step at N=4096 with random actions, through auto-resets."""
+    """Teacher-forced lock-step at N=4096 with random actions, through auto-resets.  A differing `done` is accepted only with the
+    proof that the step sits < 1e-5 from a termination threshold (parity.knife_edge_margin); at most 8 in the whole run."""
     n, K = 4096, 60
     g, o = _pair(PA, OA, variant, n, tname, ga, residual_blob)
     g.env.max_steps = 40            # every env is truncated (and auto-reset) inside the window
     o.env.set_limits(40, 0.01)
     g.reset(); o.reset()
     rng = np.random.default_rng(5)
-    tot_done = 0
+    tot_done, mismatches = 0, 0
     for k in range(K):
         wo, do, to, so = o.get_state()
         g.set_state(wo, do if variant == E2E else None, to, so)
@@ -75,7 +76,7 @@ def test_lockstep_vs_oracle(PA, OA, variant, tname, ga, residual_blob):
         og, rg, dng, trg = g.step(a)
         oo, ro, dno, tro = o.step(a)
         mism = dng != dno
-        assert mism.sum() <= 1, f"step {k}: {mism.sum()} done mismatches"  # knife-edge threshold cases only
+        mismatches += P.assert_knife_edges(variant, mism, wo, a, do, residual_blob, P.tracks()[tname], to, where=f"step {k}")
         ok = ~mism
         wg, dg, tg, sg = g.get_state()
         wo2, do2, to2, so2 = o.get_state()
@@ -92,23 +93,31 @@ def test_lockstep_vs_oracle(PA, OA, variant, tname, ga, residual_blob):
             assert P.rel_err(wg[live], wo2[live]).max() < P.TOL_STEP_STATE
         assert P.obs_err(og[ok], oo[ok], wo2[ok]).max() < P.TOL_STEP_OBS
         tot_done += int(dno.sum())
-    assert tot_done >= n
+    assert tot_done >= n and mismatches <= 8, (tot_done, mismatches)
 
 
 @pytest.mark.parametrize("variant", [E2E, INDI])
 def test_full_size_one_step_vs_oracle(PA, OA, variant, residual_blob):
-    """BASELINE size N=65536: one reset + three steps, product vs oracle."""
+    """BASELINE size N=65536: one reset + three steps, product vs oracle, free-running.  An env whose `done` differs leaves the
+    comparison from that step on (its two sides follow different episodes), and only with the proof that the ORACLE's state before
+    that step sits < 1e-5 from a termination threshold; at most 8 such envs in the run."""
     n = FULL_N
-    g, o = _pair(PA, OA, variant, n, "zigzag" if variant == E2E else "square", 1, residual_blob, seed=3)
+    tname = "zigzag" if variant == E2E else "square"
+    g, o = _pair(PA, OA, variant, n, tname, 1, residual_blob, seed=3)
     g.reset(); o.reset()
     np.testing.assert_array_equal(g.get_state()[0], o.get_state()[0])
     rng = np.random.default_rng(9)
+    valid = np.ones(n, bool)
     for k in range(3):
         a = rng.uniform(-1, 1, size=(n, 4)).astype(np.float32)
+        w_pre, d_pre, t_pre, _ = o.get_state()
         og, rg, dng, _ = g.step(a)
         oo, ro, dno, _ = o.step(a)
-        ok = dng == dno
-        assert (~ok).sum() <= 2
+        mism = (dng != dno) & valid
+        P.assert_knife_edges(variant, mism, w_pre, a, d_pre, residual_blob, P.tracks()[tname], t_pre, where=f"step {k}")
+        valid &= ~mism
+        assert (~valid).sum() <= 8
+        ok = valid
         wg, wo = g.get_state()[0], o.get_state()[0]
         live = ok & ~dno
         # free-running (no re-injection): error compounds over the three steps
