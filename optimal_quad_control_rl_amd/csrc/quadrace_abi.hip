@@ -190,6 +190,47 @@ int check_term_rows(const qr_env* e, int K, const char* who) {
     return QR_OK;
 }
 
+// What every closed-loop evaluator (qr_evaluate_policy, _bank, _grid) refuses about its own arguments and the handle's mode, in the
+// order they all refuse it.  gates_per_lap: the entry point's argument, or nullptr where it has none (the grid evaluator takes it
+// from its condition headers, which qr_condition_bank_set has checked).
+int check_eval_args(const qr_env* e, int K, const int32_t* gates_per_lap, int flags, const int32_t* rec_dev, const float* recf_dev,
+                    const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!rec_dev) return fail(QR_E_INVALID, w + "rec_dev is required");
+    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, w + "the record buffers must be 16-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, w + "num_steps must be >= 1");
+    if (gates_per_lap && *gates_per_lap < 1) return fail(QR_E_INVALID, w + "gates_per_lap must be >= 1");
+    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_F32CLASS or 0");
+    if (e->num_gates < 2) return fail(QR_E_INVALID, w + "the track has one gate: a pass cannot move the target, so passes cannot be counted");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, w + "lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    return QR_OK;
+}
+
+// Group shape of the bank and grid evaluators: `groups` groups (argument `count_name`) of envs_per_<unit> envs each, whole workgroups,
+// covering the handle exactly.  groups >= 1 is the caller's check (its message differs between the two).
+int check_group_shape(const qr_env* e, int groups, int envs_per_group, const char* count_name, const char* unit, const char* who) {
+    const std::string w = std::string(who) + ": ", envs_name = std::string("envs_per_") + unit;
+    if (envs_per_group < qr::kBlock || envs_per_group % qr::kBlock != 0)
+        return fail(QR_E_INVALID, w + envs_name + " must be a multiple of 256, at least 256 (one workgroup serves one " + unit + ")");
+    if ((int64_t)groups * envs_per_group != (int64_t)e->cfg.num_envs)
+        return fail(QR_E_INVALID, w + count_name + " * " + envs_name + " must equal the env count of the handle");
+    return QR_OK;
+}
+
+// One launch on `st` inside the hipEvent bracket of want_events: QR_TIMED_LAUNCH(e, st, launcher call).  A failed launch reports the
+// call's text, as QR_HIP does.
+#define QR_TIMED_LAUNCH(e, st, expr) timed_launch(e, st, #expr, [&] { return (expr); })
+template <typename Launch>
+int timed_launch(qr_env* e, hipStream_t st, const char* what, Launch&& launch) {
+    const bool ev = want_events(e, st);
+    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
+    if (hipError_t err = launch()) return fail(QR_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
+    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
+    e->timing_valid = ev;
+    return QR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -564,15 +605,7 @@ int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_pe
                        float* recf_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
     if (!policy) return fail(QR_E_INVALID, "qr_evaluate_policy: null policy handle");
-    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy: rec_dev is required");
-    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy: the record buffers must be 16-byte aligned");
-    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy: num_steps must be >= 1");
-    if (gates_per_lap < 1) return fail(QR_E_INVALID, "qr_evaluate_policy: gates_per_lap must be >= 1");
-    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy: `flags` takes QR_ROLLOUT_F32CLASS or 0");
-    if (e->num_gates < 2)
-        return fail(QR_E_INVALID, "qr_evaluate_policy: the track has one gate: a pass cannot move the target, so passes cannot be counted");
-    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, "qr_evaluate_policy: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (int rc = check_eval_args(e, K, &gates_per_lap, flags, rec_dev, recf_dev, "qr_evaluate_policy")) return rc;
     if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy: policy obs_len != env obs_len");
     if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy: policy on another GPU");
     const qr::half8* w = qr::policy_weights(policy);
@@ -583,12 +616,7 @@ int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_pe
     A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
     A.deterministic = 1;
     hipStream_t st = (hipStream_t)stream;
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(qr::launch_eval_policy(e->cfg.variant, e->P, A, K, gates_per_lap, rec_dev, recf_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy(e->cfg.variant, e->P, A, K, gates_per_lap, rec_dev, recf_dev, st));
 }
 
 // The refusals come first and in full: nothing is enqueued (no event, no launch) unless every argument is valid.
@@ -596,33 +624,17 @@ int qr_evaluate_policy_bank(qr_env* e, qr_policy_bank* bank, int32_t num_policie
                             int32_t gates_per_lap, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
     if (!bank) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: null bank handle");
-    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: rec_dev is required");
-    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: the record buffers must be 16-byte aligned");
-    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_steps must be >= 1");
-    if (gates_per_lap < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: gates_per_lap must be >= 1");
-    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: `flags` takes QR_ROLLOUT_F32CLASS or 0");
-    if (e->num_gates < 2)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: the track has one gate: a pass cannot move the target, so passes cannot be counted");
-    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, "qr_evaluate_policy_bank: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (int rc = check_eval_args(e, K, &gates_per_lap, flags, rec_dev, recf_dev, "qr_evaluate_policy_bank")) return rc;
     if (qr::bank_obs_len(bank) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank obs_len != env obs_len");
     if (qr::bank_device(bank) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank on another GPU");
     if (num_policies < 1 || num_policies > qr::bank_capacity(bank))
         return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_policies must be in 1..capacity");
-    if (envs_per_policy < qr::kBlock || envs_per_policy % qr::kBlock != 0)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: envs_per_policy must be a multiple of 256, at least 256 (one workgroup serves one policy)");
-    if ((int64_t)num_policies * envs_per_policy != (int64_t)e->cfg.num_envs)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_policies * envs_per_policy must equal the env count of the handle");
+    if (int rc = check_group_shape(e, num_policies, envs_per_policy, "num_policies", "policy", "qr_evaluate_policy_bank")) return rc;
     const int unset = qr::bank_first_unset(bank, num_policies);
     if (unset >= 0) return fail(QR_E_STATE, "qr_evaluate_policy_bank: slot " + std::to_string(unset) + " of the bank has no weights");
     hipStream_t st = (hipStream_t)stream;
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(qr::launch_eval_policy_bank(e->cfg.variant, e->P, qr::bank_weights(bank), qr::bank_weights_lo(bank), (flags & QR_ROLLOUT_F32CLASS) != 0,
+    return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_bank(e->cfg.variant, e->P, qr::bank_weights(bank), qr::bank_weights_lo(bank), (flags & QR_ROLLOUT_F32CLASS) != 0,
                                        num_policies, envs_per_policy, K, gates_per_lap, rec_dev, recf_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
 }
 
 // ---- bank of flight conditions (qr_evaluate_policy_grid) ----
@@ -710,23 +722,13 @@ int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_ba
     if (!policies) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: null policy bank handle");
     if (!conditions) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: null condition bank handle");
     if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the two group maps are required");
-    if (!rec_dev) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: rec_dev is required");
-    if (((uintptr_t)rec_dev | (uintptr_t)recf_dev) & 15) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the record buffers must be 16-byte aligned");
-    if (K < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_steps must be >= 1");
-    if (flags & ~QR_ROLLOUT_F32CLASS) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: `flags` takes QR_ROLLOUT_F32CLASS or 0");
-    if (e->num_gates < 2)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the track has one gate: a pass cannot move the target, so passes cannot be counted");
-    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, "qr_evaluate_policy_grid: lap accounting is defined for the default mode, not for pause / pause_if_collision");
+    if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, "qr_evaluate_policy_grid")) return rc;
     if (qr::bank_obs_len(policies) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: bank obs_len != env obs_len");
     if (qr::bank_device(policies) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: policy bank on another GPU");
     if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank of another variant");
     if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank on another GPU");
     if (num_groups < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_groups must be >= 1");
-    if (envs_per_group < qr::kBlock || envs_per_group % qr::kBlock != 0)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: envs_per_group must be a multiple of 256, at least 256 (one workgroup serves one group)");
-    if ((int64_t)num_groups * envs_per_group != (int64_t)e->cfg.num_envs)
-        return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_groups * envs_per_group must equal the env count of the handle");
+    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", "qr_evaluate_policy_grid")) return rc;
     const int pcap = qr::bank_capacity(policies);
     for (int g = 0; g < num_groups; ++g) {
         const int p = policy_of_group[g], c = condition_of_group[g];
@@ -767,13 +769,8 @@ int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_ba
         QR_HIP(hipMemcpy(e->d_group_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         e->group_map_host = map;
     }
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
+    return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
                                        e->d_group_map, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
 }
 
 int qr_record_row_len(const qr_env* e) { return e ? e->S + QR_RECORD_EXTRA : QR_E_INVALID; }
@@ -806,12 +803,7 @@ int qr_record_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_s
     A.step_hi = (uint32_t)(first_step >> 32);
     A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(qr::launch_record_policy(e->cfg.variant, e->P, A, K, rec_envs, rows_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_record_policy(e->cfg.variant, e->P, A, K, rec_envs, rows_dev, st));
 }
 
 int qr_observe(qr_env* e, float* obs_out_dev, void* stream) {

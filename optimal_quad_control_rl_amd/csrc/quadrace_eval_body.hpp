@@ -1,0 +1,156 @@
+// quadrace_eval_body.hpp -- the ONE body of the closed-loop policy evaluators: K x [obs -> MFMA policy -> action = clip(mean) ->
+// env.step] with the lap / crash accounting a user reads after training (gate passes, crashes, time-limit ends, lap durations by lap
+// number, episode returns) kept in registers next to the env state.  eval_policy_kernel (quadrace_eval.hip), eval_policy_bank_kernel
+// (quadrace_eval_bank.hip) and eval_policy_grid_kernel (quadrace_eval_grid.hip) each derive their inputs and call it; the record and
+// its accounting exist here and in tests/eval_spec.py, nowhere else.
+//
+// The step loop is rollout_policy_kernel's (quadrace_env_kernels.hpp) without everything an evaluation throws away: no action noise
+// (no Philox / Box-Muller slices between the matrix instructions), no observation tile, no observation / action / log-prob / reward /
+// done rows -- NO global store inside the step loop.  What leaves the kernel is one 24-int record and one 4-float record per env
+// (layout: include/quadrace.h, restated on the CPU in tests/eval_spec.py) and the env state after K steps, stored exactly as the
+// rollout kernel stores it.
+//
+// All times are integer step counts, so every sum is exact; the float record is three sequential float32 sums (one add per step, one
+// multiply and two adds per finished episode, no FMA), which NumPy float32 reproduces bit for bit.
+#pragma once
+#include "../../include/quadrace.h"
+#include "quadrace_env_kernels.hpp"
+
+namespace qr {
+
+static_assert(QR_EVAL_REC_INTS == 24 && QR_EVAL_MAX_LAPS == 8 && QR_EVAL_REC_FLOATS == 4, "record layout of include/quadrace.h");
+
+// dynamic LDS of a kernel that calls eval_policy_body: policy image (f16) | reset table | gate rows | lap sums and counts [16][kBlock]
+// (the carve-up at the top of eval_policy_body)
+template <int L>
+constexpr size_t eval_lds_bytes() {
+    return (size_t)PolicyDims<L>::kTotalHalf8 * 16 + sizeof(float) * (kResetTableFloats + kMaxGates * kGateStride + 2 * QR_EVAL_MAX_LAPS * kBlock);
+}
+
+// What a kernel supplies (256-thread workgroups, eval_lds_bytes<L>() of dynamic LDS, called by every lane):
+//   P              the Params to fly under (the handle's, or a copy with a condition's scalars)
+//   img, img_lo    the policy image this workgroup flies and its low pieces (f32-class form only), workgroup-uniform
+//   tab            the [reset table | gate rows] image to stage, 16-byte aligned, workgroup-uniform
+//   i              the lane's env: state planes, rec and recf are indexed by it
+//   rid            the lane's id in the reset stream: the Philox counter's env id is P.gid + rid (64-bit carry as everywhere)
+//   gates_per_lap  passes that make a lap
+// kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
+// for every lane, every lane is an env and every lane stores.
+template <int V, int GA, bool kF32, bool kTail>
+__device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
+                                                 const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,
+                                                 int4* __restrict__ rec, float4* __restrict__ recf) {
+    constexpr int L = obs_len<V, GA>();
+    using D = PolicyDims<L>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half8* W = reinterpret_cast<half8*>(smem);                                   // policy weights (f16) of THIS workgroup's policy
+    float* rtab = reinterpret_cast<float*>(smem + (size_t)D::kTotalHalf8 * 16);  // reset table | gate rows | lap sums and counts
+    float* gates = rtab + kResetTableFloats;
+    const int lane = threadIdx.x & 63;
+    const bool active = !kTail || i < P.n;
+    const int ii = active ? i : 0;
+    Env<V> e;
+    load_env<V>(P, ii, e);
+    // the lane's record: read here, written behind the loop (a caller continues an evaluation by passing the same buffers again)
+    const int4 r0 = rec[(size_t)ii * 6], r1 = rec[(size_t)ii * 6 + 1];
+    // lap sums / counts [16][kBlock] live in LDS: they are touched at lap boundaries only (a few times per thousand steps), indexed by
+    // the lap number, and 16 registers held through the policy forward are 16 registers the f32-class forward does not have
+    int* laps = reinterpret_cast<int*>(gates + kMaxGates * kGateStride) + threadIdx.x;
+    {   // (register pressure: v[] lives only from these four loads to the 16 LDS writes below, all ahead of the weight staging and the loop)
+        const int4 b = rec[(size_t)ii * 6 + 2], c = rec[(size_t)ii * 6 + 3], d = rec[(size_t)ii * 6 + 4], f = rec[(size_t)ii * 6 + 5];
+        const int v[2 * QR_EVAL_MAX_LAPS] = {r1.z, r1.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w, f.x, f.y};
+#pragma unroll
+        for (int q = 0; q < 2 * QR_EVAL_MAX_LAPS; ++q) laps[q * kBlock] = v[q];   // own column only: no barrier needed
+    }
+    int n_gates = r0.x, n_crash = r0.y, n_limit = r0.z, since = r0.w, lap_t0 = r1.x, now = r1.y;
+    // passes into the running lap and laps finished since the (re)start: kept instead of dividing `since` on every step
+    int lap_no = since / gates_per_lap, in_lap = since - lap_no * gates_per_lap;
+    float ep_ret = 0.0f, ret_sum = 0.0f, ret_sq = 0.0f;
+    if (recf) {
+        const float4 f = recf[ii];
+        ep_ret = f.x; ret_sum = f.y; ret_sq = f.z;
+    }
+    MlpRegs mlp;
+    const bool use_mlp = (V == kE2E) && (P.flags & kFlagResidual);
+    if (use_mlp) mlp_load_regs(P.tables, lane, mlp);
+    {
+        const float4* s4 = reinterpret_cast<const float4*>(img);
+        float4* d4 = reinterpret_cast<float4*>(W);
+        for (int j = threadIdx.x; j < D::kTotalHalf8; j += kBlock) d4[j] = s4[j];
+    }
+    {   // [reset table | gate rows], as stage_tables copies the handle's (counts are multiples of 4)
+        const float4* s4 = reinterpret_cast<const float4*>(tab);
+        float4* d4 = reinterpret_cast<float4*>(rtab);
+        const int count4 = (kResetTableFloats + P.num_gates * kGateStride) / 4;
+        for (int j = threadIdx.x; j < count4; j += kBlock) d4[j] = s4[j];
+    }
+    __syncthreads();
+    const uint32_t gid_lo = P.gid_lo + (uint32_t)(active ? rid : 0);
+    const uint32_t gid_hi = P.gid_hi + (gid_lo < P.gid_lo ? 1u : 0u);
+    bool any_reset = false;
+    float stash[reset_value_count<V>()];   // the lane's own next reset draws (reset_from_stash)
+    bool stash_ok = false;
+    float o[L];
+    observe<V, GA>(P, gates, e, o);
+    for (int k = 0; k < K; ++k) {
+        float mean[4];
+        if constexpr (kF32) policy_forward_f32class<L>(W, img_lo, lane, o, mean);
+        else policy_forward<L>(W, lane, o, mean);
+        const float u[4] = {fminf(fmaxf(mean[0], -1.0f), 1.0f), fminf(fmaxf(mean[1], -1.0f), 1.0f),
+                            fminf(fmaxf(mean[2], -1.0f), 1.0f), fminf(fmaxf(mean[3], -1.0f), 1.0f)};
+        const int target_before = e.target;
+        bool done, trunc, did_reset;
+        const float reward = step_env<V>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,
+                                         [](bool) {}, [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); });
+        any_reset |= did_reset;
+        // ---- accounting (tests/eval_spec.py, same order).  A pass on the step that ends the episode is not counted: the reset has
+        // replaced the target, and that episode's lap count is void anyway.
+        now += 1;
+        const bool pass = !done && e.target != target_before;
+        if (pass) {
+            n_gates += 1;
+            since += 1;
+            in_lap += 1;
+            if (in_lap == gates_per_lap) {   // a lap boundary: rare and divergent, so a branch (skipped by the whole wave most steps)
+                in_lap = 0;
+                lap_no += 1;
+                if (lap_no <= QR_EVAL_MAX_LAPS) {
+                    laps[(lap_no - 1) * kBlock] += now - lap_t0;
+                    laps[(QR_EVAL_MAX_LAPS + lap_no - 1) * kBlock] += 1;
+                }
+                lap_t0 = now;
+            }
+        }
+        ep_ret = add_rn(ep_ret, reward);
+        if (done) {
+            if (trunc) n_limit += 1; else n_crash += 1;
+            since = 0; in_lap = 0; lap_no = 0;
+            lap_t0 = now;
+            ret_sum = add_rn(ret_sum, ep_ret);
+            ret_sq = add_rn(ret_sq, mul_rn(ep_ret, ep_ret));
+            ep_ret = 0.0f;
+        }
+        observe<V, GA>(P, gates, e, o);
+    }
+    if (!active) return;
+    int4* row = rec + (size_t)i * 6;
+    int lap_sum[QR_EVAL_MAX_LAPS], lap_cnt[QR_EVAL_MAX_LAPS];
+#pragma unroll
+    for (int q = 0; q < QR_EVAL_MAX_LAPS; ++q) {
+        lap_sum[q] = laps[q * kBlock];
+        lap_cnt[q] = laps[(QR_EVAL_MAX_LAPS + q) * kBlock];
+    }
+    row[0] = make_int4(n_gates, n_crash, n_limit, since);
+    row[1] = make_int4(lap_t0, now, lap_sum[0], lap_sum[1]);
+    row[2] = make_int4(lap_sum[2], lap_sum[3], lap_sum[4], lap_sum[5]);
+    row[3] = make_int4(lap_sum[6], lap_sum[7], lap_cnt[0], lap_cnt[1]);
+    row[4] = make_int4(lap_cnt[2], lap_cnt[3], lap_cnt[4], lap_cnt[5]);
+    row[5] = make_int4(lap_cnt[6], lap_cnt[7], 0, 0);
+    if (recf) recf[i] = make_float4(ep_ret, ret_sum, ret_sq, 0.0f);
+    define_exit_values<V>(e);
+    P.ts[i] = pack_ts<V>(e);
+    store_world<V>(P, i, e);
+    if (any_reset) store_dist<V>(P, i, e);
+}
+
+}  // namespace qr

@@ -136,6 +136,13 @@ def _f32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _precision_flags(precision):
+    """Flag bits of the policy forward's precision (QR_ROLLOUT_F32CLASS for "f32")."""
+    if precision not in ("f16-operands", "f32"):
+        raise ValueError("precision must be 'f16-operands' or 'f32'")
+    return 2 if precision == "f32" else 0
+
+
 class Quadcopter3DGates(_Base):
     """End-to-end (motor command) Bebop race environment, vectorised on one MI355X.  Mirrors R:287-620.
 
@@ -615,8 +622,7 @@ class Quadcopter3DGates(_Base):
         `policy` is an optimal_quad_control_rl_amd.policy.MfmaPolicy.  Returns device tensors
         (obs[K,N,L], actions[K,N,4] unclipped, logp[K,N], reward[K,N], done[K,N] u8, trunc[K,N] u8, last_obs[N,L]).
         precision="f32": the policy forward inside the kernel at the reference's precision (QR_ROLLOUT_F32CLASS)."""
-        if precision not in ("f16-operands", "f32"):
-            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        flags = _precision_flags(precision)
         K, n, dev = int(num_steps), self.num_envs, self.device
         if out is None:
             out = (torch.empty((K, n, self.state_len), dtype=torch.float32, device=dev),
@@ -629,23 +635,26 @@ class Quadcopter3DGates(_Base):
         ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
                                   dtype=np.float32).reshape(4)
         _lib.check(self._L.qr_rollout_policy(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
-                                             int(bool(deterministic)) | (2 if precision == "f32" else 0), _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
+                                             int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
                                              _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
         self._last_obs = self._obs
         return obs, act, logp, rew, done, trunc, self._obs
+
+    def _check_eval_records(self, rec, recf):
+        """The evaluators' record tensors: `rec` int32 [N, 24], `recf` float32 [N, 4] or None, both on the device and contiguous."""
+        n = self.num_envs
+        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
+        if recf is not None:
+            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
 
     def evaluate_device(self, policy, num_steps, gates_per_lap, rec, recf=None, precision="f16-operands"):
         """Closed-loop deterministic evaluation in ONE kernel (qr_evaluate_policy): K x [obs -> MFMA policy -> env.step(clip(mean))]
         with the lap / crash accounting on the device and nothing stored per step.  `rec` int32 CUDA tensor [N, 24] and `recf`
         float32 [N, 4] (optional) are read at the start and written at the end: zero them for a fresh evaluation, pass them again
         to continue one (record layout: include/quadrace.h; summary: evaluation.summarize_eval).  Returns (rec, recf)."""
-        if precision not in ("f16-operands", "f32"):
-            raise ValueError("precision must be 'f16-operands' or 'f32'")
-        n = self.num_envs
-        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
-        if recf is not None:
-            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
-        _lib.check(self._L.qr_evaluate_policy(self._h, policy._h, int(num_steps), int(gates_per_lap), 2 if precision == "f32" else 0,
+        flags = _precision_flags(precision)
+        self._check_eval_records(rec, recf)
+        _lib.check(self._L.qr_evaluate_policy(self._h, policy._h, int(num_steps), int(gates_per_lap), flags,
                                               _ptr(rec), _ptr(recf), self._stream()))
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return rec, recf
@@ -656,15 +665,11 @@ class Quadcopter3DGates(_Base):
         Records as in evaluate_device: rows [p E, (p + 1) E) of `rec` [N, 24] / `recf` [N, 4] belong to policy p.  Inside this call an env
         that ends its episode restarts from the reset stream of its index WITHIN its group, so groups that start equal (share_starts)
         see the same starts, disturbances and restarts; every other call on this env resets with the ordinary ids.  Returns (rec, recf)."""
-        if precision not in ("f16-operands", "f32"):
-            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        flags = _precision_flags(precision)
         fn = _lib.require(self._L, "qr_evaluate_policy_bank")
-        n = self.num_envs
-        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
-        if recf is not None:
-            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        self._check_eval_records(rec, recf)
         _lib.check(fn(self._h, bank._h, int(num_policies), int(envs_per_policy), int(num_steps), int(gates_per_lap),
-                      2 if precision == "f32" else 0, _ptr(rec), _ptr(recf), self._stream()))
+                      flags, _ptr(rec), _ptr(recf), self._stream()))
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return rec, recf
 
@@ -694,20 +699,16 @@ class Quadcopter3DGates(_Base):
         configured with its condition flies (condition_starts gives those starts).  Afterwards the env's observation buffer holds,
         for every group, the observation a handle under the group's condition has of the state the call left (one reconfigure +
         observe per distinct condition of the map, then the env's own configuration again).  Returns (rec, recf)."""
-        if precision not in ("f16-operands", "f32"):
-            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        flags = _precision_flags(precision)
         fn = _lib.require(self._L, "qr_evaluate_policy_grid")
-        n = self.num_envs
         pol = np.ascontiguousarray(policy_of_group, dtype=np.int32).reshape(-1)
         cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
         if pol.shape != cond.shape:
             raise ValueError("policy_of_group and condition_of_group must have one entry per group each")
-        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
-        if recf is not None:
-            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        self._check_eval_records(rec, recf)
         i32p = C.POINTER(C.c_int32)
         _lib.check(fn(self._h, policy_bank._h, condition_bank._h, int(pol.shape[0]), int(envs_per_group), pol.ctypes.data_as(i32p),
-                      cond.ctypes.data_as(i32p), int(num_steps), 2 if precision == "f32" else 0, _ptr(rec), _ptr(recf), self._stream()))
+                      cond.ctypes.data_as(i32p), int(num_steps), flags, _ptr(rec), _ptr(recf), self._stream()))
         # the kernel stores no observation: refresh the env's own buffer from the state it left, every group as ITS condition observes it
         self._observe_under(condition_bank.conditions, cond, int(envs_per_group))
         return rec, recf
@@ -802,8 +803,7 @@ class Quadcopter3DGates(_Base):
         the env received (clip(action, -1, 1)), then reward, end code (0 running / 1 crash / 2 time limit), target gate before the
         step, step count before the step (time = steps * dt).  recording.FlightRecord gives the columns names.  `out`: a tensor of
         that shape to write into.  Same noise stream and env state afterwards as rollout_policy_device with the same arguments."""
-        if precision not in ("f16-operands", "f32"):
-            raise ValueError("precision must be 'f16-operands' or 'f32'")
+        flags = _precision_flags(precision)
         fn = _lib.require(self._L, "qr_record_policy")
         K, n, dev = int(num_steps), self.num_envs, self.device
         m = n if rec_envs is None else int(rec_envs)
@@ -815,7 +815,7 @@ class Quadcopter3DGates(_Base):
         ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
                                   dtype=np.float32).reshape(4)
         _lib.check(fn(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
-                      int(bool(deterministic)) | (2 if precision == "f32" else 0), m, _ptr(out), self._stream()))
+                      int(bool(deterministic)) | flags, m, _ptr(out), self._stream()))
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return out
 

@@ -3,7 +3,6 @@
 equal an E-env twin handle (same seed, track, limits, disturbance ranges) flown by evaluate_device with the same weights in an
 MfmaPolicy: integer records equal, float records bit-equal, the five state tensors bit-equal.  No tolerance anywhere.  Non-vacuity is
 asserted on the twins' own data (eval_spec.nonvacuous_*), so a comparison of nothing with nothing fails instead of passing."""
-import ctypes as C
 import statistics
 import types
 
@@ -12,48 +11,12 @@ import pytest
 import torch
 
 import eval_spec as S
+from eval_helpers import (SENTINEL, _closed_loop_layers, _constant_layers, _env, _group_equals as _slot_equals, _policy_bank as _bank, _ptr,
+                          _records)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -77777.0
 SC = S.SCENARIO
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _env(variant, n, gates_ahead, seed=SC["seed"], track=None, max_steps=SC["max_steps"]):
-    from optimal_quad_control_rl_amd import Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES
-
-    trk = S.scenario_track() if track is None else track
-    if variant == "e2e":
-        env = Quadcopter3DGates(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")   # residual MLPs: the default
-        env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
-    else:
-        env = Quadcopter3DGatesINDI(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")
-    env.max_steps = max_steps
-    env.reset_device()
-    return env
-
-
-def _constant_layers(obs_len, action):
-    """zero weights and an output bias: the action does not depend on the observation"""
-    z = np.zeros
-    return [(z((120, obs_len), np.float32), z(120, np.float32)), (z((120, 120), np.float32), z(120, np.float32)),
-            (z((120, 120), np.float32), z(120, np.float32)), (z((4, 120), np.float32), np.asarray(action, np.float32))]
-
-
-def _closed_loop_layers(obs_len, action, seed=3, gain=5.0):
-    """seeded random weights around `action`: every action depends on the observation the kernel fed to its forward"""
-    from optimal_quad_control_rl_amd.ppo import ActorCritic
-
-    torch.manual_seed(seed)
-    net = ActorCritic(obs_len, 4)
-    with torch.no_grad():
-        net.pi[-1].weight.mul_(gain)
-        net.pi[-1].bias.copy_(torch.as_tensor(action, dtype=torch.float32))
-    return [(m.weight.detach().clone(), m.bias.detach().clone()) for m in net.pi if isinstance(m, torch.nn.Linear)]
 
 
 def _four_policies(variant, obs_len):
@@ -62,25 +25,6 @@ def _four_policies(variant, obs_len):
     other = act * np.float32(0.75) + np.asarray([0.02, -0.01, 0.01, 0.03], np.float32)
     return [_constant_layers(obs_len, act), _closed_loop_layers(obs_len, act, seed=3), _constant_layers(obs_len, other),
             _closed_loop_layers(obs_len, other, seed=4)]
-
-
-def _records(env):
-    return (torch.zeros((env.num_envs, S.REC_INTS), dtype=torch.int32, device=env.device),
-            torch.zeros((env.num_envs, S.REC_FLOATS), dtype=torch.float32, device=env.device))
-
-
-def _bank(obs_len, layer_sets, capacity=None):
-    from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
-
-    bank = MfmaPolicyBank(obs_len, capacity or len(layer_sets))
-    for slot, layers in enumerate(layer_sets):
-        bank.set_weights(slot, layers)
-    return bank
-
-
-def _slot_equals(env_state, twin, lo, hi, what):
-    for name, x, y in zip(("world", "disturbances", "target", "steps", "episode"), env_state, twin.get_state_tensors()):
-        assert x is None or torch.equal(x[lo:hi], y), (what, name)
 
 
 _CASES = [(v, g, e, p) for v in ("e2e", "indi") for g in (0, 1) for e in (256, 1024) for p in ("f16-operands", "f32")]

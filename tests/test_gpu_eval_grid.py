@@ -20,15 +20,11 @@ import pytest
 import torch
 
 import eval_spec as S
+from eval_helpers import SENTINEL, _closed_loop_layers, _constant_layers, _group_equals, _policy_bank, _ptr, _records
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -77777.0
 SC = S.SCENARIO
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _other_track():
@@ -80,43 +76,10 @@ def _twin(variant, n, gates_ahead, cond, seed=SC["seed"]):
     return env
 
 
-def _constant_layers(obs_len, action):
-    """zero weights and an output bias: the action does not depend on the observation"""
-    z = np.zeros
-    return [(z((120, obs_len), np.float32), z(120, np.float32)), (z((120, 120), np.float32), z(120, np.float32)),
-            (z((120, 120), np.float32), z(120, np.float32)), (z((4, 120), np.float32), np.asarray(action, np.float32))]
-
-
-def _closed_loop_layers(obs_len, action, seed=3, gain=5.0):
-    """seeded random weights around `action`: every action depends on the observation the kernel fed to its forward"""
-    from optimal_quad_control_rl_amd.ppo import ActorCritic
-
-    torch.manual_seed(seed)
-    net = ActorCritic(obs_len, 4)
-    with torch.no_grad():
-        net.pi[-1].weight.mul_(gain)
-        net.pi[-1].bias.copy_(torch.as_tensor(action, dtype=torch.float32))
-    return [(m.weight.detach().clone(), m.bias.detach().clone()) for m in net.pi if isinstance(m, torch.nn.Linear)]
-
-
 def _two_policies(variant, obs_len):
     """slot 0: the scenario's constant action; slot 1: seeded closed loop around it"""
     act = np.asarray(SC[variant + "_action"], np.float32)
     return [_constant_layers(obs_len, act), _closed_loop_layers(obs_len, act, seed=3)]
-
-
-def _records(env):
-    return (torch.zeros((env.num_envs, S.REC_INTS), dtype=torch.int32, device=env.device),
-            torch.zeros((env.num_envs, S.REC_FLOATS), dtype=torch.float32, device=env.device))
-
-
-def _policy_bank(obs_len, layer_sets, capacity=None):
-    from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
-
-    bank = MfmaPolicyBank(obs_len, capacity or len(layer_sets))
-    for slot, layers in enumerate(layer_sets):
-        bank.set_weights(slot, layers)
-    return bank
 
 
 def _condition_bank(variant, conds, capacity=None):
@@ -126,11 +89,6 @@ def _condition_bank(variant, conds, capacity=None):
     for slot, c in enumerate(conds):
         bank.set(slot, c)
     return bank
-
-
-def _group_equals(env_state, twin, lo, hi, what):
-    for name, x, y in zip(("world", "disturbances", "target", "steps", "episode"), env_state, twin.get_state_tensors()):
-        assert x is None or torch.equal(x[lo:hi], y), (what, name)
 
 
 def _grid_against_twins(variant, gates_ahead, E, precision, pol, cog, K=SC["steps"]):

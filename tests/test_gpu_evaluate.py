@@ -8,65 +8,17 @@ already establishes that the closed-loop kernels are bit-identical to this loop)
 of 16 gates 0.4 m apart, time limit 250, 600 steps, a constant action from a zero-weight policy with an output bias) is shown on the
 CPU oracle to produce passes, laps in every slot, crashes and time-limit ends (tests/test_eval_spec.py); the same conditions are
 asserted here on the reference loop's own data, so a vacuous comparison fails instead of passing."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
 import eval_spec as S
+from eval_helpers import SENTINEL, _closed_loop_policy, _constant_policy, _env, _ptr, _records
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -77777.0
 SC = S.SCENARIO
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _env(variant, n, gates_ahead, seed=SC["seed"], track=None, max_steps=SC["max_steps"]):
-    from optimal_quad_control_rl_amd import Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES
-
-    trk = S.scenario_track() if track is None else track
-    if variant == "e2e":
-        env = Quadcopter3DGates(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")   # residual MLPs: the default
-        env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
-    else:
-        env = Quadcopter3DGatesINDI(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none")
-    env.max_steps = max_steps
-    env.reset_device()
-    return env
-
-
-def _constant_policy(obs_len, action):
-    """zero weights and an output bias: the action does not depend on the observation"""
-    from optimal_quad_control_rl_amd.policy import MfmaPolicy
-
-    z = np.zeros
-    return MfmaPolicy(obs_len).set_weights([(z((120, obs_len), np.float32), z(120, np.float32)), (z((120, 120), np.float32), z(120, np.float32)),
-                                            (z((120, 120), np.float32), z(120, np.float32)),
-                                            (z((4, 120), np.float32), np.asarray(action, np.float32))])
-
-
-def _closed_loop_policy(obs_len, action, seed=3, gain=5.0):
-    """seeded random weights around the scenario's action: action = bias + an observation-dependent term of a few hundredths, so the
-    scenario keeps its character while every action depends on the observation the kernel fed to its forward"""
-    from optimal_quad_control_rl_amd.policy import MfmaPolicy
-    from optimal_quad_control_rl_amd.ppo import ActorCritic
-
-    torch.manual_seed(seed)
-    net = ActorCritic(obs_len, 4)
-    with torch.no_grad():
-        net.pi[-1].weight.mul_(gain)
-        net.pi[-1].bias.copy_(torch.as_tensor(action, dtype=torch.float32))
-    return MfmaPolicy(obs_len).load_torch(net.pi)
-
-
-def _records(env):
-    return (torch.zeros((env.num_envs, S.REC_INTS), dtype=torch.int32, device=env.device),
-            torch.zeros((env.num_envs, S.REC_FLOATS), dtype=torch.float32, device=env.device))
 
 
 def _target(env, out):
