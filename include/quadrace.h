@@ -52,7 +52,7 @@ extern "C" {
 #define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
                              qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
                              qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
-                             qr_condition_bank_* / qr_evaluate_policy_grid (round 11) */
+                             qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12) */
 
 enum {
     QR_OK = 0,
@@ -318,6 +318,38 @@ int qr_condition_bank_set(qr_condition_bank* bank, int32_t slot, const float* ga
 int qr_evaluate_policy_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups,
                             int32_t envs_per_group, const int32_t* policy_of_group, const int32_t* condition_of_group,
                             int32_t num_steps, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Closed-loop rollout across a MIX of flight conditions in one launch: PPO's collect phase (qr_rollout_policy: same policy forward, same
+ * action noise, same rows, terminal-observation rows, last_obs and state write-back) with the group map and the condition bank of
+ * qr_evaluate_policy_grid, so that one policy trains on several tracks, disturbance ranges / scales or time limits without one handle
+ * and one launch per condition.  Group g in [0, num_groups) = envs [g E, (g + 1) E) of the handle, E = envs_per_group, flies under slot
+ * condition_of_group[g] of `conditions` (HOST int32 array of num_groups entries, any order, repeats allowed): a 256-env workgroup stages
+ * the table image of ITS condition; num_gates, max_steps and the observation scaling of the disturbances are the condition's (its
+ * gates_per_lap is not used).  The residual weights, dt, flags and gates_ahead stay the handle's, and the handle's own track /
+ * disturbance / max_steps configuration is not used by this call.  The E2E observation's disturbance terms are therefore normalised
+ * by each condition's own ranges, as on a handle configured with it.
+ * ORDINARY ENV IDS: unlike the two bank evaluators, the reset stream and the action noise are keyed by env_id_base + i, as in
+ * qr_rollout_policy -- training wants independent envs, not common random numbers across groups.
+ * CONTRACT: group g produces bit for bit (rows [t][g E, (g + 1) E) of every output, its terminal-observation rows, its last_obs rows
+ * and the env state afterwards) what an E-env handle produces under qr_rollout_policy with the same policy, log_std, noise_seed,
+ * first_step and flags, when that handle has been configured by qr_set_track, qr_set_disturbance (not called where the condition's
+ * dist_ranges is NULL) and qr_set_limits with the values of condition condition_of_group[g], has env_id_base = this handle's + g E,
+ * the same seed, variant, gates_ahead, residual weights and dt, and starts from the same state.  COROLLARY: when every group names a
+ * condition equal to the handle's own configuration, the call equals qr_rollout_policy on the handle itself, bit for bit.
+ * A registered terminal-observation buffer is honoured (num_steps <= its rows, as in every K-step entry point).  The map is validated
+ * on the host -- no index reaches the device unchecked -- and copied to the device array the handle owns under the rule of
+ * qr_evaluate_policy_grid: a map that differs from the previous call's is copied after a device synchronisation.
+ * Refused before anything is launched or copied (qr_last_error set, outputs and state untouched): everything qr_rollout_policy refuses;
+ * QR_E_INVALID: NULL condition bank or map, num_groups < 1, envs_per_group < 256 or not a multiple of 256, num_groups * envs_per_group
+ * != qr_num_envs(env), an index outside the bank's capacity, a bank of another variant or device; QR_E_STATE: a referenced slot that
+ * was never set, pause / pause_if_collision set, or a new map while `stream` is being captured.
+ * flags: QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS.  qr_last_step_many_ms() reports this launch too. */
+int qr_rollout_policy_conditions(qr_env* env, qr_policy* policy, qr_condition_bank* conditions,
+                                 int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group,
+                                 int32_t num_steps, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                                 int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev,
+                                 float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                                 float* last_obs_dev, void* stream);
 
 /* Closed-loop FLIGHT RECORDER: the K steps of qr_rollout_policy (same policy forward, same action noise keyed by (noise_seed, global env id,
  * first_step + t), same env arithmetic and reset stream: the env state afterwards is bit-identical to qr_rollout_policy with the same

@@ -131,3 +131,38 @@ class ConditionBank:
                                                       int(cond.max_steps), int(cond.gates_per_lap)))
         self.conditions[int(slot)] = cond
         return self
+
+
+def plan_condition_groups(num_envs, num_conditions, envs_per_group=256, weights=None):
+    """The blocked `condition_of_group` map of `env.rollout_policy_conditions_device` / `PPO(conditions=...)`: num_envs // envs_per_group
+    groups, condition c holding a contiguous run of them.  weights None: equal shares; otherwise shares proportional to `weights`
+    (one non-negative number per condition), rounded by largest remainder.  Groups that do not divide evenly go to the lowest indices
+    (ties of the remainders likewise).  ValueError for sizes the library refuses (envs_per_group not a multiple of 256 or below it,
+    num_envs not a whole number of groups) and when a condition would get no group (fewer groups than conditions, or a weight too
+    small for one): a condition in the list is a condition to train on."""
+    n, c, e = int(num_envs), int(num_conditions), int(envs_per_group)
+    if c < 1:
+        raise ValueError("num_conditions must be >= 1")
+    if e < 256 or e % 256 != 0:
+        raise ValueError("envs_per_group must be a multiple of 256, at least 256 (one workgroup serves one group)")
+    if n < e or n % e != 0:
+        raise ValueError("num_envs must be a whole number of groups of envs_per_group envs")
+    groups = n // e
+    if weights is None:
+        w = [1.0] * c
+    else:
+        w = [float(x) for x in weights]
+        if len(w) != c:
+            raise ValueError("weights must hold one entry per condition")
+        if any(not np.isfinite(x) or x < 0.0 for x in w) or sum(w) <= 0.0:
+            raise ValueError("weights must be finite and non-negative, with a positive sum")
+    total = sum(w)
+    quota = [groups * x / total for x in w]
+    share = [int(np.floor(q)) for q in quota]
+    # largest remainder, ties to the lowest index (sorted is stable)
+    for i in sorted(range(c), key=lambda i: -(quota[i] - share[i]))[:groups - sum(share)]:
+        share[i] += 1
+    if min(share) < 1:
+        raise ValueError("%d group(s) for %d conditions with these weights leave condition %d without a group"
+                         % (groups, c, share.index(min(share))))
+    return [i for i in range(c) for _ in range(share[i])]

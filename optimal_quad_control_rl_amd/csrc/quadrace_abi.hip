@@ -218,6 +218,29 @@ int check_group_shape(const qr_env* e, int groups, int envs_per_group, const cha
     return QR_OK;
 }
 
+// The group map of qr_evaluate_policy_grid / qr_rollout_policy_conditions: interleaved (policy, condition) per group, in a device array
+// of the handle.  An equal map is already there; another one is copied after a device synchronisation, like the tables (an earlier
+// launch may still read the array), which a stream under capture does not allow.
+int upload_group_map(qr_env* e, const std::vector<int32_t>& map, int num_groups, hipStream_t st, const char* who) {
+    if (e->d_group_map && map == e->group_map_host) return QR_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(QR_E_STATE, std::string(who) + ": a new group map is uploaded after a device synchronisation, which a stream under "
+                                                   "capture does not allow; call once with this map outside the capture");
+    QR_HIP(hipDeviceSynchronize());
+    e->group_map_host.clear();   // nothing valid on the device until the copy below has succeeded
+    if (num_groups > e->group_map_cap) {
+        if (e->d_group_map) (void)hipFree(e->d_group_map);
+        e->d_group_map = nullptr;
+        e->group_map_cap = 0;
+        QR_HIP(hipMalloc((void**)&e->d_group_map, sizeof(int2) * (size_t)num_groups));
+        e->group_map_cap = num_groups;
+    }
+    QR_HIP(hipMemcpy(e->d_group_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    e->group_map_host = map;
+    return QR_OK;
+}
+
 // One launch on `st` inside the hipEvent bracket of want_events: QR_TIMED_LAUNCH(e, st, launcher call).  A failed launch reports the
 // call's text, as QR_HIP does.
 #define QR_TIMED_LAUNCH(e, st, expr) timed_launch(e, st, #expr, [&] { return (expr); })
@@ -556,27 +579,28 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
     return QR_OK;
 }
 
-int qr_rollout_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed,
-                      uint64_t first_step, int32_t deterministic, float* obs_out_dev, float* act_out_dev,
-                      float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
-                      float* last_obs_dev, void* stream) {
-    if (int rc = check_ready(e)) return rc;
-    if (K < 1 || !policy || !log_std) return fail(QR_E_INVALID, "qr_rollout_policy: bad argument");
-    if (int rc = check_term_rows(e, K, "qr_rollout_policy")) return rc;
+// What qr_rollout_policy and qr_rollout_policy_conditions refuse about their shared arguments and the handle's mode, in one order; on
+// success A holds the sampling arguments of the launch.
+static int rollout_policy_args(const qr_env* e, qr_policy* policy, int K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                               int flags, const float* obs_out_dev, const float* act_out_dev, const float* logp_out_dev,
+                               const float* rew_out_dev, const uint8_t* done_out_dev, const char* who, qr::PolicyArgs& A) {
+    const std::string w = std::string(who) + ": ";
+    if (K < 1 || !policy || !log_std) return fail(QR_E_INVALID, w + "bad argument");
+    if (int rc = check_term_rows(e, K, who)) return rc;
     if (!obs_out_dev || !act_out_dev || !logp_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, "qr_rollout_policy: obs/act/logp/rew/done buffers are required");
+        return fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
     if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, "qr_rollout_policy: pause / pause_if_collision envs are evaluation modes; use qr_step");
-    const qr::half8* w = qr::policy_weights(policy);
-    if (!w) return fail(QR_E_STATE, "qr_rollout_policy: the policy has no weights");
-    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_rollout_policy: policy obs_len != env obs_len");
-    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_rollout_policy: policy on another GPU");
-    if (deterministic < 0 || deterministic > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
-        return fail(QR_E_INVALID, "qr_rollout_policy: `deterministic` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
-    qr::PolicyArgs A{};
-    A.weights = w;
+        return fail(QR_E_STATE, w + "pause / pause_if_collision envs are evaluation modes; use qr_step");
+    const qr::half8* wt = qr::policy_weights(policy);
+    if (!wt) return fail(QR_E_STATE, w + "the policy has no weights");
+    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, w + "policy obs_len != env obs_len");
+    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, w + "policy on another GPU");
+    if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return fail(QR_E_INVALID, w + "`deterministic` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    A = qr::PolicyArgs{};
+    A.weights = wt;
     A.weights_lo = qr::policy_weights_lo(policy);
-    A.f32class = (deterministic & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
     float sum_log_std = 0.0f;
     for (int c = 0; c < 4; ++c) {
         A.std[c] = expf(log_std[c]);
@@ -590,7 +614,19 @@ int qr_rollout_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_
     A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
     A.step_lo = (uint32_t)first_step;
     A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (deterministic & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    return QR_OK;
+}
+
+int qr_rollout_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed,
+                      uint64_t first_step, int32_t deterministic, float* obs_out_dev, float* act_out_dev,
+                      float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                      float* last_obs_dev, void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    qr::PolicyArgs A{};
+    if (int rc = rollout_policy_args(e, policy, K, log_std, noise_seed, first_step, deterministic, obs_out_dev, act_out_dev, logp_out_dev,
+                                     rew_out_dev, done_out_dev, "qr_rollout_policy", A))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool ev = want_events(e, st);
     if (ev) QR_HIP(hipEventRecord(e->ev0, st));
@@ -744,33 +780,46 @@ int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_ba
             return fail(QR_E_STATE, "qr_evaluate_policy_grid: slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
     }
     hipStream_t st = (hipStream_t)stream;
-    // the group map: interleaved (policy, condition) per group, in a device array of the handle.  An equal map is already there;
-    // another one is copied after a device synchronisation, like the tables (an earlier launch may still read the array), which a
-    // stream under capture does not allow.
     std::vector<int32_t> map(2 * (size_t)num_groups);
     for (int g = 0; g < num_groups; ++g) {
         map[2 * (size_t)g + 0] = policy_of_group[g];
         map[2 * (size_t)g + 1] = condition_of_group[g];
     }
-    if (!e->d_group_map || map != e->group_map_host) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(QR_E_STATE, "qr_evaluate_policy_grid: a new group map is uploaded after a device synchronisation, which a stream under "
-                                    "capture does not allow; call once with this map outside the capture");
-        QR_HIP(hipDeviceSynchronize());
-        e->group_map_host.clear();   // nothing valid on the device until the copy below has succeeded
-        if (num_groups > e->group_map_cap) {
-            if (e->d_group_map) (void)hipFree(e->d_group_map);
-            e->d_group_map = nullptr;
-            e->group_map_cap = 0;
-            QR_HIP(hipMalloc((void**)&e->d_group_map, sizeof(int2) * (size_t)num_groups));
-            e->group_map_cap = num_groups;
-        }
-        QR_HIP(hipMemcpy(e->d_group_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        e->group_map_host = map;
-    }
+    if (int rc = upload_group_map(e, map, num_groups, st, "qr_evaluate_policy_grid")) return rc;
     return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
                                        e->d_group_map, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
+}
+
+// The refusals come first and in full, as in qr_evaluate_policy_grid; the map travels in that call's (policy, condition) array with
+// the policy half zero.
+int qr_rollout_policy_conditions(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, int32_t num_groups, int32_t envs_per_group,
+                                 const int32_t* condition_of_group, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                                 int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
+                                 uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, void* stream) {
+    const char* who = "qr_rollout_policy_conditions";
+    if (int rc = check_ready(e)) return rc;
+    qr::PolicyArgs A{};
+    if (int rc = rollout_policy_args(e, policy, K, log_std, noise_seed, first_step, flags, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
+                                     done_out_dev, who, A))
+        return rc;
+    if (!conditions) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: null condition bank handle");
+    if (!condition_of_group) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: the group map is required");
+    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition bank of another variant");
+    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition bank on another GPU");
+    if (num_groups < 1) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: num_groups must be >= 1");
+    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", who)) return rc;
+    for (int g = 0; g < num_groups; ++g)
+        if (condition_of_group[g] < 0 || condition_of_group[g] >= conditions->capacity)
+            return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
+    for (int g = 0; g < num_groups; ++g)
+        if (!conditions->is_set[(size_t)condition_of_group[g]])
+            return fail(QR_E_STATE, "qr_rollout_policy_conditions: slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> map(2 * (size_t)num_groups, 0);
+    for (int g = 0; g < num_groups; ++g) map[2 * (size_t)g + 1] = condition_of_group[g];
+    if (int rc = upload_group_map(e, map, num_groups, st, who)) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_cond(e->cfg.variant, e->P, A, conditions->d_slots, e->d_group_map, num_groups, envs_per_group, K,
+                                       obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
 int qr_record_row_len(const qr_env* e) { return e ? e->S + QR_RECORD_EXTRA : QR_E_INVALID; }

@@ -132,6 +132,12 @@ hipError_t launch_eval_policy_bank(int variant, const Params& P, const half8* ba
 hipError_t launch_eval_policy_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const int2* map,
                                    bool f32class, int num_groups, int envs_per_group, int K, int32_t* rec, float* recf, hipStream_t st);
 
+// quadrace_rollout_cond.hip: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions): the workgroups of
+// group g fly under condition map[g].y (map[g].x is not read); conds = slot 0 of [capacity][kCondSlotFloats]
+hipError_t launch_rollout_policy_cond(int variant, const Params& P, const PolicyArgs& A, const float* conds, const int2* map, int num_groups,
+                                      int envs_per_group, int K, float* obs, float* act, float* logp, float* rew, uint8_t* done,
+                                      uint8_t* trunc, float* last_obs, hipStream_t st);
+
 // quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
 hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
 

@@ -285,7 +285,8 @@ class PPO:
     def __init__(self, env, n_steps=32, batch_size=None, n_epochs=5, gamma=0.999, gae_lambda=0.95, clip_range=0.2,
                  learning_rate=3e-4, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, net_arch=(120, 120, 120),
                  log_std_init=0.0, seed=0, target_kl=None, lr_final_frac=1.0, total_timesteps_hint=None,
-                 fused_collect=False, native_update=False, truncation_bootstrap=True, policy_forward="torch", update_precision="f16-operands"):
+                 fused_collect=False, native_update=False, truncation_bootstrap=True, policy_forward="torch", update_precision="f16-operands",
+                 conditions=None, envs_per_group=256, condition_weights=None):
         self.env = env
         self.n_envs, self.dev = env.num_envs, env.device
         self.n_steps, self.n_epochs = n_steps, n_epochs
@@ -317,7 +318,20 @@ class PPO:
         self._trunc_u8 = torch.empty((T, N), dtype=torch.uint8, device=self.dev)
         self.num_timesteps = 0
         self._kl_first_trips, self._kl_lr_scale = 0, 1.0
-        self.obs = env.reset_device().clone()
+        # conditions (a list of conditions.Condition): the collect phase flies a MIX of flight conditions in one launch
+        # (qr_rollout_policy_conditions): groups of envs_per_group envs, each under its own track / disturbances / time limit, shares by
+        # condition_weights (conditions.plan_condition_groups).  Fused collect only; everything behind the rollout buffers is unchanged.
+        self.conditions = self.condition_of_group = self._cond_bank = None
+        self.envs_per_group = int(envs_per_group)
+        if conditions is not None:
+            if not fused_collect:
+                raise ValueError("conditions need fused_collect=True: the mix of conditions exists in the closed-loop kernel only")
+            from .conditions import plan_condition_groups
+
+            self._set_conditions(list(conditions), plan_condition_groups(self.n_envs, len(conditions), self.envs_per_group, condition_weights))
+            self.obs = env.condition_reset(self.conditions, self.condition_of_group, self.envs_per_group).clone()
+        else:
+            self.obs = env.reset_device().clone()
         # on-device episode statistics (what VecMonitor provides in the reference, R:769)
         self.ep_ret = torch.zeros(N, **f32)
         self.ep_len = torch.zeros(N, **f32)
@@ -365,6 +379,51 @@ class PPO:
             self._term_obs = torch.zeros((T, N, obs_dim) if fused_collect else (N, obs_dim), **f32)
             env.set_terminal_obs_buffer(self._term_obs)
 
+    def _set_conditions(self, conditions, condition_of_group):
+        """The mix of flight conditions of collect_fused: the list, the group map and the device bank built from them."""
+        from .conditions import ConditionBank
+
+        if len(conditions) < 1:
+            raise ValueError("conditions must hold at least one Condition")
+        self.conditions, self.condition_of_group = conditions, [int(c) for c in condition_of_group]
+        self._cond_bank = ConditionBank(self.env.VARIANT, len(conditions), self.dev.index)
+        for slot, c in enumerate(conditions):
+            self._cond_bank.set(slot, c)
+        self._cond_ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)   # running episodes, carried between rollouts
+        self._cond_len = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)
+
+    @torch.no_grad()
+    def _condition_stats(self, rew, done, trunc):
+        """stats["per_condition"]: per condition, the episodes that ended in this rollout -- count, mean return and length (episodes
+        running across rollouts carry their sums), crashes (done & ~trunc) and time-limit ends.  A fixed number of torch operations
+        whatever n_steps is: the return of an episode ending at row t is a difference of the column's running sum."""
+        T, N, C_ = rew.shape[0], rew.shape[1], len(self.conditions)
+        d = done.to(torch.bool)
+        tr = trunc.to(torch.bool) & d
+        df = d.to(torch.float32)
+        rows = torch.arange(1, T + 1, device=self.dev, dtype=torch.long).unsqueeze(1)
+        last = torch.cummax(rows * d.to(torch.long), 0).values              # 1 + row of the latest end at or before t (0: none yet)
+        prev = torch.cat([torch.zeros((1, N), dtype=torch.long, device=self.dev), last[:-1]])   # ... strictly before t
+        csum = torch.cat([torch.zeros((1, N), dtype=torch.float32, device=self.dev), torch.cumsum(rew, 0)])
+        first = (prev == 0).to(torch.float32)
+        ep_ret = csum[1:] - csum.gather(0, prev) + first * self._cond_ret
+        ep_len = (rows - prev).to(torch.float32) + first * self._cond_len
+        per_env = torch.stack([df.sum(0), (ep_ret * df).sum(0), (ep_len * df).sum(0), (d & ~tr).to(torch.float32).sum(0),
+                               tr.to(torch.float32).sum(0)])
+        open_ = (last[-1:] == 0).to(torch.float32)
+        self._cond_ret = (csum[T:] - csum.gather(0, last[-1:]) + open_ * self._cond_ret).squeeze(0)
+        self._cond_len = ((T - last[-1:]).to(torch.float32) + open_ * self._cond_len).squeeze(0)
+        # per group on the device (a fixed-order sum: the same buffers give the same statistics), groups -> conditions on the host
+        per_group = per_env.view(5, -1, self.envs_per_group).sum(-1).tolist()
+        tot = [[0.0] * C_ for _ in range(5)]
+        for g, c in enumerate(self.condition_of_group):
+            for q in range(5):
+                tot[q][c] += per_group[q][g]
+        nan = float("nan")
+        self.stats["per_condition"] = [dict(name=c.name, episodes=int(tot[0][k]), mean_return=tot[1][k] / tot[0][k] if tot[0][k] else nan,
+                                            mean_length=tot[2][k] / tot[0][k] if tot[0][k] else nan, crashes=int(tot[3][k]),
+                                            time_limits=int(tot[4][k])) for k, c in enumerate(self.conditions)]
+
     @torch.no_grad()
     def _value_f32class_loader(self):
         """Load the current value network into the second policy-kernel handle (last layer [1, 120] zero-padded to [4, 120]) and return
@@ -398,10 +457,15 @@ class PPO:
         self._mfma.load_torch(self.policy.pi)
         first_step = self.noise_step
         self.noise_step += self.n_steps
-        obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_device(
-            self._mfma, self.n_steps, self.policy.log_std, noise_seed=self.noise_seed, first_step=first_step,
-            out=(self.buf_obs, self.buf_act, self.buf_lp, self.buf_rew, self._done_u8, self._trunc_u8),
-            precision="f32" if self.policy_forward == "f32class" else "f16-operands")
+        kw = dict(noise_seed=self.noise_seed, first_step=first_step,
+                  out=(self.buf_obs, self.buf_act, self.buf_lp, self.buf_rew, self._done_u8, self._trunc_u8),
+                  precision="f32" if self.policy_forward == "f32class" else "f16-operands")
+        if self.conditions is None:
+            obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_device(self._mfma, self.n_steps, self.policy.log_std, **kw)
+        else:
+            obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_conditions_device(
+                self._mfma, self._cond_bank, self.condition_of_group, self.envs_per_group, self.n_steps, self.policy.log_std, **kw)
+            self._condition_stats(rew, done, trunc)
         self.buf_done.copy_(done)
         T, N = self.n_steps, self.n_envs
         self.num_timesteps += T * N
@@ -693,7 +757,17 @@ class PPO:
         return dict(optimizer=opt, num_timesteps=int(self.num_timesteps), ep_ret=self.ep_ret.cpu(), ep_len=self.ep_len.cpu(),
                     ep_gates=self.ep_gates.cpu(), stats=dict(self.stats), noise_seed=int(self.noise_seed), noise_step=int(self.noise_step),
                     lr0=float(self.lr0), lr_final_frac=float(self.lr_final_frac), total_hint=self.total_hint,
-                    kl_trips=int(getattr(self, "_kl_first_trips", 0)), kl_lr_scale=float(getattr(self, "_kl_lr_scale", 1.0)), env=env, rng=self._gen.get_state())
+                    kl_trips=int(getattr(self, "_kl_first_trips", 0)), kl_lr_scale=float(getattr(self, "_kl_lr_scale", 1.0)), env=env, rng=self._gen.get_state(),
+                    conditions=self._conditions_state())
+
+    def _conditions_state(self):
+        """The mix of flight conditions as plain arrays and scalars (None without one): a resumed run flies the same mix."""
+        if self.conditions is None:
+            return None
+        fields = ("name", "gate_pos", "gate_yaw", "start_pos", "disturbance_ranges", "disturbance_scale", "max_steps", "gates_per_lap")
+        copy = lambda v: v.copy() if hasattr(v, "copy") else v
+        return dict(conditions=[{f: copy(getattr(c, f)) for f in fields} for c in self.conditions], condition_of_group=list(self.condition_of_group),
+                    envs_per_group=int(self.envs_per_group), ep_ret=self._cond_ret.cpu(), ep_len=self._cond_len.cpu())
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -721,6 +795,18 @@ class PPO:
         self._kl_lr_scale = float(sd.get("kl_lr_scale", 1.0))
         e = sd["env"]
         self.env.set_state_tensors(world=e["world"], dist=e["dist"], target=e["target"], steps=e["steps"], episode=e["episode"])
-        self.env.update_states()
+        cs = sd.get("conditions")
+        if cs is not None:
+            from .conditions import Condition
+
+            if not self.fused_collect:
+                raise ValueError("the checkpoint flies a mix of conditions: construct the PPO with fused_collect=True")
+            self.envs_per_group = int(cs["envs_per_group"])
+            self._set_conditions([Condition(**c) for c in cs["conditions"]], cs["condition_of_group"])
+            self._cond_ret.copy_(cs["ep_ret"]); self._cond_len.copy_(cs["ep_len"])
+            self.env._observe_under(self.conditions, self.condition_of_group, self.envs_per_group)
+        else:
+            self.conditions = self.condition_of_group = self._cond_bank = None
+            self.env.update_states()
         self.obs = self.env.states_tensor.clone()
         self._gen.set_state(sd["rng"])

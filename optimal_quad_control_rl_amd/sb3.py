@@ -185,6 +185,9 @@ class PPO:
                  native_update="auto",          # (+) minibatch updates in libquadrace's matrix-core kernels when the shapes allow
                  fused_collect="auto",          # (+) rollouts as one closed-loop kernel
                  precision=None,                # (+) "f16-operands" (default) | "f32": see below
+                 conditions=None,               # (+) a list of conditions.Condition: collect across this mix of flight conditions (fused collect)
+                 envs_per_group=256,            # (+) envs per group of the mix (a multiple of 256)
+                 condition_weights=None,        # (+) share of the groups per condition (None: equal)
                  _init_trainer=True):
         # precision: the throughput kernels (closed-loop collection, PPO update) compute with f16 matrix-core operands and f32 accumulation
         # (policy mean within 7e-4 of the reference's float32 nn_forward, gradient cosine >= 0.9985 against float32 autograd).
@@ -238,7 +241,8 @@ class PPO:
                                     max_grad_norm=max_grad_norm, net_arch=self.net_arch, log_std_init=self.log_std_init,
                                     seed=self.seed, target_kl=target_kl, fused_collect=fused, native_update=native,
                                     policy_forward="f32class" if (precision in ("f32", "f32-collect") and tuple(self.net_arch) == (120, 120, 120)) else "torch",
-                                    update_precision="f32" if precision == "f32" else "f16-operands")
+                                    update_precision="f32" if precision == "f32" else "f16-operands",
+                                    conditions=conditions, envs_per_group=envs_per_group, condition_weights=condition_weights)
             self._net = self._trainer.policy
             self.observation_dim = int(core.state_len)
         else:

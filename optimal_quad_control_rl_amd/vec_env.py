@@ -793,7 +793,72 @@ class Quadcopter3DGates(_Base):
         self._observe_under(conditions, cog, e)
         return self
 
-    RECORD_EXTRA = 8   # QR_RECORD_EXTRA of include/quadrace.h
+    def rollout_policy_conditions_device(self, policy, condition_bank, condition_of_group, envs_per_group, num_steps, log_std, noise_seed=0,
+                                         first_step=0, deterministic=False, out=None, precision="f16-operands"):
+        """rollout_policy_device across a MIX of flight conditions in ONE kernel (qr_rollout_policy_conditions): group g = envs
+        [g E, (g + 1) E), E = envs_per_group (a multiple of 256; len(condition_of_group) * E == num_envs), flies under slot
+        condition_of_group[g] of `condition_bank` (conditions.ConditionBank): track, start, disturbance ranges and scale and max_steps
+        are the condition's (its gates_per_lap is not used); residual weights, dt and gates_ahead this env's.  Reset stream and action
+        noise use the env's ORDINARY ids (unlike evaluate_grid_device): group g computes bit for bit what an E-env handle with
+        env_id_base + g E, configured with its condition, computes under rollout_policy_device (condition_reset gives the starts).
+        The E2E observation's disturbance terms are scaled by each condition's own ranges.  Same return tuple as
+        rollout_policy_device; a registered terminal-observation buffer is honoured."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_rollout_policy_conditions")
+        cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        if out is None:
+            out = (torch.empty((K, n, self.state_len), dtype=torch.float32, device=dev),
+                   torch.empty((K, n, 4), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.uint8, device=dev),
+                   torch.empty((K, n), dtype=torch.uint8, device=dev))
+        obs, act, logp, rew, done, trunc = out
+        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
+                                  dtype=np.float32).reshape(4)
+        _lib.check(fn(self._h, policy._h, condition_bank._h, int(cond.shape[0]), int(envs_per_group), cond.ctypes.data_as(C.POINTER(C.c_int32)),
+                      K, _f32p(ls), int(noise_seed), int(first_step), int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp),
+                      _ptr(rew), _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
+        self._last_obs = self._obs
+        return obs, act, logp, rew, done, trunc, self._obs
+
+    def condition_reset(self, conditions, condition_of_group, envs_per_group, seed=None):
+        """The training counterpart of condition_starts: reset every group g of E = envs_per_group envs under
+        conditions[condition_of_group[g]] with the env's ORDINARY ids.  Per distinct condition the handle takes the condition's track,
+        start, disturbances and max_steps, is seeded (s = `seed`, default: the seed this env was last seeded with) and reset over all N
+        envs, and the rows of the groups flying that condition are kept; then the env's own configuration is restored and the assembled
+        state set.  Group g then starts where an E-env handle with env_id_base + g E, configured with its condition, starts after
+        `seed(s); reset_device()` -- the twin of rollout_policy_conditions_device's contract.  Returns the observation tensor, rows of
+        group g as its condition observes them."""
+        e, n = int(envs_per_group), self.num_envs
+        cog = [int(c) for c in condition_of_group]
+        if e < 1 or len(cog) * e != n:
+            raise ValueError("len(condition_of_group) * envs_per_group must equal num_envs")
+        if any(c < 0 or c >= len(conditions) for c in cog):
+            raise ValueError("condition_of_group holds an index outside `conditions`")
+        s = self._seed if seed is None else int(seed)
+        state = None
+
+        def reset(c):
+            nonlocal state
+            self.seed(s)
+            self.reset_device()
+            fresh = self.get_state_tensors()
+            if state is None:
+                state = [None if t is None else torch.empty_like(t) for t in fresh]
+            for g, cg in enumerate(cog):
+                if cg == c:
+                    for dst, src in zip(state, fresh):
+                        if dst is not None:
+                            dst[g * e:(g + 1) * e].copy_(src[g * e:(g + 1) * e])
+
+        self._under_each_condition(conditions, cog, reset)
+        self.set_state_tensors(*state)
+        self._observe_under(conditions, cog, e)
+        return self._obs
+
+    RECORD_EXTRA = 8  # QR_RECORD_EXTRA of include/quadrace.h
 
     def record_policy_device(self, policy, num_steps, log_std, noise_seed=0, first_step=0, deterministic=True, rec_envs=None, out=None,
                              precision="f16-operands"):

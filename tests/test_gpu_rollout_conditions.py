@@ -1,0 +1,459 @@
+"""GPU: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions, rollout_policy_cond_kernel<V, GA, kF32>)
+against the closed-loop rollout itself (qr_rollout_policy), which the existing suite pins.  Group g of a launch must equal a 256-env
+twin handle that was configured with the group's condition through the ordinary Python setters, has env_id_base = g * 256, was seeded
+alike and flown by rollout_policy_device: start state, every output row, the terminal-observation rows, last_obs and the five state
+tensors bit-equal.  No tolerance anywhere.
+
+Shapes: N = 768 = 3 groups x 256 (group boundaries at workgroup boundaries, the only place they can be), K = 64.  The conditions:
+the handle's own; another track with another gate count (12 vs 16) and another start; the own track with max_steps = 40 < K and, for
+E2E, disturbance scale 2.  What must happen inside K steps is FORCED by arithmetic, not hoped for: rows 3, 70 and 255 of every group
+start 5 mm above the ground sinking at 2 m/s (z' = -0.005 + 0.01 * 2 > 0: a ground crash at the first step), rows 5 and 130 start
+1 cm in front of gate 0 at 3 m/s (x' = +0.02: a pass, the target moves), and no env can fall 1.5 m in 40 steps, so group 2 ends
+episodes by the time limit.  All three are asserted on the twins' own outputs, so a comparison of nothing with nothing fails."""
+import ctypes as C
+import statistics
+
+import numpy as np
+import pytest
+import torch
+
+import eval_spec as S
+from eval_helpers import SENTINEL, _closed_loop_layers, _group_equals, _ptr
+
+pytestmark = pytest.mark.gpu
+
+SC = S.SCENARIO
+E, G, K = 256, 3, 64
+LOG_STD = np.full(4, -1.0, np.float32)
+GROUND_ROWS, GATE_ROWS = (3, 70, 255), (5, 130)
+OTHER_RANGES = np.array([[0.01, 0.01], [-0.02, 0.04], [-0.015, 0.005], [-0.1, 0.1], [-0.05, 0.15], [-0.2, -0.2]], dtype=np.float32)
+
+
+def _other_track():
+    """12 gates 0.5 m apart, a little higher and off the axis, with another start"""
+    g = 12
+    pos = np.stack([0.5 * np.arange(g), np.full(g, 0.05), np.full(g, -1.4)], axis=1).astype(np.float32)
+    return pos, np.zeros(g, np.float32), np.asarray((-0.8, 0.1, -1.4), np.float32)
+
+
+def _conditions(variant):
+    from optimal_quad_control_rl_amd import TRAIN_DISTURBANCE_RANGES
+    from optimal_quad_control_rl_amd.conditions import Condition
+
+    a, b = S.scenario_track(), _other_track()
+    if variant == "e2e":
+        return [Condition("own", *a, TRAIN_DISTURBANCE_RANGES, 1.0, SC["max_steps"], 1),
+                Condition("other track", *b, OTHER_RANGES, 1.5, 180, 1),
+                Condition("short x2", *a, TRAIN_DISTURBANCE_RANGES, 2.0, 40, 1)]
+    return [Condition("own", *a, None, 1.0, SC["max_steps"], 2), Condition("other track", *b, None, 1.0, 180, 1),
+            Condition("short", *a, None, 1.0, 40, 2)]
+
+
+def _handle(variant, n, gates_ahead, cond, env_id_base=0, seed=SC["seed"]):
+    """an n-env handle configured with `cond` through the ordinary setters, seeded and reset"""
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, Quadcopter3DGatesINDI
+
+    trk = (cond.gate_pos, cond.gate_yaw, cond.start_pos)
+    if variant == "e2e":
+        env = Quadcopter3DGates(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none", env_id_base=env_id_base)
+        env.disturbance_ranges = cond.disturbance_ranges
+        env.disturbance_scale = cond.disturbance_scale
+    else:
+        env = Quadcopter3DGatesINDI(n, *trk, gates_ahead=gates_ahead, seed=seed, infos_mode="none", env_id_base=env_id_base)
+    env.max_steps = cond.max_steps
+    env.reset_device()
+    return env
+
+
+def _bank(variant, conds, capacity=None):
+    from optimal_quad_control_rl_amd.conditions import ConditionBank
+
+    bank = ConditionBank(0 if variant == "e2e" else 1, capacity or len(conds))
+    for slot, c in enumerate(conds):
+        bank.set(slot, c)
+    return bank
+
+
+def _policy(variant, obs_len):
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+
+    return MfmaPolicy(obs_len).set_weights(_closed_loop_layers(obs_len, np.asarray(SC[variant + "_action"], np.float32), seed=3))
+
+
+def _force_rows(env, groups):
+    """the forced starts of the module docstring, in every group of E rows of `env`"""
+    world = env.get_state_tensors()[0]
+    for g in range(groups):
+        for r in GROUND_ROWS:
+            world[g * E + r, 2] = -0.005
+            world[g * E + r, 5] = 2.0
+        for r in GATE_ROWS:
+            world[g * E + r, :6] = torch.tensor([-0.01, 0.0, -1.5, 3.0, 0.0, 0.0], device=world.device)
+    env.set_state_tensors(world=world)
+
+
+def _term_buffer(env, k):
+    tb = torch.full((k, env.num_envs, env.state_len), SENTINEL, device=env.device)
+    env.set_terminal_obs_buffer(tb)
+    return tb
+
+
+def _against_twins(variant, gates_ahead, precision, cog):
+    conds = _conditions(variant)
+    env = _handle(variant, G * E, gates_ahead, conds[0])
+    bank, pol = _bank(variant, conds), _policy(variant, env.state_len)
+    own = (env.gate_pos.copy(), env.start_pos.copy(), env.max_steps)
+    obs0 = env.condition_reset(conds, cog, E)
+    assert np.array_equal(own[0], env.gate_pos) and np.array_equal(own[1], env.start_pos) and own[2] == env.max_steps
+    start = env.get_state_tensors()
+    obs0 = obs0.clone()
+    _force_rows(env, G)
+    tb = _term_buffer(env, K)
+    out = env.rollout_policy_conditions_device(pol, bank, cog, E, K, LOG_STD, noise_seed=11, first_step=7, precision=precision)
+    out = [t.clone() for t in out]
+    after = env.get_state_tensors()
+    names = ("obs", "actions", "log-probs", "rewards", "dones", "truncs")
+    for g in range(G):
+        lo, hi = g * E, (g + 1) * E
+        twin = _handle(variant, E, gates_ahead, conds[cog[g]], env_id_base=lo)
+        _group_equals(start, twin, lo, hi, "condition_reset, group %d" % g)          # every group starts as its twin does
+        assert torch.equal(obs0[lo:hi], twin.states_tensor), ("condition_reset observation", g)
+        _force_rows(twin, 1)
+        ttb = _term_buffer(twin, K)
+        tout = twin.rollout_policy_device(pol, K, LOG_STD, noise_seed=11, first_step=7, precision=precision)
+        # non-vacuity, on the twin's own outputs
+        t_done, t_trunc, t_rew = tout[4].bool(), tout[5].bool(), tout[3]
+        crashes, limits, passes = int((t_done & ~t_trunc).sum()), int(t_trunc.sum()), int((t_rew > 5.0).sum())
+        moved = int((twin.get_state_tensors()[2] != 0).sum())
+        print(variant, gates_ahead, precision, "group", g, "condition", conds[cog[g]].name, "crashes", crashes, "time limits", limits,
+              "gate passes", passes, "targets off gate 0 at the end", moved)
+        assert crashes >= len(GROUND_ROWS) and passes >= 1, (g, crashes, passes)     # a pass is what moves the target gate (R:556)
+        assert bool(t_rew[0, list(GATE_ROWS)].gt(5.0).all()) and bool((t_done & ~t_trunc)[0, list(GROUND_ROWS)].all())
+        if conds[cog[g]].max_steps < K:
+            assert limits >= 1, (g, limits)
+        for name, x, y in zip(names, out, tout):
+            assert torch.equal(x[:, lo:hi], y), (name, g, int((x[:, lo:hi] != y).sum()))
+        assert torch.equal(out[6][lo:hi], tout[6]), ("last_obs", g)
+        assert torch.equal(tb[:, lo:hi], ttb), ("terminal-observation rows", g)
+        assert int((ttb[..., 0] != SENTINEL).sum()) == int(t_done.sum()) > 0         # one row per finished episode, the rest untouched
+        _group_equals(after, twin, lo, hi, "state after, group %d" % g)
+        twin.close()
+    env.close(); bank.close(); pol.close()
+
+
+_CASES = [(v, g, p) for v in ("e2e", "indi") for g in (0, 1) for p in ("f16-operands", "f32")]
+
+
+@pytest.mark.parametrize("variant,gates_ahead,precision", _CASES, ids=["%s-ga%d-%s" % c for c in _CASES])
+def test_every_group_equals_its_twin(variant, gates_ahead, precision):
+    _against_twins(variant, gates_ahead, precision, [0, 1, 2])
+
+
+@pytest.mark.parametrize("variant", ["e2e", "indi"])
+def test_a_permuted_map_with_a_repeated_condition_matches_the_twins(variant):
+    _against_twins(variant, 1, "f16-operands", [2, 0, 2])
+
+
+@pytest.mark.parametrize("variant", ["e2e", "indi"])
+@pytest.mark.parametrize("precision", ["f16-operands", "f32"])
+def test_own_condition_in_every_group_is_the_plain_rollout(variant, precision):
+    from optimal_quad_control_rl_amd.conditions import Condition
+
+    conds = _conditions(variant)
+    a, b = _handle(variant, G * E, 1, conds[0]), _handle(variant, G * E, 1, conds[0])
+    bank = _bank(variant, [conds[1], Condition.from_env(a)], capacity=3)             # slot 1 = the handle's own configuration
+    pol = _policy(variant, a.state_len)
+    _force_rows(a, G); _force_rows(b, G)
+    ta, tb = _term_buffer(a, K), _term_buffer(b, K)
+    oa = a.rollout_policy_conditions_device(pol, bank, [1, 1, 1], E, K, LOG_STD, noise_seed=5, first_step=3, precision=precision)
+    ob = b.rollout_policy_device(pol, K, LOG_STD, noise_seed=5, first_step=3, precision=precision)
+    assert int(ob[4].sum()) >= G * len(GROUND_ROWS) and int((ob[3] > 5.0).sum()) >= 1
+    for x, y in zip(oa, ob):
+        assert torch.equal(x, y)
+    assert torch.equal(ta, tb) and int((tb[..., 0] != SENTINEL).sum()) > 0
+    for x, y in zip(a.get_state_tensors(), b.get_state_tensors()):
+        assert x is None or torch.equal(x, y)
+    a.close(); b.close(); bank.close(); pol.close()
+
+
+@pytest.mark.parametrize("variant", ["e2e", "indi"])
+def test_one_call_equals_two_with_first_step_advanced(variant):
+    conds, cog, K1 = _conditions(variant), [0, 1, 2], 24
+    a, b = _handle(variant, G * E, 1, conds[0]), _handle(variant, G * E, 1, conds[0])
+    bank, pol = _bank(variant, conds), _policy(variant, a.state_len)
+    for e in (a, b):
+        e.condition_reset(conds, cog, E)
+        _force_rows(e, G)
+    oa = [t.clone() for t in a.rollout_policy_conditions_device(pol, bank, cog, E, K, LOG_STD, noise_seed=9, first_step=100)]
+    o1 = [t.clone() for t in b.rollout_policy_conditions_device(pol, bank, cog, E, K1, LOG_STD, noise_seed=9, first_step=100)]
+    o2 = b.rollout_policy_conditions_device(pol, bank, cog, E, K - K1, LOG_STD, noise_seed=9, first_step=100 + K1)
+    assert int(oa[5][K1:].sum()) >= 1 and int(oa[4][:K1].sum()) >= 1                 # ends on both sides of the cut
+    for x, y1, y2 in zip(oa[:6], o1[:6], o2[:6]):
+        assert torch.equal(x, torch.cat([y1, y2]))
+    assert torch.equal(oa[6], o2[6])
+    for x, y in zip(a.get_state_tensors(), b.get_state_tensors()):
+        assert x is None or torch.equal(x, y)
+    a.close(); b.close(); bank.close(); pol.close()
+
+
+def test_refusals_launch_nothing():
+    """Host-side argument checks only: nothing invalid is ever launched or copied."""
+    from optimal_quad_control_rl_amd import _lib
+    from optimal_quad_control_rl_amd.conditions import ConditionBank
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+
+    Kr, n = 8, 2 * E
+    conds = _conditions("indi")
+    env = _handle("indi", n, 1, conds[0])
+    L = env._L
+    pol = _policy("indi", env.state_len)
+    bank = _bank("indi", conds[:2], capacity=3)                                       # slots 0, 1 set, slot 2 never set
+    dev = env.device
+    bufs = dict(obs=torch.full((Kr, n, env.state_len), SENTINEL, device=dev), act=torch.full((Kr, n, 4), SENTINEL, device=dev),
+                logp=torch.full((Kr, n), SENTINEL, device=dev), rew=torch.full((Kr, n), SENTINEL, device=dev),
+                done=torch.full((Kr, n), 7, dtype=torch.uint8, device=dev), trunc=torch.full((Kr, n), 7, dtype=torch.uint8, device=dev),
+                last=torch.full((n, env.state_len), SENTINEL, device=dev))
+    before = env.get_state_tensors()
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    SKIP = object()
+
+    def call(e=env, p=pol, cb=bank, g=2, epg=E, cog=(1, 0), k=Kr, ls=LOG_STD, flags=0, **null):
+        ca = None if cog is None else np.asarray(cog, np.int32)
+        b = {name: (None if null.get(name, SKIP) is None else t) for name, t in bufs.items()}
+        return L.qr_rollout_policy_conditions(e._h, p._h if p is not None else None, cb._h if cb is not None else None, g, epg,
+                                              None if ca is None else ca.ctypes.data_as(i32p), k, None if ls is None else ls.ctypes.data_as(f32p),
+                                              3, 0, flags, _ptr(b["obs"]), _ptr(b["act"]), _ptr(b["logp"]), _ptr(b["rew"]), _ptr(b["done"]),
+                                              _ptr(b["trunc"]), _ptr(b["last"]), e._stream())
+
+    def untouched():
+        torch.cuda.synchronize()
+        for name, t in bufs.items():
+            assert bool((t == (7 if t.dtype == torch.uint8 else SENTINEL)).all()), name
+        for x, y in zip(before, env.get_state_tensors()):
+            assert x is None or torch.equal(x, y)
+
+    def refused(code, **kw):
+        rc = call(**kw)
+        assert rc == code, (list(kw.keys()), rc, L.qr_last_error())
+        assert len(L.qr_last_error()) > 0
+        untouched()
+
+    # everything qr_rollout_policy refuses
+    refused(_lib.QR_E_INVALID, k=0)
+    refused(_lib.QR_E_INVALID, k=-2)
+    refused(_lib.QR_E_INVALID, p=None)
+    refused(_lib.QR_E_INVALID, ls=None)
+    for name in ("obs", "act", "logp", "rew", "done"):
+        refused(_lib.QR_E_INVALID, **{name: None})
+    refused(_lib.QR_E_INVALID, flags=4)
+    refused(_lib.QR_E_INVALID, flags=-1)
+    empty = MfmaPolicy(env.state_len)
+    refused(_lib.QR_E_STATE, p=empty)                                                 # a policy without weights
+    empty.close()
+    other_len = _policy("indi", env.state_len + 4)
+    refused(_lib.QR_E_INVALID, p=other_len)
+    other_len.close()
+    small = torch.full((Kr - 1, n, env.state_len), SENTINEL, device=dev)
+    env.set_terminal_obs_buffer(small)
+    refused(_lib.QR_E_INVALID)                                                        # K exceeds the rows of the registered buffer
+    assert bool((small == SENTINEL).all())
+    env.set_terminal_obs_buffer(None)
+    env.pause = True
+    refused(_lib.QR_E_STATE)
+    env.pause = False
+    env.pause_if_collision = True
+    refused(_lib.QR_E_STATE)
+    env.pause_if_collision = False
+    # its own
+    refused(_lib.QR_E_INVALID, cb=None)
+    refused(_lib.QR_E_INVALID, cog=None)
+    refused(_lib.QR_E_INVALID, g=0, cog=())
+    refused(_lib.QR_E_INVALID, g=-1)
+    refused(_lib.QR_E_INVALID, epg=0)
+    refused(_lib.QR_E_INVALID, epg=128, g=4, cog=(0, 1, 0, 1))                        # < 256 (4 x 128 == n)
+    refused(_lib.QR_E_INVALID, epg=384)                                               # not a multiple of 256
+    refused(_lib.QR_E_INVALID, g=1, cog=(0,))                                         # G E != n
+    refused(_lib.QR_E_INVALID, g=3, cog=(0, 1, 0))
+    refused(_lib.QR_E_INVALID, g=1, epg=1024, cog=(0,))
+    refused(_lib.QR_E_INVALID, cog=(3, 0))                                            # outside the bank's capacity
+    refused(_lib.QR_E_INVALID, cog=(0, -1))
+    refused(_lib.QR_E_INVALID, cog=(0, 2 ** 31 - 1))
+    refused(_lib.QR_E_STATE, cog=(2, 0))                                              # a referenced slot that was never set
+    assert b"never set" in L.qr_last_error()
+    e2e_bank = ConditionBank(0, 2)
+    e2e_bank.set(0, _conditions("e2e")[0]); e2e_bank.set(1, _conditions("e2e")[1])
+    refused(_lib.QR_E_INVALID, cb=e2e_bank)                                           # a bank of another variant
+    assert b"variant" in L.qr_last_error()
+    e2e_bank.close()
+    if torch.cuda.device_count() > 1:
+        far = ConditionBank(1, 2, device=1)
+        far.set(0, conds[0]); far.set(1, conds[1])
+        torch.cuda.set_device(0)
+        refused(_lib.QR_E_INVALID, cb=far)                                            # ... or of another device
+        far.close()
+    # a new map while the stream is being captured
+    side = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(side):
+        assert call(cog=(0, 1)) == _lib.QR_OK                                         # this map is on the device now
+        for t in bufs.values():
+            t.fill_(7 if t.dtype == torch.uint8 else SENTINEL)
+        env.set_state_tensors(*before)
+        graph = torch.cuda.CUDAGraph()
+        graph.capture_begin()
+        rc_new = call(cog=(1, 1))
+        err = L.qr_last_error()
+        graph.capture_end()
+    assert rc_new == _lib.QR_E_STATE and b"capture" in err
+    untouched()
+    # ... and a valid call runs, writes every row, and reports its time; the trunc buffer and last_obs are optional
+    assert call(trunc=None, last=None) == _lib.QR_OK
+    torch.cuda.synchronize()
+    assert bool((bufs["obs"] != SENTINEL).all()) and bool((bufs["done"] <= 1).all()) and bool((bufs["trunc"] == 7).all())
+    assert bool((bufs["last"] == SENTINEL).all()) and env.last_rollout_ms() > 0.0
+    env.close(); bank.close(); pol.close()
+
+
+def _ppo_env(seed=21):
+    conds = _conditions("e2e")
+    env = _handle("e2e", G * E, 1, conds[0], seed=seed)
+    return env, [conds[0], conds[1], conds[2].replace(max_steps=10)]
+
+
+def test_ppo_collects_across_conditions():
+    from optimal_quad_control_rl_amd.conditions import plan_condition_groups
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import PPO
+
+    T = 16
+    env, conds = _ppo_env()
+    model = PPO(env, n_steps=T, seed=4, fused_collect=True, native_update=True, conditions=conds, envs_per_group=E)
+    assert model.condition_of_group == plan_condition_groups(G * E, 3, E) == [0, 1, 2]
+    with pytest.raises(ValueError):
+        PPO(env, n_steps=T, seed=4, fused_collect=False, conditions=conds)
+    # the start is condition_reset's; one collect_fused = the direct call for the same seed and step
+    ref, _ = _ppo_env()
+    ref.condition_reset(conds, [0, 1, 2], E)
+    for x, y in zip(env.get_state_tensors(), ref.get_state_tensors()):
+        assert torch.equal(x, y)
+    _force_rows(env, G); _force_rows(ref, G)
+    bank = _bank("e2e", conds)
+    pol = MfmaPolicy(env.state_len).load_torch(model.policy.pi)
+    want = ref.rollout_policy_conditions_device(pol, bank, [0, 1, 2], E, T, model.policy.log_std, noise_seed=model.noise_seed, first_step=0)
+    model.collect_fused()
+    got = (model.buf_obs, model.buf_act, model.buf_lp, model.buf_rew, model._done_u8, model._trunc_u8)
+    for name, x, y in zip(("obs", "act", "logp", "rew", "done", "trunc"), got, want):
+        assert torch.equal(x, y), name
+    # per-condition statistics against a NumPy recount of the buffers
+    done, trunc = model._done_u8.cpu().numpy().astype(bool), model._trunc_u8.cpu().numpy().astype(bool)
+    rew = model.buf_rew.cpu().numpy().astype(np.float64)
+    stats = model.stats["per_condition"]
+    assert [s["name"] for s in stats] == [c.name for c in conds]
+    for c, s in enumerate(stats):
+        d, t, r = done[:, c * E:(c + 1) * E], trunc[:, c * E:(c + 1) * E], rew[:, c * E:(c + 1) * E]
+        assert s["episodes"] == int(d.sum()) and s["crashes"] == int((d & ~t).sum()) and s["time_limits"] == int((d & t).sum()), (c, s)
+        assert s["crashes"] >= len(GROUND_ROWS)
+        rets, lens = [], []
+        for i in range(E):
+            acc, n = 0.0, 0
+            for k in range(T):
+                acc += r[k, i]; n += 1
+                if d[k, i]:
+                    rets.append(acc); lens.append(n); acc, n = 0.0, 0
+        assert s["mean_length"] == pytest.approx(np.mean(lens), rel=1e-5) and s["mean_return"] == pytest.approx(np.mean(rets), rel=1e-4, abs=1e-4)
+    assert stats[2]["time_limits"] >= E - len(GROUND_ROWS)                             # max_steps = 10 < T
+    model.train()
+    # two more rollouts at n_steps = 16 leave finite parameters
+    model.learn(model.num_timesteps + 2 * T * G * E, log_every=0)
+    assert all(bool(torch.isfinite(p).all()) for p in model.policy.parameters())
+    # state_dict -> load_state_dict restores the map and the conditions, and the resumed trainer collects the same rollout
+    sd, params = model.state_dict(), {k: v.clone() for k, v in model.policy.state_dict().items()}
+    env2, _ = _ppo_env()
+    model2 = PPO(env2, n_steps=T, seed=4, fused_collect=True, native_update=True, conditions=[conds[1], conds[0]], envs_per_group=E,
+                 condition_weights=[2, 1])
+    assert model2.condition_of_group == [0, 0, 1]
+    model2.policy.load_state_dict(params)
+    model2.load_state_dict(sd)
+    assert model2.condition_of_group == [0, 1, 2] and [c.name for c in model2.conditions] == [c.name for c in conds]
+    for x, y in zip(model2.conditions, conds):
+        assert np.array_equal(x.gate_pos, y.gate_pos) and np.array_equal(x.start_pos, y.start_pos) and x.max_steps == y.max_steps
+        assert np.array_equal(x.disturbance_ranges, y.disturbance_ranges) and x.disturbance_scale == y.disturbance_scale
+    model.collect_fused(); model2.collect_fused()
+    for x, y in zip((model.buf_obs, model.buf_act, model.buf_rew, model._done_u8), (model2.buf_obs, model2.buf_act, model2.buf_rew, model2._done_u8)):
+        assert torch.equal(x, y)
+    assert repr(model.stats["per_condition"]) == repr(model2.stats["per_condition"])      # (repr: a condition without an ended episode has nan means)
+    for e in (env, ref, env2):
+        e.close()
+    bank.close(); pol.close()
+
+
+def test_ppo_without_conditions_is_unchanged():
+    """Without `conditions` collect_fused still calls rollout_policy_device, and the buffers are that call's."""
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import PPO
+
+    T = 16
+    env, _ = _ppo_env()
+    ref, _ = _ppo_env()
+    ref.reset_device()                                                                 # the trainer resets its env once more
+    model = PPO(env, n_steps=T, seed=4, fused_collect=True, native_update=True)
+    for x, y in zip(env.get_state_tensors(), ref.get_state_tensors()):
+        assert torch.equal(x, y)
+    assert model.conditions is None and "conditions" in model.state_dict() and model.state_dict()["conditions"] is None
+    calls = []
+    plain, mixed = env.rollout_policy_device, env.rollout_policy_conditions_device
+    env.rollout_policy_device = lambda *a, **k: (calls.append("plain"), plain(*a, **k))[1]
+    env.rollout_policy_conditions_device = lambda *a, **k: (calls.append("conditions"), mixed(*a, **k))[1]
+    pol = MfmaPolicy(env.state_len).load_torch(model.policy.pi)
+    ref.set_terminal_obs_buffer(torch.zeros((T, G * E, env.state_len), device=env.device))
+    want = ref.rollout_policy_device(pol, T, model.policy.log_std, noise_seed=model.noise_seed, first_step=0)
+    model.collect_fused()
+    assert calls == ["plain"] and "per_condition" not in model.stats
+    for x, y in zip((model.buf_obs, model.buf_act, model.buf_lp, model.buf_rew, model._done_u8, model._trunc_u8), want):
+        assert torch.equal(x, y)
+    env.close(); ref.close(); pol.close()
+
+
+def test_conditions_launch_not_slower_than_the_plain_rollout():
+    """The per-step work of a workgroup is rollout_policy_kernel's; one map load, a dozen scalar loads of the header and a condition
+    image staged in place of the handle's differ, once per launch.  N = 65 536 = 256 groups x 256 envs, four conditions round-robin
+    (disturbance scales 0.5, 1, 2 and the zigzag track), E2E + residual MLPs + training disturbances, K = 1 000; against
+    qr_rollout_policy on the same handle in the same process: alternating launches from the same seeded reset, one warm-up pair, medians
+    of 5 (f32: of 3), times from qr_last_step_many_ms.  f16 operands: <= 1.03 x (the margin DESIGN section 8 asserts for the grid launch
+    over the bank launch, for the same added work).  The f32 ratio is printed WITHOUT a bound."""
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, TRAIN_DISTURBANCE_RANGES, disturbance_sweep, square_track, zigzag_track
+    from optimal_quad_control_rl_amd.conditions import Condition
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    n, Kc = 65536, 1000
+    env = Quadcopter3DGates(n, *square_track(), gates_ahead=1, infos_mode="none", seed=99)
+    env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    zz = zigzag_track()
+    conds = disturbance_sweep(env, [0.5, 1.0, 2.0]) + [Condition.from_env(env, name="zigzag", gate_pos=zz[0], gate_yaw=zz[1], start_pos=zz[2])]
+    bank = _bank("e2e", conds)
+    cog = [g % 4 for g in range(n // E)]
+    torch.manual_seed(0)
+    pol = MfmaPolicy(env.state_len).load_torch(ActorCritic(env.state_len, 4).pi)
+    dev = env.device
+    out = (torch.empty((Kc, n, env.state_len), device=dev), torch.empty((Kc, n, 4), device=dev), torch.empty((Kc, n), device=dev),
+           torch.empty((Kc, n), device=dev), torch.empty((Kc, n), dtype=torch.uint8, device=dev), torch.empty((Kc, n), dtype=torch.uint8, device=dev))
+    log_std = np.zeros(4, np.float32)
+    medians = {}
+    for precision, reps in (("f16-operands", 6), ("f32", 4)):
+        t_new, t_old = [], []
+        for rep in range(reps):
+            env.seed(99); env.reset_device()
+            env.rollout_policy_conditions_device(pol, bank, cog, E, Kc, log_std, noise_seed=1, out=out, precision=precision)
+            ms_n = env.last_rollout_ms()
+            env.seed(99); env.reset_device()
+            env.rollout_policy_device(pol, Kc, log_std, noise_seed=1, out=out, precision=precision)
+            ms_o = env.last_rollout_ms()
+            if rep:
+                t_new.append(ms_n * 1e3 / Kc); t_old.append(ms_o * 1e3 / Kc)
+        mn, mo = statistics.median(t_new), statistics.median(t_old)
+        medians[precision] = (mn, mo)
+        print("%s: qr_rollout_policy_conditions %s -> median %.4f us/step; qr_rollout_policy %s -> median %.4f us/step; ratio %.4f"
+              % (precision, ["%.4f" % t for t in t_new], mn, ["%.4f" % t for t in t_old], mo, mn / mo))
+    env.close(); bank.close(); pol.close()
+    mn, mo = medians["f16-operands"]
+    assert mn <= 1.03 * mo, (mn, mo, mn / mo)

@@ -2,174 +2,237 @@
 """BASELINE config 5: PPO on the MI355X race env (GPU box).
 
     python tools/train_ppo.py [--variant indi|e2e] [--envs 65536] [--steps 3e8] [--track square|zigzag]
+        [--fused --train-scales 0.5,1,2] [--fused --train-tracks square,zigzag]
+
+--train-scales / --train-tracks (with --fused): the collect phase flies a MIX of flight conditions in one launch
+(PPO(conditions=...) -> qr_rollout_policy_conditions): one condition per disturbance scale (E2E only), per named track (its own start
+and lap length), or per (track, scale) pair when both are given.  The log then carries one line per condition, and --eval-final adds the
+final policy's robustness table over the same conditions (evaluate_grid).
 
 Prints training progress and a final deterministic evaluation on the 4-gate square track: gates per 12 s from a standing
 start, and lap times the way the reference tabulates them (FP:3474-3488: lap 1 from the start, then the flying laps; its
 simulated E2E policy flies 2.97 s then 2.51-2.59 s, INDI 3.20 s then 2.75-2.82 s)."""
 import argparse, os, sys, time, json
-import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from optimal_quad_control_rl_amd import (Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES,
-                                         square_track, zigzag_track)
-from optimal_quad_control_rl_amd.ppo import PPO
-
-ap = argparse.ArgumentParser()
-ap.add_argument("--variant", default="indi")
-ap.add_argument("--track", default="square")
-ap.add_argument("--envs", type=int, default=65536)
-ap.add_argument("--steps", type=float, default=3e8)
-ap.add_argument("--n-steps", type=int, default=32)
-ap.add_argument("--epochs", type=int, default=5)
-ap.add_argument("--minibatches", type=int, default=4)
-ap.add_argument("--lr", type=float, default=3e-4)
-ap.add_argument("--target-kl", type=float, default=0.02)
-ap.add_argument("--lr-final", type=float, default=0.1)
-ap.add_argument("--fused", action="store_true", help="collect with the closed-loop rollout kernel (qr_rollout_policy)")
-ap.add_argument("--native-update", action="store_true", help="minibatch updates in the matrix-core kernels (qr_ppo_minibatch)")
-ap.add_argument("--precision", default="f16-operands", choices=("f16-operands", "f32-collect", "f32"),
-                help="f32: the reference-precision kernels for collect, values and update (needs --fused --native-update); f32-collect: collect only")
-ap.add_argument("--ent-coef", type=float, default=0.0)
-ap.add_argument("--gamma", type=float, default=0.999)
-ap.add_argument("--seed", type=int, default=0)
-ap.add_argument("--no-trunc-bootstrap", action="store_true", help="round-1 behaviour: a time-limit truncation is a termination")
-ap.add_argument("--eval-final", action="store_true", help="evaluate the FINAL policy (no best-by-training-statistic checkpoint)")
-ap.add_argument("--save", default="", help="save an SB3-shaped checkpoint (optimal_quad_control_rl_amd.sb3 format) of the final model here")
-ap.add_argument("--curve", type=int, default=0, help="evaluate the current policy every this many rollouts (training clock stopped)")
-ap.add_argument("--lap-target", type=float, default=2.6, help="flying lap (s) that counts as the reference's level for --curve")
-ap.add_argument("--device-eval", action="store_true", help="evaluate with the on-device evaluator (evaluate_policy -> qr_evaluate_policy: two launches, gate passes "
-                "detected from the target gate) instead of the per-step loop below; opt-in, because committed profiles quote the loop's numbers")
-ap.add_argument("--out", default="")
-a = ap.parse_args()
-
-# one process per GPU under torchrun (data-parallel PPO: --envs is per GPU, env_id_base = rank * envs keys disjoint reset and
-# action-noise streams; gradients are averaged per minibatch, see MfmaPpoUpdater.minibatch)
-rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
-if "RANK" in os.environ:
-    import torch.distributed as dist
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    torch.cuda.set_device(local_rank)
-    dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    assert a.native_update, "data-parallel training uses the matrix-core update (--native-update)"
-if rank != 0:
-    sys.stdout = open(os.devnull, "w")
-
-trk = square_track() if a.track == "square" else zigzag_track()
-cls = Quadcopter3DGates if a.variant == "e2e" else Quadcopter3DGatesINDI
-env = cls(a.envs, *trk, gates_ahead=1, infos_mode="none", seed=1 + a.seed, env_id_base=rank * a.envs)
-if a.variant == "e2e":
-    env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
-model = PPO(env, seed=a.seed, ent_coef=a.ent_coef, gamma=a.gamma, n_steps=a.n_steps, n_epochs=a.epochs, batch_size=a.envs * a.n_steps // a.minibatches, learning_rate=a.lr,
-            target_kl=a.target_kl, lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps) // world, fused_collect=a.fused,
-            native_update=a.native_update, truncation_bootstrap=not a.no_trunc_bootstrap,
-            policy_forward="f32class" if a.precision != "f16-operands" else "torch", update_precision="f32" if a.precision == "f32" else "f16-operands")
-if "RANK" in os.environ:
-    model._updater.broadcast_parameters(0)   # identical start on every rank (the seed already makes it so; this guarantees it)
-    model.noise_seed = a.seed                 # same key, different global env ids -> independent action noise per rank
-# deterministic evaluation on a separate env: 2000 steps = 20 s of flight (six laps), crashes auto-reset and restart the lap count
-n_eval = 4096
-ev = cls(n_eval, *trk, gates_ahead=1, infos_mode="none", seed=99)
-if a.variant == "e2e":
-    ev.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
-ev.max_steps = 10 ** 6
-G = 4 if a.track == "square" else len(trk[0])   # square_track() lists its four gates twice: a lap is four passes
-dt = 0.01
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from robustness_sweep import condition_name, format_table, parse_scales, parse_tracks   # the sweep tool's argument forms and table
 
 
-@torch.no_grad()
-def evaluate(m):
-    ev.seed(99)
-    obs = ev.reset_device()
-    dev = obs.device
-    gates12 = torch.zeros(n_eval, device=dev); crashes12 = torch.zeros(n_eval, device=dev)
-    passed = torch.zeros(n_eval, device=dev)            # gates passed since this env's last (re)start
-    lap_start = torch.zeros(n_eval, device=dev)         # time of the last lap boundary (or restart)
-    lap_sum = torch.zeros(7, device=dev); lap_cnt = torch.zeros(7, device=dev)   # laps 1..6 (index 0 unused)
-    for k in range(2000):
-        obs, rew, done, trunc = ev.step_device(m.act_device(obs).contiguous())
-        t = (k + 1) * dt
-        g = (rew > 5).float()
-        if k < 1200:
-            gates12 += g; crashes12 += (done.float() - trunc.float()).clamp(min=0)
-        passed += g
-        lap_done = (g > 0) & (passed % G == 0) & (passed > 0)
-        lap_no = (passed / G).long().clamp(max=6)
-        if lap_done.any():
-            sel = lap_done & (passed / G <= 6)
-            lap_sum.index_add_(0, lap_no[sel], (t - lap_start)[sel])
-            lap_cnt.index_add_(0, lap_no[sel], torch.ones_like(lap_start)[sel])
-            lap_start = torch.where(lap_done, torch.full_like(lap_start, t), lap_start)
-        d = done.bool()
-        passed = torch.where(d, torch.zeros_like(passed), passed)
-        lap_start = torch.where(d, torch.full_like(lap_start, t), lap_start)
-    laps = (lap_sum / lap_cnt.clamp(min=1)).tolist()
-    return dict(eval_gates_per_12s=float(gates12.mean()), eval_crashes_per_12s=float(crashes12.mean()),
-                eval_seconds_per_gate=float(1200 * dt / gates12.mean().clamp(min=1e-9)),
-                eval_seconds_per_lap_4gates=float(4 * 1200 * dt / gates12.mean().clamp(min=1e-9)),
-                eval_lap_seconds={f"lap{i}": laps[i] for i in range(1, 7)}, eval_laps_counted=lap_cnt[1:].tolist(),
-                eval_flying_lap_seconds=float(lap_sum[2:].sum() / lap_cnt[2:].sum().clamp(min=1)))
+def train_conditions(env, variant, scales=None, tracks=None):
+    """The conditions of --train-scales / --train-tracks (parsed lists or None) around `env`'s own configuration: None without
+    either; one per scale ("scale=<s>", disturbance_sweep); one per track (named after it, with its own start and lap length); the
+    product, track-major ("<track> x<s>"), when both are given."""
+    from optimal_quad_control_rl_amd import Condition, disturbance_sweep, square_track, zigzag_track
+
+    if scales is None and tracks is None:
+        return None
+    if scales is not None and variant != "e2e":
+        raise SystemExit("--train-scales needs --variant e2e: the INDI variant has no disturbances")
+    if tracks is None:
+        return disturbance_sweep(env, scales)
+    track_of = {"square": square_track, "zigzag": zigzag_track}
+    conds = []
+    for t in tracks:
+        gate_pos, gate_yaw, start_pos = track_of[t]()
+        base = Condition.from_env(env, name=t, gate_pos=gate_pos, gate_yaw=gate_yaw, start_pos=start_pos)
+        conds += [base] if scales is None else [base.replace(name=condition_name(t, s), disturbance_scale=s) for s in scales]
+    return conds
 
 
-def evaluate_on_device(m):
-    """the same protocol and keys through evaluate_policy: 1 200-step window for the rates, 2 000 steps for the lap times"""
-    from optimal_quad_control_rl_amd import evaluate_policy
-    r = evaluate_policy(m, ev, n_eval_steps=2000, window_steps=1200, gates_per_lap=G, seed=99)
-    w, t = r["window"], r["total"]
-    g12 = max(w["gates_per_window"], 1e-9)
-    return dict(eval_gates_per_12s=w["gates_per_window"], eval_crashes_per_12s=w["crashes_per_window"], eval_seconds_per_gate=1200 * dt / g12,
-                eval_seconds_per_lap_4gates=4 * 1200 * dt / g12,
-                eval_lap_seconds={f"lap{i}": (t["lap_seconds"][i - 1] or 0.0) for i in range(1, 7)}, eval_laps_counted=[float(c) for c in t["laps_counted"][:6]],
-                eval_flying_lap_seconds=t["flying_lap_seconds"] or 0.0, eval_mean_reward=t["mean_reward"], evaluator="device")
+def format_condition_stats(per_condition):
+    """one line per entry of PPO.stats["per_condition"]"""
+    return "\n".join("     %-16s episodes %7d  ep_rew %8.2f  ep_len %7.1f  crashes %7d  time limits %6d"
+                     % (c["name"], c["episodes"], c["mean_return"], c["mean_length"], c["crashes"], c["time_limits"]) for c in per_condition)
 
 
-if a.device_eval:
-    evaluate = evaluate_on_device
+def main():
+    import torch
+    from optimal_quad_control_rl_amd import (Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES,
+                                             square_track, zigzag_track)
+    from optimal_quad_control_rl_amd.ppo import PPO
 
-best = {"gates": -1.0, "state": None}
-def keep_best(m):
-    g = m.stats.get("gates_per_episode", 0.0)
-    if g > best["gates"] and m.stats.get("ep_len_mean", 0) > 600:
-        best["gates"] = g
-        best["state"] = {k: v.clone() for k, v in m.policy.state_dict().items()}
-# --curve K: every K rollouts the CURRENT policy is evaluated (clock stopped) -> wall-clock-to-quality curve (BASELINE config 5's metric)
-curve, paused, it_no = [], [0.0], [0]
-def on_rollout(m):
-    if not a.eval_final:
-        keep_best(m)
-    it_no[0] += 1
-    if a.curve and it_no[0] % a.curve == 0 and rank == 0:
-        torch.cuda.synchronize()
-        e0 = time.perf_counter()
-        tsec = e0 - t0 - paused[0]
-        r = evaluate(m)
-        torch.cuda.synchronize()
-        paused[0] += time.perf_counter() - e0
-        curve.append(dict(train_seconds=tsec, env_steps=m.num_timesteps * world,
-                          flying_lap=r["eval_flying_lap_seconds"], crashes_per_12s=r["eval_crashes_per_12s"], gates_per_12s=r["eval_gates_per_12s"]))
-t0 = time.perf_counter()
-model.learn(int(a.steps) // world, log_every=20, callback=on_rollout)   # --steps counts env-steps of the whole job
-if best["state"] is not None and not a.eval_final:
-    model.policy.load_state_dict(best["state"])  # evaluate the best checkpoint (the reference saves one every 10 rollouts, R:823)
-torch.cuda.synchronize()
-train_s = time.perf_counter() - t0 - paused[0]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", default="indi")
+    ap.add_argument("--track", default="square")
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--steps", type=float, default=3e8)
+    ap.add_argument("--n-steps", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=5)
+    ap.add_argument("--minibatches", type=int, default=4)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--target-kl", type=float, default=0.02)
+    ap.add_argument("--lr-final", type=float, default=0.1)
+    ap.add_argument("--fused", action="store_true", help="collect with the closed-loop rollout kernel (qr_rollout_policy)")
+    ap.add_argument("--native-update", action="store_true", help="minibatch updates in the matrix-core kernels (qr_ppo_minibatch)")
+    ap.add_argument("--precision", default="f16-operands", choices=("f16-operands", "f32-collect", "f32"),
+                    help="f32: the reference-precision kernels for collect, values and update (needs --fused --native-update); f32-collect: collect only")
+    ap.add_argument("--ent-coef", type=float, default=0.0)
+    ap.add_argument("--gamma", type=float, default=0.999)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--no-trunc-bootstrap", action="store_true", help="round-1 behaviour: a time-limit truncation is a termination")
+    ap.add_argument("--eval-final", action="store_true", help="evaluate the FINAL policy (no best-by-training-statistic checkpoint)")
+    ap.add_argument("--save", default="", help="save an SB3-shaped checkpoint (optimal_quad_control_rl_amd.sb3 format) of the final model here")
+    ap.add_argument("--curve", type=int, default=0, help="evaluate the current policy every this many rollouts (training clock stopped)")
+    ap.add_argument("--lap-target", type=float, default=2.6, help="flying lap (s) that counts as the reference's level for --curve")
+    ap.add_argument("--device-eval", action="store_true", help="evaluate with the on-device evaluator (evaluate_policy -> qr_evaluate_policy: two launches, gate passes "
+                    "detected from the target gate) instead of the per-step loop below; opt-in, because committed profiles quote the loop's numbers")
+    ap.add_argument("--train-scales", default="", help="with --fused: train on one condition per disturbance scale, e.g. 0.5,1,2 (E2E only)")
+    ap.add_argument("--train-tracks", default="", help="with --fused: train on one condition per named track, e.g. square,zigzag; with --train-scales: the product")
+    ap.add_argument("--envs-per-group", type=int, default=256, help="envs per group of the condition mix (a multiple of 256)")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
 
-final = evaluate(model)
-res = dict(evaluated="final policy" if a.eval_final else "best checkpoint by training statistic", lr_final_frac=a.lr_final,
-           world_size=world, fused_collect=a.fused, native_update=a.native_update, variant=a.variant, track=a.track, envs=a.envs,
-           gamma=a.gamma, seed=a.seed, n_steps=a.n_steps, epochs=a.epochs, minibatches=a.minibatches, lr=a.lr, target_kl=a.target_kl,
-           truncation_bootstrap=not a.no_trunc_bootstrap,
-           train_steps=model.num_timesteps * world, train_seconds=train_s,
-           train_Msteps_per_s=model.num_timesteps * world / train_s / 1e6,
-           **final, **model.stats)
-sk, up_n = res.get("skipped_nonfinite", 0), res.get("updates", 0)
-if sk > 0.002 * max(1, sk + up_n):   # a handful of skips = diverged sims in a minibatch; more means something is wrong
-    print(f"WARNING: {sk} of {sk + up_n} minibatch updates were skipped for a non-finite gradient norm", file=sys.stderr, flush=True)
-if curve:
-    # first time the policy flies laps like the reference's (simulated flying laps 2.51-2.59 s, FP:3474-3488) without crashing
-    hit = [c for c in curve if 0 < c["flying_lap"] <= a.lap_target and c["crashes_per_12s"] <= 0.1]
-    res["curve"] = curve
-    res["seconds_to_reference_lap"] = hit[0]["train_seconds"] if hit else None
-    res["env_steps_to_reference_lap"] = hit[0]["env_steps"] if hit else None
-    res["lap_target"] = a.lap_target
-print(json.dumps(res))
-if a.out:
-    json.dump(res, open(a.out, "w"), indent=1)
+    # one process per GPU under torchrun (data-parallel PPO: --envs is per GPU, env_id_base = rank * envs keys disjoint reset and
+    # action-noise streams; gradients are averaged per minibatch, see MfmaPpoUpdater.minibatch)
+    rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
+    if "RANK" in os.environ:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.cuda.set_device(local_rank)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+        assert a.native_update, "data-parallel training uses the matrix-core update (--native-update)"
+    if rank != 0:
+        sys.stdout = open(os.devnull, "w")
+
+    trk = square_track() if a.track == "square" else zigzag_track()
+    cls = Quadcopter3DGates if a.variant == "e2e" else Quadcopter3DGatesINDI
+    env = cls(a.envs, *trk, gates_ahead=1, infos_mode="none", seed=1 + a.seed, env_id_base=rank * a.envs)
+    if a.variant == "e2e":
+        env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    conds = train_conditions(env, a.variant, parse_scales(a.train_scales) if a.train_scales else None,
+                             parse_tracks(a.train_tracks) if a.train_tracks else None)
+    if conds is not None and not a.fused:
+        raise SystemExit("--train-scales / --train-tracks need --fused: the mix of conditions exists in the closed-loop kernel only")
+    model = PPO(env, seed=a.seed, ent_coef=a.ent_coef, gamma=a.gamma, n_steps=a.n_steps, n_epochs=a.epochs, batch_size=a.envs * a.n_steps // a.minibatches, learning_rate=a.lr,
+                target_kl=a.target_kl, lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps) // world, fused_collect=a.fused,
+                native_update=a.native_update, truncation_bootstrap=not a.no_trunc_bootstrap,
+                policy_forward="f32class" if a.precision != "f16-operands" else "torch", update_precision="f32" if a.precision == "f32" else "f16-operands",
+                conditions=conds, envs_per_group=a.envs_per_group)
+    if "RANK" in os.environ:
+        model._updater.broadcast_parameters(0)   # identical start on every rank (the seed already makes it so; this guarantees it)
+        model.noise_seed = a.seed                 # same key, different global env ids -> independent action noise per rank
+    # deterministic evaluation on a separate env: 2000 steps = 20 s of flight (six laps), crashes auto-reset and restart the lap count
+    n_eval = 4096
+    ev = cls(n_eval, *trk, gates_ahead=1, infos_mode="none", seed=99)
+    if a.variant == "e2e":
+        ev.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    ev.max_steps = 10 ** 6
+    G = 4 if a.track == "square" else len(trk[0])   # square_track() lists its four gates twice: a lap is four passes
+    dt = 0.01
+
+
+    @torch.no_grad()
+    def evaluate(m):
+        ev.seed(99)
+        obs = ev.reset_device()
+        dev = obs.device
+        gates12 = torch.zeros(n_eval, device=dev); crashes12 = torch.zeros(n_eval, device=dev)
+        passed = torch.zeros(n_eval, device=dev)            # gates passed since this env's last (re)start
+        lap_start = torch.zeros(n_eval, device=dev)         # time of the last lap boundary (or restart)
+        lap_sum = torch.zeros(7, device=dev); lap_cnt = torch.zeros(7, device=dev)   # laps 1..6 (index 0 unused)
+        for k in range(2000):
+            obs, rew, done, trunc = ev.step_device(m.act_device(obs).contiguous())
+            t = (k + 1) * dt
+            g = (rew > 5).float()
+            if k < 1200:
+                gates12 += g; crashes12 += (done.float() - trunc.float()).clamp(min=0)
+            passed += g
+            lap_done = (g > 0) & (passed % G == 0) & (passed > 0)
+            lap_no = (passed / G).long().clamp(max=6)
+            if lap_done.any():
+                sel = lap_done & (passed / G <= 6)
+                lap_sum.index_add_(0, lap_no[sel], (t - lap_start)[sel])
+                lap_cnt.index_add_(0, lap_no[sel], torch.ones_like(lap_start)[sel])
+                lap_start = torch.where(lap_done, torch.full_like(lap_start, t), lap_start)
+            d = done.bool()
+            passed = torch.where(d, torch.zeros_like(passed), passed)
+            lap_start = torch.where(d, torch.full_like(lap_start, t), lap_start)
+        laps = (lap_sum / lap_cnt.clamp(min=1)).tolist()
+        return dict(eval_gates_per_12s=float(gates12.mean()), eval_crashes_per_12s=float(crashes12.mean()),
+                    eval_seconds_per_gate=float(1200 * dt / gates12.mean().clamp(min=1e-9)),
+                    eval_seconds_per_lap_4gates=float(4 * 1200 * dt / gates12.mean().clamp(min=1e-9)),
+                    eval_lap_seconds={f"lap{i}": laps[i] for i in range(1, 7)}, eval_laps_counted=lap_cnt[1:].tolist(),
+                    eval_flying_lap_seconds=float(lap_sum[2:].sum() / lap_cnt[2:].sum().clamp(min=1)))
+
+
+    def evaluate_on_device(m):
+        """the same protocol and keys through evaluate_policy: 1 200-step window for the rates, 2 000 steps for the lap times"""
+        from optimal_quad_control_rl_amd import evaluate_policy
+        r = evaluate_policy(m, ev, n_eval_steps=2000, window_steps=1200, gates_per_lap=G, seed=99)
+        w, t = r["window"], r["total"]
+        g12 = max(w["gates_per_window"], 1e-9)
+        return dict(eval_gates_per_12s=w["gates_per_window"], eval_crashes_per_12s=w["crashes_per_window"], eval_seconds_per_gate=1200 * dt / g12,
+                    eval_seconds_per_lap_4gates=4 * 1200 * dt / g12,
+                    eval_lap_seconds={f"lap{i}": (t["lap_seconds"][i - 1] or 0.0) for i in range(1, 7)}, eval_laps_counted=[float(c) for c in t["laps_counted"][:6]],
+                    eval_flying_lap_seconds=t["flying_lap_seconds"] or 0.0, eval_mean_reward=t["mean_reward"], evaluator="device")
+
+
+    if a.device_eval:
+        evaluate = evaluate_on_device
+
+    best = {"gates": -1.0, "state": None}
+    def keep_best(m):
+        g = m.stats.get("gates_per_episode", 0.0)
+        if g > best["gates"] and m.stats.get("ep_len_mean", 0) > 600:
+            best["gates"] = g
+            best["state"] = {k: v.clone() for k, v in m.policy.state_dict().items()}
+    # --curve K: every K rollouts the CURRENT policy is evaluated (clock stopped) -> wall-clock-to-quality curve (BASELINE config 5's metric)
+    curve, paused, it_no = [], [0.0], [0]
+    def on_rollout(m):
+        if not a.eval_final:
+            keep_best(m)
+        it_no[0] += 1
+        if conds is not None and it_no[0] % 20 == 0:   # under the trainer's own log line (log_every=20 below)
+            print(format_condition_stats(m.stats["per_condition"]), flush=True)
+        if a.curve and it_no[0] % a.curve == 0 and rank == 0:
+            torch.cuda.synchronize()
+            e0 = time.perf_counter()
+            tsec = e0 - t0 - paused[0]
+            r = evaluate(m)
+            torch.cuda.synchronize()
+            paused[0] += time.perf_counter() - e0
+            curve.append(dict(train_seconds=tsec, env_steps=m.num_timesteps * world,
+                              flying_lap=r["eval_flying_lap_seconds"], crashes_per_12s=r["eval_crashes_per_12s"], gates_per_12s=r["eval_gates_per_12s"]))
+    t0 = time.perf_counter()
+    model.learn(int(a.steps) // world, log_every=20, callback=on_rollout)   # --steps counts env-steps of the whole job
+    if best["state"] is not None and not a.eval_final:
+        model.policy.load_state_dict(best["state"])  # evaluate the best checkpoint (the reference saves one every 10 rollouts, R:823)
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0 - paused[0]
+
+    final = evaluate(model)
+    res = dict(evaluated="final policy" if a.eval_final else "best checkpoint by training statistic", lr_final_frac=a.lr_final,
+               world_size=world, fused_collect=a.fused, native_update=a.native_update, variant=a.variant, track=a.track, envs=a.envs,
+               gamma=a.gamma, seed=a.seed, n_steps=a.n_steps, epochs=a.epochs, minibatches=a.minibatches, lr=a.lr, target_kl=a.target_kl,
+               truncation_bootstrap=not a.no_trunc_bootstrap,
+               train_steps=model.num_timesteps * world, train_seconds=train_s,
+               train_Msteps_per_s=model.num_timesteps * world / train_s / 1e6,
+               **final, **model.stats)
+    if conds is not None:
+        print(format_condition_stats(model.stats["per_condition"]), flush=True)
+        if a.eval_final and rank == 0:
+            # the FINAL policy under each training condition, on the evaluation env (its seed and its time limit: episodes end by a crash only)
+            from optimal_quad_control_rl_amd import evaluate_grid
+            from optimal_quad_control_rl_amd.evaluation import robustness_table
+            ev_conds = [c.replace(max_steps=ev.max_steps) for c in conds]
+            cells = evaluate_grid([model], ev_conds, ev, envs_per_cell=256, n_eval_steps=2000, window_steps=1200, seed=99)
+            rows = robustness_table(cells, [c.name for c in ev_conds])[0]
+            print(format_table("final policy", rows), flush=True)
+            res["robustness"] = [dict(condition=n, crashes_per_window=cr, flying_lap_seconds=fl, gates_per_window=g) for n, cr, fl, g in rows]
+    sk, up_n = res.get("skipped_nonfinite", 0), res.get("updates", 0)
+    if sk > 0.002 * max(1, sk + up_n):   # a handful of skips = diverged sims in a minibatch; more means something is wrong
+        print(f"WARNING: {sk} of {sk + up_n} minibatch updates were skipped for a non-finite gradient norm", file=sys.stderr, flush=True)
+    if curve:
+        # first time the policy flies laps like the reference's (simulated flying laps 2.51-2.59 s, FP:3474-3488) without crashing
+        hit = [c for c in curve if 0 < c["flying_lap"] <= a.lap_target and c["crashes_per_12s"] <= 0.1]
+        res["curve"] = curve
+        res["seconds_to_reference_lap"] = hit[0]["train_seconds"] if hit else None
+        res["env_steps_to_reference_lap"] = hit[0]["env_steps"] if hit else None
+        res["lap_target"] = a.lap_target
+    print(json.dumps(res))
+    if a.out:
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
