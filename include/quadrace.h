@@ -52,7 +52,8 @@ extern "C" {
 #define QR_ABI_VERSION 3   /* additive since 3 (no signature changed): qr_rollout_kernel_name (round 4), qr_set_rollout_form (round 5),
                              qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
                              qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
-                             qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12) */
+                             qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12),
+                             qr_blackbox_policy (round 13) */
 
 enum {
     QR_OK = 0,
@@ -374,6 +375,34 @@ int qr_rollout_policy_conditions(qr_env* env, qr_policy* policy, qr_condition_ba
 int qr_record_row_len(const qr_env* env);   /* S + QR_RECORD_EXTRA */
 int qr_record_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const float* log_std, uint64_t noise_seed,
                      uint64_t first_step, int32_t flags, int32_t rec_envs, float* rows_dev, void* stream);
+
+/* Closed-loop BLACK BOX: the K steps of qr_record_policy (same forward, noise stream, env arithmetic, reset stream and row layout; the env
+ * state afterwards is bit-identical to qr_record_policy / qr_rollout_policy with the same arguments, whatever trigger, window and rec_envs
+ * are) in ONE kernel that keeps only the last W = window rows of each env and stops overwriting an env's rows when its episode ends the
+ * way `trigger` selects: the seconds before each crash, at W M rows instead of num_steps M.
+ * ring_dev [W][rec_envs][R] float32, 16-byte aligned, R = qr_record_row_len(): the row of call-step k of env i goes to
+ *   ring_dev[(first_step + k) mod W][i] iff env i was ARMED at the start of that step.  An armed env FREEZES at the end of a step whose end
+ *   code (row column S + 5: 1 crash, 2 time limit) has its bit in `trigger` (QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT; 0 never
+ *   freezes: the ring is then "the last W steps"), so the triggering row is the last one stored.  A frozen env keeps flying and resetting.
+ * st_dev [rec_envs][QR_BLACKBOX_ST_INTS] int32, 16-byte aligned, READ at the start of the call and written at its end: zero it for a fresh
+ *   log, pass it again to continue one.  [0] 0 armed / 1 frozen; [1] rows stored for this env so far (cumulative); [2] ring slot of the
+ *   trigger row, -1 while armed; [3] cause bits of the trigger step, 0 while armed: 1 ground (z > 0), 2 out of bounds (|x| or |y| > 10 or a
+ *   |rate| > 1000), 4 time limit, 8 gate collision (a crash with neither bit 1 nor bit 2), taken from the terminal state.
+ *   The valid rows of env i are min(st[1], W) rows that END at slot st[2] if it is frozen, at slot (first_step + num_steps - 1) mod W if it
+ *   is armed, oldest first going backwards modulo W.  Slots that hold no valid row were never written.
+ * term_dev [rec_envs][S] float32 or NULL: the world state of a frozen env at the END of its trigger step -- after the integration, before
+ *   the auto-reset (what the terminal observation is taken from).  Rows of armed envs are not written.
+ * CONTINUATION: a second call with first_step advanced by the first call's num_steps, the same window and the same three buffers gives the
+ *   ring, status and terminal states of one call over all the steps.
+ * Memory beyond [W][rec_envs][R], [rec_envs][4] and [rec_envs][S] is never written; all N envs fly (rec_envs only cuts what is kept).
+ * flags, log_std, noise_seed: as in qr_record_policy.  Refused before anything is launched (qr_last_error set, buffers and state untouched):
+ * everything qr_record_policy refuses, NULL or misaligned ring_dev / st_dev, trigger outside 0..3, window < 1.  qr_last_step_many_ms()
+ * reports this launch too. */
+#define QR_BLACKBOX_ST_INTS 4
+enum { QR_BLACKBOX_ON_CRASH = 1, QR_BLACKBOX_ON_TIME_LIMIT = 2 };
+int qr_blackbox_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const float* log_std, uint64_t noise_seed,
+                       uint64_t first_step, int32_t flags, int32_t trigger, int32_t window, int32_t rec_envs, float* ring_dev,
+                       int32_t* st_dev, float* term_dev, void* stream);
 
 /* ---- PPO minibatch update on the matrix cores (replaces SB3's PPO.train inner loop, R:783-795 / R:820) -------------
  * Networks: policy obs -> 120 -> 120 -> 120 -> 4 and value obs -> 120 -> 120 -> 120 -> 1 (ReLU), log_std[4].

@@ -9,7 +9,7 @@ from .tracks import TRAIN_DISTURBANCE_RANGES, square_track, zigzag_track  # noqa
 __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square_track", "TRAIN_DISTURBANCE_RANGES",
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
-           "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups"]
+           "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -33,6 +33,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import recording
 
         return getattr(recording, name)
+    if name in ("blackbox_policy", "CrashLog"):  # on-device black box: the last steps before each crash (qr_blackbox_policy)
+        from . import blackbox
+
+        return getattr(blackbox, name)
     if name in ("Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups"):  # flight conditions of the grid evaluator (qr_condition_bank_*)
         from . import conditions
 

@@ -76,6 +76,8 @@ SIGNATURES = {
                                                C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qr_record_row_len": (C.c_int, [_vp]),
     "qr_record_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp]),
+    "qr_blackbox_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp,
+                                     _vp]),
     "qr_profile_steps": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _f32p, _f32p]),
     "qr_ppo_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qr_ppo_create_ex": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
@@ -116,7 +118,7 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_record_policy", "qr_record_row_len", "qr_policy_bank_create", "qr_policy_bank_destroy", "qr_policy_bank_capacity",
                     "qr_policy_bank_set", "qr_evaluate_policy_bank", "qr_condition_bank_create", "qr_condition_bank_destroy",
                     "qr_condition_bank_capacity", "qr_condition_bank_set", "qr_evaluate_policy_grid",
-                    "qr_rollout_policy_conditions")   # added in rounds 5-12: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_rollout_policy_conditions", "qr_blackbox_policy")   # added in rounds 5-13: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

@@ -1,0 +1,172 @@
+"""On-device black box: the last steps before each crash (`qr_blackbox_policy`, csrc/quadrace_blackbox.hip).
+
+The question that follows every evaluation -- why does the policy crash, and where?  All N envs fly closed-loop in one kernel; each
+keeps only its last `window` recorder rows in a ring and stops overwriting them when its episode ends the way `trigger` says:
+
+    from optimal_quad_control_rl_amd import blackbox_policy
+    log = blackbox_policy(model, eval_env, n_steps=2000, window=64, trigger="crash", seed=99)
+    log.by_gate()                    # crash counts per cause x target gate of the trigger row
+    log.flight(int(log.frozen_envs()[0]))   # that env's last rows, oldest -> newest, ending at the row that crashed
+    log.save_npz("crashes.npz")
+
+Rows have the flight recorder's layout (recording.FlightRecord; include/quadrace.h): a row pairs the state with the command applied IN
+that state, so the trigger row is the state and command of the step that ended the episode; `terminal_state` is the state that step
+produced (after the integration, before the auto-reset).
+"""
+import numpy as np
+
+from .recording import RECORD_EXTRA, FlightRecord
+
+ST_INTS = 4   # QR_BLACKBOX_ST_INTS of include/quadrace.h
+TRIGGERS = {"none": 0, "crash": 1, "time_limit": 2, "any": 3}   # QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT
+CAUSE_GROUND, CAUSE_OOB, CAUSE_TIME_LIMIT, CAUSE_GATE = 1, 2, 4, 8
+CAUSE_NAMES = ((CAUSE_GROUND, "ground"), (CAUSE_OOB, "out_of_bounds"), (CAUSE_GATE, "gate"), (CAUSE_TIME_LIMIT, "time_limit"))
+
+
+def _host(x):
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
+class CrashLog:
+    """Host view of a black-box ring [W][M][R] (float32, recorder rows), its status [M][4] (int32) and the terminal states [M][S] or None,
+    after calls that covered steps first_step .. last_step (the absolute step index of the last call's last step)."""
+
+    def __init__(self, ring, status, terminal, last_step, dt):
+        ring, status = _host(ring), _host(status)
+        if ring.dtype != np.float32 or ring.ndim != 3 or ring.shape[2] - RECORD_EXTRA not in (13, 16):
+            raise ValueError("ring must be float32 [W][M][S + %d] with S = 13 or 16, got %s %s" % (RECORD_EXTRA, ring.dtype, ring.shape))
+        if status.dtype != np.int32 or status.shape != (ring.shape[1], ST_INTS):
+            raise ValueError("status must be int32 [M][%d] with the ring's M, got %s %s" % (ST_INTS, status.dtype, status.shape))
+        self.ring, self.status, self.dt = ring, status, np.float32(dt)
+        self.window, self.num_envs, self.row_len = ring.shape
+        self.state_len = self.row_len - RECORD_EXTRA
+        self.last_step = int(last_step)
+        self.terminal = None
+        if terminal is not None:
+            terminal = _host(terminal)
+            if terminal.dtype != np.float32 or terminal.shape != (self.num_envs, self.state_len):
+                raise ValueError("terminal must be float32 [M][S], got %s %s" % (terminal.dtype, terminal.shape))
+            self.terminal = terminal
+
+    # ---- status
+    @property
+    def frozen(self):
+        """bool [M]: the env's window is frozen at a trigger row"""
+        return self.status[:, 0] != 0
+
+    def frozen_envs(self):
+        return np.nonzero(self.frozen)[0]
+
+    @property
+    def valid(self):
+        """int [M]: number of valid rows of each env, min(rows stored, W)"""
+        return np.minimum(self.status[:, 1], self.window).astype(np.int64)
+
+    @property
+    def cause(self):
+        """int32 [M]: cause bits of the trigger step (1 ground, 2 out of bounds, 4 time limit, 8 gate collision), 0 for armed envs"""
+        return self.status[:, 3]
+
+    @property
+    def terminal_state(self):
+        """float32 [M][S]: the world state at the end of each frozen env's trigger step (NaN rows for armed envs), or None"""
+        if self.terminal is None:
+            return None
+        out = self.terminal.copy()
+        out[~self.frozen] = np.nan
+        return out
+
+    # ---- rows
+    def slots(self, i):
+        """Ring slots of env i's valid rows, oldest first: they end at the trigger slot if the env is frozen, at the last flown step's
+        slot if it is still armed."""
+        n, w = int(self.valid[i]), self.window
+        end = int(self.status[i, 2]) if self.status[i, 0] else self.last_step % w
+        return [(end - n + 1 + j) % w for j in range(n)]
+
+    def flight(self, i):
+        """float32 [valid[i]][R]: env i's rows oldest -> newest, unrolled from the ring"""
+        return self.ring[self.slots(i), i]
+
+    def flights(self):
+        """(rows [m][W][R] NaN-padded at the end, valid [m], envs [m]) for the m frozen envs"""
+        envs = self.frozen_envs()
+        out = np.full((len(envs), self.window, self.row_len), np.nan, np.float32)
+        for j, i in enumerate(envs):
+            f = self.flight(i)
+            out[j, :len(f)] = f
+        return out, self.valid[envs], envs
+
+    def trigger_rows(self):
+        """float32 [m][R]: the trigger row of each frozen env (frozen_envs() order)"""
+        envs = self.frozen_envs()
+        return self.ring[self.status[envs, 2], envs]
+
+    def as_flight_record(self, i):
+        """FlightRecord of env i's rows alone ([valid][1][R]): its named views and log_dict"""
+        return FlightRecord(np.ascontiguousarray(self.flight(i)[:, None, :]), self.dt)
+
+    # ---- tables
+    def cause_counts(self):
+        """{name: number of frozen envs with that cause bit} for ground, out_of_bounds, gate, time_limit (an end can carry two bits)"""
+        c = self.cause[self.frozen]
+        return {name: int(((c & bit) != 0).sum()) for bit, name in CAUSE_NAMES}
+
+    def by_gate(self, num_gates=None):
+        """int64 [4][G]: frozen envs per cause (rows: ground, out_of_bounds, gate, time_limit) x target gate of the trigger row"""
+        rows = self.trigger_rows()
+        gate = rows[:, self.state_len + 6].astype(np.int64) if len(rows) else np.zeros(0, np.int64)
+        g = int(num_gates) if num_gates is not None else (int(gate.max()) + 1 if len(gate) else 0)
+        c = self.cause[self.frozen]
+        out = np.zeros((len(CAUSE_NAMES), g), np.int64)
+        for r, (bit, _) in enumerate(CAUSE_NAMES):
+            np.add.at(out[r], gate[(c & bit) != 0], 1)
+        return out
+
+    def save_npz(self, path):
+        """ring, status, terminal (if kept), last_step, dt, and the unrolled flights of the frozen envs (flights, valid, envs)"""
+        rows, valid, envs = self.flights()
+        d = dict(ring=self.ring, status=self.status, last_step=np.int64(self.last_step), dt=self.dt, flights=rows, valid=valid, envs=envs)
+        if self.terminal is not None:
+            d["terminal"] = self.terminal
+        np.savez(path, **d)
+        return path
+
+
+def blackbox_policy(model, env, n_steps, window=64, trigger="crash", rec_envs=None, deterministic=True, seed=None, precision=None):
+    """Fly `model`'s current policy on `env` (as record_policy: a race env of this package, possibly inside a VecMonitor; an SB3-style
+    model or the native trainer) for `n_steps` in ONE kernel launch and return the CrashLog of envs [0, rec_envs) (None: all): each
+    env's last `window` rows, frozen at the first step that ends an episode by `trigger` ("crash", "time_limit", "any"; "none" never
+    freezes).  `deterministic`, `seed`, `precision` as in record_policy.  `env` keeps flying from where the call left it."""
+    if trigger not in TRIGGERS:
+        raise ValueError("trigger must be one of %s, got %r" % (sorted(TRIGGERS), trigger))
+    import torch
+
+    from .evaluation import _actor
+    from .policy import MfmaPolicy
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    if precision is None:
+        f32 = getattr(model, "precision", None) in ("f32", "f32-collect") or getattr(model, "policy_forward", None) == "f32class"
+        precision = "f32" if f32 else "f16-operands"
+    net = getattr(model, "_net", None)
+    if net is None:
+        net = model.policy
+    net = getattr(net, "net", net)
+    log_std = net.log_std.detach() if hasattr(net, "log_std") else torch.zeros(4)
+    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(_actor(model))
+    try:
+        if seed is not None:
+            core.seed(seed)
+            core.reset_device()
+        ring, st, term = core.blackbox_policy_device(policy, int(n_steps), log_std, window=int(window), trigger=TRIGGERS[trigger],
+                                                     noise_seed=0 if seed is None else int(seed), deterministic=deterministic,
+                                                     rec_envs=rec_envs, precision=precision)
+        ring, st, term = ring.cpu().numpy(), st.cpu().numpy(), term.cpu().numpy()
+    finally:
+        torch.cuda.current_stream(core.device).synchronize()
+        policy.close()
+    return CrashLog(ring, st, term, int(n_steps) - 1, core.dt)

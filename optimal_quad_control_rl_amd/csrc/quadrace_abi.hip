@@ -855,6 +855,43 @@ int qr_record_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_s
     return QR_TIMED_LAUNCH(e, st, qr::launch_record_policy(e->cfg.variant, e->P, A, K, rec_envs, rows_dev, st));
 }
 
+int qr_blackbox_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                       int32_t flags, int32_t trigger, int32_t window, int32_t rec_envs, float* ring_dev, int32_t* st_dev, float* term_dev,
+                       void* stream) {
+    if (int rc = check_ready(e)) return rc;
+    if (!policy) return fail(QR_E_INVALID, "qr_blackbox_policy: null policy handle");
+    if (!log_std) return fail(QR_E_INVALID, "qr_blackbox_policy: log_std is required");
+    if (!ring_dev || !st_dev) return fail(QR_E_INVALID, "qr_blackbox_policy: ring_dev and st_dev are required");
+    if (((uintptr_t)ring_dev | (uintptr_t)st_dev) & 15) return fail(QR_E_INVALID, "qr_blackbox_policy: ring_dev and st_dev must be 16-byte aligned");
+    if ((uintptr_t)term_dev & 3) return fail(QR_E_INVALID, "qr_blackbox_policy: term_dev must be 4-byte aligned");
+    if (K < 1) return fail(QR_E_INVALID, "qr_blackbox_policy: num_steps must be >= 1");
+    if (rec_envs < 1 || rec_envs > e->cfg.num_envs) return fail(QR_E_INVALID, "qr_blackbox_policy: rec_envs must be in 1..num_envs");
+    if (trigger < 0 || trigger > (QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT))
+        return fail(QR_E_INVALID, "qr_blackbox_policy: `trigger` takes QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT");
+    if (window < 1) return fail(QR_E_INVALID, "qr_blackbox_policy: window must be >= 1");
+    if (flags & ~(QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return fail(QR_E_INVALID, "qr_blackbox_policy: `flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, "qr_blackbox_policy: pause / pause_if_collision envs are evaluation modes; use qr_step");
+    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_blackbox_policy: policy obs_len != env obs_len");
+    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_blackbox_policy: policy on another GPU");
+    const qr::half8* w = qr::policy_weights(policy);
+    if (!w) return fail(QR_E_STATE, "qr_blackbox_policy: the policy has no weights");
+    qr::PolicyArgs A{};   // the sampling arguments of qr_record_policy / qr_rollout_policy (same noise stream)
+    A.weights = w;
+    A.weights_lo = qr::policy_weights_lo(policy);
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    for (int c = 0; c < 4; ++c) A.std[c] = expf(log_std[c]);
+    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;   // domain separation from the reset stream: see qr_rollout_policy
+    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
+    A.step_lo = (uint32_t)first_step;
+    A.step_hi = (uint32_t)(first_step >> 32);
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    const int slot0 = (int)(first_step % (uint64_t)window);   // the ring slot of the call's first step
+    hipStream_t st = (hipStream_t)stream;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_blackbox_policy(e->cfg.variant, e->P, A, K, rec_envs, trigger, window, slot0, ring_dev, st_dev, term_dev, st));
+}
+
 int qr_observe(qr_env* e, float* obs_out_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
     if (!obs_out_dev) return fail(QR_E_INVALID, "qr_observe: null output");

@@ -141,6 +141,11 @@ hipError_t launch_rollout_policy_cond(int variant, const Params& P, const Policy
 // quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
 hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
 
+// quadrace_blackbox.hip: the closed-loop black box (qr_blackbox_policy): the last `window` rows of each env in ring [window][rec_envs][S + 8],
+// frozen at the step that ends an episode the way `trigger` selects; slot0 = first_step mod window; st_rec [rec_envs][4]; term may be null
+hipError_t launch_blackbox_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, int trigger, int window, int slot0,
+                                  float* ring, int32_t* st_rec, float* term, hipStream_t st);
+
 // quadrace_policy.hip
 hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);
 hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st);

@@ -884,6 +884,44 @@ class Quadcopter3DGates(_Base):
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return out
 
+    BLACKBOX_ST_INTS = 4  # QR_BLACKBOX_ST_INTS of include/quadrace.h
+
+    def blackbox_policy_device(self, policy, num_steps, log_std, window=64, trigger=1, noise_seed=0, first_step=0, deterministic=True,
+                               rec_envs=None, ring=None, status=None, terminal=None, precision="f16-operands"):
+        """The black box (qr_blackbox_policy): the closed loop of record_policy_device in ONE kernel that keeps, per env, only the last
+        `window` recorder rows in a ring and stops overwriting them when the env's episode ends the way `trigger` selects (bit 1 crash,
+        bit 2 time limit; 0 never freezes).  Returns device tensors (ring [W, M, R] float32, status [M, 4] int32, terminal [M, S]
+        float32), M = rec_envs (None: every env; all envs fly either way): the row of call-step k sits in slot (first_step + k) % W;
+        status = (frozen, rows stored so far, slot of the trigger row or -1, cause bits); terminal = the world state at the end of a
+        frozen env's trigger step (blackbox.CrashLog unrolls all three).  Pass the returned tensors back as `ring`, `status`,
+        `terminal` with first_step advanced by num_steps and the same window to continue; fresh ones are NaN / zero filled.  Same noise
+        stream and env state afterwards as record_policy_device / rollout_policy_device with the same arguments."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_blackbox_policy")
+        K, n, dev, w = int(num_steps), self.num_envs, self.device, int(window)
+        m = n if rec_envs is None else int(rec_envs)
+        mm, r = min(max(m, 0), n), self.STATE_LEN + self.RECORD_EXTRA
+        if ring is None:
+            ring = torch.full((max(w, 1), max(mm, 1), r), float("nan"), dtype=torch.float32, device=dev)   # (never empty: the library names a bad argument)
+        else:
+            assert ring.is_cuda and ring.dtype == torch.float32 and ring.is_contiguous() and tuple(ring.shape) == (w, m, r), (ring.dtype, ring.shape)
+        if status is None:
+            status = torch.zeros((max(mm, 1), self.BLACKBOX_ST_INTS), dtype=torch.int32, device=dev)
+        else:
+            assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and tuple(status.shape) == (m, self.BLACKBOX_ST_INTS), \
+                (status.dtype, status.shape)
+        if terminal is None:
+            terminal = torch.full((max(mm, 1), self.STATE_LEN), float("nan"), dtype=torch.float32, device=dev)
+        else:
+            assert terminal.is_cuda and terminal.dtype == torch.float32 and terminal.is_contiguous() and \
+                tuple(terminal.shape) == (m, self.STATE_LEN), (terminal.dtype, terminal.shape)
+        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
+                                  dtype=np.float32).reshape(4)
+        _lib.check(fn(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step), int(bool(deterministic)) | flags,
+                      int(trigger), w, m, _ptr(ring), _ptr(status), _ptr(terminal), self._stream()))
+        self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
+        return ring, status, terminal
+
     def profile_rollout(self, actions, out):
         """Like rollout_device but every step kernel is bracketed by its own hipEvent pair on the launch stream.
         Returns (mean single-kernel duration in ms, whole-region ms).  Blocks."""

@@ -1,0 +1,529 @@
+"""GPU: the on-device black box (qr_blackbox_policy, blackbox_policy_kernel<V, GA, kF32>).  Every comparison is EQUALITY, floats bit for
+bit.  The reference in every case is qr_record_policy on a twin handle with the same seed, start and arguments -- existing, unchanged
+code -- whose rows [K][M][R] go through the NumPy bookkeeping of tests/blackbox_spec.py:
+
+  1. ring, status and env state for trigger 1, 2, 3, 0 and W = 8, 64; 2. rec_envs cut mid-wave, sentinel tails behind all three buffers;
+  3. continuation 300 = 130 + 170; 4. cause bits and the terminal state (against the terminal-observation rows of qr_rollout_policy);
+  5. refusals; 6. the Python level; 7. time against the recorder.
+
+Scenario: the recorder tests' (tests/eval_spec.py: straight track of 16 gates 0.4 m apart, seeded network around a constant action,
+seed 5) with a time limit of 100 for both variants, K = 300 steps.  Both handles first fly PRE = 93 steps with qr_record_policy, so the
+call under test starts mid-episode at first_step = 93 (a ring slot other than 0): envs that survived the pre-flight reach the time
+limit at call-step 6, which is a trigger inside the first W - 1 steps even for W = 8, and early crashes give the same for trigger 1.
+Every test asserts on the TWIN's rows that its window holds what it is about before it compares anything."""
+import ctypes as C
+import statistics
+
+import numpy as np
+import pytest
+import torch
+
+import blackbox_spec as B
+import eval_spec as S
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -77777.0
+SC = S.SCENARIO
+K_WIN, PRE, MAX_STEPS = 300, 93, 100
+STOCH = dict(log_std=(-1.5, -1.2, -1.5, -1.2), noise_seed=7)   # std 0.22 .. 0.30 around the scenario's action
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _env(variant, n, gates_ahead, seed=SC["seed"]):
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES
+
+    if variant == "e2e":
+        env = Quadcopter3DGates(n, *S.scenario_track(), gates_ahead=gates_ahead, seed=seed, infos_mode="none")   # residual MLPs: the default
+        env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    else:
+        env = Quadcopter3DGatesINDI(n, *S.scenario_track(), gates_ahead=gates_ahead, seed=seed, infos_mode="none")
+    env.max_steps = MAX_STEPS
+    env.reset_device()
+    return env
+
+
+def _policy(obs_len, action, seed=3, gain=5.0):
+    """seeded random weights around the scenario's action (tests/test_gpu_record.py::_policy)"""
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    torch.manual_seed(seed)
+    net = ActorCritic(obs_len, 4)
+    with torch.no_grad():
+        net.pi[-1].weight.mul_(gain)
+        net.pi[-1].bias.copy_(torch.as_tensor(action, dtype=torch.float32))
+    return MfmaPolicy(obs_len).load_torch(net.pi)
+
+
+def _mode(stochastic):
+    if stochastic:
+        return dict(log_std=torch.tensor(STOCH["log_std"]), noise_seed=STOCH["noise_seed"], deterministic=False)
+    return dict(log_std=torch.zeros(4), noise_seed=0, deterministic=True)
+
+
+def _started(variant, n, gates_ahead, pol, mode, precision):
+    """a handle at the start of the call under test: seeded, reset, PRE steps flown"""
+    env = _env(variant, n, gates_ahead)
+    env.record_policy_device(pol, PRE, first_step=0, rec_envs=1, precision=precision, **mode)
+    return env
+
+
+def _state(env):
+    return [None if t is None else t.cpu() for t in env.get_state_tensors()]
+
+
+def _u32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _same_bits(a, b, what):
+    a, b = _u32(a), _u32(b)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    bad = a != b
+    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
+
+
+def _same_state(got, want, what):
+    for name, x, y in zip(("world", "disturbances", "target", "steps", "episode"), got, want):
+        if x is not None:
+            _same_bits(x.numpy(), y.numpy(), "%s: %s" % (what, name))   # float tensors bit for bit
+
+
+_TWINS = {}
+
+
+def _twin(variant, gates_ahead, n, precision, stochastic):
+    """The reference flight, computed once per scenario and left unchanged: the recorder's rows [K][n][R] of the K steps after the
+    pre-flight (host), the state before and after them."""
+    key = (variant, gates_ahead, n, precision, stochastic)
+    if key not in _TWINS:
+        mode = _mode(stochastic)
+        pol = _policy(_obs_len(variant, gates_ahead), SC[variant + "_action"])
+        env = _started(variant, n, gates_ahead, pol, mode, precision)
+        before = _state(env)
+        rows = env.record_policy_device(pol, K_WIN, first_step=PRE, precision=precision, **mode).cpu().numpy()
+        after = _state(env)
+        env.close(); pol.close()
+        rows.setflags(write=False)
+        _TWINS[key] = dict(rows=rows, before=before, after=after)
+    return _TWINS[key]
+
+
+def _obs_len(variant, gates_ahead):
+    return (20 if variant == "e2e" else 13) + 4 * gates_ahead
+
+
+def _buffers(dev, w, m, r, s, tail=0):
+    """sentinel-filled ring / terminal buffers and a zeroed status, each a view of a flat buffer with `tail` sentinel elements behind it"""
+    ring = torch.full((w * m * r + tail,), SENTINEL, dtype=torch.float32, device=dev)
+    st = torch.full((m * 4 + tail,), 12345, dtype=torch.int32, device=dev)
+    st[:m * 4] = 0
+    term = torch.full((m * s + tail,), SENTINEL, dtype=torch.float32, device=dev)
+    return ring, st, term
+
+
+def _views(ring, st, term, w, m, r, s):
+    return ring[:w * m * r].view(w, m, r), st[:m * 4].view(m, 4), term[:m * s].view(m, s)
+
+
+def _causes(term, st, rows_trigger_code):
+    """status [3] of every env restated from the terminal states: frozen envs by blackbox_spec.cause_bits, armed envs 0"""
+    want = np.zeros(len(st), np.int32)
+    for i in np.nonzero(st[:, 0] != 0)[0]:
+        want[i] = B.cause_bits(term[i], rows_trigger_code[i])
+    return want
+
+
+def _check_against_spec(rows, first_step, w, trigger, ring, st, term, what, status_in=None, ring_in=SENTINEL, term_in=None):
+    """ring / status / terminal rows (host arrays [W][M][R], [M][4], [M][S]) against the spec fed with the twin's rows[:, :M]"""
+    m, s = ring.shape[1], ring.shape[2] - 8
+    rows = rows[:, :m]
+    source, want_st, trig = B.run_arrays(rows, first_step, w, trigger, status_in)
+    _same_bits(ring, B.ring_from_source(rows, source, ring_in), what + ": ring (written slots = the twin's rows, the others untouched)")
+    assert np.array_equal(st[:, :3], want_st[:, :3]), (what, "status", np.argwhere(st[:, :3] != want_st[:, :3])[:4].tolist())
+    new = trig >= 0
+    code = np.zeros(m, np.int64)
+    code[new] = rows[trig[new], np.nonzero(new)[0], s + 5].astype(np.int64)
+    want_cause = _causes(term, st, code)
+    if status_in is not None:                                   # envs frozen by an earlier call keep that call's cause and terminal row
+        old = np.asarray(status_in)[:, 0] != 0
+        want_cause[old] = np.asarray(status_in)[old, 3]
+    assert np.array_equal(st[:, 3], want_cause), (what, "cause bits", np.argwhere(st[:, 3] != want_cause)[:4].tolist())
+    keep = ~new if term_in is None else None
+    if term_in is None:
+        assert (term[keep] == SENTINEL).all(), what + ": terminal rows of envs that did not freeze in this call were written"
+    assert not (term[new] == SENTINEL).any()
+    return source, want_st, trig
+
+
+def _fly(env, pol, mode, precision, trigger, w, m, K, first_step, bufs):
+    s, r = env.STATE_LEN, env.STATE_LEN + 8
+    ring, st, term = _views(*bufs, w, m, r, s)
+    got = env.blackbox_policy_device(pol, K, window=w, trigger=trigger, first_step=first_step, rec_envs=m, ring=ring, status=st, terminal=term,
+                                     precision=precision, **mode)
+    assert got[0].data_ptr() == bufs[0].data_ptr() and got[1].data_ptr() == bufs[1].data_ptr() and got[2].data_ptr() == bufs[2].data_ptr()
+    return ring.cpu().numpy(), st.cpu().numpy(), term.cpu().numpy()
+
+
+def _tails_intact(bufs, w, m, r, s):
+    ring, st, term = bufs
+    assert bool((ring[w * m * r:] == SENTINEL).all()), "memory behind ring [W][M][R] was written"
+    assert bool((st[m * 4:] == 12345).all()), "memory behind st [M][4] was written"
+    assert bool((term[m * s:] == SENTINEL).all()), "memory behind term [M][S] was written"
+
+
+def _scenario_facts(rows, m, what, need_survivor=True):
+    """What the twin's rows hold, printed and asserted: crash and time-limit ends, and (case 1) an env that never crashes."""
+    s = rows.shape[2] - 8
+    end = rows[:, :m, s + 5]
+    facts = dict(crashes=int((end == 1).sum()), time_limits=int((end == 2).sum()), envs_never_crashing=int(((end == 1).sum(axis=0) == 0).sum()))
+    print(what, facts)
+    assert facts["crashes"] >= 1 and facts["time_limits"] >= 1 and (facts["envs_never_crashing"] >= 1 or not need_survivor), (what, facts)
+    return facts
+
+
+def _trigger_facts(trig, w, m, what):
+    """From the spec's trigger steps: a trigger inside the first W - 1 steps (the window is not yet full), and a wave (64 consecutive
+    envs) that holds armed and frozen lanes at the same step."""
+    early = int(((trig >= 0) & (trig < w - 1)).sum())
+    mixed = 0
+    for a in range(0, m, 64):
+        t = trig[a:a + 64]
+        froze = np.where(t >= 0, t, np.iinfo(np.int64).max)
+        mixed += int(froze.min() < K_WIN - 1 and froze.min() != froze.max())     # after the first freeze and before the last, both kinds
+    print(what, dict(triggers=int((trig >= 0).sum()), before_window_full=early, mixed_waves=mixed))
+    assert early >= 1 and mixed >= 1, (what, early, mixed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 1. ring, status and state
+# ---------------------------------------------------------------------------------------------------------------------------------
+# (on the CPU oracle with this network the E2E scenario ends 4 of 5 episodes in a crash: of 1 024 envs a handful never crash in 300 steps, of
+# 293 none does, so the E2E cases that must hold such an env fly 1 024; INDI: 683 of 1 024 and 206 of 293)
+_CASES = [("e2e", 1, 1024, "f16-operands", False), ("e2e", 0, 1024, "f16-operands", True), ("indi", 0, 1024, "f16-operands", True),
+          ("indi", 1, 256 + 37, "f16-operands", False), ("indi", 1, 256 + 37, "f32", True)]
+_IDS = ["%s-ga%d-n%d-%s-%s" % (c[0], c[1], c[2], c[3], "stoch" if c[4] else "det") for c in _CASES]
+
+
+@pytest.mark.parametrize("variant,gates_ahead,n,precision,stochastic", _CASES, ids=_IDS)
+def test_ring_status_and_state_equal_the_recorder_through_the_spec(variant, gates_ahead, n, precision, stochastic):
+    tw = _twin(variant, gates_ahead, n, precision, stochastic)
+    rows, mode = tw["rows"], _mode(stochastic)
+    what = "%s ga%d n%d %s %s" % (variant, gates_ahead, n, precision, stochastic)
+    _scenario_facts(rows, n, what)
+    pol = _policy(_obs_len(variant, gates_ahead), SC[variant + "_action"])
+    for w in (8, 64):
+        for trigger in (1, 2, 3, 0):
+            env = _started(variant, n, gates_ahead, pol, mode, precision)
+            _same_state(_state(env), tw["before"], what + ": start")
+            s, r = env.STATE_LEN, env.STATE_LEN + 8
+            bufs = _buffers(env.device, w, n, r, s)
+            ring, st, term = _fly(env, pol, mode, precision, trigger, w, n, K_WIN, PRE, bufs)
+            label = "%s W%d trigger%d" % (what, w, trigger)
+            _, want_st, trig = _check_against_spec(rows, PRE, w, trigger, ring, st, term, label)
+            if trigger:
+                _trigger_facts(trig, w, n, label)
+                assert 0 < int(st[:, 0].sum()) and (trigger != 1 or int(st[:, 0].sum()) < n)
+            else:
+                assert not st[:, 0].any() and (st[:, 1] == K_WIN).all() and not (ring == SENTINEL).any()
+            _same_state(_state(env), tw["after"], label + ": env state afterwards")
+            env.close()
+    pol.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 2. rec_envs cut mid-wave
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,m", [("e2e", 100), ("indi", 100), ("indi", 130), ("e2e", 1)])
+def test_rec_envs_cuts_the_log_not_the_flight(variant, m):
+    """M = 100: wave 0 is a block (for INDI: 100 is a multiple of 4), wave 1 is cut by M; INDI M = 130: no block is 16-byte aligned, every
+    row leaves per lane, wave 2 is cut.  A sentinel tail lies behind each of the three buffers."""
+    n, w, tail = 256 + 37, 16, 1024
+    tw = _twin(variant, 1, n, "f16-operands", True)
+    mode = _mode(True)
+    pol = _policy(_obs_len(variant, 1), SC[variant + "_action"])
+    if m > 1:
+        _scenario_facts(tw["rows"], m, "rec_envs %s M %d" % (variant, m), need_survivor=False)
+    for trigger in (3, 0):
+        env = _started(variant, n, 1, pol, mode, "f16-operands")
+        s, r = env.STATE_LEN, env.STATE_LEN + 8
+        bufs = _buffers(env.device, w, m, r, s, tail)
+        ring, st, term = _fly(env, pol, mode, "f16-operands", trigger, w, m, K_WIN, PRE, bufs)
+        _tails_intact(bufs, w, m, r, s)
+        _, _, trig = _check_against_spec(tw["rows"], PRE, w, trigger, ring, st, term, "rec_envs %s M %d trigger %d" % (variant, m, trigger))
+        if trigger and m > 64:
+            _trigger_facts(trig, w, m, "rec_envs %s M %d" % (variant, m))
+        _same_state(_state(env), tw["after"], "rec_envs: env state afterwards")
+        env.close()
+    pol.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 3. continuation
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,n", [("e2e", 1024), ("indi", 256 + 37)])
+@pytest.mark.parametrize("trigger,K1", [(1, 130), (3, 130), (3, 40)])
+def test_one_call_equals_two_with_the_same_buffers(variant, n, trigger, K1):
+    """300 = 130 + 170.  Under trigger 3 an episode of at most 100 steps ends inside the first call for every env, so the second call
+    of that split must leave ring, status and terminal states alone; 40 + 260 puts triggers of that kind into both calls."""
+    w = 64
+    tw = _twin(variant, 1, n, "f16-operands", True)
+    mode = _mode(True)
+    pol = _policy(_obs_len(variant, 1), SC[variant + "_action"])
+    one, two = (_started(variant, n, 1, pol, mode, "f16-operands") for _ in range(2))
+    s, r = one.STATE_LEN, one.STATE_LEN + 8
+    whole = _fly(one, pol, mode, "f16-operands", trigger, w, n, K_WIN, PRE, _buffers(one.device, w, n, r, s))
+    _, _, trig = _check_against_spec(tw["rows"], PRE, w, trigger, *whole, "whole %s" % variant)
+    assert ((trig >= 0) & (trig < K1)).any()                                                 # frozen in the first call,
+    assert (trig >= K1).any() or (trigger == 3 and K1 >= MAX_STEPS and (trig >= 0).all())    # in the second, unless all episodes ended before
+    assert (trig < 0).any() or trigger == 3 or variant == "e2e"                              # never (INDI under trigger 1)
+    bufs = _buffers(two.device, w, n, r, s)
+    first = _fly(two, pol, mode, "f16-operands", trigger, w, n, K1, PRE, bufs)
+    _check_against_spec(tw["rows"][:K1], PRE, w, trigger, *first, "first part %s" % variant)
+    second = _fly(two, pol, mode, "f16-operands", trigger, w, n, K_WIN - K1, PRE + K1, bufs)
+    _check_against_spec(tw["rows"][K1:], PRE + K1, w, trigger, *second, "second part %s" % variant, status_in=first[1], ring_in=first[0], term_in=first[2])
+    for a, b, name in zip(second, whole, ("ring", "status", "terminal states")):
+        _same_bits(a, b, "%d + %d against 300: %s" % (K1, K_WIN - K1, name))
+    _same_state(_state(two), _state(one), "continuation")
+    _same_state(_state(two), tw["after"], "continuation against the twin")
+    one.close(); two.close(); pol.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 4. cause bits and terminal state
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _target_after(pre_world, target_before, term):
+    """The target gate after the trigger step, from the row's pre-step state and the terminal state: the gate-pass test of the env step
+    on the scenario's track, whose gates all have yaw 0 (cos 1, sin 0: the projection on the gate normal is the x offset itself)."""
+    pos, yaw, _ = S.scenario_track()
+    assert not yaw.any()
+    g = pos[target_before]
+    ox = pre_world[:, 0] - g[:, 0]
+    nx, ny, nz = term[:, 0] - g[:, 0], term[:, 1] - g[:, 1], term[:, 2] - g[:, 2]
+    passed = (ox < 0) & (nx > 0) & (np.abs(nx) < np.float32(0.5)) & (np.abs(ny) < np.float32(0.5)) & (np.abs(nz) < np.float32(0.5))
+    return np.where(passed, (target_before + 1) % len(pos), target_before).astype(np.int32), passed
+
+
+@pytest.mark.parametrize("variant,gates_ahead,n", [("e2e", 1, 1024), ("indi", 0, 256 + 37)])
+def test_cause_bits_and_terminal_state(variant, gates_ahead, n):
+    from optimal_quad_control_rl_amd import _lib
+
+    w, precision, mode = 64, "f16-operands", _mode(True)
+    tw = _twin(variant, gates_ahead, n, precision, True)
+    pol = _policy(_obs_len(variant, gates_ahead), SC[variant + "_action"])
+    env = _started(variant, n, gates_ahead, pol, mode, precision)
+    s, r = env.STATE_LEN, env.STATE_LEN + 8
+    ring, st, term = _fly(env, pol, mode, precision, 3, w, n, K_WIN, PRE, _buffers(env.device, w, n, r, s))
+    _, _, trig = _check_against_spec(tw["rows"], PRE, w, 3, ring, st, term, "cause %s" % variant)
+    frozen = np.nonzero(st[:, 0])[0]
+    code = ring[st[frozen, 2], frozen, s + 5]
+    cause = st[frozen, 3]
+    counts = {b: int(((cause & b) != 0).sum()) for b in (1, 2, 4, 8)}
+    print("cause %s: %d frozen, bits" % (variant, len(frozen)), counts)
+    assert ((code == 1) | (code == 2)).all() and (code == 1).any() and (code == 2).any()
+    assert np.array_equal((cause & 4) != 0, code == 2)                                       # bit 4 <=> end code 2
+    crash = code == 1
+    assert np.array_equal(((cause[crash] & 3) != 0) ^ ((cause[crash] & 8) != 0), np.ones(int(crash.sum()), bool))   # exactly one of {1 | 2, 8}
+    assert not (cause[~crash] & 8).any()
+    t = term[frozen]
+    assert np.array_equal((cause & 1) != 0, t[:, 2] > 0)
+    oob = (np.abs(t[:, 0]) > 10) | (np.abs(t[:, 1]) > 10) | (np.abs(t[:, 9:12]) > 1000).any(axis=1)
+    assert np.array_equal((cause & 2) != 0, oob)
+    assert counts[4] >= 1 and counts[1] + counts[2] + counts[8] >= int(crash.sum()) >= 1     # (which crash causes occur is the scenario's business)
+    # the terminal observation: terminal state + the env's disturbances from before the call + the target after the step, through
+    # qr_set_state + qr_observe on a helper handle, against the row qr_rollout_policy writes on a twin with a terminal-observation buffer
+    roll = _started(variant, n, gates_ahead, pol, mode, precision)
+    tb = torch.full((K_WIN, n, roll.state_len), SENTINEL, device=roll.device)
+    roll.set_terminal_obs_buffer(tb)
+    done = roll.rollout_policy_device(pol, K_WIN, first_step=PRE, precision=precision, **mode)[4].cpu().numpy().astype(bool)
+    roll.set_terminal_obs_buffer(None)
+    first_end = np.where(done.any(axis=0), done.argmax(axis=0), -1)
+    assert np.array_equal(first_end, trig)                                                   # under trigger 3 the trigger is the first episode end
+    want = tb.cpu().numpy()[first_end[frozen], frozen]
+    assert not (want == SENTINEL).any()
+    trow = ring[st[frozen, 2], frozen]
+    target_after, passed = _target_after(trow[:, :s], trow[:, s + 6].astype(np.int64), t)
+    print("cause %s: %d of the trigger steps pass their gate" % (variant, int(passed.sum())))
+    world0, dist0, target0, steps0, _ = tw["before"]
+    world, target = world0.numpy().copy(), target0.numpy().copy()
+    world[frozen], target[frozen] = t, target_after
+    helper = _env(variant, n, gates_ahead)
+    helper.set_state_tensors(world=world, dist=None if dist0 is None else dist0.numpy(), target=target, steps=steps0.numpy())
+    obs = torch.empty((n, helper.state_len), device=helper.device)
+    _lib.check(helper._L.qr_observe(helper._h, _ptr(obs), helper._stream()))
+    _same_bits(obs.cpu().numpy()[frozen], want, "terminal observation of the trigger step")
+    _same_state(_state(roll), _state(env), "rollout twin")
+    for e in (env, roll, helper):
+        e.close()
+    pol.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 5. refusals
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_launch_nothing():
+    from optimal_quad_control_rl_amd import _lib
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+
+    n, K, w = 300, 8, 4
+    env = _env("indi", n, 1)
+    env.max_steps = 5
+    L, s, r = env._L, env.STATE_LEN, env.STATE_LEN + 8
+    pol = _policy(env.state_len, SC["indi_action"])
+    other_len = MfmaPolicy(env.state_len + 4)
+    ring, st, term = _buffers(env.device, w, n, r, s, 8)
+    st[:] = 12345
+    log_std = (C.c_float * 4)(0.0, 0.0, 0.0, 0.0)
+    before = env.get_state_tensors()
+
+    def call(p=pol, k=K, ls=log_std, flags=1, trigger=3, window=w, m=n, rg=ring, sv=st, tm=term):
+        return L.qr_blackbox_policy(env._h, p._h if p is not None else None, k, ls, 0, 0, flags, trigger, window, m, _ptr(rg), _ptr(sv), _ptr(tm),
+                                    env._stream())
+
+    def refused(code, **kw):
+        rc = call(**kw)
+        assert rc == code, (list(kw.keys()), rc)
+        assert b"qr_blackbox_policy" in L.qr_last_error()
+        torch.cuda.synchronize()
+        assert bool((ring == SENTINEL).all()) and bool((st == 12345).all()) and bool((term == SENTINEL).all())
+        for x, y in zip(before, env.get_state_tensors()):
+            assert x is None or torch.equal(x, y)
+
+    refused(_lib.QR_E_INVALID, p=None)
+    refused(_lib.QR_E_INVALID, ls=None)
+    refused(_lib.QR_E_INVALID, rg=None)
+    refused(_lib.QR_E_INVALID, sv=None)
+    refused(_lib.QR_E_INVALID, rg=ring[1:])          # not 16-byte aligned
+    refused(_lib.QR_E_INVALID, rg=ring[2:])
+    refused(_lib.QR_E_INVALID, sv=st[1:])
+    refused(_lib.QR_E_INVALID, sv=st[2:])
+    refused(_lib.QR_E_INVALID, k=0)
+    refused(_lib.QR_E_INVALID, k=-3)
+    refused(_lib.QR_E_INVALID, m=0)
+    refused(_lib.QR_E_INVALID, m=n + 1)
+    refused(_lib.QR_E_INVALID, trigger=-1)
+    refused(_lib.QR_E_INVALID, trigger=4)
+    refused(_lib.QR_E_INVALID, window=0)
+    refused(_lib.QR_E_INVALID, window=-2)
+    refused(_lib.QR_E_INVALID, flags=4)
+    refused(_lib.QR_E_INVALID, flags=-1)
+    refused(_lib.QR_E_INVALID, p=other_len)
+    no_weights = MfmaPolicy(env.state_len)
+    refused(_lib.QR_E_STATE, p=no_weights)
+    no_weights.close()
+    env.pause = True
+    refused(_lib.QR_E_STATE)
+    env.pause = False
+    env.pause_if_collision = True
+    refused(_lib.QR_E_STATE)
+    env.pause_if_collision = False
+    with pytest.raises(_lib.QuadraceError, match="window"):
+        env.blackbox_policy_device(pol, K, torch.zeros(4), window=0)
+    # a call that runs: NULL term_dev is accepted, the time limit of 5 freezes every env at call-step 4 in slot 0, the launch is timed
+    st[:] = 0
+    st[n * 4:] = 12345
+    assert call(tm=None) == _lib.QR_OK
+    torch.cuda.synchronize()
+    got = st[:n * 4].view(n, 4).cpu().numpy()
+    assert (got[:, 0] == 1).all() and (got[:, 1] == 5).all() and (got[:, 2] == 0).all() and ((got[:, 3] & 4) != 0).all()
+    assert bool((term == SENTINEL).all()) and bool((st[n * 4:] == 12345).all()) and bool((ring[w * n * r:] == SENTINEL).all())
+    assert not bool((ring[:w * n * r] == SENTINEL).any())
+    assert env.last_rollout_ms() > 0.0
+    env.close(); pol.close(); other_len.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. the Python level
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_python_blackbox_policy_round_trip(tmp_path):
+    from optimal_quad_control_rl_amd import (PPO, CrashLog, Quadcopter3DGates, TRAIN_DISTURBANCE_RANGES, VecMonitor, blackbox_policy,
+                                             record_policy, square_track)
+
+    train = VecMonitor(Quadcopter3DGates(256, *square_track(), gates_ahead=1, seed=1))
+    train.venv.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    model = PPO("MlpPolicy", train, policy_kwargs=dict(activation_fn=torch.nn.ReLU, net_arch=[dict(pi=[120] * 3, vf=[120] * 3)], log_std_init=0),
+                n_steps=8, batch_size=256, n_epochs=1, seed=3)
+    with torch.no_grad():
+        model._net.pi[-1].bias.copy_(torch.as_tensor(SC["e2e_action"]))
+    n, K, w = 256 + 37, K_WIN, 32
+    ev, tw = VecMonitor(_env("e2e", n, 1, seed=99)), VecMonitor(_env("e2e", n, 1, seed=99))
+    fr = record_policy(model, tw, K, seed=99)
+    for trigger, bits in (("crash", 1), ("any", 3), ("none", 0)):
+        log = blackbox_policy(model, ev, K, window=w, trigger=trigger, seed=99)
+        assert isinstance(log, CrashLog) and log.ring.shape == (w, n, 24) and log.dt == np.float32(ev.venv.dt)
+        _, want_st, trig = B.run_arrays(fr.rows, 0, w, bits)
+        assert np.array_equal(log.status[:, :3], want_st[:, :3]) and np.array_equal(log.frozen, trig >= 0)
+        assert (bits == 0) or log.frozen.any()
+        for i in range(n):
+            last = trig[i] if trig[i] >= 0 else K - 1
+            v = min(last + 1, w)
+            assert log.valid[i] == v
+            _same_bits(log.flight(i), fr.rows[last - v + 1:last + 1, i], "flight(%d) under %s" % (i, trigger))
+        rows, valid, envs = log.flights()
+        assert np.array_equal(envs, np.nonzero(trig >= 0)[0]) and np.array_equal(valid, log.valid[envs])
+        for j, i in enumerate(envs):
+            _same_bits(rows[j, :valid[j]], log.flight(i), "flights()")
+            assert np.isnan(rows[j, valid[j]:]).all()
+        if bits:
+            i = int(envs[0])
+            one = log.as_flight_record(i)
+            assert one.rows.shape == (log.valid[i], 1, 24)
+            assert int(one.end[-1, 0]) & bits and not (one.end[:-1, 0].astype(np.int64) & bits).any()   # the trigger row is the last, and the first of its kind
+            assert np.isnan(log.terminal_state[~log.frozen]).all() and not np.isnan(log.terminal_state[log.frozen]).any()
+            assert sum(log.cause_counts().values()) >= len(envs) and log.by_gate(16).sum() == sum(log.cause_counts().values())
+            with np.load(log.save_npz(str(tmp_path / ("crashes_%s.npz" % trigger)))) as z:
+                assert np.array_equal(z["envs"], envs) and np.array_equal(_u32(z["ring"]), _u32(log.ring))
+    ev.venv.close(); tw.venv.close(); train.venv.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 7. time
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [65536, 4096])
+def test_not_slower_than_the_recorder(n):
+    """With trigger 0, W = 64 and rec_envs = N the black box stores one row per env-step, like qr_record_policy with rec_envs = N, into a
+    ring of 64 slots instead of K: median us/step of 5 launches <= 1.03 x the recorder's (3 % = the project's allowance for box-to-box
+    and run-to-run spread).  The protocol of tests/test_gpu_record.py::test_not_slower_than_the_rollout_kernel: K = 2 000, E2E +
+    residual MLPs + training disturbances, square track, gates_ahead 1, f16 operands; the kernels alternate from the same seeded start
+    with the same seeded network, one warm-up round first, times from qr_last_step_many_ms.  Printed without a bound: trigger 1 and
+    trigger 3 (mixed waves on the per-lane path, then fully frozen waves)."""
+    from optimal_quad_control_rl_amd import Quadcopter3DGates, TRAIN_DISTURBANCE_RANGES, square_track
+    from optimal_quad_control_rl_amd.policy import MfmaPolicy
+    from optimal_quad_control_rl_amd.ppo import ActorCritic
+
+    K, w = 2000, 64
+    env = Quadcopter3DGates(n, *square_track(), gates_ahead=1, infos_mode="none", seed=99)
+    env.disturbance_ranges = TRAIN_DISTURBANCE_RANGES
+    env.max_steps = 10 ** 6
+    torch.manual_seed(0)
+    pol = MfmaPolicy(env.state_len).load_torch(ActorCritic(env.state_len, 4).pi)
+    dev = env.device
+    rows = torch.empty((K, n, 24), device=dev)
+    ring, st, term = torch.empty((w, n, 24), device=dev), torch.zeros((n, 4), dtype=torch.int32, device=dev), torch.empty((n, 16), device=dev)
+    t = {"rec": [], 0: [], 1: [], 3: []}
+    frozen = {}
+    for rep in range(6):
+        env.seed(99); env.reset_device()
+        env.record_policy_device(pol, K, torch.zeros(4), deterministic=True, out=rows)
+        ms = {"rec": env.last_rollout_ms()}
+        for trigger in (0, 1, 3):
+            env.seed(99); env.reset_device()
+            st.zero_()
+            env.blackbox_policy_device(pol, K, torch.zeros(4), window=w, trigger=trigger, deterministic=True, ring=ring, status=st, terminal=term)
+            ms[trigger] = env.last_rollout_ms()
+            frozen[trigger] = int(st[:, 0].sum())
+        if rep:
+            for k in t:
+                t[k].append(ms[k] * 1e3 / K)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    for k in t:
+        print("n %d: %s %s -> median %.4f us/step (ratio to the recorder %.4f)%s"
+              % (n, "qr_record_policy" if k == "rec" else "qr_blackbox_policy trigger %d" % k, ["%.4f" % x for x in t[k]], med[k], med[k] / med["rec"],
+                 "" if k == "rec" else "; %d of %d envs frozen" % (frozen[k], n)))
+    del rows, ring
+    env.close(); pol.close()
+    assert med[0] <= 1.03 * med["rec"], (med[0], med["rec"], med[0] / med["rec"])
