@@ -17,6 +17,7 @@
  *   q3_step                    step_async() + step_wait(): f_func (cell 2) forward-Euler step, reward,
  *                              termination, auto-reset; returns `self.states`
  *   q3_step_many               K x q3_step in one kernel with the state held in registers
+ *   q3_rollout_policy          SB3's collect_rollouts() on these envs: K x [policy forward, Gaussian sample, clip, q3_step] in one kernel
  *   q3_get_state/q3_set_state  attribute access to env.states / target_gates / step_counts
  *
  * Conventions are those of quadrace.h: 0 on success, QR_E_* (<0) on error with text in qr_last_error();
@@ -71,6 +72,32 @@ int q3_step_many(q3_env* env, const float* actions_dev, int num_steps, void* rew
  * done_out / trunc_out [K][N] (the last three may be NULL).  Same results as K x q3_step, bit for bit. */
 int q3_rollout(q3_env* env, const float* actions_dev, int num_steps, void* states_steps_out_dev, void* rew_out_dev,
                uint8_t* done_out_dev, uint8_t* trunc_out_dev, void* stream);
+
+/* Closed-loop rollout: K x [obs = float32(env.states) -> policy (quadrace.h: qr_policy with obs_len 16, 3 x 120 ReLU, on the matrix
+ * cores) -> action = mean + exp(log_std) * N(0,1) -> q3_step(clip(action, -1, 1))] in ONE kernel, for either kind.  Bit for bit what K
+ * rounds of [qr_policy_forward (or qr_policy_forward_f32class) on the float32 cast of the states, the sampling arithmetic
+ * a = fmaf(std, eps, mean), q3_step] give.  The noise stream is qr_rollout_policy's: Philox4x32-10 with counter (global env id lo, hi,
+ * step lo, hi), global env id = env_id_base + i, step = first_step + k, key = noise_seed ^ (0x9E3779B9, 0x85EBCA6B); Box-Muller.
+ *   flags: QR_ROLLOUT_DETERMINISTIC (action = mean) | QR_ROLLOUT_F32CLASS (the reference-precision forward); log_std: host float[4].
+ *   Outputs are float32 / uint8 for BOTH kinds: obs_out [K][N][16] = the observation each action was computed from, act_out [K][N][4]
+ *   = the UNCLIPPED action, logp_out [K][N] its log-probability, rew_out [K][N] = (float)reward, done_out / trunc_out [K][N].
+ *   term_obs_dev [K][N][16] (may be NULL): row [k][i] receives the float32 cast of the state after the integration and BEFORE the
+ *   auto-reset for an env whose step k ended; rows of envs that did not finish are not written.
+ *   last_obs_dev [N][16] (may be NULL): float32 cast of env.states after the last step.  states_out_dev [N][16] T (may be NULL): env.states
+ *   after the last step in the env's own type, as in q3_step_many.  trunc_out_dev may be NULL.
+ * Refused before anything is launched (env state and buffers untouched, text in qr_last_error()).  QR_E_INVALID: a null env, policy,
+ * log_std or required output; num_steps < 1; another flag bit; a policy whose obs_len is not 16 or that lives on another device; an
+ * obs_out / act_out / term_obs / last_obs / states_out pointer that is not 16-byte aligned.  QR_E_STATE: a policy without weights, a
+ * gates env without a track. */
+struct qr_policy;
+int q3_rollout_policy(q3_env* env, struct qr_policy* policy, int32_t num_steps, const float* log_std, uint64_t noise_seed,
+                      uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev,
+                      float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* term_obs_dev,
+                      float* last_obs_dev, void* states_out_dev, void* stream);
+
+/* episode counters [N] u32 (the position of each env in its reset stream; q3_seed zeroes them): set_dev (may be NULL) is copied in first,
+ * then get_dev (may be NULL) receives them.  With q3_get_state / q3_set_state this is everything a checkpoint needs to resume bit for bit. */
+int q3_episode_counts(q3_env* env, uint32_t* get_dev, const uint32_t* set_dev, void* stream);
 
 /* states [N][16] T, target [N] i32 (gates only; ignored / zero for hover), steps [N] i32; any may be NULL */
 int q3_get_state(q3_env* env, void* states_dev, int32_t* target_dev, int32_t* steps_dev, void* stream);

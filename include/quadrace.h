@@ -190,6 +190,8 @@ int qr_profile_steps(qr_env* env, int32_t num_steps, const float* actions_dev, f
  * c_code/neural_network.c:397-430 nn_forward).  f16 operands, f32 accumulation.  Replaces `model.predict(env.states,
  * deterministic=True)` (R:801) between env steps without leaving the GPU.
  *   weights: host float32 arrays in torch.nn.Linear layout, w[out][in], b[out].
+ *   obs_len: an observation length of the race envs (13 + 4 gates_ahead, 20 + 4 gates_ahead; gates_ahead 0..4) or 16, the raw-state
+ *   observation of the predecessor envs (quad3d.h); anything else is QR_E_INVALID.  The same holds for qr_policy_bank_create.
  * --------------------------------------------------------------------------------------------------------------- */
 typedef struct qr_policy qr_policy;
 int qr_policy_create(int32_t obs_len, int32_t device, qr_policy** out);
@@ -414,7 +416,7 @@ int qr_blackbox_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const 
  * accumulation; parameters, gradient accumulation and Adam are f32.
  * Rollout rows (obs [rows][obs_len], act [rows][4], old_logp / adv / ret [rows]) are device arrays; idx_dev[B] selects
  * the rows of this minibatch (64 <= B <= max_minibatch; a last, partial group of 64 rows is masked inside the gradient kernel --
- * the reference's batch_size is 5000, R:792). */
+ * the reference's batch_size is 5000, R:792).  obs_len: the lengths qr_policy_create accepts (the race envs' and 16). */
 typedef struct qr_ppo qr_ppo;
 int qr_ppo_create(int32_t obs_len, int32_t device, int32_t max_minibatch, qr_ppo** out);
 /* The same with explicit choices (verification / A-B; qr_ppo_create = flags 0 = the measured-fastest form; the library reads no

@@ -111,6 +111,9 @@ SIGNATURES = {
     "q3_rollout": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "q3_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "q3_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "q3_rollout_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
+    "q3_episode_counts": (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 

@@ -22,10 +22,7 @@
 #include "../../include/quad3d.h"
 #include "../../include/quadrace.h"
 #include "quadrace_device.hpp"
-
-namespace qr {
-int set_last_error(int code, const std::string& msg);  // quadrace_abi.hip
-}
+#include "quadrace_launch.hpp"   // set_last_error, launch_dynamic_lds, the policy accessors; quadrace_policy.hpp (the MFMA forward)
 
 namespace {
 
@@ -234,9 +231,18 @@ __device__ __forceinline__ void q3_reset_env(const Q3Params& P, int i, Q3Env<flo
     e.target = seg;
 }
 
+// before_reset(): called for an env whose step ended, with e.s = the state after the integration, before q3_reset_env replaces it
+// (the terminal observation of the closed-loop kernel); the other kernels pass nothing
+// (taken BY VALUE: as a forwarding reference the empty default perturbed operand order and copy placement in q3_step_kernel and
+// q3_rollout_kernel; by value they compile to the instructions they had without the hook -- tools/isa_digest.py)
+struct Q3NoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+
 // Quadcopter3DVec.step_wait (Q3 cell 6)
+template <class BeforeReset = Q3NoHook>
 __device__ __forceinline__ double q3_step_env(const Q3Params& P, int i, Q3Env<double>& e, const float u[4], bool& done,
-                                              bool& trunc) {
+                                              bool& trunc, BeforeReset before_reset = BeforeReset()) {
     double ds[16];
     e.steps += 1;
     f_q3<double>(e.s, u, ds);
@@ -258,13 +264,17 @@ __device__ __forceinline__ double q3_step_env(const Q3Params& P, int i, Q3Env<do
     const bool max_steps = e.steps >= P.max_steps;
     done = goal || oob || max_steps;
     trunc = max_steps || oob;
-    if (done) q3_reset_env(P, i, e);
+    if (done) {
+        before_reset();
+        q3_reset_env(P, i, e);
+    }
     return reward;
 }
 
 // Quadcopter3DVecGates.step_wait (Q3 cell 14)
+template <class BeforeReset = Q3NoHook>
 __device__ __forceinline__ float q3_step_env(const Q3Params& P, int i, Q3Env<float>& e, const float u[4], bool& done,
-                                             bool& trunc) {
+                                             bool& trunc, BeforeReset before_reset = BeforeReset()) {
     float ds[16], ns[16];
     const float dt = (float)P.dt;
     const float* s = e.s;
@@ -299,7 +309,10 @@ __device__ __forceinline__ float q3_step_env(const Q3Params& P, int i, Q3Env<flo
     trunc = max_steps;
 #pragma unroll
     for (int k = 0; k < 16; ++k) e.s[k] = ns[k];
-    if (done) q3_reset_env(P, i, e);
+    if (done) {
+        before_reset();
+        q3_reset_env(P, i, e);
+    }
     return reward;
 }
 
@@ -511,6 +524,161 @@ __global__ __launch_bounds__(kQ3Block) void q3_copy_state_kernel(int n, Q3Buffer
     if (steps_out) steps_out[i] = B.steps[i];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Closed-loop rollout (q3_rollout_policy): policy network + Gaussian action sampling + env step, K times in one kernel -- PPO's collect
+// phase for the two predecessor envs.  The step RESTATES rollout_policy_kernel's (quadrace_env_kernels.hpp) statement for statement with
+// the q3 env in the middle: same noise slices in the second hidden layer's shadow, same observation-row store under the third layer,
+// same sampling arithmetic, one 256-env workgroup per CU.  The observation of both envs is the state row itself, rounded to float32.
+//   T = double (hover) / float (gates); kF32: the f32-class forward (policy_forward_f32class) instead of the f16-operand one.
+// ---------------------------------------------------------------------------------------------------
+constexpr int kQ3ObsLen = 16;
+constexpr int kQ3ObsTileChunks = 64 * RowTile<float>::kStride;   // one wave's [64][16] float32 rows, row stride padded (16-byte chunks)
+constexpr size_t kQ3PolicyLdsBytes = (size_t)qr::PolicyDims<kQ3ObsLen>::kTotalHalf8 * 16 + (size_t)(kQ3Block / 64) * kQ3ObsTileChunks * 16;
+
+__device__ __forceinline__ void q3_obs_tile_write(float4* __restrict__ tile, int lane, const float* o) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tile[lane * RowTile<float>::kStride + k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// full waves only: 256 chunks, every round with the whole wave
+__device__ __forceinline__ void q3_obs_tile_flush(const float4* __restrict__ tile, float* __restrict__ obs_out, size_t wave_first_env, int lane) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float4* g4 = reinterpret_cast<float4*>(obs_out + wave_first_env * kQ3ObsLen);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int cidx = q * 64 + lane;
+        qr::stream_store(g4 + cidx, tile[(cidx >> 2) * RowTile<float>::kStride + (cidx & 3)]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void q3_store_obs(float* __restrict__ obs_out, size_t i, const float* o) {
+    float4* r4 = reinterpret_cast<float4*>(obs_out + i * kQ3ObsLen);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qr::stream_store(r4 + k, make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]));
+}
+
+template <typename T, bool kF32>
+__global__ void __launch_bounds__(kQ3Block, 1)
+q3_rollout_policy_kernel(Q3Params P, Q3Buffers<T> B, qr::PolicyArgs A, int K, float* __restrict__ obs_out, float4* __restrict__ act_out,
+                         float* __restrict__ logp_out, float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
+                         uint8_t* __restrict__ trunc_out, float* __restrict__ term_obs, float* __restrict__ last_obs_out,
+                         T* __restrict__ states_out) {
+    using namespace qr;
+    constexpr int L = kQ3ObsLen;
+    using D = PolicyDims<L>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half8* W = reinterpret_cast<half8*>(smem);   // policy weights (f16) | obs tiles
+    const int i = blockIdx.x * kQ3Block + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    {
+        const float4* s4 = reinterpret_cast<const float4*>(A.weights);
+        float4* d4 = reinterpret_cast<float4*>(W);
+        for (int j = threadIdx.x; j < D::kTotalHalf8; j += kQ3Block) d4[j] = s4[j];
+    }
+    __syncthreads();
+    const int wave_first = i - lane;
+    if (wave_first >= P.n) return;              // whole wave past the end (no workgroup barrier follows)
+    const bool active = i < P.n;
+    const int ii = active ? i : wave_first;     // ragged-tail lanes shadow the wave's first env: they take part in every matrix
+                                                // instruction and wave barrier and store nothing
+    const bool full_wave = wave_first + 64 <= P.n;
+    float4* tile = reinterpret_cast<float4*>(smem + (size_t)D::kTotalHalf8 * 16) + (threadIdx.x >> 6) * kQ3ObsTileChunks;
+    Q3Env<T> e;
+    q3_load(B, ii, e);
+    const uint32_t gid_lo = P.gid_lo + (uint32_t)ii;
+    const uint32_t gid_hi = P.gid_hi + (gid_lo < P.gid_lo ? 1u : 0u);
+    const size_t n = (size_t)P.n;
+    float o[L];
+#pragma unroll
+    for (int c = 0; c < L; ++c) o[c] = (float)e.s[c];
+    for (int k = 0; k < K; ++k) {
+        // Action noise eps ~ N(0, 1)^4: rollout_policy_kernel's slices, verbatim (drawn in deterministic mode too and then multiplied out)
+        float mean[4];
+        float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t pc[4];
+        float bm_u1a, bm_u2a, bm_u1b, bm_u2b, bm_ra, bm_rb, bm_sa, bm_ca, bm_sb, bm_cb;
+        auto pin_u = [](uint32_t& x) { asm volatile("" : "+v"(x)); };
+        auto pin_f = [](float& x) { asm volatile("" : "+v"(x)); };
+        auto noise_slice = [&](int slot) {
+            if (slot >= 1 && slot <= 11) { pin_u(pc[0]); pin_u(pc[1]); pin_u(pc[2]); pin_u(pc[3]); }
+            if (slot == 12) pin_f(bm_u1a);
+            if (slot == 13) pin_f(bm_u1b);
+            if (slot == 14) pin_f(bm_u2a);
+            if (slot == 15) pin_f(bm_u2b);
+            if (slot == 16) { pin_f(bm_ra); pin_f(bm_rb); pin_f(bm_sa); pin_f(bm_sb); }
+            if (slot == 0) {
+                const uint32_t s_lo = A.step_lo + (uint32_t)k;
+                pc[0] = gid_lo; pc[1] = gid_hi; pc[2] = s_lo; pc[3] = A.step_hi + (s_lo < A.step_lo ? 1u : 0u);
+            } else if (slot <= 10) {
+                philox4x32_round(pc, A.seed_lo, A.seed_hi, slot - 1);
+            } else if (slot == 11) {  // Box-Muller: two pairs of normals from four uniforms (u1 in (0,1], u2 in [0,1))
+                bm_u1a = (float)((pc[0] >> 8) + 1u) * 5.9604644775390625e-8f; bm_u2a = u01(pc[1]);
+                bm_u1b = (float)((pc[2] >> 8) + 1u) * 5.9604644775390625e-8f; bm_u2b = u01(pc[3]);
+            } else if (slot == 12) {
+                bm_ra = fast_sqrt(-2.0f * __logf(bm_u1a));
+            } else if (slot == 13) {
+                bm_rb = fast_sqrt(-2.0f * __logf(bm_u1b));
+            } else if (slot == 14) {
+                qr_sincos(6.283185307179586f * bm_u2a, bm_sa, bm_ca);
+            } else if (slot == 15) {
+                qr_sincos(6.283185307179586f * bm_u2b, bm_sb, bm_cb);
+            } else if (slot == 16) {
+                eps[0] = bm_ra * bm_ca; eps[1] = bm_ra * bm_sa; eps[2] = bm_rb * bm_cb; eps[3] = bm_rb * bm_sb;
+            }
+        };
+        // the observation row of this step (the policy's input) is stored under the third layer's MFMAs (full waves)
+        auto obs_slice = [&](int slot) {
+            if (slot == 0 && full_wave) q3_obs_tile_write(tile, lane, o);
+            if (slot == 2 && full_wave) q3_obs_tile_flush(tile, obs_out + (size_t)k * n * L, (size_t)wave_first, lane);
+        };
+        if constexpr (kF32) {
+#pragma unroll
+            for (int slot = 0; slot <= 16; ++slot) noise_slice(slot);
+            obs_slice(0);
+            obs_slice(2);
+            policy_forward_f32class<L>(W, A.weights_lo, lane, o, mean);
+        } else {
+            policy_forward<L>(W, lane, o, mean, noise_slice, obs_slice);
+        }
+        float a[4] = {mean[0], mean[1], mean[2], mean[3]};
+        float logp = A.logp_const;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float ec = A.deterministic ? 0.0f : eps[c];   // fmaf(std, 0, mean) = mean, fmaf(-0, 0, logp) = logp
+            a[c] = fmaf(A.std[c], ec, mean[c]);
+            logp = fmaf(-0.5f * ec, ec, logp);
+        }
+        // rollout buffer row t: the observation the action was computed from (stored above), the unclipped action, its log-prob
+        if (!full_wave && active) q3_store_obs(obs_out + (size_t)k * n * L, (size_t)i, o);
+        if (active) {
+            stream_store(act_out + (size_t)k * n + i, make_float4(a[0], a[1], a[2], a[3]));
+            stream_store(logp_out + (size_t)k * n + i, logp);
+        }
+        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
+                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        bool done, trunc;
+        const T reward = q3_step_env(P, ii, e, u, done, trunc, [&]() {
+            if (term_obs == nullptr || !active) return;   // the final state of the episode, before the auto-reset replaces it
+            float* row = term_obs + ((size_t)k * n + i) * L;
+#pragma unroll
+            for (int c = 0; c < L; ++c) row[c] = (float)e.s[c];
+        });
+        if (active) {
+            stream_store(rew_out + (size_t)k * n + i, (float)reward);
+            stream_store(done_out + (size_t)k * n + i, (uint8_t)(done ? 1 : 0));
+            if (trunc_out) stream_store(trunc_out + (size_t)k * n + i, (uint8_t)(trunc ? 1 : 0));
+        }
+#pragma unroll
+        for (int c = 0; c < L; ++c) o[c] = (float)e.s[c];
+    }
+    if (!active) return;
+    if (last_obs_out) q3_store_obs(last_obs_out, (size_t)i, o);
+    q3_store(B, i, e);
+    if (states_out) store_row<T>(states_out, i, e.s);
+}
+
 int q3fail(int code, const std::string& m) { return qr::set_last_error(code, m); }
 
 #define Q3_HIP(expr)                                                                          \
@@ -540,6 +708,21 @@ int q3_ready(const q3_env* e) {
     if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, "q3_set_track has not been called");
     return QR_OK;
 }
+
+template <typename T>
+hipError_t q3_launch_rollout_policy(q3_env* e, const qr::PolicyArgs& A, int K, float* obs, float* act, float* logp, float* rew,
+                                           uint8_t* done, uint8_t* trunc, float* term_obs, float* last_obs, void* states_out, hipStream_t st) {
+    float4* act4 = reinterpret_cast<float4*>(act);
+    T* so = static_cast<T*>(states_out);
+    if (A.f32class)
+        return qr::launch_dynamic_lds<q3_rollout_policy_kernel<T, true>>(dim3(e->grid()), dim3(kQ3Block), kQ3PolicyLdsBytes, st, e->P,
+                                                                         e->buffers<T>(), A, K, obs, act4, logp, rew, done, trunc, term_obs,
+                                                                         last_obs, so);
+    return qr::launch_dynamic_lds<q3_rollout_policy_kernel<T, false>>(dim3(e->grid()), dim3(kQ3Block), kQ3PolicyLdsBytes, st, e->P,
+                                                                      e->buffers<T>(), A, K, obs, act4, logp, rew, done, trunc, term_obs,
+                                                                      last_obs, so);
+}
+
 }  // namespace
 
 extern "C" {
@@ -715,6 +898,49 @@ int q3_rollout(q3_env* e, const float* actions, int K, void* states_steps_out, v
     return q3_launch_rollout(e, actions, K, states_steps_out, rew_out, done_out, trunc_out, nullptr, stream);
 }
 
+// Every refusal comes before anything is enqueued: a failed call leaves the env and the buffers untouched.
+int q3_rollout_policy(q3_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags,
+                      float* obs_out, float* act_out, float* logp_out, float* rew_out, uint8_t* done_out, uint8_t* trunc_out, float* term_obs,
+                      float* last_obs, void* states_out, void* stream) {
+    const std::string w = "q3_rollout_policy: ";
+    if (!e) return q3fail(QR_E_INVALID, w + "null q3_env handle");
+    if (!policy || !log_std) return q3fail(QR_E_INVALID, w + "null policy handle or log_std");
+    if (K < 1) return q3fail(QR_E_INVALID, w + "num_steps must be >= 1");
+    if (!obs_out || !act_out || !logp_out || !rew_out || !done_out) return q3fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
+    if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return q3fail(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (qr::policy_obs_len(policy) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "policy obs_len must be 16 (the state row is the observation)");
+    if (qr::policy_device(policy) != e->device) return q3fail(QR_E_INVALID, w + "policy on another GPU");
+    if (((uintptr_t)obs_out | (uintptr_t)act_out | (uintptr_t)term_obs | (uintptr_t)last_obs | (uintptr_t)states_out) & 15u)
+        return q3fail(QR_E_INVALID, w + "obs_out / act_out / term_obs / last_obs / states_out must be 16-byte aligned");
+    const qr::half8* wt = qr::policy_weights(policy);
+    if (!wt) return q3fail(QR_E_STATE, w + "the policy has no weights");
+    if (int rc = q3_ready(e)) return rc;
+    qr::PolicyArgs A{};
+    A.weights = wt;
+    A.weights_lo = qr::policy_weights_lo(policy);
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    float sum_log_std = 0.0f;
+    for (int c = 0; c < 4; ++c) {
+        A.std[c] = expf(log_std[c]);
+        sum_log_std += log_std[c];
+    }
+    A.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
+    // the action-noise stream of qr_rollout_policy: Philox(counter = (env id, step), key = noise seed with the same fixed tweak)
+    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;
+    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
+    A.step_lo = (uint32_t)first_step;
+    A.step_hi = (uint32_t)(first_step >> 32);
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    Q3_HIP(hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (e->kind == Q3_KIND_HOVER)
+        Q3_HIP(q3_launch_rollout_policy<double>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
+    else
+        Q3_HIP(q3_launch_rollout_policy<float>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
+    return QR_OK;
+}
+
 int q3_get_state(q3_env* e, void* states, int32_t* target, int32_t* steps, void* stream) {
     if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
     Q3_HIP(hipSetDevice(e->device));
@@ -740,6 +966,16 @@ int q3_set_state(q3_env* e, const void* states, const int32_t* target, const int
         q3_copy_state_kernel<float><<<e->grid(), kQ3Block, 0, st>>>(e->P.n, e->buffers<float>(), nullptr, nullptr, nullptr,
                                                                    static_cast<const float*>(states), target, steps);
     Q3_HIP(hipGetLastError());
+    return QR_OK;
+}
+
+int q3_episode_counts(q3_env* e, uint32_t* get_dev, const uint32_t* set_dev, void* stream) {
+    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
+    Q3_HIP(hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bytes = (size_t)e->P.n * 4;
+    if (set_dev) Q3_HIP(hipMemcpyAsync(e->d_episode, set_dev, bytes, hipMemcpyDeviceToDevice, st));
+    if (get_dev) Q3_HIP(hipMemcpyAsync(get_dev, e->d_episode, bytes, hipMemcpyDeviceToDevice, st));
     return QR_OK;
 }
 

@@ -45,12 +45,14 @@ hipError_t dispatch_vg(int variant, int gates_ahead, F&& f) {
         return variant == kE2E ? f(std::integral_constant<int, kE2E>{}, ga) : f(std::integral_constant<int, kINDI>{}, ga);
     });
 }
-// observation length -> f(integral_constant<int, L>): every length the two env variants can produce (gates_ahead 0..4).  The caller
+// observation length -> f(integral_constant<int, L>): every length the two env variants can produce (gates_ahead 0..4: 13 + 4g, 20 + 4g)
+// and 16, the raw-state observation of the predecessor envs (include/quad3d.h).  The caller
 // supplies what an illegal length yields: `invalid()` runs only then (it may record an error message).
 template <typename F, typename Invalid>
 auto dispatch_L(int L, F&& f, Invalid&& invalid) -> decltype(invalid()) {
     switch (L) {
         case 13: return f(std::integral_constant<int, 13>{});
+        case 16: return f(std::integral_constant<int, 16>{});
         case 17: return f(std::integral_constant<int, 17>{});
         case 21: return f(std::integral_constant<int, 21>{});
         case 25: return f(std::integral_constant<int, 25>{});

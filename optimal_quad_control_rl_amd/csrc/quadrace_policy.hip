@@ -201,7 +201,7 @@ int qr_policy_create(int32_t obs_len, int32_t device, qr_policy** out) {
     if (!out) return pfail(QR_E_INVALID, "qr_policy_create: null output");
     *out = nullptr;
     if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
-        return pfail(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs");
+        return pfail(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return pfail(QR_E_NO_DEVICE, "qr_policy_create: no HIP device visible (no CPU fallback)");
@@ -270,7 +270,7 @@ int qr_policy_bank_create(int32_t obs_len, int32_t device, int32_t capacity, qr_
     if (!out) return pfail(QR_E_INVALID, "qr_policy_bank_create: null output");
     *out = nullptr;
     if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
-        return pfail(QR_E_INVALID, "qr_policy_bank_create: obs_len must be an observation length of the race envs");
+        return pfail(QR_E_INVALID, "qr_policy_bank_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
     if (capacity < 1) return pfail(QR_E_INVALID, "qr_policy_bank_create: capacity must be >= 1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)

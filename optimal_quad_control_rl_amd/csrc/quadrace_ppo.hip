@@ -1737,7 +1737,7 @@ struct PpoOps {
 
 template <typename F>
 int dispatch_L(int L, F&& f) {   // qr::dispatch_L with this file's failure: the message goes to qr_last_error()
-    return qr::dispatch_L(L, f, [] { return ppofail(QR_E_INVALID, "obs_len must be an observation length of the race envs"); });
+    return qr::dispatch_L(L, f, [] { return ppofail(QR_E_INVALID, "obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)"); });
 }
 
 int fill_batch(qr_ppo* p, qr::PpoBatch& b, const float* theta, const float* obs, const float* act, const float* old_logp,

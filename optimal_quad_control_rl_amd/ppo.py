@@ -294,6 +294,12 @@ class PPO:
         self.gamma, self.lam, self.clip = gamma, gae_lambda, clip_range
         self.vf_coef, self.ent_coef, self.max_grad_norm = vf_coef, ent_coef, max_grad_norm
         self.target_kl, self.lr0, self.lr_final_frac, self.total_hint = target_kl, learning_rate, lr_final_frac, total_timesteps_hint
+        # the predecessor envs (quad3d.py) have one collect path: the closed-loop kernel.  Their hover observations are float64 and there is no
+        # per-step terminal-observation buffer, so the per-step path is refused instead of training on something else.
+        self._q3 = hasattr(env, "KIND") and hasattr(env, "trainer_state")
+        if self._q3 and not fused_collect:
+            raise ValueError("Quadcopter3DVec / Quadcopter3DVecGates train with fused_collect=True only: there is no per-step "
+                             "(fused_collect=False) collect path for them (float64 hover observations, no per-step terminal buffer)")
         torch.manual_seed(seed)
         # minibatch permutations come from the trainer's OWN generator (checkpointed; independent of whatever else draws from
         # torch's global generators in the process)
@@ -751,9 +757,12 @@ class PPO:
                        betas=tuple(self._updater.betas), eps=float(self._updater.eps), lr=float(self.opt.param_groups[0]["lr"]))
         else:
             opt = dict(kind="torch_adam", state=self.opt.state_dict())
-        world, dist, target, steps, episode = self.env.get_state_tensors()
-        env = dict(world=world.cpu(), dist=None if dist is None else dist.cpu(), target=target.cpu(), steps=steps.cpu(),
-                   episode=episode.cpu())
+        if self._q3:
+            env = self.env.trainer_state()
+        else:
+            world, dist, target, steps, episode = self.env.get_state_tensors()
+            env = dict(world=world.cpu(), dist=None if dist is None else dist.cpu(), target=target.cpu(), steps=steps.cpu(),
+                       episode=episode.cpu())
         return dict(optimizer=opt, num_timesteps=int(self.num_timesteps), ep_ret=self.ep_ret.cpu(), ep_len=self.ep_len.cpu(),
                     ep_gates=self.ep_gates.cpu(), stats=dict(self.stats), noise_seed=int(self.noise_seed), noise_step=int(self.noise_step),
                     lr0=float(self.lr0), lr_final_frac=float(self.lr_final_frac), total_hint=self.total_hint,
@@ -794,6 +803,11 @@ class PPO:
         self._kl_first_trips = int(sd.get("kl_trips", 0))
         self._kl_lr_scale = float(sd.get("kl_lr_scale", 1.0))
         e = sd["env"]
+        if self._q3:
+            self.env.load_trainer_state(e)
+            self.obs = self.env.states_tensor.clone()
+            self._gen.set_state(sd["rng"])
+            return
         self.env.set_state_tensors(world=e["world"], dist=e["dist"], target=e["target"], steps=e["steps"], episode=e["episode"])
         cs = sd.get("conditions")
         if cs is not None:

@@ -6,6 +6,8 @@
 Same constructors, methods and public attributes (`states`, `step_counts`, `target_gates`, `max_steps`, `dt`, the hover
 thresholds, `render()`), on top of include/quad3d.h in libquadrace.so: one HIP kernel per step over all envs, plus a
 device-tensor path (`reset_device`, `step_device`, `rollout_device`) without host round trips.  No NumPy fallback.
+`rollout_policy_device` is the closed loop a trainer collects with (policy forward, sampling and env step K times in one
+kernel): `ppo.PPO(env, fused_collect=True)` and `sb3.PPO("MlpPolicy", env)` train both envs through it.
 
 Differences that are this build's own (documented, not the reference's): resets draw from a counter-based Philox
 stream (`seed`, `env_id_base`) instead of NumPy's global generator; the per-step `print()` calls of the reference
@@ -17,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vec_env import _Base, _f32p, _make_box, _ptr
+from .vec_env import _Base, _f32p, _make_box, _precision_flags, _ptr
 
 Q3_KIND_HOVER, Q3_KIND_GATES = 0, 1
 _KEYS = ['x', 'y', 'z', 'vx', 'vy', 'vz', 'phi', 'theta', 'psi', 'p', 'q', 'r', 'w1', 'w2', 'w3', 'w4']
@@ -27,6 +29,7 @@ class _Quad3DBase(_Base):
     KIND = None
     DTYPE = None        # torch dtype of states / rewards
     NP_DTYPE = None
+    state_len = 16      # the observation is the state row itself (float32 cast of it for the policy)
 
     def _create(self, num_envs, device, seed, env_id_base):
         self._h = None
@@ -54,6 +57,8 @@ class _Quad3DBase(_Base):
         self._trunc_d = torch.zeros(n, dtype=torch.uint8, device=self.device)
         self._act_d = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
         self._act_h = torch.zeros((n, 4), dtype=torch.float32).pin_memory()
+        self._obs32_d = None      # float32 observation after the last closed-loop rollout (allocated on first use)
+        self._term_obs_buf = None
         _lib.check(self._L.q3_seed(self._h, int(seed)))
 
     def __del__(self):
@@ -182,6 +187,67 @@ class _Quad3DBase(_Base):
         _lib.check(self._L.q3_rollout(self._h, _ptr(actions), K, _ptr(st), _ptr(rew), _ptr(done), _ptr(trunc), self._stream()))
         self._states_d.copy_(st[K - 1])
         return out
+
+    def set_terminal_obs_buffer(self, buf):
+        """Register (or, with None, remove) a float32 CUDA tensor [K, N, 16] for rollout_policy_device: row [k, env] receives the
+        float32 cast of the final state of an episode that ended at step k -- taken after the integration, before the auto-reset.
+        Rows of envs that did not finish are left untouched.  Kept on this side and handed to every q3_rollout_policy call."""
+        if buf is not None:
+            if not (torch.is_tensor(buf) and buf.is_cuda and buf.device == self.device and buf.dtype == torch.float32 and buf.is_contiguous()
+                    and buf.dim() == 3 and tuple(buf.shape[1:]) == (self.num_envs, 16)):
+                raise ValueError("the terminal-observation buffer must be a contiguous float32 tensor [K, num_envs, 16] on the env's device")
+        self._term_obs_buf = buf
+
+    def rollout_policy_device(self, policy, num_steps, log_std, noise_seed=0, first_step=0, deterministic=False, out=None,
+                              precision="f16-operands"):
+        """Closed-loop rollout in ONE kernel (q3_rollout_policy): K x [obs = float32(states) -> MFMA policy -> sample -> step(clip)].
+        `policy` is an optimal_quad_control_rl_amd.policy.MfmaPolicy with obs_len 16.  Returns device tensors
+        (obs[K,N,16], actions[K,N,4] unclipped, logp[K,N], reward[K,N], done[K,N] u8, trunc[K,N] u8, last_obs[N,16]); everything is
+        float32 / uint8 for both envs.  precision="f32": the policy forward at the reference's precision (QR_ROLLOUT_F32CLASS)."""
+        flags = _precision_flags(precision)
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        term = self._term_obs_buf
+        if term is not None and K > int(term.shape[0]):
+            raise ValueError(f"num_steps = {K} exceeds the {int(term.shape[0])} rows of the terminal-observation buffer")
+        if out is None:
+            out = (torch.empty((K, n, 16), dtype=torch.float32, device=dev),
+                   torch.empty((K, n, 4), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.float32, device=dev),
+                   torch.empty((K, n), dtype=torch.uint8, device=dev),
+                   torch.empty((K, n), dtype=torch.uint8, device=dev))
+        obs, act, logp, rew, done, trunc = out
+        if self._obs32_d is None:
+            self._obs32_d = torch.zeros((n, 16), dtype=torch.float32, device=dev)
+        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
+                                  dtype=np.float32).reshape(4)
+        _lib.check(self._L.q3_rollout_policy(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
+                                             int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
+                                             _ptr(done), _ptr(trunc), _ptr(term), _ptr(self._obs32_d), _ptr(self._states_d),
+                                             self._stream()))
+        return obs, act, logp, rew, done, trunc, self._obs32_d
+
+    # ---- what a trainer's checkpoint holds of the env (ppo.PPO.state_dict): with the same constructor arguments, loading it continues
+    # the run bit for bit (the episode counters are the env's positions in its reset streams)
+    def trainer_state(self):
+        st, tg, sc = self._get()
+        ep = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self._L.q3_episode_counts(self._h, _ptr(ep), None, self._stream()))
+        return dict(kind="q3", states=st.cpu(), target=tg.cpu(), steps=sc.cpu(), episode=ep.cpu())
+
+    def load_trainer_state(self, d):
+        if d.get("kind") != "q3":
+            raise ValueError("the checkpoint's env state was not written by a Quadcopter3DVec / Quadcopter3DVecGates env")
+        self._set(d["states"], d["target"], d["steps"])
+        ep = d["episode"].to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.check(self._L.q3_episode_counts(self._h, None, _ptr(ep), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
+        self._states_d.copy_(self._get()[0])
+
+    @property
+    def states_tensor(self):
+        """env.states on the device, as the last reset_device / step_device / rollout call left it (the env's own buffer)."""
+        return self._states_d
 
     # ---- the VecEnv surface of the reference ---------------------------------------------------------------------------
     def reset_(self, dones):
