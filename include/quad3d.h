@@ -18,6 +18,9 @@
  *                              termination, auto-reset; returns `self.states`
  *   q3_step_many               K x q3_step in one kernel with the state held in registers
  *   q3_rollout_policy          SB3's collect_rollouts() on these envs: K x [policy forward, Gaussian sample, clip, q3_step] in one kernel
+ *   q3_evaluate_policy         the loop a user writes after training: fly the deterministic policy, count how the episodes end and how
+ *                              long the successful ones take -- one kernel, one 12-int record per env, nothing stored per step
+ *   q3_evaluate_policy_bank    the same for many policies (checkpoints of a run) in one launch, every one on the same starts
  *   q3_get_state/q3_set_state  attribute access to env.states / target_gates / step_counts
  *
  * Conventions are those of quadrace.h: 0 on success, QR_E_* (<0) on error with text in qr_last_error();
@@ -94,6 +97,41 @@ int q3_rollout_policy(q3_env* env, struct qr_policy* policy, int32_t num_steps, 
                       uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev,
                       float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* term_obs_dev,
                       float* last_obs_dev, void* states_out_dev, void* stream);
+
+/* Closed-loop evaluation: K x [obs = float32(env.states) -> policy -> q3_step(clip(mean, -1, 1))] in ONE kernel with NO store inside the
+ * step loop, for either kind: what a user does right after training -- fly the deterministic policy, count how its episodes end, time
+ * the ones that succeed.  The env state after the call equals q3_rollout_policy(QR_ROLLOUT_DETERMINISTIC) after the same num_steps.
+ *   flags: 0 or QR_ROLLOUT_F32CLASS (the reference-precision forward).
+ *   rec_dev [N][Q3_EVAL_REC_INTS] int32, rows 16-byte aligned; READ at the start and written at the end: zero it for a fresh evaluation,
+ *   pass it again to continue one.  All times are in steps.
+ *     [0] steps evaluated (cumulative)   [1] SUCCESS ends   [2] TIMEOUT ends   [3] OOB ends   [4] GROUND ends (hover: 0)
+ *     [5] COLLISION ends (hover: 0)      [6] sum of the lengths of SUCCESS episodes           [7] sum of the lengths of all ended episodes
+ *     [8] gate passes on steps that do not end the episode (hover: 0)   [9] shortest SUCCESS episode so far, 0 = none yet   [10], [11] 0
+ *   An episode's length is the env's step counter at its end (after the increment, before the reset).  The end causes are exclusive:
+ *     hover  SUCCESS = goal reached inside the bounds before the limit (done and no TimeLimit.truncated); else TIMEOUT if the step
+ *            counter reached max_steps; else OOB
+ *     gates  SUCCESS = final gate passed; else TIMEOUT if max_steps was reached; else GROUND (pre-step z > 0); else OOB (the reference's
+ *            pre-step predicate on x, y, p, q, r); else COLLISION
+ *   recf_dev [N][Q3_EVAL_REC_FLOATS] float32 (may be NULL), read and written like rec_dev: {return of the running episode, sum of the
+ *   returns of the finished episodes, sum of their squares, 0}, sequential float32 sums of (float)reward in step order, no FMA.
+ * Refused before anything is enqueued (env state and records untouched, text in qr_last_error()).  QR_E_INVALID: a null env, policy or
+ * rec_dev; num_steps < 1; another flag bit; a policy whose obs_len is not 16 or that lives on another device; a rec_dev / recf_dev that
+ * is not 16-byte aligned.  QR_E_STATE: a policy without weights, a gates env without a track. */
+#define Q3_EVAL_REC_INTS 12
+#define Q3_EVAL_REC_FLOATS 4
+int q3_evaluate_policy(q3_env* env, struct qr_policy* policy, int32_t num_steps, int32_t flags, int32_t* rec_dev, float* recf_dev,
+                       void* stream);
+
+/* The same for a BANK of policies in one launch (quadrace.h: qr_policy_bank_create(16, capacity, ...)): slot p, p < num_policies, flies
+ * envs [p E, (p + 1) E), E = envs_per_policy; rows [p E, (p + 1) E) of rec_dev / recf_dev belong to it.  Inside this call an env that
+ * ends its episode restarts from the reset stream of its index WITHIN its group (env id = env_id_base + (i mod E)), so groups that start
+ * equal see the same starts and restarts, and group p flies bit for bit what an E-env handle with the same seed and env_id_base flies
+ * under q3_evaluate_policy with policy p.
+ * Refusals as above, and QR_E_INVALID: a null bank; envs_per_policy not a positive multiple of 256; num_policies * envs_per_policy !=
+ * num_envs; num_policies above the bank's capacity.  QR_E_STATE: a slot below num_policies that was never set (named in the message). */
+struct qr_policy_bank;
+int q3_evaluate_policy_bank(q3_env* env, struct qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy, int32_t num_steps,
+                            int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* episode counters [N] u32 (the position of each env in its reset stream; q3_seed zeroes them): set_dev (may be NULL) is copied in first,
  * then get_dev (may be NULL) receives them.  With q3_get_state / q3_set_state this is everything a checkpoint needs to resume bit for bit. */

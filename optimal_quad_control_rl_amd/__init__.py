@@ -9,7 +9,8 @@ from .tracks import TRAIN_DISTURBANCE_RANGES, square_track, zigzag_track  # noqa
 __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square_track", "TRAIN_DISTURBANCE_RANGES",
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
-           "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog"]
+           "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
+           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -26,6 +27,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
 
         return getattr(sb3, name)
     if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
+        from . import evaluation
+
+        return getattr(evaluation, name)
+    if name in ("evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval"):  # the same for the predecessor envs: how episodes end (q3_evaluate_policy)
         from . import evaluation
 
         return getattr(evaluation, name)

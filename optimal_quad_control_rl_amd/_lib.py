@@ -114,6 +114,8 @@ SIGNATURES = {
     "q3_rollout_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp]),
     "q3_episode_counts": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "q3_evaluate_policy": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "q3_evaluate_policy_bank": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
 }
 
 
@@ -121,7 +123,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_record_policy", "qr_record_row_len", "qr_policy_bank_create", "qr_policy_bank_destroy", "qr_policy_bank_capacity",
                     "qr_policy_bank_set", "qr_evaluate_policy_bank", "qr_condition_bank_create", "qr_condition_bank_destroy",
                     "qr_condition_bank_capacity", "qr_condition_bank_set", "qr_evaluate_policy_grid",
-                    "qr_rollout_policy_conditions", "qr_blackbox_policy")   # added in rounds 5-13: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
+                    "q3_evaluate_policy_bank")   # added in rounds 5-13 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

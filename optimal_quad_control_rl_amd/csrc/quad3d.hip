@@ -679,6 +679,162 @@ q3_rollout_policy_kernel(Q3Params P, Q3Buffers<T> B, qr::PolicyArgs A, int K, fl
     if (states_out) store_row<T>(states_out, i, e.s);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Closed-loop evaluation (q3_evaluate_policy, q3_evaluate_policy_bank): q3_rollout_policy_kernel's step loop without everything an
+// evaluation throws away -- no noise slices, no observation tile, no obs / act / logp / rew / done / term rows, NO global store inside
+// the step loop.  What leaves the kernel is one 12-int record and one 4-float record per env (layout: include/quad3d.h, restated on
+// the CPU in tests/q3_eval_spec.py, same order) and the env state after K steps, which equals q3_rollout_policy's in deterministic mode.
+// How an episode ended is decided from the pre-step state (gates: ground and out of bounds are the reference's PRE-step predicates),
+// from what the before_reset hook sees (step counter and target after the step, before the reset replaces them) and from done / trunc:
+//   hover  SUCCESS = done && !trunc (goal, inside bounds, before the limit); else TIMEOUT if the step counter reached max_steps; else OOB
+//   gates  SUCCESS = final gate passed; else TIMEOUT if trunc; else GROUND; else OOB; else COLLISION
+// All times are integer step counts; the float record is three sequential float32 sums without FMA, as in eval_policy_body.
+//   i: the lane's env (state, rec, recf);  rid: its id in the reset stream (what q3_step_env / q3_block receive as `i`)
+//   kTail: lanes with i >= P.n exist: they shadow the wave's first env (MFMA is wave-wide) and store nothing
+// ---------------------------------------------------------------------------------------------------
+static_assert(Q3_EVAL_REC_INTS == 12 && Q3_EVAL_REC_FLOATS == 4, "record layout of include/quad3d.h");
+constexpr size_t kQ3EvalLdsBytes = (size_t)qr::PolicyDims<kQ3ObsLen>::kTotalHalf8 * 16;   // the policy image, nothing else
+
+template <typename T, bool kF32, bool kTail>
+__device__ __forceinline__ void q3_eval_body(const Q3Params& P, const qr::half8* __restrict__ img, const qr::half8* __restrict__ img_lo,
+                                             int i, int rid, int K, int4* __restrict__ rec, float4* __restrict__ recf,
+                                             const Q3Buffers<T>& B) {
+    using namespace qr;
+    constexpr int L = kQ3ObsLen;
+    constexpr bool kGates = sizeof(T) == sizeof(float);
+    using D = PolicyDims<L>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half8* W = reinterpret_cast<half8*>(smem);   // policy weights (f16) of THIS workgroup's policy
+    const int lane = threadIdx.x & 63;
+    {
+        const float4* s4 = reinterpret_cast<const float4*>(img);
+        float4* d4 = reinterpret_cast<float4*>(W);
+        for (int j = threadIdx.x; j < D::kTotalHalf8; j += kQ3Block) d4[j] = s4[j];
+    }
+    __syncthreads();
+    bool active = true;
+    int ii = i, rr = rid;
+    if constexpr (kTail) {
+        const int wave_first = i - lane;
+        if (wave_first >= P.n) return;          // whole wave past the end (no workgroup barrier follows)
+        active = i < P.n;
+        if (!active) {                          // ragged-tail lanes shadow the wave's first env and store nothing
+            ii = wave_first;
+            rr = rid - lane;
+        }
+    }
+    Q3Env<T> e;
+    q3_load(B, ii, e);
+    // the lane's record: read here, written behind the loop (a caller continues an evaluation by passing the same buffers again)
+    const int4 r0 = rec[(size_t)ii * 3], r1 = rec[(size_t)ii * 3 + 1], r2 = rec[(size_t)ii * 3 + 2];
+    int n_steps = r0.x, n_success = r0.y, n_timeout = r0.z, n_oob = r0.w, n_ground = r1.x, n_collision = r1.y;
+    int len_success = r1.z, len_all = r1.w, n_pass = r2.x, best = r2.y;
+    float ep_ret = 0.0f, ret_sum = 0.0f, ret_sq = 0.0f;
+    if (recf) {
+        const float4 f = recf[ii];
+        ep_ret = f.x; ret_sum = f.y; ret_sq = f.z;
+    }
+    float o[L];
+#pragma unroll
+    for (int c = 0; c < L; ++c) o[c] = (float)e.s[c];
+    for (int k = 0; k < K; ++k) {
+        float mean[4];
+        if constexpr (kF32) {
+            // The low pieces are read from global memory at the same addresses every step, and this loop has no store that could
+            // alias them: left alone the compiler hoists all of those loads in front of the loop and spills them (1.8-1.9 KB of
+            // scratch per lane, 1.5 x the rollout kernel's time).  An opaque copy of the (workgroup-uniform) base per step keeps
+            // them inside the step, where the rollout kernel has them.
+            const half8* lo = img_lo;
+            asm volatile("" : "+s"(lo));
+            policy_forward_f32class<L>(W, lo, lane, o, mean);
+        } else {
+            policy_forward<L>(W, lane, o, mean);
+        }
+        const float u[4] = {fminf(fmaxf(mean[0], -1.0f), 1.0f), fminf(fmaxf(mean[1], -1.0f), 1.0f),
+                            fminf(fmaxf(mean[2], -1.0f), 1.0f), fminf(fmaxf(mean[3], -1.0f), 1.0f)};
+        const int target_before = e.target;
+        bool pre_ground = false, pre_oob = false;
+        if constexpr (kGates) {                 // the reference tests the PRE-step state for these two
+            pre_ground = e.s[2] > (T)0;
+            pre_oob = fabsf((float)e.s[0]) > 10.0f || fabsf((float)e.s[1]) > 10.0f || fabsf((float)e.s[9]) > 1000.0f ||
+                      fabsf((float)e.s[10]) > 1000.0f || fabsf((float)e.s[11]) > 1000.0f;
+        }
+        int end_len = 0;                        // the step counter at the end: after the increment, before the reset
+        bool end_final = false;                 // the target at the end: after e.target += 1, before the reset
+        bool done, trunc;
+        const T reward = q3_step_env(P, rr, e, u, done, trunc, [&]() {
+            end_len = e.steps;
+            if constexpr (kGates) end_final = e.target >= P.num_gates;
+        });
+        // ---- accounting (tests/q3_eval_spec.py, same order).  A pass on the step that ends the episode is not counted here: a final
+        // pass is the SUCCESS end, and any other end has replaced the target
+        n_steps += 1;
+        if (!done && e.target != target_before) n_pass += 1;
+        ep_ret = add_rn(ep_ret, (float)reward);
+        if (done) {
+            bool success, timeout;
+            if constexpr (kGates) {
+                success = end_final;
+                timeout = !success && trunc;
+                const bool ground = !success && !timeout && pre_ground;
+                const bool oob = !success && !timeout && !ground && pre_oob;
+                const bool collision = !success && !timeout && !ground && !oob;
+                n_ground += ground ? 1 : 0;
+                n_oob += oob ? 1 : 0;
+                n_collision += collision ? 1 : 0;
+            } else {
+                success = !trunc;
+                timeout = !success && end_len >= P.max_steps;
+                n_oob += (!success && !timeout) ? 1 : 0;
+            }
+            n_success += success ? 1 : 0;
+            n_timeout += timeout ? 1 : 0;
+            len_all += end_len;
+            if (success) {
+                len_success += end_len;
+                best = (best == 0 || end_len < best) ? end_len : best;
+            }
+            ret_sum = add_rn(ret_sum, ep_ret);
+            ret_sq = add_rn(ret_sq, mul_rn(ep_ret, ep_ret));
+            ep_ret = 0.0f;
+        }
+#pragma unroll
+        for (int c = 0; c < L; ++c) o[c] = (float)e.s[c];
+    }
+    if (!active) return;
+    int4* row = rec + (size_t)i * 3;
+    row[0] = make_int4(n_steps, n_success, n_timeout, n_oob);
+    row[1] = make_int4(n_ground, n_collision, len_success, len_all);
+    row[2] = make_int4(n_pass, best, 0, 0);
+    if (recf) recf[i] = make_float4(ep_ret, ret_sum, ret_sq, 0.0f);
+    q3_store(B, i, e);
+}
+
+template <typename T, bool kF32>
+__global__ void __launch_bounds__(kQ3Block, 1)
+q3_eval_policy_kernel(Q3Params P, Q3Buffers<T> B, const qr::half8* __restrict__ img, const qr::half8* __restrict__ img_lo, int K,
+                      int4* __restrict__ rec, float4* __restrict__ recf) {
+    const int i = blockIdx.x * kQ3Block + threadIdx.x;
+    q3_eval_body<T, kF32, true>(P, img, img_lo, i, i, K, rec, recf, B);
+}
+
+// A bank of policies in one launch: P policies x E envs per policy, E a multiple of kQ3Block and N = P E exactly (no tail lanes: the
+// host refuses anything else).  Workgroup b stages image b / (E / kQ3Block) of the bank, and the reset stream is group-local: lane i
+// draws with env id (i mod E), so group p flies exactly what an E-env handle with the same seed and env_id_base flies under
+// q3_evaluate_policy.  The policy index, both image bases and the group's first env are derived from blockIdx alone.
+template <typename T, bool kF32>
+__global__ void __launch_bounds__(kQ3Block, 1)
+q3_eval_policy_bank_kernel(Q3Params P, Q3Buffers<T> B, const qr::half8* __restrict__ bank, const qr::half8* __restrict__ bank_lo,
+                           int wgs_per_policy, int K, int4* __restrict__ rec, float4* __restrict__ recf) {
+    using D = qr::PolicyDims<kQ3ObsLen>;
+    const int pol = (int)blockIdx.x / wgs_per_policy;
+    const int local0 = ((int)blockIdx.x - pol * wgs_per_policy) * kQ3Block;
+    const qr::half8* __restrict__ img = bank + (size_t)pol * D::kTotalHalf8;
+    const qr::half8* __restrict__ img_lo = bank_lo + (size_t)pol * D::kTotalHalf8;
+    const int i = blockIdx.x * kQ3Block + threadIdx.x;   // < P.n: the grid is exactly P.n / kQ3Block workgroups
+    q3_eval_body<T, kF32, false>(P, img, img_lo, i, local0 + (int)threadIdx.x, K, rec, recf, B);
+}
+
 int q3fail(int code, const std::string& m) { return qr::set_last_error(code, m); }
 
 #define Q3_HIP(expr)                                                                          \
@@ -721,6 +877,47 @@ hipError_t q3_launch_rollout_policy(q3_env* e, const qr::PolicyArgs& A, int K, f
     return qr::launch_dynamic_lds<q3_rollout_policy_kernel<T, false>>(dim3(e->grid()), dim3(kQ3Block), kQ3PolicyLdsBytes, st, e->P,
                                                                       e->buffers<T>(), A, K, obs, act4, logp, rew, done, trunc, term_obs,
                                                                       last_obs, so);
+}
+
+template <typename T>
+hipError_t q3_launch_eval_policy(q3_env* e, const qr::half8* img, const qr::half8* img_lo, bool f32class, int K, int32_t* rec, float* recf,
+                                 hipStream_t st) {
+    int4* rec4 = reinterpret_cast<int4*>(rec);
+    float4* recf4 = reinterpret_cast<float4*>(recf);
+    if (f32class)
+        return qr::launch_dynamic_lds<q3_eval_policy_kernel<T, true>>(dim3(e->grid()), dim3(kQ3Block), kQ3EvalLdsBytes, st, e->P, e->buffers<T>(),
+                                                                      img, img_lo, K, rec4, recf4);
+    return qr::launch_dynamic_lds<q3_eval_policy_kernel<T, false>>(dim3(e->grid()), dim3(kQ3Block), kQ3EvalLdsBytes, st, e->P, e->buffers<T>(), img,
+                                                                   img_lo, K, rec4, recf4);
+}
+
+// The caller guarantees envs_per_policy % kQ3Block == 0 and num_policies * envs_per_policy == P.n (checked again here: a grid that does
+// not match P.n would read and write out of bounds).
+template <typename T>
+hipError_t q3_launch_eval_policy_bank(q3_env* e, const qr::half8* bank, const qr::half8* bank_lo, bool f32class, int num_policies,
+                                      int envs_per_policy, int K, int32_t* rec, float* recf, hipStream_t st) {
+    if (num_policies < 1 || envs_per_policy < kQ3Block || envs_per_policy % kQ3Block != 0 ||
+        (long long)num_policies * envs_per_policy != (long long)e->P.n)
+        return hipErrorInvalidValue;
+    int4* rec4 = reinterpret_cast<int4*>(rec);
+    float4* recf4 = reinterpret_cast<float4*>(recf);
+    const dim3 grid((unsigned)(e->P.n / kQ3Block));
+    const int wgs = envs_per_policy / kQ3Block;
+    if (f32class)
+        return qr::launch_dynamic_lds<q3_eval_policy_bank_kernel<T, true>>(grid, dim3(kQ3Block), kQ3EvalLdsBytes, st, e->P, e->buffers<T>(), bank,
+                                                                           bank_lo, wgs, K, rec4, recf4);
+    return qr::launch_dynamic_lds<q3_eval_policy_bank_kernel<T, false>>(grid, dim3(kQ3Block), kQ3EvalLdsBytes, st, e->P, e->buffers<T>(), bank,
+                                                                        bank_lo, wgs, K, rec4, recf4);
+}
+
+// what q3_evaluate_policy and q3_evaluate_policy_bank refuse alike (`who` names the entry point in the message)
+int q3_check_eval_args(const q3_env* e, int K, int flags, const int32_t* rec, const float* recf, const std::string& w) {
+    if (!e) return q3fail(QR_E_INVALID, w + "null q3_env handle");
+    if (!rec) return q3fail(QR_E_INVALID, w + "rec_dev is null");
+    if (K < 1) return q3fail(QR_E_INVALID, w + "num_steps must be >= 1");
+    if (flags != 0 && flags != QR_ROLLOUT_F32CLASS) return q3fail(QR_E_INVALID, w + "`flags` takes 0 or QR_ROLLOUT_F32CLASS");
+    if (((uintptr_t)rec | (uintptr_t)recf) & 15u) return q3fail(QR_E_INVALID, w + "rec_dev / recf_dev must be 16-byte aligned");
+    return QR_OK;
 }
 
 }  // namespace
@@ -938,6 +1135,53 @@ int q3_rollout_policy(q3_env* e, qr_policy* policy, int32_t K, const float* log_
         Q3_HIP(q3_launch_rollout_policy<double>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
     else
         Q3_HIP(q3_launch_rollout_policy<float>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
+    return QR_OK;
+}
+
+// Every refusal comes before anything is enqueued: a failed call leaves the env and the records untouched.
+int q3_evaluate_policy(q3_env* e, qr_policy* policy, int32_t K, int32_t flags, int32_t* rec, float* recf, void* stream) {
+    const std::string w = "q3_evaluate_policy: ";
+    if (!policy) return q3fail(QR_E_INVALID, w + "null policy handle");
+    if (int rc = q3_check_eval_args(e, K, flags, rec, recf, w)) return rc;
+    if (qr::policy_obs_len(policy) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "policy obs_len must be 16 (the state row is the observation)");
+    if (qr::policy_device(policy) != e->device) return q3fail(QR_E_INVALID, w + "policy on another GPU");
+    const qr::half8* wt = qr::policy_weights(policy);
+    if (!wt) return q3fail(QR_E_STATE, w + "the policy has no weights");
+    if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, w + "q3_set_track has not been called");
+    const bool f32class = (flags & QR_ROLLOUT_F32CLASS) != 0;
+    Q3_HIP(hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (e->kind == Q3_KIND_HOVER)
+        Q3_HIP(q3_launch_eval_policy<double>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
+    else
+        Q3_HIP(q3_launch_eval_policy<float>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
+    return QR_OK;
+}
+
+int q3_evaluate_policy_bank(q3_env* e, qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy, int32_t K, int32_t flags,
+                            int32_t* rec, float* recf, void* stream) {
+    const std::string w = "q3_evaluate_policy_bank: ";
+    if (!bank) return q3fail(QR_E_INVALID, w + "null bank handle");
+    if (int rc = q3_check_eval_args(e, K, flags, rec, recf, w)) return rc;
+    if (qr::bank_obs_len(bank) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "bank obs_len must be 16 (the state row is the observation)");
+    if (qr::bank_device(bank) != e->device) return q3fail(QR_E_INVALID, w + "bank on another GPU");
+    if (num_policies < 1 || num_policies > qr::bank_capacity(bank)) return q3fail(QR_E_INVALID, w + "num_policies must be in 1..capacity");
+    if (envs_per_policy < kQ3Block || envs_per_policy % kQ3Block != 0)
+        return q3fail(QR_E_INVALID, w + "envs_per_policy must be a positive multiple of 256 (one workgroup serves one policy)");
+    if ((long long)num_policies * envs_per_policy != (long long)e->P.n)
+        return q3fail(QR_E_INVALID, w + "num_policies * envs_per_policy must equal num_envs");
+    const int unset = qr::bank_first_unset(bank, num_policies);
+    if (unset >= 0) return q3fail(QR_E_STATE, w + "slot " + std::to_string(unset) + " of the bank has no weights");
+    if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, w + "q3_set_track has not been called");
+    const bool f32class = (flags & QR_ROLLOUT_F32CLASS) != 0;
+    Q3_HIP(hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (e->kind == Q3_KIND_HOVER)
+        Q3_HIP(q3_launch_eval_policy_bank<double>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
+                                                  rec, recf, st));
+    else
+        Q3_HIP(q3_launch_eval_policy_bank<float>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
+                                                 rec, recf, st));
     return QR_OK;
 }
 

@@ -24,6 +24,14 @@ csrc/quadrace_eval_grid.hip):
     results = evaluate_grid([model], conds, eval_env, envs_per_cell=256, seed=0)      # results[p][c]
     rows = robustness_table(results, [c.name for c in conds])
 
+The predecessor envs of "3D quad.ipynb" (quad3d.Quadcopter3DVec, Quadcopter3DVecGates) have outcomes of their own -- goal reached / track
+finished, out of bounds, ground, gate collision, time limit -- counted by `q3_evaluate_policy` / `q3_evaluate_policy_bank` (csrc/quad3d.hip):
+
+    from optimal_quad_control_rl_amd import evaluate_q3_policy, evaluate_q3_policies
+    s = evaluate_q3_policy(model, eval_env, n_eval_steps=2000, seed=1)
+    s["success_rate"], s["mean_success_seconds"], s["collisions"]
+    curve = evaluate_q3_policies(checkpoints, eval_env, envs_per_policy=256, seed=1)   # one summary per checkpoint, same starts
+
 All times inside the records are integer step counts; seconds appear only here (steps x env.dt).
 """
 import math
@@ -31,6 +39,7 @@ import math
 import numpy as np
 
 REC_INTS, MAX_LAPS, REC_FLOATS = 24, 8, 4   # QR_EVAL_REC_INTS, QR_EVAL_MAX_LAPS, QR_EVAL_REC_FLOATS of include/quadrace.h
+Q3_REC_INTS, Q3_REC_FLOATS = 12, 4          # Q3_EVAL_REC_INTS, Q3_EVAL_REC_FLOATS of include/quad3d.h
 
 
 def _host(a):
@@ -324,3 +333,122 @@ def rank_policies(results, max_crashes_per_window=0.1):
     good.sort(key=lambda i: (fly(results[i]), crashes(results[i]), i))
     rest.sort(key=lambda i: (crashes(results[i]), i))
     return good + rest
+
+
+# ---- the predecessor envs (quad3d.py): how episodes end, and how long the successful ones take ------------------------------------
+def summarize_q3_eval(rec, recf, dt):
+    """Summary of q3 evaluation records (`rec` [N, 12] int32, `recf` [N, 4] float32 or None; tensors or arrays; layout: include/quad3d.h)
+    as a dict: envs, steps (per env), episodes (ended ones), successes / timeouts / out_of_bounds / ground / collisions (totals over the
+    envs; the causes are exclusive and add up to `episodes`), success_rate (None without episodes), mean_success_seconds /
+    best_success_seconds (None without a success), mean_episode_seconds and gates_per_episode = (passes + successes) / episodes (None
+    without episodes; a success is the pass of the final gate), mean_reward / std_reward of the finished episodes (None without
+    episodes or without `recf`)."""
+    rec = _host(rec).astype(np.int64)
+    assert rec.ndim == 2 and rec.shape[1] == Q3_REC_INTS, rec.shape
+    n, dt = rec.shape[0], float(dt)
+    tot = rec.sum(axis=0)
+    successes, timeouts, oob, ground, collisions = (int(tot[c]) for c in (1, 2, 3, 4, 5))
+    episodes = successes + timeouts + oob + ground + collisions
+    best = rec[:, 9][rec[:, 9] > 0]
+    mean_reward = std_reward = None
+    recf = _host(recf)
+    if recf is not None and episodes > 0:
+        assert recf.shape == (n, Q3_REC_FLOATS), recf.shape
+        s1, s2 = float(recf[:, 1].astype(np.float64).sum()), float(recf[:, 2].astype(np.float64).sum())
+        mean_reward = s1 / episodes
+        std_reward = math.sqrt(max(s2 / episodes - mean_reward * mean_reward, 0.0))
+    return dict(envs=n, steps=int(rec[:, 0].max()) if n else 0, episodes=episodes,
+                successes=successes, timeouts=timeouts, out_of_bounds=oob, ground=ground, collisions=collisions,
+                success_rate=successes / episodes if episodes else None,
+                mean_success_seconds=int(tot[6]) * dt / successes if successes else None,
+                best_success_seconds=int(best.min()) * dt if best.size else None,
+                mean_episode_seconds=int(tot[7]) * dt / episodes if episodes else None,
+                gates_per_episode=(int(tot[8]) + successes) / episodes if episodes else None,
+                mean_reward=mean_reward, std_reward=std_reward)
+
+
+def _model_precision(models):
+    f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for m in models)
+    return "f32" if f32 else "f16-operands"
+
+
+def evaluate_q3_policy(model, env, n_eval_steps=2000, precision=None, seed=None):
+    """Deterministic evaluation of `model`'s current policy on `env` (a Quadcopter3DVec / Quadcopter3DVecGates, possibly inside a
+    VecMonitor) as ONE kernel launch of `n_eval_steps` steps (q3_evaluate_policy).  Returns summarize_q3_eval's dict.  `model`: what
+    evaluate_q3_policies accepts as an entry.  `seed`: reseed and reset the env first, so that two evaluations see the same starts; None
+    continues from the env's current state.  `precision`: "f16-operands" | "f32" (None: the model's own collect precision).  `env`
+    keeps flying from where the evaluation left it."""
+    import torch
+
+    from .policy import MfmaPolicy
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    n_eval_steps = int(n_eval_steps)
+    if n_eval_steps < 1:
+        raise ValueError("need n_eval_steps >= 1")
+    actor, owner = _as_actor(model)
+    if precision is None:
+        precision = _model_precision([owner])
+    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(actor)
+    try:
+        if seed is not None:
+            core.seed(seed)
+            core.reset_device()
+        rec = torch.zeros((core.num_envs, Q3_REC_INTS), dtype=torch.int32, device=core.device)
+        recf = torch.zeros((core.num_envs, Q3_REC_FLOATS), dtype=torch.float32, device=core.device)
+        core.evaluate_device(policy, n_eval_steps, rec, recf, precision=precision)
+        return summarize_q3_eval(rec, recf, core.dt)
+    finally:
+        torch.cuda.current_stream(core.device).synchronize()
+        policy.close()
+
+
+def evaluate_q3_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, precision=None, seed=0):
+    """evaluate_q3_policy for a LIST of policies, `env.num_envs // envs_per_policy` of them per launch (q3_evaluate_policy_bank): policy
+    p of a batch flies envs [p E, (p + 1) E) of `env`.  Every batch starts from `seed(seed); reset_device(); share_starts(E)` and the
+    kernel keys restarts by the env's index within its group, so ALL policies -- within a batch and across batches -- see bit-identical
+    starts and restarts for as long as their own flying allows, the ones an E-env handle sees under evaluate_q3_policy(..., seed=seed).
+    Entries: a checkpoint path written by `model.save`, an SB3-shaped PPO, a native trainer, or a torch actor.  envs_per_policy: a
+    multiple of 256; env.num_envs must be a multiple of it.  precision: None = "f32" if any model collects in f32, else "f16-operands".
+    The last batch is padded by repeating its last policy.  Returns one summarize_q3_eval dict per policy, in order."""
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    E, n = int(envs_per_policy), int(core.num_envs)
+    if E < 256 or E % 256 != 0:
+        raise ValueError("envs_per_policy must be a multiple of 256 (one workgroup serves one policy)")
+    if n % E != 0:
+        raise ValueError("env.num_envs must be a multiple of envs_per_policy")
+    n_eval_steps = int(n_eval_steps)
+    if n_eval_steps < 1:
+        raise ValueError("need n_eval_steps >= 1")
+    policies = list(policies)
+    slots = n // E
+    plan = plan_policy_batches(len(policies), slots)
+
+    import torch
+
+    from .policy import MfmaPolicyBank
+
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        precision = _model_precision([m for _, m in actors])
+    results = [None] * len(actors)
+    bank = MfmaPolicyBank(core.state_len, slots, core.device.index)
+    try:
+        for indices, kept in plan:
+            for slot, idx in enumerate(indices):
+                bank.load_torch(slot, actors[idx][0])
+            core.seed(seed)
+            core.reset_device()
+            core.share_starts(E)
+            rec = torch.zeros((n, Q3_REC_INTS), dtype=torch.int32, device=core.device)
+            recf = torch.zeros((n, Q3_REC_FLOATS), dtype=torch.float32, device=core.device)
+            core.evaluate_bank_device(bank, slots, E, n_eval_steps, rec, recf, precision=precision)
+            for slot in range(kept):
+                results[indices[slot]] = summarize_q3_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt)
+    finally:
+        torch.cuda.current_stream(core.device).synchronize()
+        bank.close()
+    return results

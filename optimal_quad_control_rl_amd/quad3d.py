@@ -8,6 +8,8 @@ thresholds, `render()`), on top of include/quad3d.h in libquadrace.so: one HIP k
 device-tensor path (`reset_device`, `step_device`, `rollout_device`) without host round trips.  No NumPy fallback.
 `rollout_policy_device` is the closed loop a trainer collects with (policy forward, sampling and env step K times in one
 kernel): `ppo.PPO(env, fused_collect=True)` and `sb3.PPO("MlpPolicy", env)` train both envs through it.
+`evaluate_device` / `evaluate_bank_device` fly the deterministic policy in one kernel and count how its episodes end (goal or finished
+track, out of bounds, ground, gate collision, time limit): `evaluation.evaluate_q3_policy`, `evaluate_q3_policies`.
 
 Differences that are this build's own (documented, not the reference's): resets draw from a counter-based Philox
 stream (`seed`, `env_id_base`) instead of NumPy's global generator; the per-step `print()` calls of the reference
@@ -226,6 +228,77 @@ class _Quad3DBase(_Base):
                                              _ptr(done), _ptr(trunc), _ptr(term), _ptr(self._obs32_d), _ptr(self._states_d),
                                              self._stream()))
         return obs, act, logp, rew, done, trunc, self._obs32_d
+
+    # ---- on-device evaluation (q3_evaluate_policy, q3_evaluate_policy_bank; summary: evaluation.summarize_q3_eval) ---------------
+    def _check_eval_records(self, rec, recf):
+        n = self.num_envs
+        if not (torch.is_tensor(rec) and rec.is_cuda and rec.device == self.device and rec.dtype == torch.int32 and rec.is_contiguous()
+                and tuple(rec.shape) == (n, 12)):
+            raise ValueError("rec must be a contiguous int32 tensor [num_envs, 12] on the env's device")
+        if recf is not None and not (torch.is_tensor(recf) and recf.is_cuda and recf.device == self.device and recf.dtype == torch.float32
+                                     and recf.is_contiguous() and tuple(recf.shape) == (n, 4)):
+            raise ValueError("recf must be a contiguous float32 tensor [num_envs, 4] on the env's device")
+
+    def _refresh_states(self):
+        """env.states -> the env's own device buffer (the evaluators store no per-step row and take no states_out)."""
+        _lib.check(self._L.q3_get_state(self._h, _ptr(self._states_d), None, None, self._stream()))
+
+    def evaluate_device(self, policy, num_steps, rec, recf=None, precision="f16-operands"):
+        """Closed-loop deterministic evaluation in ONE kernel (q3_evaluate_policy): K x [obs = float32(states) -> MFMA policy ->
+        step(clip(mean))] with the outcome accounting on the device and nothing stored per step.  `rec` int32 CUDA tensor [N, 12] and
+        `recf` float32 [N, 4] (optional) are read at the start and written at the end: zero them for a fresh evaluation, pass them
+        again to continue one (record layout: include/quad3d.h).  The env ends where rollout_policy_device(deterministic=True) would
+        leave it.  Returns (rec, recf)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "q3_evaluate_policy")
+        self._check_eval_records(rec, recf)
+        _lib.check(fn(self._h, policy._h, int(num_steps), flags, _ptr(rec), _ptr(recf), self._stream()))
+        self._refresh_states()
+        return rec, recf
+
+    def evaluate_bank_device(self, bank, num_policies, envs_per_policy, num_steps, rec, recf=None, precision="f16-operands"):
+        """A bank of policies in ONE kernel (q3_evaluate_policy_bank): slot p of `bank` (policy.MfmaPolicyBank with obs_len 16),
+        p < num_policies, flies envs [p E, (p + 1) E), E = envs_per_policy (a multiple of 256; num_policies * E == num_envs).  Rows
+        [p E, (p + 1) E) of `rec` / `recf` belong to policy p.  Inside this call an env that ends its episode restarts from the reset
+        stream of its index WITHIN its group, so groups that start equal (share_starts) see the same starts and restarts; every other
+        call on this env resets with the ordinary ids.  Returns (rec, recf)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "q3_evaluate_policy_bank")
+        self._check_eval_records(rec, recf)
+        _lib.check(fn(self._h, bank._h, int(num_policies), int(envs_per_policy), int(num_steps), flags, _ptr(rec), _ptr(recf),
+                      self._stream()))
+        self._refresh_states()
+        return rec, recf
+
+    def get_episode_counts(self):
+        """Episode counters [N] int32 on the device: each env's position in its reset stream."""
+        ep = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self._L.q3_episode_counts(self._h, _ptr(ep), None, self._stream()))
+        return ep
+
+    def set_episode_counts(self, episode):
+        ep = torch.as_tensor(episode).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(ep.shape) != (self.num_envs,):
+            raise ValueError(f"expected shape {(self.num_envs,)}, got {tuple(ep.shape)}")
+        _lib.check(self._L.q3_episode_counts(self._h, None, _ptr(ep), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def share_starts(self, envs_per_policy):
+        """Copy states, targets, step counts and episode counters of envs [0, E) onto every following group of E envs (E =
+        envs_per_policy divides num_envs).  After `seed(s); reset_device(); share_starts(E)` every group is bit-equal to an E-env
+        handle after `seed(s); reset_device()`: the common starts evaluate_bank_device's group-local reset stream continues from."""
+        e, n = int(envs_per_policy), self.num_envs
+        if e < 1 or n % e != 0:
+            raise ValueError("envs_per_policy must divide num_envs")
+        reps = n // e
+        if reps > 1:
+            st, tg, sc = self._get()
+            ep = self.get_episode_counts()
+            tile = lambda t: t[:e].repeat((reps,) + (1,) * (t.dim() - 1)).contiguous()
+            self._set(tile(st), tile(tg), tile(sc))
+            self.set_episode_counts(tile(ep))
+        self._refresh_states()
+        return self
 
     # ---- what a trainer's checkpoint holds of the env (ppo.PPO.state_dict): with the same constructor arguments, loading it continues
     # the run bit for bit (the episode counters are the env's positions in its reset streams)
