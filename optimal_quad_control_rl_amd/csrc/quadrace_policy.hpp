@@ -62,15 +62,20 @@ __device__ __forceinline__ half8 relu_pack(const f32x16p& acc, int s) {
     return __builtin_elementwise_min(__builtin_elementwise_max(b, zero), top);
 }
 
-// f32 -> f16 with saturation to the finite range; NaN becomes 0 (maxnum/minnum drop the NaN operand)
+// f32 -> f16 with saturation to the finite range; NaN becomes 0.  maxnum / minnum drop the NaN operand, so the positive and the negative
+// part are each clamped against 0 first: max(NaN, 0) = 0 on both sides and the difference is 0.  (min(max(x, -65504), 65504) alone turned
+// a NaN into -65504: a policy fed a NaN observation then saw the largest negative input instead of none.)  Exact for every other input:
+// one of the two parts is 0.
 __device__ __forceinline__ half8 sat_pack(const float* v) {
     half8 b;
 #pragma unroll
     for (int j = 0; j < 8; ++j) b[j] = (_Float16)v[j];
     const _Float16 m = (_Float16)65504.0f;
     const half8 top = {m, m, m, m, m, m, m, m};
-    const half8 bot = {-m, -m, -m, -m, -m, -m, -m, -m};
-    return __builtin_elementwise_min(__builtin_elementwise_max(b, bot), top);
+    const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    const half8 pos = __builtin_elementwise_min(__builtin_elementwise_max(b, zero), top);
+    const half8 neg = __builtin_elementwise_min(__builtin_elementwise_max(-b, zero), top);
+    return pos - neg;
 }
 
 // relu + saturation + f16 pack of two accumulator values (v_cvt_pk_f16_f32, v_pk_max_f16 against 0, v_pk_min_f16 against

@@ -300,6 +300,10 @@ class PPO:
         if self._q3 and not fused_collect:
             raise ValueError("Quadcopter3DVec / Quadcopter3DVecGates train with fused_collect=True only: there is no per-step "
                              "(fused_collect=False) collect path for them (float64 hover observations, no per-step terminal buffer)")
+        # the per-episode count of rewards above 5 (ep_gates): a gate pass on the race envs (10 - 10 d).  On the predecessor envs only the hover
+        # goal (+100) and the final gate (+10) pay that much -- an intermediate gate earns the ordinary progress reward -- so there the same
+        # count is successes per episode, and the statistic is named for what it is
+        self._gates_key = "successes_per_episode" if self._q3 else "gates_per_episode"
         torch.manual_seed(seed)
         # minibatch permutations come from the trainer's OWN generator (checkpointed; independent of whatever else draws from
         # torch's global generators in the process)
@@ -455,7 +459,7 @@ class PPO:
             self.ep_gates *= keep
         f = fin.tolist()
         if f[3] > 0:
-            self.stats.update(ep_rew_mean=f[0] / f[3], ep_len_mean=f[1] / f[3], gates_per_episode=f[2] / f[3], episodes=f[3])
+            self.stats.update({"ep_rew_mean": f[0] / f[3], "ep_len_mean": f[1] / f[3], self._gates_key: f[2] / f[3], "episodes": f[3]})
         self.stats["reward_per_step"] = float(rew.mean())
 
     @torch.no_grad()
@@ -578,9 +582,12 @@ class PPO:
             self.buf_lp[bad] = 0.0
             self.buf_rew[bad] = 0.0
             self.buf_val[bad] = 0.0
-            self.last_val = torch.nan_to_num(self.last_val)
-            if self.buf_term_val is not None:
-                self.buf_term_val.nan_to_num_()
+        # V(last observation) and V(terminal rows) belong to observations that are NOT buffered rows: they can be non-finite behind rows
+        # that are all finite (a float64 hover state whose float32 cast overflows in the step that ends the rollout or the episode), so
+        # they are cleaned whatever `bad` says.  A non-finite value is no estimate: no bootstrap from it.
+        self.last_val = torch.nan_to_num(self.last_val, nan=0.0, posinf=0.0, neginf=0.0)
+        if self.buf_term_val is not None:
+            self.buf_term_val.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
 
     def _gae_native(self):
         fin = torch.zeros(4, dtype=torch.float32, device=self.dev)
@@ -594,7 +601,7 @@ class PPO:
             self._stats_pending = False
             f = fin.tolist() + [float(self.buf_rew.mean())]
             if f[3] > 0:
-                self.stats.update(ep_rew_mean=f[0] / f[3], ep_len_mean=f[1] / f[3], gates_per_episode=f[2] / f[3], episodes=f[3])
+                self.stats.update({"ep_rew_mean": f[0] / f[3], "ep_len_mean": f[1] / f[3], self._gates_key: f[2] / f[3], "episodes": f[3]})
             self.stats["reward_per_step"] = f[4]
         return adv, ret
 
@@ -726,7 +733,7 @@ class PPO:
                 s = self.stats
                 print(f"it {it:4d}  steps {self.num_timesteps/1e6:8.1f}M  {self.num_timesteps/el/1e6:6.2f} Msteps/s  "
                       f"ep_rew {s.get('ep_rew_mean', float('nan')):8.2f}  ep_len {s.get('ep_len_mean', float('nan')):7.1f}  "
-                      f"gates/ep {s.get('gates_per_episode', float('nan')):6.2f}  std {s.get('std', 0):.3f}", flush=True)
+                      f"{'successes/ep' if self._q3 else 'gates/ep'} {s.get(self._gates_key, float('nan')):6.2f}  std {s.get('std', 0):.3f}", flush=True)
             if callback is not None and callback(self) is False:
                 break
         return self
@@ -797,6 +804,8 @@ class PPO:
         self.num_timesteps = int(sd["num_timesteps"])
         self.ep_ret.copy_(sd["ep_ret"]); self.ep_len.copy_(sd["ep_len"]); self.ep_gates.copy_(sd["ep_gates"])
         self.stats = dict(sd["stats"])
+        if self._q3 and "gates_per_episode" in self.stats:   # a checkpoint from before the statistic was named for what it counts
+            self.stats["successes_per_episode"] = self.stats.pop("gates_per_episode")
         self.noise_seed = int(sd["noise_seed"])
         self.noise_step = int(sd.get("noise_step", self.num_timesteps // self.n_envs))   # older checkpoints: derived from the step count
         self.lr0, self.lr_final_frac, self.total_hint = float(sd["lr0"]), float(sd["lr_final_frac"]), sd["total_hint"]

@@ -124,3 +124,27 @@ def test_minibatch_step_matches_restated_gradient_through_adam_at_16():
     assert st[1] == want[-3] and st[3] == want[-1]
     assert abs(st[0] - want[-4]) <= bound[-4] and abs(st[2] - want[-2]) <= bound[-2]
     up.close()
+
+
+def test_ppo_forward_and_scatter_repack_are_bit_exact_at_16():
+    """tests/test_gpu_exact_forward.py::test_ppo_forward_and_scatter_repack_are_bit_exact, at L = 16: qr_ppo_forward for both heads (the
+    value head fills buf_val, last_val and buf_term_val of the predecessor envs' trainer in the f16-operand mode) and the scatter re-pack
+    after qr_ppo_apply / qr_ppo_minibatch."""
+    from test_gpu_exact_forward import test_ppo_forward_and_scatter_repack_are_bit_exact
+
+    test_ppo_forward_and_scatter_repack_are_bit_exact(L)
+
+
+def test_apply_matches_float64_adam_and_clip_at_16():
+    """tests/test_gpu_adam_apply.py::test_apply_matches_float64_adam_and_clip, at L = 16 (the parameter count, and with it the tail of
+    ppo_apply_kernel, depends on L)."""
+    from test_gpu_adam_apply import test_apply_matches_float64_adam_and_clip
+
+    test_apply_matches_float64_adam_and_clip(L)
+
+
+def test_minibatch_step_matches_float64_adam_on_its_own_gradient_at_16():
+    """tests/test_gpu_adam_apply.py::test_minibatch_step_matches_float64_adam_on_its_own_gradient, at L = 16."""
+    from test_gpu_adam_apply import test_minibatch_step_matches_float64_adam_on_its_own_gradient
+
+    test_minibatch_step_matches_float64_adam_on_its_own_gradient(L)
