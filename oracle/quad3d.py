@@ -89,6 +89,10 @@ class Quad3DOracle:
     def set_limits(self, max_steps, dt=0.01):
         self.L.q3o_set_limits(self.h, max_steps, dt)
 
+    def set_thresholds(self, pos, vel, ang, rat):
+        """Hover goal thresholds (Q3 cell 6 __init__: pos_threshold, vel_threshold, ang_threshold, rat_threshold)."""
+        self.L.q3o_set_thresholds(self.h, pos, vel, ang, rat)
+
     def set_threads(self, t):
         self.L.q3o_set_threads(self.h, t)
 
