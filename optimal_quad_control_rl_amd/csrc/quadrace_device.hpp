@@ -448,8 +448,98 @@ __device__ __forceinline__ void qr_sincos(float x, float& sn, float& cs) {
     cs = ((q + 1) & 2) ? -b : b;
 }
 
+// ---- hand-packed forms (kPk) ---------------------------------------------------------------------
+// The one-wave fused E2E + residual-MLP rollout is bound by the number of instructions its lone wave issues, and a
+// v_pk_{fma,mul,add}_f32 costs that wave what a plain one does.  Under the compile-time flag kPk (off everywhere else: at two waves
+// per SIMD a packed instruction costs 1.3 x a plain one) independent PAIRS of the step are evaluated as one packed instruction:
+// the same operation with the same operands in the same order per element, so every result bit stays (the packed forms round
+// like the plain ones; tests/test_gpu_fused_mlp_issue.py compares with the per-step kernel, which never packs).  Pairs are chosen
+// where both operands already sit in, or are produced into, adjacent registers -- a pair that costs a v_mov to form gains nothing.
+typedef float f32x2p __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2p pk2(float a, float b) { const f32x2p v = {a, b}; return v; }
+__device__ __forceinline__ f32x2p pk1(float a) { const f32x2p v = {a, a}; return v; }
+__device__ __forceinline__ f32x2p pk_fma(f32x2p a, f32x2p b, f32x2p c) { return __builtin_elementwise_fma(a, b, c); }
+// a pair the optimiser must take as it is: without it, a packed operation on two pairs built from scalars whose halves are then read
+// one by one is split back into its two plain halves before instruction selection
+__device__ __forceinline__ f32x2p pk_keep(f32x2p v) { asm("" : "+v"(v)); return v; }
+
+// qr_sincos() of THREE angles: (x.x, x.y) packed -- the reduction and both polynomials of the pair cost 14 instructions instead of 28 --
+// and y plain, same arithmetic per angle as qr_sincos().  A packed instruction's result cannot be read by the very next instruction
+// without a wait state (the compiler pads with s_nop, which costs the lone wave an issue slot like any instruction), so the
+// dependent head of the pair's evaluation is INTERLEAVED with y's, in source order pinned by scheduling barriers; from z on the
+// pair's sine and cosine polynomials fill each other's gaps.
+__device__ __forceinline__ void qr_sincos3(f32x2p x, float y, f32x2p& sn, f32x2p& cs, float& sny, float& csy) {
+#define QR_SB() __builtin_amdgcn_sched_barrier(0)
+    const f32x2p t = x * pk1(0.6366197723675814f);                           QR_SB();
+    const float ty = y * 0.6366197723675814f;                                QR_SB();
+    const f32x2p k = {rintf(t.x), rintf(t.y)};                               QR_SB();
+    const float ky = rintf(ty);                                              QR_SB();
+    const f32x2p nk = -k;
+    f32x2p r = pk_fma(nk, pk1(1.5707963705062866f), x);                      QR_SB();
+    float ry = fmaf(-ky, 1.5707963705062866f, y);                            QR_SB();
+    r = pk_fma(nk, pk1(-4.371139000186241e-8f), r);                          QR_SB();
+    ry = fmaf(-ky, -4.371139000186241e-8f, ry);                              QR_SB();
+    r = pk_fma(nk, pk1(-1.7151245100059e-15f), r);                           QR_SB();
+    ry = fmaf(-ky, -1.7151245100059e-15f, ry);                               QR_SB();
+    const f32x2p z = r * r;                                                  QR_SB();
+    const float zy = ry * ry;                                                QR_SB();
+    f32x2p sp = pk_fma(z, pk1(2.7183114939898219e-6f), pk1(-0.00019839334836563469f));   QR_SB();
+    f32x2p cp = pk_fma(z, pk1(2.4390448796277409e-5f), pk1(-0.0013886763774609929f));    QR_SB();
+    const f32x2p rz = r * z;                                                 QR_SB();
+    sp = pk_fma(z, sp, pk1(0.0083333375930786133f));                         QR_SB();
+    cp = pk_fma(z, cp, pk1(0.041666623323739063f));                          QR_SB();
+    float spy = fmaf(zy, 2.7183114939898219e-6f, -0.00019839334836563469f);  QR_SB();
+    sp = pk_fma(z, sp, pk1(-0.16666667163372040f));                          QR_SB();
+    cp = pk_fma(z, cp, pk1(-0.49999999725103100f));                          QR_SB();
+    spy = fmaf(zy, spy, 0.0083333375930786133f);                             QR_SB();
+    const f32x2p s = pk_fma(rz, sp, r);                                      QR_SB();
+    const f32x2p c = pk_fma(z, cp, pk1(1.0f));                               QR_SB();
+#undef QR_SB
+    spy = fmaf(zy, spy, -0.16666667163372040f);
+    const float sy = fmaf(ry * zy, spy, ry);
+    float cpy = fmaf(zy, 2.4390448796277409e-5f, -0.0013886763774609929f);
+    cpy = fmaf(zy, cpy, 0.041666623323739063f);
+    cpy = fmaf(zy, cpy, -0.49999999725103100f);
+    const float cy = fmaf(zy, cpy, 1.0f);
+    const int q0 = (int)k.x, q1 = (int)k.y, qy = (int)ky;
+    const float a0 = (q0 & 1) ? c.x : s.x, b0 = (q0 & 1) ? s.x : c.x;
+    const float a1 = (q1 & 1) ? c.y : s.y, b1 = (q1 & 1) ? s.y : c.y;
+    const float ay = (qy & 1) ? cy : sy, by = (qy & 1) ? sy : cy;
+    sn.x = (q0 & 2) ? -a0 : a0;
+    cs.x = ((q0 + 1) & 2) ? -b0 : b0;
+    sn.y = (q1 & 2) ? -a1 : a1;
+    cs.y = ((q1 + 1) & 2) ? -b1 : b1;
+    sny = (qy & 2) ? -ay : ay;
+    csy = ((qy + 1) & 2) ? -by : by;
+}
+
+template <bool kPk = false>
 __device__ __forceinline__ Rot make_rot(float phi, float theta, float psi) {
     Rot R;
+    if constexpr (kPk) {
+        // (phi, theta) are neighbours in the state.  Of the matrix, the products that are plain pairs are packed: (ss, cs) and
+        // (r21, r22) = (sin phi, cos phi) x one factor, (r00, r10) = (cos psi, sin psi) cos theta.  The four mixed elements stay plain
+        // (their pairs would need a half-negated addend, which costs what the packing saves); they are produced next to each other
+        // as the column pairs (r0j, r1j), which the world-frame acceleration of eom_e2e() consumes as pairs.
+        f32x2p sn, cs;
+        qr_sincos3(pk2(phi, theta), psi, sn, cs, R.sps, R.cps);
+        R.sph = sn.x; R.sth = sn.y; R.cph = cs.x; R.cth = cs.y;
+        const f32x2p sc_ph = {R.sph, R.cph};
+        const f32x2p sscs = sc_ph * pk1(R.sth);                    // (ss, cs)
+        const f32x2p c0 = pk2(R.cps, R.sps) * pk1(R.cth);          // (r00, r10)
+        const f32x2p r2 = sc_ph * pk1(R.cth);                      // (r21, r22)
+        const float ss = sscs.x, cs2 = sscs.y;
+        R.r00 = c0.x;
+        R.r10 = c0.y;
+        R.r20 = -R.sth;
+        R.r01 = fmaf(ss, R.cps, -(R.sps * R.cph));
+        R.r11 = fmaf(ss, R.sps, R.cph * R.cps);
+        R.r21 = r2.x;
+        R.r02 = fmaf(cs2, R.cps, R.sph * R.sps);
+        R.r12 = fmaf(cs2, R.sps, -(R.sph * R.cps));
+        R.r22 = r2.y;
+        return R;
+    }
     qr_sincos(phi, R.sph, R.cph);
     qr_sincos(theta, R.sth, R.cth);
     qr_sincos(psi, R.sps, R.cps);
@@ -606,7 +696,7 @@ __device__ __forceinline__ void dot_chunk(const float* w, const f32x16& acc, int
 
 // kMode: 0 = layer-1 weight operands in registers (MlpRegs::a);  1 = operands re-read from LDS (MlpRegs::a_lds) every call -- the fused
 //        form for two workgroups per CU, where 256 registers per wave are the budget.
-template <int kMode = 0>
+template <int kMode = 0, bool kPk = false>
 __device__ __forceinline__ void residual_mlp(const MlpRegs& m, int lane, const float x[10], float& thrust,
                                              float moment[3]) {
     constexpr bool kALds = (kMode == 1);
@@ -618,8 +708,16 @@ __device__ __forceinline__ void residual_mlp(const MlpRegs& m, int lane, const f
     unpack_f16(p0_01, h[0], h[1]); unpack_f16(p0_23, h[2], h[3]); unpack_f16(p0_45, h[4], h[5]);
     unpack_f16(p0_6o, h[6], h[10]); unpack_f16(p0_78, h[7], h[8]); unpack_f16(p0_9z, h[9], h[11]);
     float r[10];
+    if constexpr (kPk) {   // the pairs whose inputs are neighbours: (w1, w2), (w3, w4), (vbx, vby), (q, r)
+        const f32x2p r01 = pk2(x[0], x[1]) - pk2(h[0], h[1]), r23 = pk2(x[2], x[3]) - pk2(h[2], h[3]);
+        const f32x2p r45 = pk2(x[4], x[5]) - pk2(h[4], h[5]), r89 = pk2(x[8], x[9]) - pk2(h[8], h[9]);
+        r[0] = r01.x; r[1] = r01.y; r[2] = r23.x; r[3] = r23.y; r[4] = r45.x; r[5] = r45.y; r[8] = r89.x; r[9] = r89.y;
+        r[6] = x[6] - h[6];
+        r[7] = x[7] - h[7];
+    } else {
 #pragma unroll
-    for (int k = 0; k < 10; ++k) r[k] = x[k] - h[k];
+        for (int k = 0; k < 10; ++k) r[k] = x[k] - h[k];
+    }
     const uint32_t p1_01 = pack_f16(r[0], r[1]), p1_23 = pack_f16(r[2], r[3]), p1_45 = pack_f16(r[4], r[5]);
     const uint32_t p1_6z = pack_f16(r[6], 0.0f), p1_78 = pack_f16(r[7], r[8]), p1_9z = pack_f16(r[9], 0.0f);
     // ---- B operands of both env tiles: O1 = (X0 of inputs 0..6 + bias | X1 of inputs 0..6), O2 = (p, q, r terms, both halves) ----
@@ -684,6 +782,21 @@ __device__ __forceinline__ void residual_mlp(const MlpRegs& m, int lane, const f
         part[0][1 + g] = dM0[g].sum();
         part[1][1 + g] = dM1[g].sum();
     }
+    if constexpr (kPk) {
+        // thrust / moment[] come in holding the external (Fz, Mx, My, Mz) and go out with the residual added: the two half sums, the
+        // bias and the external value of (moment x, moment y) and of (moment z, thrust) are added as pairs -- (Mx, My) and (Mz, Fz)
+        // are neighbours in the disturbance registers
+        float lo[4], hi[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) pair_to_tiles(part[0][o], part[1][o], lo[o], hi[o]);
+        const f32x2p mxy = pk2(moment[0], moment[1]) + ((pk2(lo[1], lo[2]) + pk2(hi[1], hi[2])) + pk2(m.b2[1], m.b2[2]));
+        const f32x2p mzt = pk2(moment[2], thrust) + ((pk2(lo[3], lo[0]) + pk2(hi[3], hi[0])) + pk2(m.b2[3], m.b2[0]));
+        moment[0] = mxy.x;
+        moment[1] = mxy.y;
+        moment[2] = mzt.x;
+        thrust = mzt.y;
+        return;
+    }
     float out[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) {  // lanes 0..31: tile-0 halves; lanes 32..63: tile-1 halves -> env = lane
@@ -715,14 +828,24 @@ __device__ __forceinline__ float fast_sqrt(float x) {
 // Equations of motion: ds = f(s, u, d)
 // -------------------------------------------------------------------------------------------------
 // E2E Bebop model (R:57-152; constants pre-folded as in SURVEY Appendix A)
+template <bool kPk = false>
 __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const float vb[3], const float u[4],
                                         const float M[3], const float F[3], float* ds) {
     const float p = s[9], q = s[10], r = s[11];
     const float w1 = s[12], w2 = s[13], w3 = s[14], w4 = s[15];
-    const float W1 = fmaf(4000.0f, w1, 7000.0f), W2 = fmaf(4000.0f, w2, 7000.0f);   // R:106-109
-    const float W3 = fmaf(4000.0f, w3, 7000.0f), W4 = fmaf(4000.0f, w4, 7000.0f);
-    const float S = (W1 + W2) + (W3 + W4);
-    const float W1s = W1 * W1, W2s = W2 * W2, W3s = W3 * W3, W4s = W4 * W4;
+    float W1, W2, W3, W4, S, W1s, W2s, W3s, W4s;
+    if constexpr (kPk) {   // the four motors as two pairs
+        const f32x2p W12 = pk_fma(pk1(4000.0f), pk2(w1, w2), pk1(7000.0f)), W34 = pk_fma(pk1(4000.0f), pk2(w3, w4), pk1(7000.0f));
+        const f32x2p Q12 = W12 * W12, Q34 = W34 * W34;
+        W1 = W12.x; W2 = W12.y; W3 = W34.x; W4 = W34.y;
+        S = (W1 + W2) + (W3 + W4);
+        W1s = Q12.x; W2s = Q12.y; W3s = Q34.x; W4s = Q34.y;
+    } else {
+        W1 = fmaf(4000.0f, w1, 7000.0f); W2 = fmaf(4000.0f, w2, 7000.0f);   // R:106-109
+        W3 = fmaf(4000.0f, w3, 7000.0f); W4 = fmaf(4000.0f, w4, 7000.0f);
+        S = (W1 + W2) + (W3 + W4);
+        W1s = W1 * W1; W2s = W2 * W2; W3s = W3 * W3; W4s = W4 * W4;
+    }
     const float Fx = fmaf(-1.07933887e-5f * vb[0], S, F[0]);                          // R:125
     const float Fy = fmaf(-9.65250793e-6f * vb[1], S, F[1]);                          // R:126
     float T = fmaf(-4.36301076e-8f, (W1s + W2s) + (W3s + W4s), F[2]);                 // R:124
@@ -731,8 +854,14 @@ __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const floa
     ds[0] = s[3];
     ds[1] = s[4];
     ds[2] = s[5];
-    ds[3] = fmaf(R.r00, Fx, fmaf(R.r01, Fy, R.r02 * T));                              // R:138
-    ds[4] = fmaf(R.r10, Fx, fmaf(R.r11, Fy, R.r12 * T));
+    if constexpr (kPk) {   // rows 0 and 1 of R (the column pairs of make_rot<true>)
+        const f32x2p a = pk_fma(pk2(R.r00, R.r10), pk1(Fx), pk_fma(pk2(R.r01, R.r11), pk1(Fy), pk2(R.r02, R.r12) * pk1(T)));
+        ds[3] = a.x;
+        ds[4] = a.y;
+    } else {
+        ds[3] = fmaf(R.r00, Fx, fmaf(R.r01, Fy, R.r02 * T));                          // R:138
+        ds[4] = fmaf(R.r10, Fx, fmaf(R.r11, Fy, R.r12 * T));
+    }
     ds[5] = fmaf(R.r20, Fx, fmaf(R.r21, Fy, fmaf(R.r22, T, 9.81f)));
     const float inv_cth = fast_rcp(R.cth);
     const float tth = R.sth * inv_cth;
@@ -751,10 +880,16 @@ __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const floa
                        fmaf(-0.395780237098345f, r,
                             fmaf(-13.3373373580007f, (u[0] - u[1]) + (u[2] - u[3]),
                                  8.33177659850698f * ((w1 - w2) + (w3 - w4))))));                            // R:146,131
-    ds[12] = 16.6666666666667f * (u[0] - w1);                                         // R:112-115
-    ds[13] = 16.6666666666667f * (u[1] - w2);
-    ds[14] = 16.6666666666667f * (u[2] - w3);
-    ds[15] = 16.6666666666667f * (u[3] - w4);
+    if constexpr (kPk) {
+        const f32x2p d12 = pk1(16.6666666666667f) * pk_keep(pk2(u[0], u[1]) - pk2(w1, w2));
+        const f32x2p d34 = pk1(16.6666666666667f) * pk_keep(pk2(u[2], u[3]) - pk2(w3, w4));
+        ds[12] = d12.x; ds[13] = d12.y; ds[14] = d34.x; ds[15] = d34.y;
+    } else {
+        ds[12] = 16.6666666666667f * (u[0] - w1);                                     // R:112-115
+        ds[13] = 16.6666666666667f * (u[1] - w2);
+        ds[14] = 16.6666666666667f * (u[2] - w3);
+        ds[15] = 16.6666666666667f * (u[3] - w4);
+    }
 }
 
 // INDI inner-loop model (I:43-110)
@@ -811,14 +946,34 @@ __device__ __forceinline__ void read_gates_ahead(const Params& P, const float* _
     }
 }
 
-template <int V, int GA, bool kCachedOd = false>
+// the same rows from the loop-invariant offsets wrap[a] = (a + 1) mod num_gates (the caller forms them once): target < num_gates, so
+// target + wrap[a] < 2 num_gates and one conditional subtraction gives (target + a + 1) mod num_gates -- the index read_gates_ahead()
+// reaches with its wave-uniform branch and loop, which cost the one-wave rollout five instructions per gate and step
+template <int GA>
+__device__ __forceinline__ void read_gates_ahead_wrapped(const Params& P, const float* __restrict__ gates, int target, const int* wrap,
+                                                         float4* rel) {
+#pragma unroll
+    for (int a = 0; a < GA; ++a) {
+        int idx = target + wrap[a];
+        if (idx >= P.num_gates) idx -= P.num_gates;
+        rel[a] = *reinterpret_cast<const float4*>(gates + __mul24(kGateStride, idx) + 8);
+    }
+}
+
+template <int V, int GA, bool kCachedOd = false, bool kPk = false>
 __device__ __forceinline__ void observe_with(const Params& P, const GateRow& g, const float4* rel, const Env<V>& e, float* o) {
     constexpr int S = Env<V>::S;
     const float4 g0 = g.g0;
     const float2 cs = g.cs;
-    const float dx = e.s[0] - g0.x, dy = e.s[1] - g0.y;
-    o[0] = fmaf(dx, cs.x, dy * cs.y);            // R:380-382
-    o[1] = fmaf(dy, cs.x, -(dx * cs.y));
+    if constexpr (kPk) {   // (x, y) and the gate's (x, y) are neighbours (the rotation itself has a half-negated addend: plain)
+        const f32x2p d = pk_keep(pk2(e.s[0], e.s[1]) - pk2(g0.x, g0.y));
+        o[0] = fmaf(d.x, cs.x, d.y * cs.y);
+        o[1] = fmaf(d.y, cs.x, -(d.x * cs.y));
+    } else {
+        const float dx = e.s[0] - g0.x, dy = e.s[1] - g0.y;
+        o[0] = fmaf(dx, cs.x, dy * cs.y);            // R:380-382
+        o[1] = fmaf(dy, cs.x, -(dx * cs.y));
+    }
     o[2] = e.s[2] - g0.z;                        // R:383
     o[3] = fmaf(e.s[3], cs.x, e.s[4] * cs.y);    // R:386-389
     o[4] = fmaf(e.s[4], cs.x, -(e.s[3] * cs.y));
@@ -871,12 +1026,12 @@ __device__ __forceinline__ void observe(const Params& P, const float* __restrict
 // for the terminal observation SB3 bootstraps time-limit truncations from (R:589-594).
 // `do_reset(need)` performs the auto-reset of the lanes with `need` (all lanes call it); the default is reset_done_lanes().
 // the arithmetic of one step from the pre-step state: new state `nw`, reward, flags, the target after the step
-template <int V, int kMode = 0>
+template <int V, int kMode = 0, bool kPk = false>
 __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& gate, const MlpRegs& mlp, bool use_mlp, int lane,
                                                const Env<V>& e, const float u[4], float* nw, int& new_target, bool& done,
                                                bool& trunc) {
     constexpr int S = Env<V>::S;
-    const Rot R = make_rot(e.s[6], e.s[7], e.s[8]);
+    const Rot R = make_rot<kPk>(e.s[6], e.s[7], e.s[8]);
     QR_TICK(P, 3);
     float vb[3];  // R:103 body velocity = R^T v
     vb[0] = fmaf(e.s[3], R.r00, fmaf(e.s[4], R.r10, e.s[5] * R.r20));
@@ -888,24 +1043,49 @@ __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& g
         float F[3] = {e.d[3], e.d[4], e.d[5]};
         if (use_mlp) {  // R:502-509: residual evaluated on the PRE-step state
             const float x[10] = {e.s[12], e.s[13], e.s[14], e.s[15], vb[0], vb[1], vb[2], e.s[9], e.s[10], e.s[11]};
-            float thrust, moment[3];
-            residual_mlp<kMode>(mlp, lane, x, thrust, moment);
-            M[0] += moment[0]; M[1] += moment[1]; M[2] += moment[2];
-            F[2] += thrust;
+            if constexpr (kPk) {   // the external values go in, the sums come out (residual_mlp<.., true>)
+                residual_mlp<kMode, true>(mlp, lane, x, F[2], M);
+            } else {
+                float thrust, moment[3];
+                residual_mlp<kMode>(mlp, lane, x, thrust, moment);
+                M[0] += moment[0]; M[1] += moment[1]; M[2] += moment[2];
+                F[2] += thrust;
+            }
         }
         QR_TICK(P, 4);
-        eom_e2e(e.s, R, vb, u, M, F, ds);
+        eom_e2e<kPk>(e.s, R, vb, u, M, F, ds);
     } else {
         eom_indi(e.s, R, vb, u, ds);
     }
+    if constexpr (kPk && V == kE2E) {   // Euler step of the neighbours (phi, theta), (q, r), (w1, w2), (w3, w4) as pairs
 #pragma unroll
-    for (int k = 0; k < S; ++k) nw[k] = fmaf(P.dt, ds[k], e.s[k]);  // forward Euler, R:512
+        for (int k = 0; k < S; ++k) {
+            if (k == 6 || k == 10 || k == 12 || k == 14) {
+                const f32x2p v = pk_fma(pk1(P.dt), pk2(ds[k], ds[k + 1]), pk2(e.s[k], e.s[k + 1]));
+                nw[k] = v.x;
+                nw[k + 1] = v.y;
+            } else if (!(k == 7 || k == 11 || k == 13 || k == 15)) {
+                nw[k] = fmaf(P.dt, ds[k], e.s[k]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < S; ++k) nw[k] = fmaf(P.dt, ds[k], e.s[k]);  // forward Euler, R:512
+    }
     const int steps = e.steps + 1;                                   // R:514
 
     const float4 g0 = gate.g0;                                       // R:518-519
     const float2 cs = gate.cs;
-    const float ox = e.s[0] - g0.x, oy = e.s[1] - g0.y, oz = e.s[2] - g0.z;
-    const float nx = nw[0] - g0.x, ny = nw[1] - g0.y, nz = nw[2] - g0.z;
+    float ox, oy, oz, nx, ny, nz;
+    if constexpr (kPk) {   // (x, y), old and new, against the gate's (x, y)
+        const f32x2p gxy = {g0.x, g0.y};
+        const f32x2p oxy = pk2(e.s[0], e.s[1]) - gxy, nxy = pk2(nw[0], nw[1]) - gxy;
+        ox = oxy.x; oy = oxy.y; oz = e.s[2] - g0.z;
+        nx = nxy.x; ny = nxy.y; nz = nw[2] - g0.z;
+    } else {
+        ox = e.s[0] - g0.x; oy = e.s[1] - g0.y; oz = e.s[2] - g0.z;
+        nx = nw[0] - g0.x; ny = nw[1] - g0.y; nz = nw[2] - g0.z;
+    }
     const float d2g_old = fast_sqrt(fmaf(ox, ox, fmaf(oy, oy, oz * oz)));  // R:522-525
     const float d2g_new = fast_sqrt(fmaf(nx, nx, fmaf(ny, ny, nz * nz)));
     // R:524-525: rewards = d2g_old - d2g_new - rat_penalty with rat_penalty = 0 * 0.01 * |new rates| -- zero for finite rates, NaN when a
@@ -923,8 +1103,14 @@ __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& g
     if (gate_collision) reward = -10.0f;                            // R:540
     const bool ground = nw[2] > 0.0f;                               // R:543-544
     if (ground) reward = -10.0f;
-    const bool oob = (fabsf(nw[0]) > 10.0f) || (fabsf(nw[1]) > 10.0f) || (fabsf(nw[9]) > 1000.0f) ||
-                     (fabsf(nw[10]) > 1000.0f) || (fabsf(nw[11]) > 1000.0f);           // R:549-550
+    bool oob;
+    if constexpr (kPk)   // the three rate tests as one v_max3 + one compare: a maximum that skips NaN operands exceeds the bound iff some
+                         // operand does (every operand NaN: NaN > bound is false, like the three tests), so `oob` is the same boolean
+        oob = (fabsf(nw[0]) > 10.0f) || (fabsf(nw[1]) > 10.0f) ||
+              (__builtin_fmaxf(__builtin_fmaxf(fabsf(nw[9]), fabsf(nw[10])), fabsf(nw[11])) > 1000.0f);
+    else
+        oob = (fabsf(nw[0]) > 10.0f) || (fabsf(nw[1]) > 10.0f) || (fabsf(nw[9]) > 1000.0f) ||
+              (fabsf(nw[10]) > 1000.0f) || (fabsf(nw[11]) > 1000.0f);                  // R:549-550
     if (oob) reward = -10.0f;
     trunc = steps >= P.max_steps;                                   // R:553
     new_target = e.target;

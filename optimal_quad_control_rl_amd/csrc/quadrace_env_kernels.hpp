@@ -451,6 +451,7 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
     constexpr int kVec = 16 * L;                 // float4 elements of a wave's [64][L] observation block
     constexpr int kFlush = (kVec + 63) / 64;     // store instructions per block
     constexpr bool kALds = kLean && kMlp;
+    constexpr bool kPk = (V == kE2E) && kMlp && !kLean;   // hand-packed pairs: the one-wave E2E + residual-MLP form only (quadrace_device.hpp)
     constexpr int kOffA = kResetTableFloats + kMaxGates * kGateStride + kBlock * L + 4 * kBlock * kActChunk;
     constexpr int kOffWho = kOffA + (kALds ? 4 * kMlpQuads * 64 : 0);   // lean: [4 waves][16] dwords, then the reset pool [4][64][NB] float4
     constexpr int kOffPool = kOffWho + 4 * 16;
@@ -554,10 +555,23 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
     float* rew_step = rew_out;
     uint8_t* done_step = done_out;
     uint8_t* trunc_step = trunc_out;
+    // kPk: reward / done / trunc of step k go to element k n + i of their arrays -- ONE per-lane 64-bit index advanced by one vector add
+    // per step, instead of three scalar row pointers (an add + add-with-carry pair each, the trunc pointer behind a null test and two
+    // selects): four vector instructions per step where there were three vector and eleven scalar ones
+    size_t out_idx = (size_t)i;
     GateRow gate = read_gate_row(gates, e.target);
     float4 rel[GA > 0 ? GA : 1];
     read_gates_ahead<GA>(P, gates, e.target, rel);
+    int wrap[GA > 0 ? GA : 1] = {0};           // kPk: (a + 1) mod num_gates, for read_gates_ahead_wrapped()
+    if constexpr (kPk) {
+#pragma unroll
+        for (int a = 0; a < GA; ++a) {
+            wrap[a] = (a + 1) % P.num_gates;
+            asm volatile("" : "+s"(wrap[a]));  // a scalar register each, formed here and not again in every step
+        }
+    }
     bool any_reset = false;
+    uint32_t reset_seen = 0u;                  // kPk: any_reset as one per-lane value (one v_cndmask per step instead of four mask operations)
     bool pending = false;                      // a tile written by the previous step waits to be streamed out (full waves)
     QR_CLOCK_STAMP(P, 1);
     for (int k0 = 0; k0 < K; k0 += kActChunk) {
@@ -594,7 +608,7 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
             float nw[S];
             int new_target;
             bool done, trunc;
-            const float reward = step_dynamics<V, kALds ? 1 : 0>(P, gate, mlp, kMlp, lane, e, u, nw, new_target, done, trunc);
+            const float reward = step_dynamics<V, kALds ? 1 : 0, kPk>(P, gate, mlp, kMlp, lane, e, u, nw, new_target, done, trunc);
             QR_TICK(P, 5);
             if (pending) {
                 if constexpr (kLean) read_block();
@@ -611,7 +625,8 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
             e.steps = e.steps + 1;
 #pragma unroll
             for (int q = 0; q < S; ++q) e.s[q] = nw[q];
-            any_reset |= done;
+            if constexpr (kPk) reset_seen = done ? 1u : reset_seen;
+            else any_reset |= done;
             if constexpr (kLean) {
                 reset_pooled<V>(P, rtab, who, pool, lane, done && active, e, gid_lo, gid_hi, pool_ok);
                 if constexpr (V == kE2E) {
@@ -621,16 +636,23 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
                 reset_from_stash<V>(P, rtab, done && active, e, gid_lo, gid_hi, stash, stash_ok, (V == kE2E) ? stash_od : nullptr);
             }
             if (active) {
-                stream_store(rew_step + i, reward);
-                stream_store(done_step + i, (uint8_t)(done ? 1 : 0));
-                if (trunc_step) stream_store(trunc_step + i, (uint8_t)(trunc ? 1 : 0));
+                if constexpr (kPk) {
+                    stream_store(rew_out + out_idx, reward);
+                    stream_store(done_out + out_idx, (uint8_t)(done ? 1 : 0));
+                    if (trunc_out) stream_store(trunc_out + out_idx, (uint8_t)(trunc ? 1 : 0));
+                } else {
+                    stream_store(rew_step + i, reward);
+                    stream_store(done_step + i, (uint8_t)(done ? 1 : 0));
+                    if (trunc_step) stream_store(trunc_step + i, (uint8_t)(trunc ? 1 : 0));
+                }
             }
             QR_TICK(P, 6);
             // the row of the (possibly new) target: this step's observation and the next step's gate
             gate = read_gate_row(gates, e.target);
-            read_gates_ahead<GA>(P, gates, e.target, rel);
+            if constexpr (kPk) read_gates_ahead_wrapped<GA>(P, gates, e.target, wrap, rel);
+            else read_gates_ahead<GA>(P, gates, e.target, rel);
             float o[L];
-            observe_with<V, GA, true>(P, gate, rel, e, o);
+            observe_with<V, GA, true, kPk>(P, gate, rel, e, o);
             if (full_wave) {
                 obs_tile_store_rows<V, GA>(tile, lane, o);   // streamed out in the middle of the NEXT step (worth ~600 cycles per step, r04)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -641,9 +663,13 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
             }
             QR_TICK(P, 7);
             obs_step += n * L;
-            rew_step += n;
-            done_step += n;
-            if (trunc_step) trunc_step += n;
+            if constexpr (kPk) {
+                out_idx += n;
+            } else {
+                rew_step += n;
+                done_step += n;
+                if (trunc_step) trunc_step += n;
+            }
         }
     }
     QR_CLOCK_STAMP(P, 2);
@@ -652,7 +678,7 @@ __device__ __forceinline__ void rollout_fast_body_impl(Params P, int K, const fl
     define_exit_values<V>(e);
     P.ts[i] = pack_ts<V>(e);
     store_world<V>(P, i, e);
-    if (any_reset) store_dist<V>(P, i, e);
+    if (kPk ? reset_seen != 0u : any_reset) store_dist<V>(P, i, e);
     QR_CLOCK_STAMP(P, 3);
 }
 template <int V, int GA, bool kMlp, bool kLean>
