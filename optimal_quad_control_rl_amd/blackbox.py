@@ -15,18 +15,14 @@ produced (after the integration, before the auto-reset).
 """
 import numpy as np
 
+from ._closed_loop import _host, flying_policy, model_log_std
+
 from .recording import RECORD_EXTRA, FlightRecord
 
 ST_INTS = 4   # QR_BLACKBOX_ST_INTS of include/quadrace.h
 TRIGGERS = {"none": 0, "crash": 1, "time_limit": 2, "any": 3}   # QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT
 CAUSE_GROUND, CAUSE_OOB, CAUSE_TIME_LIMIT, CAUSE_GATE = 1, 2, 4, 8
 CAUSE_NAMES = ((CAUSE_GROUND, "ground"), (CAUSE_OOB, "out_of_bounds"), (CAUSE_GATE, "gate"), (CAUSE_TIME_LIMIT, "time_limit"))
-
-
-def _host(x):
-    if hasattr(x, "detach"):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x)
 
 
 class CrashLog:
@@ -142,31 +138,9 @@ def blackbox_policy(model, env, n_steps, window=64, trigger="crash", rec_envs=No
     freezes).  `deterministic`, `seed`, `precision` as in record_policy.  `env` keeps flying from where the call left it."""
     if trigger not in TRIGGERS:
         raise ValueError("trigger must be one of %s, got %r" % (sorted(TRIGGERS), trigger))
-    import torch
-
-    from .evaluation import _actor
-    from .policy import MfmaPolicy
-    from .sb3 import _unwrap
-
-    core = _unwrap(env)
-    if precision is None:
-        f32 = getattr(model, "precision", None) in ("f32", "f32-collect") or getattr(model, "policy_forward", None) == "f32class"
-        precision = "f32" if f32 else "f16-operands"
-    net = getattr(model, "_net", None)
-    if net is None:
-        net = model.policy
-    net = getattr(net, "net", net)
-    log_std = net.log_std.detach() if hasattr(net, "log_std") else torch.zeros(4)
-    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(_actor(model))
-    try:
-        if seed is not None:
-            core.seed(seed)
-            core.reset_device()
-        ring, st, term = core.blackbox_policy_device(policy, int(n_steps), log_std, window=int(window), trigger=TRIGGERS[trigger],
+    with flying_policy(model, env, precision, seed) as (core, policy, precision, owner):
+        ring, st, term = core.blackbox_policy_device(policy, int(n_steps), model_log_std(owner), window=int(window), trigger=TRIGGERS[trigger],
                                                      noise_seed=0 if seed is None else int(seed), deterministic=deterministic,
                                                      rec_envs=rec_envs, precision=precision)
         ring, st, term = ring.cpu().numpy(), st.cpu().numpy(), term.cpu().numpy()
-    finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        policy.close()
     return CrashLog(ring, st, term, int(n_steps) - 1, core.dt)

@@ -19,9 +19,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-
-def _f32p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
+from ._closed_loop import _f32p
 
 
 @dataclass(frozen=True, eq=False)

@@ -34,20 +34,27 @@ finished, out of bounds, ground, gate collision, time limit -- counted by `q3_ev
 
 All times inside the records are integer step counts; seconds appear only here (steps x env.dt).
 """
+import copy
 import math
 
 import numpy as np
+
+from ._closed_loop import _actor, _as_actor, _host, _model_precision, fly_batches, flying_policy, group_size, zero_records  # noqa: F401 (_actor: tools/)
 
 REC_INTS, MAX_LAPS, REC_FLOATS = 24, 8, 4   # QR_EVAL_REC_INTS, QR_EVAL_MAX_LAPS, QR_EVAL_REC_FLOATS of include/quadrace.h
 Q3_REC_INTS, Q3_REC_FLOATS = 12, 4          # Q3_EVAL_REC_INTS, Q3_EVAL_REC_FLOATS of include/quad3d.h
 
 
-def _host(a):
-    if a is None:
-        return None
-    if hasattr(a, "detach"):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a)
+def _reward_stats(recf, n, episodes):
+    """(mean, std) of the finished episodes' rewards from `recf` [n, 4] (either kind of record: columns 1, 2 = sum, sum of squares);
+    (None, None) without episodes or without `recf`"""
+    recf = _host(recf)
+    if recf is None or episodes <= 0:
+        return None, None
+    assert recf.shape == (n, REC_FLOATS) and REC_FLOATS == Q3_REC_FLOATS, recf.shape
+    s1, s2 = float(recf[:, 1].astype(np.float64).sum()), float(recf[:, 2].astype(np.float64).sum())
+    mean = s1 / episodes
+    return mean, math.sqrt(max(s2 / episodes - mean * mean, 0.0))
 
 
 def summarize_eval(rec, recf, dt, gates_per_lap):
@@ -63,13 +70,7 @@ def summarize_eval(rec, recf, dt, gates_per_lap):
     fly_sum, fly_cnt = int(lap_sum[1:].sum()), int(lap_cnt[1:].sum())
     gates, crashes, timeouts = int(rec[:, 0].sum()), int(rec[:, 1].sum()), int(rec[:, 2].sum())
     episodes = crashes + timeouts
-    mean_reward = std_reward = None
-    recf = _host(recf)
-    if recf is not None and episodes > 0:
-        assert recf.shape == (n, REC_FLOATS), recf.shape
-        s1, s2 = float(recf[:, 1].astype(np.float64).sum()), float(recf[:, 2].astype(np.float64).sum())
-        mean_reward = s1 / episodes
-        std_reward = math.sqrt(max(s2 / episodes - mean_reward * mean_reward, 0.0))
+    mean_reward, std_reward = _reward_stats(recf, n, episodes)
     return dict(envs=n, steps=int(rec[:, 5].max()) if n else 0, gates_per_lap=int(gates_per_lap),
                 gates=gates, crashes=crashes, timeouts=timeouts, episodes=episodes,
                 gates_per_env=gates / n if n else 0.0, crashes_per_env=crashes / n if n else 0.0,
@@ -89,52 +90,38 @@ def default_gates_per_lap(env):
     return g
 
 
-def _actor(model):
-    """the torch actor (Linear, ReLU, ..., Linear) of the SB3-shaped PPO (sb3.PPO) or of the native trainer (ppo.PPO)"""
-    net = getattr(model, "_net", None)
-    if net is None:
-        net = model.policy
-    net = getattr(net, "net", net)   # sb3.ActorCriticPolicy wraps the ActorCritic
-    return net.pi
+def _phases(n_eval_steps, window_steps):
+    """[window, rest] of an evaluation, the rest dropped when it is 0"""
+    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
+    if not 1 <= window_steps <= n_eval_steps:
+        raise ValueError("need 1 <= window_steps <= n_eval_steps")
+    return [window_steps, n_eval_steps - window_steps][:2 if n_eval_steps > window_steps else 1]
+
+
+def _window_total(summaries):
+    """{"window", "total"} of the per-phase summaries of one policy: the first with the per-window names of its rates, the last"""
+    window = copy.deepcopy(summaries[0])
+    window["crashes_per_window"], window["gates_per_window"] = window["crashes_per_env"], window["gates_per_env"]
+    return {"window": window, "total": summaries[-1]}
 
 
 def evaluate_policy(model, env, n_eval_steps=2000, window_steps=1200, gates_per_lap=None, precision=None, seed=None):
     """Deterministic evaluation of `model`'s current policy on `env` (a race env of this package, possibly inside a VecMonitor), as
     two kernel launches: `window_steps` (the "per 12 s" window of the crash / gate rates), then the rest of `n_eval_steps` (lap times
     need the longer flight).  Returns {"window": summary after the first call, "total": summary after both} (summarize_eval), the
-    window with `crashes_per_window` / `gates_per_window` (per-env means).  `seed`: reseed and reset the env first, so that two
-    evaluations see the same starts; None continues from the env's current state.  `precision`: "f16-operands" | "f32" (None: the
-    model's own collect precision).  `env` keeps flying from where the evaluation left it."""
-    import torch
-
-    from .policy import MfmaPolicy
-    from .sb3 import _unwrap
-
-    core = _unwrap(env)
-    if precision is None:
-        f32 = getattr(model, "precision", None) in ("f32", "f32-collect") or getattr(model, "policy_forward", None) == "f32class"
-        precision = "f32" if f32 else "f16-operands"
-    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
-    if not 1 <= window_steps <= n_eval_steps:
-        raise ValueError("need 1 <= window_steps <= n_eval_steps")
-    gpl = default_gates_per_lap(core) if gates_per_lap is None else int(gates_per_lap)
-    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(_actor(model))
-    try:
-        if seed is not None:
-            core.seed(seed)
-            core.reset_device()
-        rec = torch.zeros((core.num_envs, REC_INTS), dtype=torch.int32, device=core.device)
-        recf = torch.zeros((core.num_envs, REC_FLOATS), dtype=torch.float32, device=core.device)
-        core.evaluate_device(policy, window_steps, gpl, rec, recf, precision=precision)
-        window = summarize_eval(rec, recf, core.dt, gpl)
-        window["crashes_per_window"], window["gates_per_window"] = window["crashes_per_env"], window["gates_per_env"]
-        if n_eval_steps > window_steps:
-            core.evaluate_device(policy, n_eval_steps - window_steps, gpl, rec, recf, precision=precision)
-        total = summarize_eval(rec, recf, core.dt, gpl)
-    finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        policy.close()
-    return {"window": window, "total": total}
+    window with `crashes_per_window` / `gates_per_window` (per-env means).  `model`: what evaluate_policies accepts as an entry.
+    `seed`: reseed and reset the env first, so that two evaluations see the same starts; None continues from the env's current state.
+    `precision`: "f16-operands" | "f32" (None: the model's own collect precision).  `env` keeps flying from where the evaluation left
+    it."""
+    phases = _phases(n_eval_steps, window_steps)
+    with flying_policy(model, env, precision, seed) as (core, policy, precision, _):
+        gpl = default_gates_per_lap(core) if gates_per_lap is None else int(gates_per_lap)
+        rec, recf = zero_records(core.num_envs, (REC_INTS, REC_FLOATS), core.device)
+        summaries = []
+        for steps in phases:
+            core.evaluate_device(policy, steps, gpl, rec, recf, precision=precision)
+            summaries.append(summarize_eval(rec, recf, core.dt, gpl))
+    return _window_total(summaries)
 
 
 def plan_policy_batches(num_policies, slots):
@@ -153,20 +140,23 @@ def plan_policy_batches(num_policies, slots):
     return plan
 
 
-def _as_actor(entry):
-    """(torch actor, model or None) of one entry of evaluate_policies: a checkpoint path written by `model.save`, an SB3-shaped PPO,
-    a native trainer, or a bare torch actor (Linear, ReLU, ..., Linear)."""
-    import os
+def _shared_starts(core, bank, actors, E, seed):
+    """the per-batch step of the two bank evaluators: the batch's policies into the bank's slots, then the same starts for every group"""
+    def start(indices):
+        for slot, idx in enumerate(indices):
+            bank.load_torch(slot, actors[idx][0])
+        core.seed(seed)
+        core.reset_device()
+        core.share_starts(E)
+    return start
 
+
+def _sync_and_close(core, *banks):
     import torch
 
-    if isinstance(entry, (str, os.PathLike)):
-        from .sb3 import PPO
-
-        entry = PPO.load(os.fspath(entry))   # needs no env
-    if isinstance(entry, torch.nn.Module) and not hasattr(entry, "pi") and not hasattr(entry, "net"):
-        return entry, None
-    return _actor(entry), entry
+    torch.cuda.current_stream(core.device).synchronize()
+    for bank in banks:
+        bank.close()
 
 
 def evaluate_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, window_steps=1200, gates_per_lap=None, precision=None, seed=0):
@@ -178,51 +168,33 @@ def evaluate_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, win
     native trainer, or a torch actor.  envs_per_policy: a multiple of 256; env.num_envs must be a multiple of it.  precision: None =
     "f32" if any model collects in f32, else "f16-operands" (one launch has one precision).  Returns one {"window", "total"} dict per
     policy, in order, each what evaluate_policy returns for that policy on an E-env handle."""
-    import torch
-
     from .policy import MfmaPolicyBank
     from .sb3 import _unwrap
 
     core = _unwrap(env)
-    E, n = int(envs_per_policy), core.num_envs
-    if E < 256 or E % 256 != 0:
-        raise ValueError("envs_per_policy must be a multiple of 256 (one workgroup serves one policy)")
-    if n % E != 0:
-        raise ValueError("env.num_envs must be a multiple of envs_per_policy")
-    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
-    if not 1 <= window_steps <= n_eval_steps:
-        raise ValueError("need 1 <= window_steps <= n_eval_steps")
+    E, slots = group_size(envs_per_policy, core.num_envs, "envs_per_policy", "policy")
+    phases = _phases(n_eval_steps, window_steps)
+    policies = list(policies)
+    plan = plan_policy_batches(len(policies), slots)
     actors = [_as_actor(p) for p in policies]
     if precision is None:
-        f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for _, m in actors)
-        precision = "f32" if f32 else "f16-operands"
+        precision = _model_precision([m for _, m in actors])
     gpl = default_gates_per_lap(core) if gates_per_lap is None else int(gates_per_lap)
-    slots = n // E
     results = [None] * len(actors)
     bank = MfmaPolicyBank(core.state_len, slots, core.device.index)
+
+    def launch(_, steps, rec, recf):
+        core.evaluate_bank_device(bank, slots, E, steps, gpl, rec, recf, precision=precision)
+
+    def summarise(_, rec, recf):
+        return summarize_eval(rec, recf, core.dt, gpl)
+
     try:
-        for indices, kept in plan_policy_batches(len(actors), slots):
-            for slot, idx in enumerate(indices):
-                bank.load_torch(slot, actors[idx][0])
-            core.seed(seed)
-            core.reset_device()
-            core.share_starts(E)
-            rec = torch.zeros((n, REC_INTS), dtype=torch.int32, device=core.device)
-            recf = torch.zeros((n, REC_FLOATS), dtype=torch.float32, device=core.device)
-            core.evaluate_bank_device(bank, slots, E, window_steps, gpl, rec, recf, precision=precision)
-            windows = []
-            for slot in range(kept):
-                w = summarize_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt, gpl)
-                w["crashes_per_window"], w["gates_per_window"] = w["crashes_per_env"], w["gates_per_env"]
-                windows.append(w)
-            if n_eval_steps > window_steps:
-                core.evaluate_bank_device(bank, slots, E, n_eval_steps - window_steps, gpl, rec, recf, precision=precision)
-            for slot in range(kept):
-                total = summarize_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt, gpl)
-                results[indices[slot]] = {"window": windows[slot], "total": total}
+        for idx, summaries in fly_batches(plan, _shared_starts(core, bank, actors, E, seed), launch, phases, (REC_INTS, REC_FLOATS), summarise,
+                                          core.num_envs, E, core.device):
+            results[idx] = _window_total(summaries)
     finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        bank.close()
+        _sync_and_close(core, bank)
     return results
 
 
@@ -252,55 +224,40 @@ def evaluate_grid(policies, conditions, env, envs_per_cell=256, n_eval_steps=200
     all cells see the same uniform draws (only the condition's own scaling of them differs), and cell (p, c) is what an E-env
     handle configured with condition c sees under evaluate_policy(policies[p], ..., seed=seed).  Entries of `policies` and
     `precision`: as evaluate_policies.  Returns results[p][c], each a {"window", "total"} dict.  `env` keeps its own configuration."""
-    import torch
-
     from .conditions import ConditionBank
     from .policy import MfmaPolicyBank
     from .sb3 import _unwrap
 
     core = _unwrap(env)
-    E, n = int(envs_per_cell), core.num_envs
-    if E < 256 or E % 256 != 0:
-        raise ValueError("envs_per_cell must be a multiple of 256 (one workgroup serves one cell)")
-    if n % E != 0:
-        raise ValueError("env.num_envs must be a multiple of envs_per_cell")
-    n_eval_steps, window_steps = int(n_eval_steps), int(window_steps)
-    if not 1 <= window_steps <= n_eval_steps:
-        raise ValueError("need 1 <= window_steps <= n_eval_steps")
-    conditions = list(conditions)
+    E, slots = group_size(envs_per_cell, core.num_envs, "envs_per_cell", "cell")
+    phases = _phases(n_eval_steps, window_steps)
+    conditions, policies = list(conditions), list(policies)
+    plan = plan_grid_batches(len(policies), len(conditions), slots)
     actors = [_as_actor(p) for p in policies]
     if precision is None:
-        f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for _, m in actors)
-        precision = "f32" if f32 else "f16-operands"
-    slots = n // E
+        precision = _model_precision([m for _, m in actors])
     results = [[None] * len(conditions) for _ in actors]
     pbank = MfmaPolicyBank(core.state_len, len(actors), core.device.index)
     cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
+
+    def start(cells):
+        core.condition_starts(conditions, [c for _, c in cells], E, seed=seed)
+
+    def launch(cells, steps, rec, recf):
+        core.evaluate_grid_device(pbank, cbank, [p for p, _ in cells], [c for _, c in cells], E, steps, rec, recf, precision=precision)
+
+    def summarise(cell, rec, recf):
+        return summarize_eval(rec, recf, core.dt, conditions[cell[1]].gates_per_lap)
+
     try:
         for p, (actor, _) in enumerate(actors):
             pbank.load_torch(p, actor)
         for c, cond in enumerate(conditions):
             cbank.set(c, cond)
-        for cells, kept in plan_grid_batches(len(actors), len(conditions), slots):
-            pol, cog = [p for p, _ in cells], [c for _, c in cells]
-            core.condition_starts(conditions, cog, E, seed=seed)
-            rec = torch.zeros((n, REC_INTS), dtype=torch.int32, device=core.device)
-            recf = torch.zeros((n, REC_FLOATS), dtype=torch.float32, device=core.device)
-            core.evaluate_grid_device(pbank, cbank, pol, cog, E, window_steps, rec, recf, precision=precision)
-            windows = []
-            for g in range(kept):
-                w = summarize_eval(rec[g * E:(g + 1) * E], recf[g * E:(g + 1) * E], core.dt, conditions[cog[g]].gates_per_lap)
-                w["crashes_per_window"], w["gates_per_window"] = w["crashes_per_env"], w["gates_per_env"]
-                windows.append(w)
-            if n_eval_steps > window_steps:
-                core.evaluate_grid_device(pbank, cbank, pol, cog, E, n_eval_steps - window_steps, rec, recf, precision=precision)
-            for g in range(kept):
-                total = summarize_eval(rec[g * E:(g + 1) * E], recf[g * E:(g + 1) * E], core.dt, conditions[cog[g]].gates_per_lap)
-                results[pol[g]][cog[g]] = {"window": windows[g], "total": total}
+        for (p, c), summaries in fly_batches(plan, start, launch, phases, (REC_INTS, REC_FLOATS), summarise, core.num_envs, E, core.device):
+            results[p][c] = _window_total(summaries)
     finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        pbank.close()
-        cbank.close()
+        _sync_and_close(core, pbank, cbank)
     return results
 
 
@@ -350,13 +307,7 @@ def summarize_q3_eval(rec, recf, dt):
     successes, timeouts, oob, ground, collisions = (int(tot[c]) for c in (1, 2, 3, 4, 5))
     episodes = successes + timeouts + oob + ground + collisions
     best = rec[:, 9][rec[:, 9] > 0]
-    mean_reward = std_reward = None
-    recf = _host(recf)
-    if recf is not None and episodes > 0:
-        assert recf.shape == (n, Q3_REC_FLOATS), recf.shape
-        s1, s2 = float(recf[:, 1].astype(np.float64).sum()), float(recf[:, 2].astype(np.float64).sum())
-        mean_reward = s1 / episodes
-        std_reward = math.sqrt(max(s2 / episodes - mean_reward * mean_reward, 0.0))
+    mean_reward, std_reward = _reward_stats(recf, n, episodes)
     return dict(envs=n, steps=int(rec[:, 0].max()) if n else 0, episodes=episodes,
                 successes=successes, timeouts=timeouts, out_of_bounds=oob, ground=ground, collisions=collisions,
                 success_rate=successes / episodes if episodes else None,
@@ -367,88 +318,50 @@ def summarize_q3_eval(rec, recf, dt):
                 mean_reward=mean_reward, std_reward=std_reward)
 
 
-def _model_precision(models):
-    f32 = any(getattr(m, "precision", None) in ("f32", "f32-collect") or getattr(m, "policy_forward", None) == "f32class" for m in models)
-    return "f32" if f32 else "f16-operands"
-
-
 def evaluate_q3_policy(model, env, n_eval_steps=2000, precision=None, seed=None):
-    """Deterministic evaluation of `model`'s current policy on `env` (a Quadcopter3DVec / Quadcopter3DVecGates, possibly inside a
-    VecMonitor) as ONE kernel launch of `n_eval_steps` steps (q3_evaluate_policy).  Returns summarize_q3_eval's dict.  `model`: what
-    evaluate_q3_policies accepts as an entry.  `seed`: reseed and reset the env first, so that two evaluations see the same starts; None
-    continues from the env's current state.  `precision`: "f16-operands" | "f32" (None: the model's own collect precision).  `env`
-    keeps flying from where the evaluation left it."""
-    import torch
-
-    from .policy import MfmaPolicy
-    from .sb3 import _unwrap
-
-    core = _unwrap(env)
+    """evaluate_policy for the predecessor envs: deterministic evaluation of `model`'s current policy on `env` (a Quadcopter3DVec /
+    Quadcopter3DVecGates, possibly inside a VecMonitor) as ONE kernel launch of `n_eval_steps` steps (q3_evaluate_policy).  Returns
+    summarize_q3_eval's dict.  `model`, `seed`, `precision` and where `env` is left: as evaluate_policy."""
     n_eval_steps = int(n_eval_steps)
     if n_eval_steps < 1:
         raise ValueError("need n_eval_steps >= 1")
-    actor, owner = _as_actor(model)
-    if precision is None:
-        precision = _model_precision([owner])
-    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(actor)
-    try:
-        if seed is not None:
-            core.seed(seed)
-            core.reset_device()
-        rec = torch.zeros((core.num_envs, Q3_REC_INTS), dtype=torch.int32, device=core.device)
-        recf = torch.zeros((core.num_envs, Q3_REC_FLOATS), dtype=torch.float32, device=core.device)
+    with flying_policy(model, env, precision, seed) as (core, policy, precision, _):
+        rec, recf = zero_records(core.num_envs, (Q3_REC_INTS, Q3_REC_FLOATS), core.device)
         core.evaluate_device(policy, n_eval_steps, rec, recf, precision=precision)
         return summarize_q3_eval(rec, recf, core.dt)
-    finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        policy.close()
 
 
 def evaluate_q3_policies(policies, env, envs_per_policy=256, n_eval_steps=2000, precision=None, seed=0):
     """evaluate_q3_policy for a LIST of policies, `env.num_envs // envs_per_policy` of them per launch (q3_evaluate_policy_bank): policy
-    p of a batch flies envs [p E, (p + 1) E) of `env`.  Every batch starts from `seed(seed); reset_device(); share_starts(E)` and the
-    kernel keys restarts by the env's index within its group, so ALL policies -- within a batch and across batches -- see bit-identical
-    starts and restarts for as long as their own flying allows, the ones an E-env handle sees under evaluate_q3_policy(..., seed=seed).
-    Entries: a checkpoint path written by `model.save`, an SB3-shaped PPO, a native trainer, or a torch actor.  envs_per_policy: a
-    multiple of 256; env.num_envs must be a multiple of it.  precision: None = "f32" if any model collects in f32, else "f16-operands".
-    The last batch is padded by repeating its last policy.  Returns one summarize_q3_eval dict per policy, in order."""
+    p of a batch flies envs [p E, (p + 1) E) of `env`.  Batches, shared starts and restarts, entries, envs_per_policy, precision and the
+    padding of the last batch: as evaluate_policies, so every policy flies what an E-env handle sees under
+    evaluate_q3_policy(..., seed=seed).  Returns one summarize_q3_eval dict per policy, in order."""
+    from .policy import MfmaPolicyBank
     from .sb3 import _unwrap
 
     core = _unwrap(env)
-    E, n = int(envs_per_policy), int(core.num_envs)
-    if E < 256 or E % 256 != 0:
-        raise ValueError("envs_per_policy must be a multiple of 256 (one workgroup serves one policy)")
-    if n % E != 0:
-        raise ValueError("env.num_envs must be a multiple of envs_per_policy")
+    E, slots = group_size(envs_per_policy, core.num_envs, "envs_per_policy", "policy")
     n_eval_steps = int(n_eval_steps)
     if n_eval_steps < 1:
         raise ValueError("need n_eval_steps >= 1")
     policies = list(policies)
-    slots = n // E
     plan = plan_policy_batches(len(policies), slots)
-
-    import torch
-
-    from .policy import MfmaPolicyBank
-
     actors = [_as_actor(p) for p in policies]
     if precision is None:
         precision = _model_precision([m for _, m in actors])
     results = [None] * len(actors)
     bank = MfmaPolicyBank(core.state_len, slots, core.device.index)
+
+    def launch(_, steps, rec, recf):
+        core.evaluate_bank_device(bank, slots, E, steps, rec, recf, precision=precision)
+
+    def summarise(_, rec, recf):
+        return summarize_q3_eval(rec, recf, core.dt)
+
     try:
-        for indices, kept in plan:
-            for slot, idx in enumerate(indices):
-                bank.load_torch(slot, actors[idx][0])
-            core.seed(seed)
-            core.reset_device()
-            core.share_starts(E)
-            rec = torch.zeros((n, Q3_REC_INTS), dtype=torch.int32, device=core.device)
-            recf = torch.zeros((n, Q3_REC_FLOATS), dtype=torch.float32, device=core.device)
-            core.evaluate_bank_device(bank, slots, E, n_eval_steps, rec, recf, precision=precision)
-            for slot in range(kept):
-                results[indices[slot]] = summarize_q3_eval(rec[slot * E:(slot + 1) * E], recf[slot * E:(slot + 1) * E], core.dt)
+        for idx, (summary,) in fly_batches(plan, _shared_starts(core, bank, actors, E, seed), launch, [n_eval_steps],
+                                           (Q3_REC_INTS, Q3_REC_FLOATS), summarise, core.num_envs, E, core.device):
+            results[idx] = summary
     finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        bank.close()
+        _sync_and_close(core, bank)
     return results

@@ -11,10 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _f32p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
+from ._closed_loop import _f32p
 
 
 def _weight_arrays(obs_len, layers):

@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vec_env import _Base, _f32p, _make_box, _precision_flags, _ptr
+from ._closed_loop import _f32p, _precision_flags, check_records, log_std_array, rollout_outputs
+from .vec_env import _Base, _make_box, _ptr
 
 Q3_KIND_HOVER, Q3_KIND_GATES = 0, 1
 _KEYS = ['x', 'y', 'z', 'vx', 'vy', 'vz', 'phi', 'theta', 'psi', 'p', 'q', 'r', 'w1', 'w2', 'w3', 'w4']
@@ -212,17 +213,11 @@ class _Quad3DBase(_Base):
         if term is not None and K > int(term.shape[0]):
             raise ValueError(f"num_steps = {K} exceeds the {int(term.shape[0])} rows of the terminal-observation buffer")
         if out is None:
-            out = (torch.empty((K, n, 16), dtype=torch.float32, device=dev),
-                   torch.empty((K, n, 4), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev))
+            out = rollout_outputs(K, n, 16, dev)
         obs, act, logp, rew, done, trunc = out
         if self._obs32_d is None:
             self._obs32_d = torch.zeros((n, 16), dtype=torch.float32, device=dev)
-        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
-                                  dtype=np.float32).reshape(4)
+        ls = log_std_array(log_std)
         _lib.check(self._L.q3_rollout_policy(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
                                              int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
                                              _ptr(done), _ptr(trunc), _ptr(term), _ptr(self._obs32_d), _ptr(self._states_d),
@@ -231,13 +226,7 @@ class _Quad3DBase(_Base):
 
     # ---- on-device evaluation (q3_evaluate_policy, q3_evaluate_policy_bank; summary: evaluation.summarize_q3_eval) ---------------
     def _check_eval_records(self, rec, recf):
-        n = self.num_envs
-        if not (torch.is_tensor(rec) and rec.is_cuda and rec.device == self.device and rec.dtype == torch.int32 and rec.is_contiguous()
-                and tuple(rec.shape) == (n, 12)):
-            raise ValueError("rec must be a contiguous int32 tensor [num_envs, 12] on the env's device")
-        if recf is not None and not (torch.is_tensor(recf) and recf.is_cuda and recf.device == self.device and recf.dtype == torch.float32
-                                     and recf.is_contiguous() and tuple(recf.shape) == (n, 4)):
-            raise ValueError("recf must be a contiguous float32 tensor [num_envs, 4] on the env's device")
+        check_records(rec, recf, self.num_envs, (12, 4), ValueError, self.device)
 
     def _refresh_states(self):
         """env.states -> the env's own device buffer (the evaluators store no per-step row and take no states_out)."""

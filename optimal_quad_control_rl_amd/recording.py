@@ -16,6 +16,8 @@ later).  Shift `world` by one row to get the cell's pairing.
 """
 import numpy as np
 
+from ._closed_loop import _host, flying_policy, model_log_std
+
 RECORD_EXTRA = 8   # QR_RECORD_EXTRA of include/quadrace.h
 LOG_KEYS = ("t", "x", "y", "z", "vx", "vy", "vz", "V", "phi", "theta", "psi", "u1", "u2", "u3", "u4", "u")   # the reference's log_dict
 END_RUNNING, END_CRASH, END_TIME_LIMIT = 0.0, 1.0, 2.0
@@ -29,9 +31,7 @@ class FlightRecord:
     def __init__(self, rows, dt, final_target=None):
         """final_target [M] (optional): the target gate of each env AFTER the last recorded step (qr_get_state), which stands in for the
         "next row" of the last row, so that a pass on the last step is seen; without it that step cannot show a pass."""
-        if hasattr(rows, "detach"):
-            rows = rows.detach().cpu().numpy()
-        rows = np.asarray(rows)
+        rows = _host(rows)
         if rows.dtype != np.float32 or rows.ndim != 3 or rows.shape[2] - RECORD_EXTRA not in (13, 16):
             raise ValueError("rows must be float32 [K][M][S + %d] with S = 13 or 16, got %s %s" % (RECORD_EXTRA, rows.dtype, rows.shape))
         self.rows, self.dt = rows, np.float32(dt)
@@ -40,9 +40,7 @@ class FlightRecord:
         self.reward, self.end, self.target, self.steps = rows[:, :, s + 4], rows[:, :, s + 5], rows[:, :, s + 6], rows[:, :, s + 7]
         self.final_target = None
         if final_target is not None:
-            if hasattr(final_target, "detach"):
-                final_target = final_target.detach().cpu().numpy()
-            self.final_target = np.asarray(final_target).astype(np.float32).reshape(rows.shape[1])
+            self.final_target = _host(final_target).astype(np.float32).reshape(rows.shape[1])
 
     @property
     def num_steps(self):
@@ -114,31 +112,9 @@ def record_policy(model, env, n_steps, envs=None, deterministic=True, seed=None,
     actions with the model's log_std (noise keyed by `seed` or 0).  `seed`: reseed and reset the env first, so that a record and an
     evaluate_policy with the same seed see the same flights; None continues from the env's current state.  `precision` as in
     evaluate_policy.  `env` keeps flying from where the record left it."""
-    import torch
-
-    from .evaluation import _actor
-    from .policy import MfmaPolicy
-    from .sb3 import _unwrap
-
-    core = _unwrap(env)
-    if precision is None:
-        f32 = getattr(model, "precision", None) in ("f32", "f32-collect") or getattr(model, "policy_forward", None) == "f32class"
-        precision = "f32" if f32 else "f16-operands"
-    net = getattr(model, "_net", None)
-    if net is None:
-        net = model.policy
-    net = getattr(net, "net", net)
-    log_std = net.log_std.detach() if hasattr(net, "log_std") else torch.zeros(4)
-    policy = MfmaPolicy(core.state_len, core.device.index).load_torch(_actor(model))
-    try:
-        if seed is not None:
-            core.seed(seed)
-            core.reset_device()
-        rows = core.record_policy_device(policy, int(n_steps), log_std, noise_seed=0 if seed is None else int(seed), deterministic=deterministic,
-                                         rec_envs=envs, precision=precision)
+    with flying_policy(model, env, precision, seed) as (core, policy, precision, owner):
+        rows = core.record_policy_device(policy, int(n_steps), model_log_std(owner), noise_seed=0 if seed is None else int(seed),
+                                         deterministic=deterministic, rec_envs=envs, precision=precision)
         host = rows.cpu().numpy()
         final_target = core.get_state_tensors()[2][:host.shape[1]].cpu().numpy()
-    finally:
-        torch.cuda.current_stream(core.device).synchronize()
-        policy.close()
     return FlightRecord(host, core.dt, final_target)

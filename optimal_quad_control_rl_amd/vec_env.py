@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._closed_loop import _f32p, _precision_flags, check_records, log_std_array, rollout_outputs
 from ._lib import QR_VARIANT_E2E, QR_VARIANT_INDI
 
 try:  # the reference imports `gymnasium.spaces` (R:284) / `gym.spaces` (I:139); neither is required here
@@ -130,17 +131,6 @@ class _DeviceBackedArray(np.ndarray):
     def fill(self, value):
         super().fill(value)
         self._push()
-
-
-def _f32p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _precision_flags(precision):
-    """Flag bits of the policy forward's precision (QR_ROLLOUT_F32CLASS for "f32")."""
-    if precision not in ("f16-operands", "f32"):
-        raise ValueError("precision must be 'f16-operands' or 'f32'")
-    return 2 if precision == "f32" else 0
 
 
 class Quadcopter3DGates(_Base):
@@ -625,15 +615,9 @@ class Quadcopter3DGates(_Base):
         flags = _precision_flags(precision)
         K, n, dev = int(num_steps), self.num_envs, self.device
         if out is None:
-            out = (torch.empty((K, n, self.state_len), dtype=torch.float32, device=dev),
-                   torch.empty((K, n, 4), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev))
+            out = rollout_outputs(K, n, self.state_len, dev)
         obs, act, logp, rew, done, trunc = out
-        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
-                                  dtype=np.float32).reshape(4)
+        ls = log_std_array(log_std)
         _lib.check(self._L.qr_rollout_policy(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
                                              int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
                                              _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
@@ -642,10 +626,7 @@ class Quadcopter3DGates(_Base):
 
     def _check_eval_records(self, rec, recf):
         """The evaluators' record tensors: `rec` int32 [N, 24], `recf` float32 [N, 4] or None, both on the device and contiguous."""
-        n = self.num_envs
-        assert rec.is_cuda and rec.dtype == torch.int32 and rec.is_contiguous() and tuple(rec.shape) == (n, 24), (rec.dtype, rec.shape)
-        if recf is not None:
-            assert recf.is_cuda and recf.dtype == torch.float32 and recf.is_contiguous() and tuple(recf.shape) == (n, 4), (recf.dtype, recf.shape)
+        check_records(rec, recf, self.num_envs, (24, 4), AssertionError)
 
     def evaluate_device(self, policy, num_steps, gates_per_lap, rec, recf=None, precision="f16-operands"):
         """Closed-loop deterministic evaluation in ONE kernel (qr_evaluate_policy): K x [obs -> MFMA policy -> env.step(clip(mean))]
@@ -766,6 +747,16 @@ class Quadcopter3DGates(_Base):
             self._push_disturbance()
         self.max_steps = max_steps
 
+    def _group_map(self, conditions, condition_of_group, envs_per_group, seed):
+        """(E, condition_of_group as ints, seed to use) of condition_starts / condition_reset, the map checked against the env"""
+        e = int(envs_per_group)
+        cog = [int(c) for c in condition_of_group]
+        if e < 1 or len(cog) * e != self.num_envs:
+            raise ValueError("len(condition_of_group) * envs_per_group must equal num_envs")
+        if any(c < 0 or c >= len(conditions) for c in cog):
+            raise ValueError("condition_of_group holds an index outside `conditions`")
+        return e, cog, self._seed if seed is None else int(seed)
+
     def condition_starts(self, conditions, condition_of_group, envs_per_group, seed=None):
         """Give every group g of E = envs_per_group envs the start an E-env handle configured with conditions[condition_of_group[g]]
         gets from `seed(s); reset_device()` (s = `seed`, default: the seed this env was last seeded with): per distinct condition the
@@ -773,13 +764,7 @@ class Quadcopter3DGates(_Base):
         kept; then the env's own configuration is restored and the assembled state set.  Groups under the same condition start
         bit-equal; groups under conditions that differ in the disturbance scale only differ in `disturbances` only.  A few N-env
         resets; the episode counters and step counts are those of a fresh reset."""
-        e, n = int(envs_per_group), self.num_envs
-        cog = [int(c) for c in condition_of_group]
-        if e < 1 or len(cog) * e != n:
-            raise ValueError("len(condition_of_group) * envs_per_group must equal num_envs")
-        if any(c < 0 or c >= len(conditions) for c in cog):
-            raise ValueError("condition_of_group holds an index outside `conditions`")
-        s = self._seed if seed is None else int(seed)
+        e, cog, s = self._group_map(conditions, condition_of_group, envs_per_group, seed)
         starts = {}
 
         def start(c):
@@ -808,15 +793,9 @@ class Quadcopter3DGates(_Base):
         cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
         K, n, dev = int(num_steps), self.num_envs, self.device
         if out is None:
-            out = (torch.empty((K, n, self.state_len), dtype=torch.float32, device=dev),
-                   torch.empty((K, n, 4), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.float32, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev),
-                   torch.empty((K, n), dtype=torch.uint8, device=dev))
+            out = rollout_outputs(K, n, self.state_len, dev)
         obs, act, logp, rew, done, trunc = out
-        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
-                                  dtype=np.float32).reshape(4)
+        ls = log_std_array(log_std)
         _lib.check(fn(self._h, policy._h, condition_bank._h, int(cond.shape[0]), int(envs_per_group), cond.ctypes.data_as(C.POINTER(C.c_int32)),
                       K, _f32p(ls), int(noise_seed), int(first_step), int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp),
                       _ptr(rew), _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
@@ -831,13 +810,7 @@ class Quadcopter3DGates(_Base):
         state set.  Group g then starts where an E-env handle with env_id_base + g E, configured with its condition, starts after
         `seed(s); reset_device()` -- the twin of rollout_policy_conditions_device's contract.  Returns the observation tensor, rows of
         group g as its condition observes them."""
-        e, n = int(envs_per_group), self.num_envs
-        cog = [int(c) for c in condition_of_group]
-        if e < 1 or len(cog) * e != n:
-            raise ValueError("len(condition_of_group) * envs_per_group must equal num_envs")
-        if any(c < 0 or c >= len(conditions) for c in cog):
-            raise ValueError("condition_of_group holds an index outside `conditions`")
-        s = self._seed if seed is None else int(seed)
+        e, cog, s = self._group_map(conditions, condition_of_group, envs_per_group, seed)
         state = None
 
         def reset(c):
@@ -877,8 +850,7 @@ class Quadcopter3DGates(_Base):
             out = torch.empty((max(K, 0), min(max(m, 0), n), r), dtype=torch.float32, device=dev)
         else:
             assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (K, m, r), (out.dtype, out.shape)
-        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
-                                  dtype=np.float32).reshape(4)
+        ls = log_std_array(log_std)
         _lib.check(fn(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step),
                       int(bool(deterministic)) | flags, m, _ptr(out), self._stream()))
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
@@ -915,8 +887,7 @@ class Quadcopter3DGates(_Base):
         else:
             assert terminal.is_cuda and terminal.dtype == torch.float32 and terminal.is_contiguous() and \
                 tuple(terminal.shape) == (m, self.STATE_LEN), (terminal.dtype, terminal.shape)
-        ls = np.ascontiguousarray(log_std.detach().cpu().numpy() if isinstance(log_std, torch.Tensor) else log_std,
-                                  dtype=np.float32).reshape(4)
+        ls = log_std_array(log_std)
         _lib.check(fn(self._h, policy._h, K, _f32p(ls), int(noise_seed), int(first_step), int(bool(deterministic)) | flags,
                       int(trigger), w, m, _ptr(ring), _ptr(status), _ptr(terminal), self._stream()))
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
