@@ -53,7 +53,7 @@ extern "C" {
                              qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
                              qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
                              qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12),
-                             qr_blackbox_policy (round 13) */
+                             qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14) */
 
 enum {
     QR_OK = 0,
@@ -352,6 +352,37 @@ int qr_rollout_policy_conditions(qr_env* env, qr_policy* policy, qr_condition_ba
                                  int32_t num_steps, const float* log_std, uint64_t noise_seed, uint64_t first_step,
                                  int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev,
                                  float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                                 float* last_obs_dev, void* stream);
+
+/* Closed-loop rollout for a POPULATION of policies in one launch: qr_rollout_policy_conditions with the policy half of the group map
+ * read too and the sampling arguments per group, so that P learners of a seed or hyper-parameter sweep collect in one launch instead
+ * of P handles and P launches of a few workgroups each.  Group g in [0, num_groups) = envs [g E, (g + 1) E) of the handle, E =
+ * envs_per_group, flies slot policy_of_group[g] of `policies` under slot condition_of_group[g] of `conditions` (HOST int32 arrays of
+ * num_groups entries, any order, repeats allowed), sampling with log_std[g] (HOST float [num_groups][4]) and the action-noise key
+ * noise_seed[g] (HOST uint64 [num_groups]).  first_step and flags are launch-wide.  A 256-env workgroup stages the weight image of ITS
+ * slot and the table image of ITS condition; everything else is qr_rollout_policy_conditions': ORDINARY ENV IDS (reset stream and
+ * action noise keyed by env_id_base + i), the same rows, terminal-observation rows, last_obs and state write-back.
+ * CONTRACT: group g produces bit for bit (rows [t][g E, (g + 1) E) of every output, its terminal-observation rows, its last_obs rows
+ * and the env state afterwards) what an E-env handle produces under qr_rollout_policy with the weights of slot policy_of_group[g],
+ * log_std[g], noise_seed[g], the same first_step and flags, when that handle is configured with the values of condition
+ * condition_of_group[g] (as in qr_rollout_policy_conditions' contract), has env_id_base = this handle's + g E, the same seed, variant,
+ * gates_ahead, residual weights and dt, and starts from the same state.  COROLLARY: with one slot, one log_std and one seed in every
+ * group the call equals qr_rollout_policy_conditions with that slot's weights, bit for bit.
+ * The map and the per-group sampling values are validated / computed on the host (the values with the arithmetic of
+ * qr_rollout_policy) and copied to device arrays the handle owns under the rule of qr_evaluate_policy_grid: contents that differ from
+ * the previous call's are copied after a device synchronisation.
+ * Refused before anything is launched or copied (qr_last_error set, outputs and state untouched): everything
+ * qr_rollout_policy_conditions refuses; everything qr_evaluate_policy_grid refuses about its policy bank (QR_E_INVALID: NULL bank, bank
+ * obs_len != qr_obs_len(env), bank on another GPU, an index outside its capacity; QR_E_STATE: a referenced slot without weights);
+ * QR_E_INVALID: NULL policy_of_group, log_std or noise_seed; QR_E_STATE: a new map, log_std or noise_seed while `stream` is being
+ * captured.
+ * flags: QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS.  qr_last_step_many_ms() reports this launch too. */
+int qr_rollout_policy_population(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions,
+                                 int32_t num_groups, int32_t envs_per_group,
+                                 const int32_t* policy_of_group, const int32_t* condition_of_group,
+                                 int32_t num_steps, const float* log_std, const uint64_t* noise_seed,
+                                 uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev,
+                                 float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
                                  float* last_obs_dev, void* stream);
 
 /* Closed-loop FLIGHT RECORDER: the K steps of qr_rollout_policy (same policy forward, same action noise keyed by (noise_seed, global env id,

@@ -34,6 +34,27 @@ def log_std_array(log_std):
     return np.ascontiguousarray(_host(log_std), dtype=np.float32).reshape(4)
 
 
+def log_std_rows(log_stds, num_groups):
+    """log_std_array's twin for a population launch: `log_stds` (a [G][4] tensor or array, or a sequence of G entries log_std_array
+    takes) as the contiguous float32 [G, 4] host array the library reads, G = num_groups."""
+    g = int(num_groups)
+    if hasattr(log_stds, "detach") or isinstance(log_stds, np.ndarray):
+        rows = np.ascontiguousarray(_host(log_stds), dtype=np.float32)
+    else:
+        rows = np.stack([log_std_array(r) for r in log_stds]) if len(log_stds) else np.zeros((0, 4), np.float32)
+    if rows.shape != (g, 4):
+        raise ValueError("log_stds must hold one row of 4 values per group (%d groups)" % g)
+    return np.ascontiguousarray(rows)
+
+
+def noise_seed_array(noise_seeds, num_groups):
+    """One action-noise seed per group as the contiguous uint64 [G] host array the library reads."""
+    seeds = np.array([int(s) & (2 ** 64 - 1) for s in noise_seeds], dtype=np.uint64)
+    if seeds.shape != (int(num_groups),):
+        raise ValueError("noise_seeds must hold one seed per group (%d groups)" % int(num_groups))
+    return seeds
+
+
 def rollout_outputs(K, n, obs_len, device):
     """Fresh (obs[K,n,obs_len], actions[K,n,4], logp[K,n], reward[K,n], done[K,n] u8, trunc[K,n] u8) of a closed-loop rollout."""
     import torch

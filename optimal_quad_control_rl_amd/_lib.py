@@ -74,6 +74,8 @@ SIGNATURES = {
                                           _vp, _vp, _vp]),
     "qr_rollout_policy_conditions": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _f32p, C.c_uint64, C.c_uint64,
                                                C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qr_rollout_policy_population": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _f32p,
+                                               C.POINTER(C.c_uint64), C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qr_record_row_len": (C.c_int, [_vp]),
     "qr_record_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp]),
     "qr_blackbox_policy": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp,
@@ -124,7 +126,7 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_policy_bank_set", "qr_evaluate_policy_bank", "qr_condition_bank_create", "qr_condition_bank_destroy",
                     "qr_condition_bank_capacity", "qr_condition_bank_set", "qr_evaluate_policy_grid",
                     "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
-                    "q3_evaluate_policy_bank")   # added in rounds 5-13 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "q3_evaluate_policy_bank", "qr_rollout_policy_population")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

@@ -45,6 +45,10 @@ struct qr_env {
     int2* d_group_map = nullptr;
     int group_map_cap = 0;
     std::vector<int32_t> group_map_host;
+    // qr_rollout_policy_population: the device copy of the last per-group sampling table, [pop_table_cap] entries, and its host mirror
+    qr::PopulationEntry* d_pop_table = nullptr;
+    int pop_table_cap = 0;
+    std::vector<qr::PopulationEntry> pop_table_host;
 };
 
 // A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
@@ -241,6 +245,32 @@ int upload_group_map(qr_env* e, const std::vector<int32_t>& map, int num_groups,
     return QR_OK;
 }
 
+// The per-group sampling table of qr_rollout_policy_population, in a device array of the handle under the rule of upload_group_map:
+// an equal table (byte for byte; the pad is zero) is already there, another one is copied after a device synchronisation, which a
+// stream under capture does not allow.
+int upload_population_table(qr_env* e, const std::vector<qr::PopulationEntry>& table, hipStream_t st, const char* who) {
+    const size_t bytes = table.size() * sizeof(qr::PopulationEntry);
+    if (e->d_pop_table && table.size() == e->pop_table_host.size() && std::memcmp(table.data(), e->pop_table_host.data(), bytes) == 0)
+        return QR_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(QR_E_STATE, std::string(who) + ": a new sampling table (log_std, noise_seed per group) is uploaded after a device "
+                                                   "synchronisation, which a stream under capture does not allow; call once with these "
+                                                   "values outside the capture");
+    QR_HIP(hipDeviceSynchronize());
+    e->pop_table_host.clear();   // nothing valid on the device until the copy below has succeeded
+    if ((int)table.size() > e->pop_table_cap) {
+        if (e->d_pop_table) (void)hipFree(e->d_pop_table);
+        e->d_pop_table = nullptr;
+        e->pop_table_cap = 0;
+        QR_HIP(hipMalloc((void**)&e->d_pop_table, bytes));
+        e->pop_table_cap = (int)table.size();
+    }
+    QR_HIP(hipMemcpy(e->d_pop_table, table.data(), bytes, hipMemcpyHostToDevice));
+    e->pop_table_host = table;
+    return QR_OK;
+}
+
 // One launch on `st` inside the hipEvent bracket of want_events: QR_TIMED_LAUNCH(e, st, launcher call).  A failed launch reports the
 // call's text, as QR_HIP does.
 #define QR_TIMED_LAUNCH(e, st, expr) timed_launch(e, st, #expr, [&] { return (expr); })
@@ -339,6 +369,7 @@ int qr_destroy(qr_env* e) {
     if (e->slab) (void)hipFree(e->slab);
     if (e->d_tables) (void)hipFree(e->d_tables);
     if (e->d_group_map) (void)hipFree(e->d_group_map);
+    if (e->d_pop_table) (void)hipFree(e->d_pop_table);
     delete e;
     return QR_OK;
 }
@@ -820,6 +851,76 @@ int qr_rollout_policy_conditions(qr_env* e, qr_policy* policy, qr_condition_bank
     if (int rc = upload_group_map(e, map, num_groups, st, who)) return rc;
     return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_cond(e->cfg.variant, e->P, A, conditions->d_slots, e->d_group_map, num_groups, envs_per_group, K,
                                        obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
+}
+
+// The refusals come first and in full: what qr_rollout_policy_conditions refuses, what qr_evaluate_policy_grid refuses about its policy
+// bank, and the NULL arrays; nothing is enqueued or copied before the last of them.  The per-group sampling entries are computed with
+// the statements of rollout_policy_args, so that entry g holds the bits qr_rollout_policy would use for log_std[g] and noise_seed[g].
+int qr_rollout_policy_population(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups, int32_t envs_per_group,
+                                 const int32_t* policy_of_group, const int32_t* condition_of_group, int32_t K, const float* log_std,
+                                 const uint64_t* noise_seed, uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev,
+                                 float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev,
+                                 void* stream) {
+    const char* who = "qr_rollout_policy_population";
+    const std::string w = std::string(who) + ": ";
+    if (int rc = check_ready(e)) return rc;
+    if (K < 1 || !policies || !log_std || !noise_seed) return fail(QR_E_INVALID, w + "bad argument");
+    if (int rc = check_term_rows(e, K, who)) return rc;
+    if (!obs_out_dev || !act_out_dev || !logp_out_dev || !rew_out_dev || !done_out_dev)
+        return fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, w + "pause / pause_if_collision envs are evaluation modes; use qr_step");
+    if (qr::bank_obs_len(policies) != e->L) return fail(QR_E_INVALID, w + "bank obs_len != env obs_len");
+    if (qr::bank_device(policies) != e->cfg.device) return fail(QR_E_INVALID, w + "policy bank on another GPU");
+    if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return fail(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
+    if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, w + "the two group maps are required");
+    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, w + "condition bank of another variant");
+    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, w + "condition bank on another GPU");
+    if (num_groups < 1) return fail(QR_E_INVALID, w + "num_groups must be >= 1");
+    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", who)) return rc;
+    const int pcap = qr::bank_capacity(policies);
+    for (int g = 0; g < num_groups; ++g) {
+        const int p = policy_of_group[g], c = condition_of_group[g];
+        if (p < 0 || p >= pcap) return fail(QR_E_INVALID, w + "policy_of_group[" + std::to_string(g) + "] is outside the policy bank");
+        if (c < 0 || c >= conditions->capacity)
+            return fail(QR_E_INVALID, w + "condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
+    }
+    for (int g = 0; g < num_groups; ++g) {
+        if (!qr::bank_slot_set(policies, policy_of_group[g]))
+            return fail(QR_E_STATE, w + "slot " + std::to_string(policy_of_group[g]) + " of the policy bank has no weights");
+        if (!conditions->is_set[(size_t)condition_of_group[g]])
+            return fail(QR_E_STATE, w + "slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
+    }
+    qr::PolicyArgs A{};   // launch-wide: the step counter and the two flags; weights and sampling values are per group
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    A.step_lo = (uint32_t)first_step;
+    A.step_hi = (uint32_t)(first_step >> 32);
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    std::vector<int32_t> map(2 * (size_t)num_groups);
+    std::vector<qr::PopulationEntry> table((size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g) {
+        map[2 * (size_t)g + 0] = policy_of_group[g];
+        map[2 * (size_t)g + 1] = condition_of_group[g];
+        qr::PopulationEntry& t = table[(size_t)g];
+        std::memset(&t, 0, sizeof(t));
+        const float* ls = log_std + 4 * (size_t)g;
+        float sum_log_std = 0.0f;   // rollout_policy_args' statements, per group
+        for (int c = 0; c < 4; ++c) {
+            t.std[c] = expf(ls[c]);
+            sum_log_std += ls[c];
+        }
+        t.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
+        t.seed_lo = (uint32_t)noise_seed[g] ^ 0x9E3779B9u;         // the noise key's domain separation, as there
+        t.seed_hi = (uint32_t)(noise_seed[g] >> 32) ^ 0x85EBCA6Bu;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = upload_group_map(e, map, num_groups, st, who)) return rc;
+    if (int rc = upload_population_table(e, table, st, who)) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_population(e->cfg.variant, e->P, A, qr::bank_weights(policies), qr::bank_weights_lo(policies),
+                                       conditions->d_slots, e->d_group_map, e->d_pop_table, num_groups, envs_per_group, K, obs_out_dev,
+                                       act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
 int qr_record_row_len(const qr_env* e) { return e ? e->S + QR_RECORD_EXTRA : QR_E_INVALID; }

@@ -140,6 +140,21 @@ hipError_t launch_rollout_policy_cond(int variant, const Params& P, const Policy
                                       int envs_per_group, int K, float* obs, float* act, float* logp, float* rew, uint8_t* done,
                                       uint8_t* trunc, float* last_obs, hipStream_t st);
 
+// quadrace_rollout_population.hip: the closed-loop rollout for a population of policies (qr_rollout_policy_population): the workgroups of
+// group g fly policy map[g].x under condition map[g].y and sample with table[g]; A carries the launch-wide step counter, deterministic
+// and f32class only.  One entry = what rollout_policy_args computes for one (log_std, noise seed): 32 bytes, read by one scalar load.
+struct PopulationEntry {
+    float std[4];               // exp(log_std)
+    float logp_const;           // -sum(log_std) - 2*log(2*pi)
+    uint32_t seed_lo, seed_hi;  // Philox key of the action noise
+    uint32_t pad;
+};
+static_assert(sizeof(PopulationEntry) == 32, "PopulationEntry is the 32-byte device table entry");
+hipError_t launch_rollout_policy_population(int variant, const Params& P, const PolicyArgs& A, const half8* bank, const half8* bank_lo,
+                                            const float* conds, const int2* map, const PopulationEntry* table, int num_groups, int envs_per_group,
+                                            int K, float* obs, float* act, float* logp, float* rew, uint8_t* done, uint8_t* trunc, float* last_obs,
+                                            hipStream_t st);
+
 // quadrace_record.hip: the closed-loop flight recorder (qr_record_policy): one packed row per env-step, rows [K][rec_envs][S + 8]
 hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, float* rows, hipStream_t st);
 

@@ -1,0 +1,220 @@
+"""A population of PPO learners on ONE env handle, collecting in ONE launch (`qr_rollout_policy_population`,
+csrc/quadrace_rollout_population.hip).
+
+Per-seed outcomes of a training run are chaotic: the practical answer is to train several seeds or hyper-parameter
+settings and keep the best.  `evaluate_policies` / `rank_policies` rank a bank of policies in one launch; this module is the other
+half: P members share an env of P x E envs, member p owns envs [p E, (p + 1) E), and every round's collect phase is one kernel launch
+in which each 256-env workgroup stages ITS member's weights and samples with ITS member's log_std and noise seed.  A collect launch of
+E = 256 envs alone occupies one of the GPU's 256 CUs.
+
+Each member is an ordinary `ppo.PPO(fused_collect=True)` built on a thin view of the env (`_MemberEnv`): ppo.py is not changed and
+does not know it is one of many.  The kernel's contract (include/quadrace.h) makes member p bit-equal to a standalone PPO on an E-env
+handle with env_id_base + p E.  The P updates still run one after another, each through its member's own updater.
+
+Selection and mutation schedules are not here: `.members` are the learners, `.bank` holds their current actors for
+`evaluate_policies` / `rank_policies`, and `state_dict` / `load_state_dict` nest the members', so a user can write them."""
+import torch
+
+from ._closed_loop import group_size
+from .ppo import PPO
+
+
+class _MemberEnv:
+    """What ppo.PPO asks of its env, for envs [lo, hi) of the population's handle: num_envs, state_len, device, the member's slices of
+    the reset observation, of the state and of the terminal-observation buffer, and a rollout_policy_device that hands back the
+    member's slice of the shared launch copied into the member's own contiguous buffers."""
+
+    def __init__(self, owner, index):
+        self._owner, self._index = owner, index
+        self._lo, self._hi = index * owner.envs_per_member, (index + 1) * owner.envs_per_member
+        self.num_envs, self.state_len, self.device = owner.envs_per_member, owner.env.state_len, owner.env.device
+        self.VARIANT = owner.env.VARIANT
+        self._term = None
+
+    def reset_device(self):
+        """The member's rows of the observation of the population's one reset (PopulationPPO.__init__); not a reset of its own."""
+        return self._owner._obs0[self._lo:self._hi]
+
+    def set_terminal_obs_buffer(self, buf):
+        assert buf is None or (buf.dim() == 3 and tuple(buf.shape[1:]) == (self.num_envs, self.state_len))
+        self._term = buf
+
+    def rollout_policy_device(self, policy, num_steps, log_std, noise_seed=0, first_step=0, deterministic=False, out=None,
+                              precision="f16-operands"):
+        """The member's slice of the launch PopulationPPO.collect() made.  `policy` (the member's own MfmaPolicy) is not flown: the
+        launch read the member's bank slot, loaded from the same actor."""
+        launch = self._owner._launch
+        if launch is None or self._index in launch["taken"]:
+            raise RuntimeError("member %d has no collected rollout to take: call PopulationPPO.collect() first" % self._index)
+        if (int(num_steps), int(first_step), int(noise_seed), bool(deterministic), precision) != \
+                (launch["K"], launch["first_step"], launch["seeds"][self._index], False, launch["precision"]):
+            raise RuntimeError("member %d asks for another rollout than the population launched" % self._index)
+        launch["taken"].add(self._index)
+        lo, hi = self._lo, self._hi
+        parts = [t[:, lo:hi] for t in launch["out"][:6]]
+        if out is None:
+            out = tuple(p.contiguous() for p in parts)
+        else:
+            for dst, src in zip(out, parts):
+                dst.copy_(src)
+        if self._term is not None:
+            self._term.copy_(self._owner._term_obs[:, lo:hi])
+        return (*out, launch["out"][6][lo:hi].contiguous())
+
+    # checkpoints (ppo.PPO.state_dict / load_state_dict)
+    def get_state_tensors(self):
+        return tuple(None if t is None else t[self._lo:self._hi].contiguous() for t in self._owner.env.get_state_tensors())
+
+    def set_state_tensors(self, world=None, dist=None, target=None, steps=None, episode=None):
+        env = self._owner.env
+        full = list(env.get_state_tensors())
+        for k, part in enumerate((world, dist, target, steps, episode)):
+            if part is not None and full[k] is not None:
+                full[k][self._lo:self._hi] = torch.as_tensor(part).to(device=full[k].device, dtype=full[k].dtype)
+        env.set_state_tensors(*full)
+
+    def update_states(self):
+        self._owner._refresh_obs()
+
+    @property
+    def states_tensor(self):
+        return self._owner.env.states_tensor[self._lo:self._hi]
+
+
+class PopulationPPO:
+    """P = len(members) PPO learners on `env` (P * envs_per_member envs), one collect launch per round.
+
+    members: a list of dicts of per-member `ppo.PPO` keywords (seed, learning_rate, ent_coef, clip_range, target_kl, log_std_init, ...);
+    shared_hyper: `ppo.PPO` keywords every member gets (n_steps, batch_size, n_epochs, native_update, policy_forward, ...).  n_steps and
+    policy_forward must be the same for all: one launch has one K and one forward.  A member's `seed` seeds its network, its
+    minibatch permutations and its action noise, as in ppo.PPO.
+    conditions / condition_of_member: a list of conditions.Condition and, per member, the index of the one its envs fly under
+    (default: all under the first); without `conditions` the single condition is Condition.from_env(env).
+    The env is reset once here (condition_reset with `conditions`), which is every member's start."""
+
+    def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, **shared_hyper):
+        from .conditions import Condition, ConditionBank
+        from .policy import MfmaPolicyBank
+
+        members = [dict(m) for m in members]
+        if len(members) < 1:
+            raise ValueError("members must hold at least one dict of PPO keywords")
+        self.envs_per_member, slots = group_size(envs_per_member, env.num_envs, "envs_per_member", "member")
+        if slots != len(members):
+            raise ValueError("len(members) * envs_per_member must equal env.num_envs (%d * %d != %d)"
+                             % (len(members), self.envs_per_member, env.num_envs))
+        hyper = [{**shared_hyper, **m} for m in members]
+        for key, default in (("n_steps", 32), ("policy_forward", "torch")):
+            if len({h.get(key, default) for h in hyper}) != 1:
+                raise ValueError("%s is shared by the whole population (one launch has one K and one forward): give one value" % key)
+        if any(not h.get("fused_collect", True) for h in hyper):
+            raise ValueError("a population collects in the closed-loop kernel: fused_collect=False is not available")
+        if any(h.get("conditions") is not None for h in hyper):
+            raise ValueError("give `conditions` to PopulationPPO itself, with condition_of_member")
+        self.env, self.n_steps = env, int(hyper[0].get("n_steps", 32))
+        self.precision = "f32" if hyper[0].get("policy_forward", "torch") == "f32class" else "f16-operands"
+        if conditions is None:
+            if condition_of_member is not None:
+                raise ValueError("condition_of_member needs `conditions`")
+            self.conditions, self.condition_of_member = [Condition.from_env(env)], [0] * len(members)
+            self._obs0 = env.reset_device().clone()
+        else:
+            self.conditions = list(conditions)
+            self.condition_of_member = [0] * len(members) if condition_of_member is None else [int(c) for c in condition_of_member]
+            if len(self.condition_of_member) != len(members) or any(c < 0 or c >= len(self.conditions) for c in self.condition_of_member):
+                raise ValueError("condition_of_member must hold one index into `conditions` per member")
+            self._obs0 = env.condition_reset(self.conditions, self.condition_of_member, self.envs_per_member).clone()
+        self._cond_bank = ConditionBank(env.VARIANT, len(self.conditions), env.device.index)
+        for slot, c in enumerate(self.conditions):
+            self._cond_bank.set(slot, c)
+        self.bank = MfmaPolicyBank(env.state_len, len(members), env.device.index)
+        self._launch = None
+        self._out = None
+        self._views = [_MemberEnv(self, p) for p in range(len(members))]
+        self.members = [PPO(view, **{**h, "fused_collect": True}) for view, h in zip(self._views, hyper)]
+        # the launch writes terminal observations of all N envs into one buffer; the views hand each member its columns
+        self._term_obs = None
+        if any(v._term is not None for v in self._views):
+            self._term_obs = torch.zeros((self.n_steps, env.num_envs, env.state_len), dtype=torch.float32, device=env.device)
+        env.set_terminal_obs_buffer(self._term_obs)
+        self.load_bank()
+
+    # ---------------------------------------------------------------------------------------------------------------- rounds
+    def load_bank(self):
+        """Slot p of `.bank` <- member p's current actor: done by collect(); call it yourself before ranking after a train()."""
+        for p, m in enumerate(self.members):
+            self.bank.load_torch(p, m.policy.pi)
+        return self.bank
+
+    @torch.no_grad()
+    def collect(self):
+        """Load every member's actor into its bank slot and fly all members' n_steps in one launch.  The members take their slices in
+        train() (or through their own collect_fused())."""
+        steps = {int(m.noise_step) for m in self.members}
+        if len(steps) != 1:
+            raise RuntimeError("the members stand at different positions of their noise streams: they no longer share a launch")
+        self.load_bank()
+        env, K, P = self.env, self.n_steps, len(self.members)
+        if self._out is None:
+            from ._closed_loop import rollout_outputs
+
+            self._out = rollout_outputs(K, env.num_envs, env.state_len, env.device)
+        seeds = [int(m.noise_seed) for m in self.members]
+        log_stds = torch.stack([m.policy.log_std.detach() for m in self.members])
+        first_step = steps.pop()
+        out = env.rollout_policy_population_device(self.bank, list(range(P)), self._cond_bank, self.condition_of_member, self.envs_per_member,
+                                                   K, log_stds, seeds, first_step=first_step, out=self._out, precision=self.precision)
+        self._launch = dict(K=K, first_step=first_step, seeds=seeds, precision=self.precision, out=out, taken=set())
+        return self
+
+    def train(self):
+        """Each member in turn: its collect_fused() (takes its slice of the launch, evaluates its values) and its train()."""
+        if self._launch is None:
+            raise RuntimeError("call collect() before train()")
+        for m in self.members:
+            m.collect_fused()
+            m.train()
+        self._launch = None
+        return self
+
+    def learn(self, total_timesteps_per_member, callback=None):
+        """Rounds of collect() + train() until every member has seen `total_timesteps_per_member` env steps.  callback(self) after each
+        round; returning False stops."""
+        while self.members[0].num_timesteps < total_timesteps_per_member:
+            self.collect()
+            self.train()
+            if callback is not None and callback(self) is False:
+                break
+        return self
+
+    @property
+    def num_timesteps(self):
+        """env steps collected per member"""
+        return int(self.members[0].num_timesteps)
+
+    # ----------------------------------------------------------------------------------------------------------- checkpoints
+    def _refresh_obs(self):
+        self.env._observe_under(self.conditions, self.condition_of_member, self.envs_per_member)
+
+    def state_dict(self):
+        """The members' state_dicts (each with its rows of the env state) and their network parameters, nested."""
+        return dict(envs_per_member=int(self.envs_per_member), condition_of_member=list(self.condition_of_member),
+                    members=[dict(trainer=m.state_dict(), policy={k: v.detach().cpu().clone() for k, v in m.policy.state_dict().items()})
+                             for m in self.members])
+
+    def load_state_dict(self, sd):
+        if len(sd["members"]) != len(self.members) or int(sd["envs_per_member"]) != self.envs_per_member:
+            raise ValueError("the checkpoint holds another population shape")
+        if list(sd["condition_of_member"]) != list(self.condition_of_member):
+            raise ValueError("the checkpoint flies another condition map: construct the population with it")
+        for m, part in zip(self.members, sd["members"]):
+            m.policy.load_state_dict(part["policy"])
+            m.load_state_dict(part["trainer"])
+        self._launch = None
+        self.load_bank()
+        return self
+
+    def close(self):
+        self.env.set_terminal_obs_buffer(None)
+        self.bank.close()
+        self._cond_bank.close()

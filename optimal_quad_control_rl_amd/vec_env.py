@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._closed_loop import _f32p, _precision_flags, check_records, log_std_array, rollout_outputs
+from ._closed_loop import _f32p, _precision_flags, check_records, log_std_array, log_std_rows, noise_seed_array, rollout_outputs
 from ._lib import QR_VARIANT_E2E, QR_VARIANT_INDI
 
 try:  # the reference imports `gymnasium.spaces` (R:284) / `gym.spaces` (I:139); neither is required here
@@ -799,6 +799,34 @@ class Quadcopter3DGates(_Base):
         _lib.check(fn(self._h, policy._h, condition_bank._h, int(cond.shape[0]), int(envs_per_group), cond.ctypes.data_as(C.POINTER(C.c_int32)),
                       K, _f32p(ls), int(noise_seed), int(first_step), int(bool(deterministic)) | flags, _ptr(obs), _ptr(act), _ptr(logp),
                       _ptr(rew), _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
+        self._last_obs = self._obs
+        return obs, act, logp, rew, done, trunc, self._obs
+
+    def rollout_policy_population_device(self, bank, policy_of_group, condition_bank, condition_of_group, envs_per_group, num_steps, log_stds,
+                                         noise_seeds, first_step=0, deterministic=False, out=None, precision="f16-operands"):
+        """rollout_policy_conditions_device for a POPULATION of policies in ONE kernel (qr_rollout_policy_population): group g = envs
+        [g E, (g + 1) E), E = envs_per_group (a multiple of 256; len(policy_of_group) * E == num_envs), flies slot policy_of_group[g]
+        of `bank` (policy.MfmaPolicyBank) under slot condition_of_group[g] of `condition_bank` (conditions.ConditionBank), sampling
+        with log_stds[g] ([G][4]) and the action-noise seed noise_seeds[g] ([G]); first_step, deterministic and precision hold for the
+        whole launch.  Ordinary env ids: group g computes bit for bit what an E-env handle with env_id_base + g E, configured with its
+        condition, computes under rollout_policy_device with that slot's weights in an MfmaPolicy, its log_std and its seed.  Same
+        return tuple as rollout_policy_device; a registered terminal-observation buffer is honoured."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_rollout_policy_population")
+        pol = np.ascontiguousarray(policy_of_group, dtype=np.int32).reshape(-1)
+        cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
+        if pol.shape != cond.shape:
+            raise ValueError("policy_of_group and condition_of_group must have one entry per group each")
+        groups = int(pol.shape[0])
+        ls, seeds = log_std_rows(log_stds, groups), noise_seed_array(noise_seeds, groups)
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        if out is None:
+            out = rollout_outputs(K, n, self.state_len, dev)
+        obs, act, logp, rew, done, trunc = out
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, bank._h, condition_bank._h, groups, int(envs_per_group), pol.ctypes.data_as(i32p), cond.ctypes.data_as(i32p),
+                      K, _f32p(ls), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_step), int(bool(deterministic)) | flags, _ptr(obs),
+                      _ptr(act), _ptr(logp), _ptr(rew), _ptr(done), _ptr(trunc), _ptr(self._obs), self._stream()))
         self._last_obs = self._obs
         return obs, act, logp, rew, done, trunc, self._obs
 
