@@ -26,7 +26,10 @@ value error sum and the clipped count are exact.
 interleaved float32 chains, then x 1/B).  The value net is exact; the policy net's deltas start from the float32 dout and carry a bound
 propagated through |W|^T and the float32 accumulations.
 
-The `bug` argument models kernel bugs for the teeth tests (tests/test_exact_grad.py)."""
+The `bug` argument models kernel bugs for the teeth tests (tests/test_exact_grad.py).
+
+`edge_nets` / `make_edge_batch` (further down) put loss-layer deltas and ReLU masks at the edges of f16; `forward` and `deltas` state
+the kernel's rule there (EDGE_BUGS are its mis-models; tests/test_exact_edges.py, tests/test_gpu_operand_edges.py)."""
 import numpy as np
 
 import exact_net as E
@@ -41,6 +44,7 @@ C_NORM = float(np.float32(0.9189385332046727))
 CLIPS = (0.2, 50.0)
 VF_COEF, ENT_COEF = 0.5, 0.01
 BUGS = ("drop_row", "ragged_tail", "swap_k", "wrong_mask", "drop_bias", "biased_var", "scale_bm1", "ent_flip", "rtz", "bf16_trunc")
+EDGE_BUGS = ("neg_zero_active", "flush_delta", "no_sat_delta", "saturated_inactive")   # told apart on the edge batches only
 
 
 def make_grad_net(L, seed, out=4):
@@ -66,15 +70,20 @@ def make_grad_net(L, seed, out=4):
     return layers
 
 
-def forward(layers, x):
-    """[x|1, h1|1, h2|1, h3|1] (float64, exact) and the output [n, O]."""
+def forward(layers, x, pre=None):
+    """[x|1, h1|1, h2|1, h3|1] (float64: the f16 operands the kernel publishes -- sat_pack of the observations, relu_pack of the hidden
+    pre-activations, both the identity on the plain fixture -- with f16-rounded weights) and the output [n, O].  `pre`: a list that
+    receives the three hidden pre-activations."""
     acts = []
+    x = E.sat_pack(x)
     for k, (w, b) in enumerate(layers):
         xa = np.concatenate([x, np.ones((x.shape[0], 1))], axis=1)
         acts.append(xa)
-        x = xa @ np.concatenate([w, b[:, None]], axis=1).astype(np.float64).T
+        x = xa @ E.weights_f16(w, b).T
         if k < 3:
-            x = np.maximum(x, 0.0)
+            if pre is not None:
+                pre.append(x)
+            x = E.relu_pack(x)
     return acts, x
 
 
@@ -97,13 +106,15 @@ def _grid(x, q):
     return np.round(np.asarray(x) / q) * q
 
 
-def make_batch(L, B, seed, pi, vf, log_std, extra_rows=37, idx=None):
+def make_batch(L, B, seed, pi, vf, log_std, extra_rows=37, idx=None, obs_at=None, e_at=None):
     """Rows [B + extra_rows] and the minibatch idx [B] (a random subset in random order unless given).  Only the rows in idx are
     constructed for exactness; the others hold arbitrary data the kernel must not read."""
     rng = np.random.default_rng([int(L), int(B), int(seed), 202])
     rows = B + extra_rows if idx is None else len(idx) + extra_rows
     idx = rng.permutation(rows)[:B].astype(np.int32) if idx is None else np.asarray(idx, np.int32)
     obs = E.make_obs(rows, L, seed + 1000)
+    if obs_at is not None:                      # the edge batches: the observation / value error of minibatch POSITION p
+        obs[idx] = obs_at
     x = obs[idx].astype(np.float64)
     mean = forward(pi, x)[1]
     v = forward(vf, x)[1][:, 0]
@@ -133,6 +144,8 @@ def make_batch(L, B, seed, pi, vf, log_std, extra_rows=37, idx=None):
     old = rng.normal(size=rows).astype(np.float32) - 5.0
     old[idx] = (lp - np.log(ratio)).astype(np.float32)
     e = rng.integers(-8, 9, size=B) / 8.0
+    if e_at is not None:
+        e = np.asarray(e_at, np.float64)
     ret = rng.normal(size=rows).astype(np.float32)
     ret[idx] = (v - e).astype(np.float32)
     assert np.array_equal(v - ret[idx].astype(np.float64), e)
@@ -210,17 +223,27 @@ def _relu_mask(h):
 
 
 def _f16(x, bug):
-    return E.sat_pack(x, "rtz" if bug == "rtz" else "rne")
+    model = {"flush_delta": "flush_obs", "no_sat_delta": "no_sat"}.get(bug)
+    return E.sat_pack(x, "rtz" if bug == "rtz" else "rne", model)
 
 
 def deltas(acts, layers, dout, bug=None):
     """[d1, d2, d3, d4] (float64) of one net: d4 = sat_pack(dout), d_l = relu'(h_l) * sat_pack(W_(l+1)^T d_(l+1)) -- the kernel's masks
-    come from the published f16 activations (unit active iff h > 0; pre-activation exactly 0 -> inactive)."""
+    come from the published f16 activations: a unit is active iff its f16 activation is non-zero and positive.  A saturated unit
+    (h = 65504) is active; a pre-activation that is exactly 0, rounds to +0 (in (0, 2^-25]) or to -0 (in [-2^-25, 0)) is inactive."""
     O = layers[3][0].shape[0]
     d = [None, None, None, _f16(dout[:, :O], bug)]
+    pre = []
+    if bug == "neg_zero_active":
+        forward(layers, acts[0][:, :-1], pre)
     for l in (2, 1, 0):
         m = _relu_mask(acts[l + 1 if bug != "wrong_mask" or l != 2 else l])
-        d[l] = m * _f16(d[l + 1] @ layers[l + 1][0].astype(np.float64), bug)
+        if bug == "neg_zero_active":     # v_pk_max_f16(-0, +0) handing back -0: bits 0x8000, non-zero, the unit counts as active
+            m = np.maximum(m, ((pre[l] < 0) & (E.to_f16(pre[l]) == 0)).astype(np.float64))
+        if bug == "saturated_inactive":
+            m = m * (acts[l + 1][:, :-1] < E.F16_MAX)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d[l] = m * _f16(d[l + 1] @ E.weights_f16(*layers[l + 1])[:, :-1], bug)
     return d
 
 
@@ -335,6 +358,7 @@ def restate(batch, pi, vf, clip, partial="bf16", bug=None, return_sums=False):
         bound = np.zeros(want.size)
         bound[-8:-4] = b_ls
         bound[-4] = b_surr
+        bound[-3] = b_st[1]
         bound[-2] = b_kl
         out[f] = (want, bound)
     res = out[partial] if isinstance(partial, str) else out
@@ -360,8 +384,13 @@ def _stat_terms(q, clip, depth, bug=None):
     b_kl_row = r * q["eps_ratio"] + d_lr + 2 * U * (np.abs(r - 1.0) + np.abs(q["log_ratio"])) + U * np.abs(kl)
     b_kl = 2 * b_kl_row.sum() + _gamma(depth) * (np.abs(kl) + b_kl_row).sum()
     clipped = float((np.abs(r - 1.0) > float(np.float32(clip))).sum())
-    stats = np.array([surr.sum(), float((q["err"] ** 2).sum()), kl.sum(), clipped])
-    return g_ls, b_ls, stats, np.array([b_surr, 0.0, b_kl, 0.0])
+    sq = q["err"] ** 2
+    # exact in float32 on the plain fixture (|e| <= 1 on the 1/8 grid: every square a multiple of 2^-6, the sum far below 2^24 of them);
+    # with the edge errors (1e5 down to 2^-26) the squares and their partial sums round: u per square, gamma_depth over the sum
+    g = 2.0 ** float(E._low_exp(sq).min())
+    b_sq = 0.0 if float(sq.sum()) < 2.0 ** 24 * g else (U + _gamma(depth)) * float(sq.sum()) * (1 + 1e-3)
+    stats = np.array([surr.sum(), float(sq.sum()), kl.sum(), clipped])
+    return g_ls, b_ls, stats, np.array([b_surr, b_sq, b_kl, 0.0])
 
 
 def f32class_slices(B, k_slices=64):
@@ -464,15 +493,109 @@ def grad_exactness_margin(batch, pi, vf, clip):
     return worst
 
 
-def actor_critic(L, seed, log_std):
-    """An ActorCritic(L, 4) holding make_grad_net(L, seed) / make_grad_net(L, seed + 1, out=1) and the given log_std."""
+# ---- edge fixtures: loss-layer deltas and ReLU masks at the edges of f16 -------------------------------------------------------------------
+#
+# edge_nets(L): make_grad_net networks whose first hidden units are probes in the manner of tests/exact_net.py's edge net, driven by
+# q = obs[:, L-1] (cycling through EDGE_QS) and q2 = obs[:, L-2] (0 but for four rows: 1, 5/4, 3/2, 2):
+#   layer 1   0: Q = q + 4    1: R = relu(q2)    2: N1 = 2^-24 (1 - q)    3: S1 = 65519.996 q2    4: Z1 = q - 1/2
+#   layer 2   0, 1: Q, R carried    2: N2 = 2^-24 (5 - Q)    3: S2 = 65519.996 R    4: Z2 = Q - 9/2    5: 2^15 N1 + 1/4    6: 2^-14 S1    7: Z1
+#   layer 3   0, 1: carried    5 .. 7: carried    2: 2^15 N2 + 1/4    3: 2^-14 S2    4: Z2
+# N: pre-activation exactly 0 (q = 1), in (0, 2^-25] -> +0 (q = 3/4, 1/2), in (-2^-25, 0) -> -0 (q = 5/4), an f16 subnormal (q <= 0); it
+# is read with 2^15, so an inactive unit wrongly counted as active passes a delta of 2^15 d.  S: 65504 (q2 = 1) and beyond 65520
+# (q2 > 1: f16 inf, saturated): ACTIVE; it is read with 2^-14, so its delta is an f16 subnormal.  (Only four rows saturate: 65504 times
+# a generic delta over many rows would leave the 2^24 grid steps of an exact weight-gradient sum.  A pre-activation strictly between
+# 65504 and 65520 is left to the forward fixture.)  Z: exactly 0 at q = 1/2.  The probes are the only readers of columns L-2, L-1 and
+# of each other, and every probe of layer 3 feeds one output with +-1 (the value head reads Q, R, Z only, so that the all-zero
+# observation has an exactly known value: b4 is chosen to make it 0).
+# value errors e (dout = vf_coef 2 e = e) on the first minibatch positions, by kind; the other positions hold multiples of the kind's
+# step, so that deltas 40 bits apart never meet in one weight-gradient sum:
+EDGE_E = {"sat": ((65504.0, -65504.0, 7e4, -1e5), 8.0),                                   # +-65504 and beyond it (saturated)
+          "sub": ((2.0 ** -15, -3 * 2.0 ** -22, 2.0 ** -26, -2.0 ** -26, 2.0 ** -25, 3 * 2.0 ** -25), 2.0 ** -17),   # subnormal, vanishing, ties at 0
+          "tie": ((E.TIE_DN, E.TIE_UP, -E.TIE_UP, 0.0), 0.125)}
+N_PROBES = 8
+EDGE_Q2 = (1.0, 1.25, 1.5, 2.0)
+
+
+def edge_nets(L, seed=1):
+    T24, big = E.T24, E.W_BIG
+    nets_ = []
+    for out, sd in ((4, seed), (1, seed + 1)):
+        layers = [(w.copy(), b.copy()) for w, b in make_grad_net(L, sd, out)]
+        P = N_PROBES
+        (w1, b1), (w2, b2), (w3, b3), (w4, b4) = layers
+        w1[:, L - 2:] = 0.0
+        w1[:P], b1[:P] = 0.0, 0.0
+        for u, (col, w, b) in enumerate(((1, 1.0, 4.0), (2, 1.0, 0.0), (1, -T24, T24), (2, big, 0.0), (1, 1.0, -0.5))):
+            w1[u, L - col], b1[u] = w, b
+        for wk, bk in ((w2, b2), (w3, b3)):
+            wk[:, :P] = 0.0
+            wk[:P], bk[:P] = 0.0, 0.0
+        for u, (src, w, b) in enumerate(((0, 1.0, 0.0), (1, 1.0, 0.0), (0, -T24, 5 * T24), (1, big, 0.0), (0, 1.0, -4.5), (2, 2.0 ** 15, 0.25),
+                                         (3, 2.0 ** -14, 0.0), (4, 1.0, 0.0))):
+            w2[u, src], b2[u] = w, b
+        for u, (src, w) in enumerate(((0, 1.0), (1, 1.0), (2, 2.0 ** 15), (3, 2.0 ** -14), (4, 1.0), (5, 1.0), (6, 1.0), (7, 1.0))):
+            w3[u, src] = w
+        b3[2] = 0.25                                  # the readers of N stay active where N is 0
+        w4[:, :P] = 0.0
+        for u in range(P):
+            if out == 4 or u in (0, 1, 4, 7):
+                w4[u % out, u] = -1.0 if u & 1 else 1.0
+        if out == 1:
+            b4[0] = 0.0
+            b4[0] = -forward(layers, np.zeros((1, L)))[1][0, 0]
+            assert E.to_f16(b4[0]) == b4[0]
+        nets_.append(layers)
+    return nets_
+
+
+def make_edge_batch(L, B, seed, pi, vf, log_std, kind):
+    """make_batch with q = obs[:, L-1] cycling through tests/exact_net.py's EDGE_QS over the minibatch positions and the value errors
+    EDGE_E[kind] on the first positions, whose observation is all zero (value exactly 0: ret = -e is exact in float32 down to 2^-26;
+    kind "sat": q = 1 instead, any value on the 1/4 grid does), and q2 on the four positions after them."""
+    obs_at = E.make_obs(B, L, seed + 2000)
+    obs_at[:, L - 1] = [E.EDGE_QS[p % len(E.EDGE_QS)] for p in range(B)]
+    obs_at[:, L - 2] = 0.0
+    special, step = EDGE_E[kind]
+    n = len(special)
+    if kind == "sat":
+        obs_at[:n, L - 1] = 1.0     # N = 0 on these rows: a delta of 65504 never multiplies a subnormal activation (the matrix core's window)
+    else:
+        obs_at[:n] = 0.0
+    obs_at[n:n + 4, L - 2] = EDGE_Q2
+    e_at = np.random.default_rng([L, B, seed, 505]).integers(-8, 9, size=B) * step
+    e_at[:n] = special
+    return make_batch(L, B, seed, pi, vf, log_std, obs_at=obs_at, e_at=e_at)
+
+
+def edge_grad_exactness_margin(batch, pi, vf, clip):
+    """grad_exactness_margin with the grid found per output (tests/exact_net.py: dot_margin, which also keeps every term with an f16
+    subnormal operand inside the matrix core's window): forward products, delta products and per-workgroup weight-gradient sums."""
+    B = batch["B"]
+    q = loss_rows(batch, pi, vf, clip)
+    wg, wgs = position_workgroup(B)
+    worst = 0.0
+    for net, layers in enumerate((pi, vf)):
+        acts = q["acts"][net]
+        d = deltas(acts, layers, q["dout"][net])
+        for l in range(4):
+            wa = E.weights_f16(*layers[l])
+            worst = max(worst, E.dot_margin(acts[l], wa))
+            if l < 3:
+                worst = max(worst, E.dot_margin(d[l + 1], E.weights_f16(*layers[l + 1])[:, :-1].T))
+            for w in range(wgs):
+                worst = max(worst, E.dot_margin(d[l][wg == w].T, acts[l][wg == w].T))
+    return worst
+
+
+def actor_critic(L, seed, log_std, nets=None):
+    """An ActorCritic(L, 4) holding make_grad_net(L, seed) / make_grad_net(L, seed + 1, out=1) (or `nets`) and the given log_std."""
     import torch
 
     from optimal_quad_control_rl_amd.ppo import ActorCritic
 
     ac = ActorCritic(L, 4)
     with torch.no_grad():
-        for net, layers in ((ac.pi, make_grad_net(L, seed)), (ac.vf, make_grad_net(L, seed + 1, out=1))):
+        for net, layers in zip((ac.pi, ac.vf), nets or (make_grad_net(L, seed), make_grad_net(L, seed + 1, out=1))):
             lins = [m for m in net if isinstance(m, torch.nn.Linear)]
             for lin, (w, b) in zip(lins, layers):
                 lin.weight.copy_(torch.from_numpy(w))

@@ -14,6 +14,9 @@ saturated to +-65504, NaN -> 0 (sat_pack); weights and biases -> f16 RNE; exact 
 at 65504 (relu_pack / relu_pack2); the output layer stays in float32.  With the fixture its float64 result equals the kernel's float32
 result bit for bit, so the GPU tests compare with torch.equal.  The `rounding`, `drop_bias` and `obs_len_shift` arguments model kernel
 bugs for the fixture's own "teeth" tests (tests/test_exact_net.py).
+
+`make_edge_net` / `make_edge_obs` (further down) put operands at the edges of f16 -- saturation, NaN, subnormals, ties, the two zeros --
+and stay exact; the `model` argument holds the mis-models of those edges (tests/test_exact_edges.py, tests/test_gpu_operand_edges.py).
 """
 import numpy as np
 
@@ -60,44 +63,70 @@ def to_f16(x, rounding="rne"):
     return h.astype(np.float64)
 
 
-def sat_pack(x, rounding="rne"):
+MODELS = ("flush_obs", "flush_weights", "flush_hidden", "nan_neg", "no_sat")   # mis-models of the restatement (teeth, edge fixture)
+
+
+def _has(model, name):
+    """`model` is None, one name of MODELS or a tuple of them."""
+    return model is not None and (model == name or (not isinstance(model, str) and name in model))
+
+
+def _flush(h):
+    """f16 subnormals (already rounded to f16) -> 0 of the same sign."""
+    return np.where(np.abs(h) < F16_MIN_NORMAL, np.copysign(0.0, h), h)
+
+
+def sat_pack(x, rounding="rne", model=None):
     """sat_pack (quadrace_policy.hpp): f16 rounding, saturation to +-65504, NaN -> 0."""
     h = to_f16(x, rounding)
-    h = np.where(np.isnan(h), 0.0, h)
-    return np.clip(h, -F16_MAX, F16_MAX)
+    h = np.where(np.isnan(h), -F16_MAX if _has(model, "nan_neg") else 0.0, h)
+    if _has(model, "flush_obs"):
+        h = _flush(h)
+    return h if _has(model, "no_sat") else np.clip(h, -F16_MAX, F16_MAX)
 
 
-def relu_pack(x, rounding="rne"):
+def relu_pack(x, rounding="rne", model=None):
     """relu_pack / relu_pack2: f16 rounding, max with 0 (NaN -> 0), min with 65504."""
     h = to_f16(x, rounding)
     h = np.where(np.isnan(h), 0.0, h)
-    return np.minimum(np.maximum(h, 0.0), F16_MAX)
+    if _has(model, "flush_hidden"):
+        h = _flush(h)
+    h = np.maximum(h, 0.0)
+    return h if _has(model, "no_sat") else np.minimum(h, F16_MAX)
 
 
-def layer_terms(layers, obs, k, rounding="rne", drop_bias=False, obs_len_shift=0):
+def weights_f16(w, b, rounding="rne", model=None):
+    """[rows, K + 1] f16 weight matrix with the bias column last, as the three packers round it (RNE; subnormals kept)."""
+    wa = to_f16(np.concatenate([np.asarray(w, np.float64), np.asarray(b, np.float64)[:, None]], axis=1), rounding)
+    return _flush(wa) if _has(model, "flush_weights") else wa
+
+
+def layer_terms(layers, obs, k, rounding="rne", drop_bias=False, obs_len_shift=0, model=None):
     """(operand x [n, K], f16 weight matrix W [rows, K] with the bias column last) of layer k -- what the matrix core multiplies."""
-    x = sat_pack(np.asarray(obs, np.float64), rounding)
+    x = sat_pack(np.asarray(obs, np.float64), rounding, model)
     for j in range(k + 1):
         w, b = layers[j]
-        w16 = to_f16(np.asarray(w, np.float64), rounding)
-        b16 = np.zeros(len(b)) if (drop_bias and j == 0) else to_f16(np.asarray(b, np.float64), rounding)
+        wa = weights_f16(w, b, rounding, model)
+        if drop_bias and j == 0:
+            wa[:, -1] = 0.0
         if j == 0 and obs_len_shift:
             # a kernel instantiated for L - 1 on this image: input L - 1 is its constant-1 column, the real bias column is never read
             assert obs_len_shift == -1
             x = x.copy()
             x[:, -1] = 1.0
-            b16 = np.zeros(len(b))
+            wa[:, -1] = 0.0
         xa = np.concatenate([x, np.ones((x.shape[0], 1))], axis=1)
-        wa = np.concatenate([w16, b16[:, None]], axis=1)
         if j == k:
             return xa, wa
-        x = relu_pack(xa @ wa.T, rounding)   # exact in float64 (and in float32) for the fixture
+        with np.errstate(invalid="ignore", over="ignore"):
+            x = relu_pack(xa @ wa.T, rounding, model)   # exact in float64 (and in float32) for the fixtures
 
 
-def forward64(layers, obs, rounding="rne", drop_bias=False, obs_len_shift=0):
+def forward64(layers, obs, rounding="rne", drop_bias=False, obs_len_shift=0, model=None):
     """float64 restatement of the f16-operand forward: [n, out]."""
-    xa, wa = layer_terms(layers, obs, 3, rounding, drop_bias, obs_len_shift)
-    return xa @ wa.T
+    xa, wa = layer_terms(layers, obs, 3, rounding, drop_bias, obs_len_shift, model)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return xa @ wa.T
 
 
 def forward32_in_order(layers, obs, rng):
@@ -114,30 +143,219 @@ def forward32_in_order(layers, obs, rng):
     return x
 
 
-def exactness_margin(layers, obs):
-    """Per layer: (max over outputs of sum |terms| / (2^24 grid), whether every term is a multiple of the layer's grid).  A margin below
-    1 with all terms on the grid makes every partial sum in every order exactly representable in float32."""
+def _low_exp(a):
+    """Exponent of the lowest set bit of every float64 value (a large number for 0: zero terms divide by every power of two)."""
+    a = np.asarray(a, np.float64)
+    m, e = np.frexp(a)
+    mi = np.abs(m * 2.0 ** 53).astype(np.int64)
+    tz = np.log2(np.maximum(mi & -mi, 1).astype(np.float64)).astype(np.int64)
+    return np.where(a == 0, 4096, e.astype(np.int64) - 53 + tz)
+
+
+def _nominal(a):
+    """|a| as the matrix core aligns it: an f16 subnormal operand counts with the exponent of the smallest normal, 2^-14."""
+    a = np.abs(a)
+    return np.where((a > 0) & (a < F16_MIN_NORMAL), F16_MIN_NORMAL, a)
+
+
+def dot_margin(x, w):
+    """max over the outputs of x [n, K] @ w [rows, K]^T of max(sum |terms|, 2 max nominal |term|) / (2^24 g): see exactness_margin."""
+    ex, ew = _low_exp(x), _low_exp(w)
+    s = np.abs(x) @ np.abs(w).T
+    g = (ex[:, None, :] + ew[None, :, :]).min(axis=-1)
+    xn, wn = _nominal(x), _nominal(w)
+    nom = (xn[:, None, :] * wn[None, :, :]).max(axis=-1) if ((xn != np.abs(x)).any() or (wn != np.abs(w)).any()) else 0.0
+    top = np.maximum(s, 2.0 * nom)
+    return float(np.where(top > 0, top * np.exp2(-24.0 - np.minimum(g, 1000)), 0.0).max())
+
+
+def exactness_margin(layers, obs, model=None):
+    """Per layer: (max over outputs of max(sum |terms|, 2 max NOMINAL |term|) / (2^24 g), whether every term is finite), g = the
+    largest power of two dividing every term of THAT output (operands after the kernel's roundings).  A margin below 1 makes every
+    partial sum in every order exactly representable in float32 -- and keeps every term inside the window the matrix core adds in:
+    v_mfma_f32_32x32x16_f16 aligns the products of one instruction and the accumulator at the largest exponent, where a product with
+    an f16 SUBNORMAL operand counts with that operand's nominal exponent -14, not with its value (measured on the MI355X: in
+    65504 x 3 2^-24 + 2^-24 x 1 in one K-step the second product is dropped, 25 bits below the first one's nominal 2^1 although only
+    18 below its value; see tests/test_gpu_operand_edges.py).  Only terms with a subnormal operand can exceed the sum that way.  g is found term by term for batches small enough to hold [n, rows, K]; for larger ones it
+    is bounded from below by (largest power of two dividing the row's inputs) x (... the unit's weights), and the unit's bias, and
+    the nominal term from above by (largest input) x (largest weight): a larger margin, never a smaller one."""
     out = []
     for k in range(4):
-        xa, wa = layer_terms(layers, obs, k)
-        grid = 2.0 ** -GRID[k]
-        prod_scale = np.abs(xa) @ np.abs(wa).T
-        # every term is a multiple of the grid: inputs of 2^-(GRID[k] - WEXP[k]) times weights of 2^-WEXP[k]; biases times 1
-        qx, qw, qb = xa[:, :-1] * 2.0 ** (GRID[k] - _SPEC[k][1]), wa[:, :-1] * 2.0 ** _SPEC[k][1], wa[:, -1] / grid
-        on_grid = all(bool(np.all(q == np.round(q))) for q in (qx, qw, qb))
-        out.append((float(prod_scale.max() / (2.0 ** 24 * grid)), on_grid))
+        xa, wa = layer_terms(layers, obs, k, model=model)
+        ex, ew = _low_exp(xa), _low_exp(wa)
+        s = np.abs(xa) @ np.abs(wa).T
+        xn, wn = _nominal(xa), _nominal(wa)
+        any_sub = bool((xn != np.abs(xa)).any() or (wn != np.abs(wa)).any())
+        if xa.shape[0] * wa.size <= 1 << 24:
+            g = (ex[:, None, :] + ew[None, :, :]).min(axis=-1)
+            nom = (xn[:, None, :] * wn[None, :, :]).max(axis=-1) if any_sub else 0.0
+        else:
+            g = np.minimum(ex[:, :-1].min(axis=1)[:, None] + ew[:, :-1].min(axis=1)[None, :], ew[:, -1][None, :])   # bias: times 1
+            nom = xn.max(axis=1)[:, None] * wn.max(axis=1)[None, :] if any_sub else 0.0
+        with np.errstate(invalid="ignore"):
+            top = np.maximum(s, 2.0 * nom)
+            margin = np.where(top > 0, top * np.exp2(-24.0 - np.minimum(g, 1000)), 0.0)
+        out.append((float(margin.max()), bool(np.isfinite(s).all())))
     return out
 
 
-def to_actor_critic(L, seed, log_std=(-0.3, 0.1, -0.5, 0.2)):
-    """An ActorCritic(L, 4) holding make_net(L, seed) as the policy and make_net(L, seed + 1, out=1) as the value net."""
+# ---- the edge fixture: operands at the edges of f16 --------------------------------------------------------------------------------------
+#
+# make_edge_net(L, out) is a make_net-style dense "background" network on units P .. 119 (observation columns 3 .. L-1) plus P = 22
+# sparse "probe" units per hidden layer.  Probes read only the three edge observation columns, the 1/4-grid column q = obs[:, L-1] and
+# other probes, and only probes and the output head read them: values on very fine or very coarse grids never meet the background in
+# one dot product, which keeps every partial sum exact in float32 (exactness_margin finds the grid per output).  Probe units, the same
+# index in every hidden layer ("carry" = the unit below times 1; a probe born in layer k is carried up to the head):
+#    0, 1   A+-: 2^-14 x, -3 2^-14 x of the saturation column (65504 -> 3.998, NaN -> bias alone)
+#    2, 3   B+-: +-2^15 x of the subnormal column (2^-24 -> 2^-9)
+#    4, 5   C+-: +-1 x of the tie column
+#    6, 7   Q = q + 4, R = relu(q)
+#    8 / 14 / 18   N: 2^-24 (1 - q), born in layer 1 / 2 / 3: exactly 0 at q = 1, +2^-26 and the tie 2^-25 (-> +0) at q = 3/4 and 1/2,
+#                  -2^-26 (-> -0) at q = 5/4, f16 subnormals for q <= 0; subnormal weight and bias; read above with weight 2^15
+#    9 / 15 / 19   S: 65519.996 q + (1 + 2^-11): 65505 (> 65504, rounds to it) at q = 1, > 65520 (f16 inf, saturated) beyond; read
+#                  above with weight 3 2^-14 (the head: the subnormal 2^-24)
+#   10 / 16 / 20   Z: q - 1/2: exactly 0 at q = 1/2
+#   11             W: weight 1023 2^-24, bias 2^-14 - 2^-26 (rounds up to the smallest normal); read above with 2^14
+#   12             T: weight 1 + 3 2^-11 (tie, up)
+#   13 / 17 / 21   U: weight 2^-25 (1 + 2^-20) (-> 2^-24), bias 3 2^-25 (tie -> 2^-23): subnormal, with ties at odd q; read with 2^15
+# The head reads every probe with +-2^-3, except N3 with 65519.996 (subnormal activation x the largest weight), S3 with 2^-15
+# (saturated activation x a subnormal weight), Z3 with (1 + 2^-11) 2^-3 (a tie), U3 with 2^15; row 3 of the 4-row head is a "tiny" row: the
+# subnormal activation U3 times 1 and the subnormal bias 1023 2^-24 alone.
+EDGE_P = 22
+EDGE_ROWS = 65
+C_SAT, C_SUB, C_TIE = 0, 1, 2
+T24 = 2.0 ** -24
+W_BIG = float(np.float32(65519.996))                 # 65520 - 2^-8: rounds DOWN to 65504
+SUB_UP = 2.0 ** -25 * (1 + 2.0 ** -20)               # just above the tie: rounds to 2^-24
+TIE_DN, TIE_UP = 1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11  # -> 1, -> 1 + 2^-9
+EDGE_QS = tuple(0.25 * k for k in range(-8, 8))      # q = -2 .. 1.75
+_EDGE_SPEC = ((3, 4, 64, 6), (7, 5, 512, 10), (3, 3, 1024, 10), (1, 5, 1024, 11))
+NAN_BITS = (0x7FC12345, 0xFFC54321)
+SAT_VALUES = (65504.0, -65504.0, W_BIG, -W_BIG, 65520.0, -65520.0, 7e4, -7e4, 1e30, -1e30, np.inf, -np.inf)
+SUB_VALUES = (T24, -T24, 2.0 ** -25, SUB_UP, 3 * 2.0 ** -25, 2.0 ** -15, 2.0 ** -14 - T24, 1023 * T24, 2.0 ** -14 - 2.0 ** -26, 0.0, -0.0)
+TIE_VALUES = (TIE_DN, TIE_UP, -TIE_DN, -TIE_UP)
+
+# unit -> ({source: weight}, bias); source = observation column (-1 = q) in layer 1, the probe unit of the layer below elsewhere
+def _born(n_src, r_src, b0):
+    """The probes N, S, Z, U born in one layer: N reads q (layer 1: bias 2^-24) or Q = q + 4 (bias 5 2^-24), the others q or R."""
+    return (({n_src: -T24}, b0 * T24), ({r_src: W_BIG}, TIE_DN), ({r_src: 1.0}, -0.5), ({r_src: SUB_UP}, 3 * 2.0 ** -25))
+
+
+_READ = {"N": 2.0 ** 15, "S": 3 * 2.0 ** -14, "Z": 1.0, "U": 2.0 ** 15}
+
+
+def _edge_probes():
+    n1, s1, z1, u1 = _born(-1, -1, 1)
+    l1 = {0: ({C_SAT: 2.0 ** -14}, 1.0), 1: ({C_SAT: -3 * 2.0 ** -14}, 0.5), 2: ({C_SUB: 2.0 ** 15}, 2.0 ** -6),
+          3: ({C_SUB: -2.0 ** 15}, 4.0), 4: ({C_TIE: 1.0}, 0.25), 5: ({C_TIE: -1.0}, 2.0), 6: ({-1: 1.0}, 4.0), 7: ({-1: 1.0}, 0.0),
+          8: n1, 9: s1, 10: z1, 11: ({-1: 1023 * T24}, 2.0 ** -14 - 2.0 ** -26), 12: ({-1: TIE_UP}, 0.25), 13: u1}
+    carry = lambda i, w=1.0: ({i: w}, 0.0)
+    n2, s2, z2, u2 = _born(6, 7, 5)
+    l2 = {i: carry(i, TIE_DN if i < 4 else 1.0) for i in range(14)}
+    l2.update({8: carry(8, _READ["N"]), 9: carry(9, _READ["S"]), 11: carry(11, 2.0 ** 14), 13: carry(13, _READ["U"]),
+               14: n2, 15: s2, 16: z2, 17: u2})
+    n3, s3, z3, u3 = _born(6, 7, 5)
+    l3 = {i: carry(i) for i in range(18)}
+    l3.update({4: carry(4, TIE_UP), 14: carry(14, _READ["N"]), 15: carry(15, _READ["S"]), 17: carry(17, _READ["U"]),
+               18: n3, 19: s3, 20: z3, 21: u3})
+    return l1, l2, l3
+
+
+F32CLASS_SKIP = (8, 11, 13, 14, 17, 18, 21)          # the N, W and U chains
+
+
+def make_edge_net(L, out=4, seed=5, f32class=False):
+    """The edge network (see above) as float32 arrays in make_net's layout.  f32class: the net for the two-piece forward
+    (x = X0 + X1, both f16): its operands have an ABSOLUTE floor of 2^-25 (half the f16 subnormal spacing), so the chains that
+    amplify differences below 2^-24 by 2^15 or 65504 (N, W, U) are outside float32-class accuracy by construction (measured: the N3
+    chain misses by 2^-25 x 65520 = 1.95e-3) -- the head does not read them."""
+    rng = np.random.default_rng([int(L), int(seed), int(out), 303])
+    P = EDGE_P
+    layers = []
+    for k, (wmax, wexp, bmax, bexp) in enumerate(_EDGE_SPEC):
+        fan_in = L if k == 0 else H
+        rows = out if k == 3 else H
+        w = np.ldexp(rng.integers(1, wmax + 1, size=(rows, fan_in)) * rng.choice([-1, 1], size=(rows, fan_in)), -wexp)
+        b = np.ldexp(rng.integers(1, bmax + 1, size=rows) * rng.choice([-1, 1], size=rows), -bexp)
+        w[:, :(3 if k == 0 else P)] = 0.0            # the background reads neither the edge columns nor a probe
+        if k < 3:
+            w[:P], b[:P] = 0.0, 0.0
+            for unit, (srcs, bias) in _edge_probes()[k].items():
+                for src, val in srcs.items():
+                    w[unit, src] = val
+                b[unit] = bias
+        else:
+            for r in range(rows):
+                sgn = -1.0 if r & 1 else 1.0
+                w[r, :P] = sgn * 0.125 * np.where(np.arange(P) & 1, -1.0, 1.0)   # x+ and x- probes must not cancel
+                w[r, 18], w[r, 19], w[r, 20], w[r, 21] = W_BIG, sgn * 2.0 ** -15, sgn * TIE_DN * 0.125, sgn * 2.0 ** 15
+            if rows == 4:
+                w[3], b[3] = 0.0, 1023 * T24
+                w[3, 21] = 1.0
+            if f32class:
+                w[:, list(F32CLASS_SKIP)] = 0.0
+        layers.append((w.astype(np.float32), b.astype(np.float32)))
+    return layers
+
+
+def make_edge_obs(L, seed=5):
+    """(obs [65, L] float32, {group: row indices}).  One edge value per row in its column (saturation / subnormal / tie), q = obs[:, L-1]
+    cycling through EDGE_QS, columns 3 .. L-2 random on the 1/4 grid, the edge columns 0 otherwise; rows 29 .. 64 hold no edge
+    observation: they are the rows of the hidden pre-activation edges (every q at least twice)."""
+    rng = np.random.default_rng([int(L), int(seed), 404])
+    obs = np.zeros((EDGE_ROWS, L), np.float32)
+    obs[:, 3:] = np.ldexp(rng.integers(-8, 9, size=(EDGE_ROWS, L - 3)), -OBS_EXP)
+    obs[:, L - 1] = [EDGE_QS[i % len(EDGE_QS)] for i in range(EDGE_ROWS)]
+    nan = np.array(NAN_BITS, np.uint32).view(np.float32)
+    vals = [(C_SAT, v) for v in SAT_VALUES] + [(C_SAT, v) for v in nan] + [(C_SUB, v) for v in SUB_VALUES] + [(C_TIE, v) for v in TIE_VALUES]
+    for i, (c, v) in enumerate(vals):
+        obs[i, c] = v
+    x = obs.astype(np.float64)
+    h = np.abs(to_f16(x))
+    q = x[:, L - 1]
+    groups = {"nan": np.isnan(x).any(axis=1), "inf_or_beyond": (np.abs(x) >= 65520.0).any(axis=1),
+              "subnormal_obs": ((h > 0) & (h < F16_MIN_NORMAL))[:, :3].any(axis=1), "hidden_beyond_65520": q >= 1.25,
+              "neg_zero": q == 1.25, "pos_zero": (q == 0.75) | (q == 0.5), "exact_zero": (q == 1.0) | (q == 0.5),
+              "hidden_subnormal": q <= 0.0, "plain": np.arange(EDGE_ROWS) >= len(vals)}
+    return obs, {k: np.nonzero(v)[0] for k, v in groups.items()}
+
+
+def split_obs_rows(L, seed=5):
+    """Rows for the f32-class forward (x = X0 + X1, two f16 pieces): |x| in [2^-12, 2^-3] in the subnormal column, where the low piece
+    X1 = f16(x - X0) is an f16 subnormal (that column's layer-1 weights are +-2^15: a dropped X1 moves a pre-activation by up to 2^-1);
+    the finite edge rows; and a 1e5 row (X0 saturates, X1 carries the rest)."""
+    obs, _ = make_edge_obs(L, seed)
+    x1 = np.zeros((20, L), np.float32)
+    x1[:, L - 1] = EDGE_QS[:10] * 2
+    x1[:, C_SUB] = [s * 2.0 ** -e * (1 + m * 2.0 ** -12) for s in (1, -1) for e, m in zip(range(3, 13), (1, 3, 5, 7, 9, 11, 1, 3, 5, 3))]
+    big = np.zeros((1, L), np.float32)
+    big[0, C_SAT] = 1e5
+    return np.concatenate([obs[np.isfinite(obs).all(axis=1)], x1, big]).astype(np.float32)
+
+
+SPLIT_MAX = 2 * F16_MAX      # split_pack: both pieces saturate at 65504
+
+
+def forward_plain64(layers, obs):
+    """float64 evaluation of the float32 parameters, no f16 anywhere (the reference of the f32-class forward).  Observations are
+    clipped to +-131008, split_pack's documented range."""
+    x = np.clip(np.asarray(obs, np.float64), -SPLIT_MAX, SPLIT_MAX)
+    for k, (w, b) in enumerate(layers):
+        x = x @ np.asarray(w, np.float64).T + np.asarray(b, np.float64)
+        if k < 3:
+            x = np.maximum(x, 0.0)
+    return x
+
+
+def to_actor_critic(L, seed, log_std=(-0.3, 0.1, -0.5, 0.2), nets=None):
+    """An ActorCritic(L, 4) holding make_net(L, seed) as the policy and make_net(L, seed + 1, out=1) as the value net (or `nets`)."""
     import torch
 
     from optimal_quad_control_rl_amd.ppo import ActorCritic
 
     ac = ActorCritic(L, 4)
     with torch.no_grad():
-        for net, layers in ((ac.pi, make_net(L, seed)), (ac.vf, make_net(L, seed + 1, out=1))):
+        for net, layers in ((ac.pi, make_net(L, seed)), (ac.vf, make_net(L, seed + 1, out=1))) if nets is None else zip((ac.pi, ac.vf), nets):
             lins = [m for m in net if isinstance(m, torch.nn.Linear)]
             for lin, (w, b) in zip(lins, layers):
                 lin.weight.copy_(torch.from_numpy(w))
