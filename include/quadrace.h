@@ -53,7 +53,8 @@ extern "C" {
                              qr_evaluate_policy (round 8), qr_record_policy / qr_record_row_len (round 9),
                              qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
                              qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12),
-                             qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14) */
+                             qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14),
+                             qr_ppo_population_create / _destroy / _epoch / _status (round 15) */
 
 enum {
     QR_OK = 0,
@@ -545,6 +546,47 @@ int qr_ppo_gae(qr_ppo* ppo, int32_t T, int32_t N, const float* rew_dev, const fl
 int qr_ppo_apply(qr_ppo* ppo, float* theta_dev, float* adam_m_dev, float* adam_v_dev, float* grad_dev, int32_t B,
                  float max_grad_norm, float lr, float beta1, float beta2, float eps, int32_t adam_step, float* stats_dev,
                  void* stream);
+
+/* ---- the update of a POPULATION of learners: one minibatch of all members in three launches -------------------------------------
+ * A population object BORROWS num_members existing qr_ppo handles (1..256; it does not own them: destroy it before them) that share
+ * obs_len, device and creation flags.  ALL per-member state stays in the member's handle -- operand images, stop flag, Adam step count,
+ * learning rate, shuffle seed and count, target_kl (qr_ppo_control), partial buffers -- so a member can be read and checkpointed
+ * (qr_ppo_adam_step, qr_ppo_shuffle_state, qr_ppo_status) and trained alone again (qr_ppo_epoch, qr_ppo_minibatch) afterwards; the
+ * object itself owns a device-resident table of the members' arguments and a scratch area.
+ * qr_ppo_population_epoch: for every member p what qr_ppo_epoch(members[p], args[p]..., B, num_minibatches, num_epochs, device_shuffle, ...,
+ * stream) does -- args is a HOST array [num_members] of the arguments qr_ppo_epoch takes per handle; stats_dev may be NULL, nothing
+ * else -- but one minibatch of ALL members is three launches (csrc/quadrace_ppo_population.hip): a gradient kernel over (workgroups, 2
+ * nets, members), a reduce kernel and a step kernel over (247, members).  No kernel waits for another workgroup: the kernel boundary
+ * between reduce and step replaces the single-member apply kernel's grid barrier, so the members' barrier counters are never touched
+ * (qr_ppo_status's fourth value stays what it was).  The per-epoch launches (permutation, advantage sums) are issued once per member.
+ * CONTRACT: afterwards every member is bit for bit where qr_ppo_epoch on that handle with that member's arguments leaves it: theta,
+ * both Adam moments, the operand images, the Adam step count, the status quadruple, the shuffle state, the content of perm_dev and
+ * stats_dev.  Same operations in the same order; the members do not influence each other (one member's early stop or non-finite
+ * gradient leaves the others untouched).
+ * Like qr_ppo_epoch the launches of a call are ONE linear captured hipGraph, cached while the argument set stays the same (every
+ * pointer and scalar of args except lr, B, the counts, device_shuffle, the members' shuffle seeds and target_kl); each member's lr reaches
+ * the device in the arguments of one small kernel, so a schedule does not force a re-capture.  Members created with
+ * QR_PPO_NO_EPOCH_GRAPH get plain launches.  A changed argument set is uploaded with a stream-ordered copy and ONE synchronisation of `stream`.
+ * Refused before anything is launched (QR_E_INVALID, qr_last_error set, all buffers untouched): create -- NULL members / out, a NULL or
+ * repeated handle, num_members outside 1..256, members that differ in obs_len, device or flags; epoch -- NULL pop / args, B < 64 or above
+ * any member's max_minibatch, num_minibatches or num_epochs outside qr_ppo_epoch's ranges, num_epochs > 1 without device_shuffle, a NULL
+ * member pointer other than stats_dev, a negative or NaN lr, and a `stream` that is being captured by the caller (the call uploads and
+ * synchronises, and launches a graph of its own: it cannot become nodes of another graph; no caller in this repository needs that).
+ * qr_ppo_population_status: out [num_members][4], row p as qr_ppo_status(members[p]); blocks once for all members.
+ * The f32-class gradient path and the data-parallel path have no population form. */
+typedef struct qr_ppo_population qr_ppo_population;
+typedef struct {   /* one member's arguments, the ones qr_ppo_epoch takes */
+    float *theta_dev, *adam_m_dev, *adam_v_dev;
+    const float *obs_dev, *act_dev, *old_logp_dev, *adv_dev, *ret_dev;
+    int32_t* perm_dev;
+    float clip, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, eps;
+    float* stats_dev;
+} qr_ppo_member_args;
+int qr_ppo_population_create(qr_ppo* const* members, int32_t num_members, qr_ppo_population** out);
+int qr_ppo_population_destroy(qr_ppo_population* pop);
+int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* args, int32_t B, int32_t num_minibatches,
+                            int32_t num_epochs, int32_t device_shuffle, void* stream);
+int qr_ppo_population_status(qr_ppo_population* pop, int32_t* out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

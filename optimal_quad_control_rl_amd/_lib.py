@@ -22,6 +22,12 @@ class QrConfig(C.Structure):
                 ("pause_if_collision", C.c_int32), ("reserved0", C.c_int32), ("env_id_base", C.c_uint64)]
 
 
+class QrPpoMemberArgs(C.Structure):
+    """qr_ppo_member_args of include/quadrace.h: one member's arguments of qr_ppo_population_epoch, the ones qr_ppo_epoch takes."""
+    _fields_ = ([(n, _vp) for n in ("theta_dev", "adam_m_dev", "adam_v_dev", "obs_dev", "act_dev", "old_logp_dev", "adv_dev", "ret_dev", "perm_dev")] +
+                [(n, C.c_float) for n in ("clip", "vf_coef", "ent_coef", "max_grad_norm", "lr", "beta1", "beta2", "eps")] + [("stats_dev", _vp)])
+
+
 # name -> (restype, argtypes); must list every symbol of include/quadrace.h and include/quad3d.h
 SIGNATURES = {
     "qr_abi_version": (C.c_int, []),
@@ -98,6 +104,10 @@ SIGNATURES = {
     "qr_ppo_adam_step": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32, _vp]),
     "qr_ppo_control": (C.c_int, [_vp, C.c_float, C.c_int32, _vp]),
     "qr_ppo_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
+    "qr_ppo_population_create": (C.c_int, [C.POINTER(_vp), C.c_int32, C.POINTER(_vp)]),
+    "qr_ppo_population_destroy": (C.c_int, [_vp]),
+    "qr_ppo_population_epoch": (C.c_int, [_vp, C.POINTER(QrPpoMemberArgs), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "qr_ppo_population_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
     # include/quad3d.h (predecessor environments of "3D quad.ipynb")
     "q3_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)]),
     "q3_destroy": (C.c_int, [_vp]),
@@ -126,7 +136,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_policy_bank_set", "qr_evaluate_policy_bank", "qr_condition_bank_create", "qr_condition_bank_destroy",
                     "qr_condition_bank_capacity", "qr_condition_bank_set", "qr_evaluate_policy_grid",
                     "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
-                    "q3_evaluate_policy_bank", "qr_rollout_policy_population")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "q3_evaluate_policy_bank", "qr_rollout_policy_population", "qr_ppo_population_create", "qr_ppo_population_destroy",
+                    "qr_ppo_population_epoch", "qr_ppo_population_status")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

@@ -7,9 +7,12 @@ half: P members share an env of P x E envs, member p owns envs [p E, (p + 1) E),
 in which each 256-env workgroup stages ITS member's weights and samples with ITS member's log_std and noise seed.  A collect launch of
 E = 256 envs alone occupies one of the GPU's 256 CUs.
 
-Each member is an ordinary `ppo.PPO(fused_collect=True)` built on a thin view of the env (`_MemberEnv`): ppo.py is not changed and
+Each member is an ordinary `ppo.PPO(fused_collect=True)` built on a thin view of the env (`_MemberEnv`): a member
 does not know it is one of many.  The kernel's contract (include/quadrace.h) makes member p bit-equal to a standalone PPO on an E-env
-handle with env_id_base + p E.  The P updates still run one after another, each through its member's own updater.
+handle with env_id_base + p E.  With `batched_update=False` (the default) the P updates still run one after another, each through its
+member's own updater; with `batched_update=True` they run as ONE launch sequence for all members (`qr_ppo_population_epoch`,
+csrc/quadrace_ppo_population.hip: three launches per minibatch of the whole population), and every member ends bit for bit where its own
+update would have left it.
 
 Selection and mutation schedules are not here: `.members` are the learners, `.bank` holds their current actors for
 `evaluate_policies` / `rank_policies`, and `state_dict` / `load_state_dict` nest the members', so a user can write them."""
@@ -90,9 +93,12 @@ class PopulationPPO:
     minibatch permutations and its action noise, as in ppo.PPO.
     conditions / condition_of_member: a list of conditions.Condition and, per member, the index of the one its envs fly under
     (default: all under the first); without `conditions` the single condition is Condition.from_env(env).
-    The env is reset once here (condition_reset with `conditions`), which is every member's start."""
+    The env is reset once here (condition_reset with `conditions`), which is every member's start.
+    batched_update: train() runs the members' updates through one `ppo.MfmaPpoPopulationUpdater` instead of one after another.  Needs
+    native_update=True for every member, the f16-operand kernels (no policy_forward="f32class", no update_precision="f32"), one batch_size and
+    one n_epochs for all, and a single process (no data-parallel process group): anything else is a ValueError."""
 
-    def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, **shared_hyper):
+    def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, batched_update=False, **shared_hyper):
         from .conditions import Condition, ConditionBank
         from .policy import MfmaPolicyBank
 
@@ -111,6 +117,19 @@ class PopulationPPO:
             raise ValueError("a population collects in the closed-loop kernel: fused_collect=False is not available")
         if any(h.get("conditions") is not None for h in hyper):
             raise ValueError("give `conditions` to PopulationPPO itself, with condition_of_member")
+        self.batched_update = bool(batched_update)
+        if self.batched_update:
+            from .ppo import MfmaPpoUpdater
+
+            if any(not h.get("native_update", False) for h in hyper):
+                raise ValueError("batched_update needs native_update=True for every member: it batches the matrix-core update")
+            if any(h.get("policy_forward", "torch") == "f32class" or h.get("update_precision", "f16-operands") == "f32" for h in hyper):
+                raise ValueError("batched_update has no f32-class form: policy_forward='f32class' / update_precision='f32' are not available")
+            for key in ("batch_size", "n_epochs"):
+                if len({h.get(key) for h in hyper}) != 1:
+                    raise ValueError("batched_update: %s is shared by the whole population (one launch sequence has one shape)" % key)
+            if MfmaPpoUpdater.data_parallel():
+                raise ValueError("batched_update is single-process: a data-parallel process group is initialised")
         self.env, self.n_steps = env, int(hyper[0].get("n_steps", 32))
         self.precision = "f32" if hyper[0].get("policy_forward", "torch") == "f32class" else "f16-operands"
         if conditions is None:
@@ -137,6 +156,11 @@ class PopulationPPO:
         if any(v._term is not None for v in self._views):
             self._term_obs = torch.zeros((self.n_steps, env.num_envs, env.state_len), dtype=torch.float32, device=env.device)
         env.set_terminal_obs_buffer(self._term_obs)
+        self._pop_updater = None
+        if self.batched_update:
+            from .ppo import MfmaPpoPopulationUpdater
+
+            self._pop_updater = MfmaPpoPopulationUpdater([m._updater for m in self.members])
         self.load_bank()
 
     # ---------------------------------------------------------------------------------------------------------------- rounds
@@ -168,14 +192,49 @@ class PopulationPPO:
         return self
 
     def train(self):
-        """Each member in turn: its collect_fused() (takes its slice of the launch, evaluates its values) and its train()."""
+        """Each member in turn: its collect_fused() (takes its slice of the launch, evaluates its values) and its train() -- or, with
+        batched_update, every member's part of train() before the launches, ONE update launch sequence for all, every member's part after."""
         if self._launch is None:
             raise RuntimeError("call collect() before train()")
-        for m in self.members:
-            m.collect_fused()
-            m.train()
+        if self.batched_update:
+            self._train_batched()
+        else:
+            for m in self.members:
+                m.collect_fused()
+                m.train()
         self._launch = None
         return self
+
+    def _train_batched(self):
+        batches, kl = [], []
+        for m in self.members:   # slice, values, GAE, sanitising, learning-rate schedule: exactly ppo.PPO.train's own steps
+            m.collect_fused()
+            obs, act, old_lp, adv, ret, rows = m._train_prepare()
+            lr, kl_stop, perm = m._native_begin(rows)
+            kl.append(kl_stop)
+            batches.append(dict(obs=obs, act=act, old_lp=old_lp.contiguous(), adv=adv.contiguous(), ret=ret.contiguous(), perm=perm, lr=lr,
+                                clip=m.clip, vf_coef=m.vf_coef, ent_coef=m.ent_coef, max_grad_norm=m.max_grad_norm))
+        m0 = self.members[0]
+        if not any(kl):   # no early stop anywhere: all epochs of all members are one graph launch
+            self._pop_updater.epoch(batches, m0.batch_size, num_epochs=m0.n_epochs, device_shuffle=True)
+        else:             # one launch per epoch and ONE status read for all members in between
+            ran, stopped_at = 0, [None] * len(self.members)
+            for _ in range(m0.n_epochs):
+                self._pop_updater.epoch(batches, m0.batch_size, num_epochs=1, device_shuffle=True)
+                ran += 1
+                for p, st in enumerate(self._pop_updater.status()):
+                    if st[0] and stopped_at[p] is None:
+                        stopped_at[p] = ran
+                if all(at is not None for at in stopped_at):
+                    break
+            # A member that stopped early saw nothing but no-ops afterwards, except that the later epochs still drew its permutations:
+            # its own train() would have left the loop, so its shuffle count is put back to where that leaves it.
+            for m, at in zip(self.members, stopped_at):
+                if at is not None and at < ran:
+                    seed, count = m._updater.shuffle_state()
+                    m._updater.set_shuffle(seed, count - (ran - at))
+        for m, kl_stop in zip(self.members, kl):
+            m._native_finish(kl_stop)
 
     def learn(self, total_timesteps_per_member, callback=None):
         """Rounds of collect() + train() until every member has seen `total_timesteps_per_member` env steps.  callback(self) after each
@@ -215,6 +274,8 @@ class PopulationPPO:
         return self
 
     def close(self):
+        if self._pop_updater is not None:
+            self._pop_updater.close()
         self.env.set_terminal_obs_buffer(None)
         self.bank.close()
         self._cond_bank.close()

@@ -281,6 +281,76 @@ class MfmaPpoUpdater:
         self._lib.check(self._L.qr_ppo_shuffle_state(self._h, st, 1, self._stream()))
 
 
+class MfmaPpoPopulationUpdater:
+    """The updates of several `MfmaPpoUpdater`s in one launch sequence (`qr_ppo_population_*`, csrc/quadrace_ppo_population.hip): one
+    minibatch of ALL members is three launches.  The members' handles are borrowed: every member keeps its own state and can be used
+    alone again; after `epoch` each is bit for bit where its own `epoch` with the same arguments would have left it."""
+
+    def __init__(self, updaters):
+        updaters = list(updaters)
+        if not 1 <= len(updaters) <= 256:
+            raise ValueError("a population update takes 1..256 updaters")
+        if any(not isinstance(u, MfmaPpoUpdater) for u in updaters):
+            raise ValueError("a population update is built from MfmaPpoUpdater objects")
+        if any(u.precision == "f32" for u in updaters):
+            raise ValueError("the f32-class gradient path has no population form: precision must be 'f16-operands'")
+        if len({id(u) for u in updaters}) != len(updaters):
+            raise ValueError("an updater is listed twice")
+        if MfmaPpoUpdater.data_parallel():
+            raise ValueError("the data-parallel update has no population form")
+        self.updaters = updaters
+        u0 = updaters[0]
+        self._C, self._lib, self._L, self.device = u0._C, u0._lib, u0._L, u0.device
+        self._h = None
+        C = self._C
+        handles = (C.c_void_p * len(updaters))(*[u._h.value for u in updaters])
+        h = C.c_void_p()
+        self._lib.check(self._lib.require(self._L, "qr_ppo_population_create")(handles, len(updaters), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._L.qr_ppo_population_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def epoch(self, batches, B, num_epochs=1, device_shuffle=False):
+        """batches: per member a dict with the tensors obs, act, old_lp, adv, ret, perm and the scalars lr, clip, vf_coef, ent_coef,
+        max_grad_norm -- what `MfmaPpoUpdater.epoch` takes.  Every member's perm holds num_minibatches * B rows, the same count for all."""
+        if len(batches) != len(self.updaters):
+            raise ValueError("one dict of arguments per member")
+        rows = {int(b["perm"].numel()) for b in batches}
+        if len(rows) != 1 or rows.copy().pop() % int(B) != 0:
+            raise ValueError("every member's perm must hold the same whole number of minibatches of B rows")
+        args = (self._lib.QrPpoMemberArgs * len(batches))()
+        for a, b, u in zip(args, batches, self.updaters):
+            u._check(b["obs"], b["act"], b["old_lp"], b["adv"], b["ret"], b["perm"])
+            a.theta_dev, a.adam_m_dev, a.adam_v_dev = u.theta.data_ptr(), u.m.data_ptr(), u.v.data_ptr()
+            a.obs_dev, a.act_dev, a.old_logp_dev = b["obs"].data_ptr(), b["act"].data_ptr(), b["old_lp"].data_ptr()
+            a.adv_dev, a.ret_dev, a.perm_dev = b["adv"].data_ptr(), b["ret"].data_ptr(), b["perm"].data_ptr()
+            a.clip, a.vf_coef, a.ent_coef = b.get("clip", 0.2), b.get("vf_coef", 0.5), b.get("ent_coef", 0.0)
+            a.max_grad_norm, a.lr = b.get("max_grad_norm", 0.5), float(b["lr"])
+            a.beta1, a.beta2, a.eps = u.betas[0], u.betas[1], u.eps
+            a.stats_dev = u.stats.data_ptr()
+        self._lib.check(self._L.qr_ppo_population_epoch(self._h, args, int(B), rows.pop() // int(B), int(num_epochs), int(bool(device_shuffle)),
+                                                        self._stream()))
+
+    def status(self):
+        """Per member (stopped, optimiser steps taken, updates skipped for a non-finite gradient, barrier timeouts); synchronises once."""
+        n = len(self.updaters)
+        out = (self._C.c_int32 * (4 * n))()
+        self._lib.check(self._L.qr_ppo_population_status(self._h, out, self._stream()))
+        return [(bool(out[4 * p]), int(out[4 * p + 1]), int(out[4 * p + 2]), int(out[4 * p + 3])) for p in range(n)]
+
+
 class PPO:
     def __init__(self, env, n_steps=32, batch_size=None, n_epochs=5, gamma=0.999, gae_lambda=0.95, clip_range=0.2,
                  learning_rate=3e-4, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, net_arch=(120, 120, 120),
@@ -605,7 +675,9 @@ class PPO:
             self.stats["reward_per_step"] = f[4]
         return adv, ret
 
-    def train(self):
+    def _train_prepare(self):
+        """What train() does before the first update launch: buffer sanitising, GAE (and the pending episode statistics), the flat views of
+        the rollout buffers and this round's learning rate (in self.opt.param_groups) -> (obs, act, old_lp, adv, ret, rows)."""
         self._sanitise_buffers()
         adv, ret = self._gae_native() if self._updater is not None else self._gae()
         if self.stats["non_finite_rows"]:
@@ -615,14 +687,18 @@ class PPO:
         obs = self.buf_obs.view(B, -1)
         act = self.buf_act.view(B, 4)
         old_lp, adv, ret = self.buf_lp.view(B), adv.view(B), ret.view(B)
-        losses = []
         # learning rate: SB3's `learning_rate` may be a schedule (linear decay when total_timesteps_hint is given); on top of it the
         # target-KL guard below may have halved it
         frac = min(1.0, self.num_timesteps / float(self.total_hint)) if self.total_hint else 0.0
         for g in self.opt.param_groups:
             g["lr"] = self.lr0 * (1.0 - (1.0 - self.lr_final_frac) * frac) * getattr(self, "_kl_lr_scale", 1.0)
+        return obs, act, old_lp, adv, ret, B
+
+    def train(self):
+        obs, act, old_lp, adv, ret, B = self._train_prepare()
         if self.native_update:
             return self._train_native(obs, act, old_lp.contiguous(), adv.contiguous(), ret.contiguous(), B)
+        losses = []
         stop = False
         for _ in range(self.n_epochs):
             if stop:
@@ -671,7 +747,10 @@ class PPO:
             self._kl_first_trips = 0
             self.stats["kl_lr_halvings"] = self.stats.get("kl_lr_halvings", 0) + 1
 
-    def _train_native(self, obs, act, old_lp, adv, ret, B):
+    def _native_begin(self, B):
+        """What _train_native does before its launches: arms / clears the device-side early stop, zeroes the statistics, provides the
+        permutation buffer -> (lr, kl_stop, perm).  (PopulationPPO(batched_update=True) calls this and _native_finish around ONE
+        population launch for all members.)"""
         up = self._updater
         lr = self.opt.param_groups[0]["lr"]
         kl_stop = self.target_kl is not None and self.target_kl < 1e8
@@ -685,7 +764,11 @@ class PPO:
         # between gradient and apply keeps the launches on the stream.
         if getattr(self, "_perm_buf", None) is None or self._perm_buf.numel() != B:
             self._perm_buf = torch.empty(B, dtype=torch.int32, device=self.dev)
-        perm = self._perm_buf
+        return lr, kl_stop, self._perm_buf
+
+    def _train_native(self, obs, act, old_lp, adv, ret, B):
+        up = self._updater
+        lr, kl_stop, perm = self._native_begin(B)
         if not up.data_parallel() and up.precision != "f32":
             # the permutations are drawn on the device too (a keyed bijection per epoch, no sort); without the early stop ALL
             # epochs of this train() are one graph launch, with it one launch per epoch and one status read in between
@@ -707,6 +790,11 @@ class PPO:
                                  self.max_grad_norm)
                 if kl_stop and up.status()[0]:   # identical on every rank: the KL sum travels with the all-reduced gradient
                     break
+        self._native_finish(kl_stop)
+
+    def _native_finish(self, kl_stop):
+        """What _train_native does after its launches: status read, stats, the target-KL guard."""
+        up = self._updater
         stopped, applied, skipped, timeouts = up.status()
         assert timeouts == 0, "grid barrier of the update kernel timed out"
         st = up.stats.tolist()

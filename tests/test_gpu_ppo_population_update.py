@@ -1,0 +1,350 @@
+"""GPU: the population update (qr_ppo_population_epoch: ppo_population_grad / _reduce / _step kernels, csrc/quadrace_ppo_population.hip)
+against the single-member update it restates (qr_ppo_epoch, which the existing suite pins).  The twin of member p is a fresh qr_ppo
+handle with the same flags and the same initial state, driven by qr_ppo_epoch with the member's arguments; after every call member and
+twin must be EQUAL: theta, both Adam moments, the outputs of both networks on 64 rows through qr_ppo_forward (the operand images), the
+Adam step count, the status quadruple, the shuffle state, the permutation buffer and stats.  Same operations in the same order: no
+tolerance anywhere.
+
+Inputs: seeded N(0, 1) obs / act / adv / ret, old_logp from each member's own initial policy; the members differ in their initial
+parameters (torch.manual_seed(p)), lr, clip, ent_coef, vf_coef, max_grad_norm and shuffle seed."""
+import ctypes as C
+import math
+import statistics
+import time
+
+import pytest
+import torch
+
+from test_ppo_population_update_host import _stub_env, batched_update_refusals
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+LR = (3e-4, 1e-3, 0.0)
+CLIP = (0.2, 0.1, 0.3)
+ENT = (0.0, 0.01, 0.001)
+VF = (0.5, 0.25, 1.0)
+MGN = (0.5, 1e9, 0.05)
+PARTIAL_F32, NO_EPOCH_GRAPH = 1, 8
+
+
+class _Member:
+    """One qr_ppo handle (through MfmaPpoUpdater) with its rollout, permutation buffer and hyper-parameters."""
+
+    def __init__(self, p, L, rows, max_b, flags=0, data=None):
+        from optimal_quad_control_rl_amd.ppo import ActorCritic, MfmaPpoUpdater
+
+        torch.manual_seed(p)
+        self.p, self.policy = p, ActorCritic(L, 4).to(DEV)
+        self.up = MfmaPpoUpdater(self.policy, L, DEV, max_b, flags=flags)
+        self.up.set_shuffle(1000 + 17 * p)
+        if data is None:   # the twin shares the member's (read-only) rollout
+            g = torch.Generator(device="cpu").manual_seed(100 + p)
+            obs, act = torch.randn((rows, L), generator=g).to(DEV), torch.randn((rows, 4), generator=g).to(DEV)
+            adv, ret = torch.randn(rows, generator=g).to(DEV), torch.randn(rows, generator=g).to(DEV)
+            with torch.no_grad():
+                old_lp = self.policy.log_prob_from_mean(self.up.forward(0, obs), act).contiguous()
+            data = dict(obs=obs, act=act, old_lp=old_lp, adv=adv, ret=ret)
+        self.data = data
+        self.perm = torch.zeros(rows, dtype=torch.int32, device=DEV)
+        k = p % 3
+        self.hyper = dict(lr=LR[k], clip=CLIP[k], vf_coef=VF[k], ent_coef=ENT[k], max_grad_norm=MGN[k])
+
+    def batch(self):
+        return dict(self.data, perm=self.perm, **self.hyper)
+
+    def epoch_alone(self, B, num_epochs, device_shuffle):
+        d, h = self.data, self.hyper
+        self.up.epoch(d["obs"], d["act"], d["old_lp"], d["adv"], d["ret"], self.perm, B, h["lr"], h["clip"], h["vf_coef"], h["ent_coef"],
+                      h["max_grad_norm"], num_epochs=num_epochs, device_shuffle=device_shuffle)
+
+    def state(self):
+        up, probe = self.up, self.data["obs"][:64].contiguous()
+        return dict(theta=up.theta.clone(), m=up.m.clone(), v=up.v.clone(), pi=up.forward(0, probe), vf=up.forward(1, probe), adam_step=up.step,
+                    status=up.status(), shuffle=up.shuffle_state(), perm=self.perm.clone(), stats=up.stats.clone())
+
+    def close(self):
+        self.up.close()
+
+
+def _assert_equal(members, twins, where):
+    for m, t in zip(members, twins):
+        a, b = m.state(), t.state()
+        for key in a:
+            if torch.is_tensor(a[key]):
+                # bit for bit (NaN included: a member that met a non-finite gradient may carry NaN statistics, its twin the same bits)
+                same = torch.equal(a[key].view(torch.int32), b[key].view(torch.int32))
+                assert same, (where, "member %d" % m.p, key, int((a[key].view(torch.int32) != b[key].view(torch.int32)).sum()))
+            else:
+                assert a[key] == b[key], (where, "member %d" % m.p, key, a[key], b[key])
+
+
+def _population(L, rows, max_b, P, flags=0):
+    from optimal_quad_control_rl_amd.ppo import MfmaPpoPopulationUpdater
+
+    members = [_Member(p, L, rows, max_b, flags) for p in range(P)]
+    twins = [_Member(p, L, rows, max_b, flags, data=m.data) for p, m in enumerate(members)]
+    _assert_equal(members, twins, "initial state")
+    return members, twins, MfmaPpoPopulationUpdater([m.up for m in members])
+
+
+def _both(members, twins, pop, B, num_epochs, device_shuffle, where):
+    pop.epoch([m.batch() for m in members], B, num_epochs=num_epochs, device_shuffle=device_shuffle)
+    for t in twins:
+        t.epoch_alone(B, num_epochs, device_shuffle)
+    _assert_equal(members, twins, where)
+
+
+def _close(members, twins, pop):
+    pop.close()
+    for x in members + twins:
+        x.close()
+
+
+@pytest.mark.parametrize("L,B,M,P", [(24, 5000, 2, 3),      # the reference batch size: a partial last group, 40 workgroups per net
+                                     (17, 192, 3, 3),       # an odd group count: a half-empty last pair
+                                     (16, 64, 3, 3),        # one group, one workgroup per net
+                                     (24, 16448, 1, 2)])    # 129 pairs: the 128-workgroup cap and the pass loop
+def test_every_member_equals_its_twin(L, B, M, P):
+    members, twins, pop = _population(L, B * M, (B + 63) // 64 * 64, P)
+    before = [m.up.theta.clone() for m in members]
+    _both(members, twins, pop, B, 2, True, "first call")
+    for p, m in enumerate(members):
+        assert m.up.status() == (False, 2 * M, 0, 0) and m.up.step == 2 * M, (p, m.up.status())
+        assert m.up.shuffle_state() == (1000 + 17 * p, 2)
+        assert sorted(m.perm.tolist()) == list(range(B * M))                          # a permutation was drawn into the member's buffer
+        assert torch.equal(m.up.theta, before[p]) == (m.hyper["lr"] == 0.0), p       # a step was really taken (lr = 0 moves nothing)
+        assert bool((m.up.m != 0).any()) and float(m.up.stats[1]) > 0.0              # ... and the moments and statistics were written
+    assert not torch.equal(members[0].perm, members[1].perm)                         # every member under its own key
+    for x in members + twins:   # the replay: only the learning rate changes, which must reach the device without a re-capture
+        x.hyper["lr"] = x.hyper["lr"] * 0.5 + 1e-4
+    _both(members, twins, pop, B, 2, True, "second call (replay, changed lr)")
+    assert all(m.up.step == 4 * M for m in members)
+    _close(members, twins, pop)
+
+
+def test_early_stop_of_one_member_only():
+    L, B, M = 24, 192, 3
+    members, twins, pop = _population(L, B * M, 192, 3)
+    for x in (members[1], twins[1]):
+        x.up.control(target_kl=1e-6)
+        x.hyper["lr"] = 1e-2
+    _both(members, twins, pop, B, 2, True, "early stop")
+    stopped, applied, skipped, timeouts = members[1].up.status()
+    assert stopped and applied <= 1 and skipped == 0 and timeouts == 0
+    for p in (0, 2):
+        assert members[p].up.status() == (False, 2 * M, 0, 0), p
+    # the stopped member's statistics stopped with it: a second call adds nothing to them and moves nothing
+    frozen = members[1].state()
+    _both(members, twins, pop, B, 1, True, "a call after the stop")
+    after = members[1].state()
+    for key in ("theta", "m", "v", "stats"):
+        assert torch.equal(frozen[key], after[key]), key
+    assert after["status"] == frozen["status"] and after["adam_step"] == frozen["adam_step"]
+    _close(members, twins, pop)
+
+
+def test_a_non_finite_gradient_in_one_member_only():
+    L, B, M = 24, 192, 3
+    members, twins, pop = _population(L, B * M, 192, 3)
+    bad = dict(members[0].data, adv=members[0].data["adv"].clone())
+    bad["adv"][77] = math.inf
+    members[0].data = twins[0].data = bad
+    _both(members, twins, pop, B, 2, True, "non-finite gradient")
+    skipped = members[0].up.status()[2]
+    assert skipped >= 1 and skipped == twins[0].up.status()[2]
+    for p in (1, 2):
+        assert members[p].up.status() == (False, 2 * M, 0, 0), p
+    assert bool(torch.isfinite(members[0].up.theta).all())
+    _close(members, twins, pop)
+
+
+@pytest.mark.parametrize("P,flags", [(1, 0), (3, PARTIAL_F32), (3, NO_EPOCH_GRAPH)])
+def test_corollaries_one_member_f32_partials_plain_launches(P, flags):
+    L, B, M = 24, 320, 2
+    members, twins, pop = _population(L, B * M, 320, P, flags)
+    _both(members, twins, pop, B, 2, True, "first call")
+    _both(members, twins, pop, B, 1, True, "second call")
+    assert all(m.up.status() == (False, 3 * M, 0, 0) for m in members)
+    _close(members, twins, pop)
+
+
+def test_corollaries_caller_permutations_and_training_alone_afterwards():
+    L, B, M = 24, 320, 2
+    members, twins, pop = _population(L, B * M, 320, 3)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    for m, t in zip(members, twins):
+        perm = torch.randperm(B * M, generator=g).to(torch.int32).to(DEV)
+        m.perm.copy_(perm); t.perm.copy_(perm)
+    _both(members, twins, pop, B, 1, False, "device_shuffle = 0")
+    assert all(m.up.shuffle_state()[1] == 0 and m.up.status()[1] == M for m in members)     # nothing was shuffled, every step was taken
+    # a member trained alone after the population call continues like its twin; and the population picks it up again afterwards
+    for x in (members[1], twins[1]):
+        x.epoch_alone(B, 2, True)
+    _assert_equal(members, twins, "member 1 alone")
+    _both(members, twins, pop, B, 1, True, "population again")
+    _close(members, twins, pop)
+
+
+def test_refusals_launch_nothing():
+    from optimal_quad_control_rl_amd import _lib
+
+    L_, B, M = 24, 192, 2
+    members, twins, pop = _population(L_, B * M, 256, 3)
+    lib = members[0].up._L
+    odd_len = _Member(7, 17, B * M, 256)
+    odd_flags = _Member(8, L_, B * M, 256, flags=PARTIAL_F32)
+    before = [m.state() for m in members]
+
+    def refused(rc, what):
+        assert rc == _lib.QR_E_INVALID, (what, rc)
+        assert len(lib.qr_last_error()) > 0, what
+        torch.cuda.synchronize()
+        for m, s in zip(members, before):
+            now = m.state()
+            for key in ("theta", "m", "v"):
+                assert torch.equal(now[key], s[key]), (what, key)
+            assert now["status"] == s["status"] and now["shuffle"] == s["shuffle"] and now["adam_step"] == s["adam_step"], what
+
+    def create(handles, n=None):
+        arr = (C.c_void_p * max(1, len(handles)))(*handles)
+        out = C.c_void_p(0xDEAD)
+        rc = lib.qr_ppo_population_create(arr, len(handles) if n is None else n, C.byref(out))
+        assert rc != _lib.QR_OK and not out.value, "a refused create hands out no object"
+        return rc
+
+    h = [m.up._h.value for m in members]
+    refused(create([h[0], None, h[2]]), "NULL handle")
+    refused(create([h[0], h[1], h[0]]), "repeated handle")
+    refused(create(h, 0), "num_members 0")
+    refused(create(h, 257), "num_members 257")
+    refused(create([h[0], odd_len.up._h.value]), "differing obs_len")
+    refused(create([h[0], odd_flags.up._h.value]), "differing flags")
+    refused(lib.qr_ppo_population_create(None, 3, C.byref(C.c_void_p())), "NULL members")
+
+    def epoch(B_=B, M_=M, E_=1, shuffle=1, edit=None):
+        args = (_lib.QrPpoMemberArgs * 3)()
+        for a, m in zip(args, members):
+            b, u = m.batch(), m.up
+            a.theta_dev, a.adam_m_dev, a.adam_v_dev = u.theta.data_ptr(), u.m.data_ptr(), u.v.data_ptr()
+            a.obs_dev, a.act_dev, a.old_logp_dev = b["obs"].data_ptr(), b["act"].data_ptr(), b["old_lp"].data_ptr()
+            a.adv_dev, a.ret_dev, a.perm_dev = b["adv"].data_ptr(), b["ret"].data_ptr(), b["perm"].data_ptr()
+            a.clip, a.vf_coef, a.ent_coef, a.max_grad_norm, a.lr = b["clip"], b["vf_coef"], b["ent_coef"], b["max_grad_norm"], b["lr"]
+            a.beta1, a.beta2, a.eps, a.stats_dev = 0.9, 0.999, 1e-5, u.stats.data_ptr()
+        if edit:
+            edit(args)
+        return lib.qr_ppo_population_epoch(pop._h, args, B_, M_, E_, shuffle, pop._stream())
+
+    refused(epoch(B_=63), "B < 64")
+    refused(epoch(B_=320), "B above max_minibatch")
+    refused(epoch(M_=0), "num_minibatches 0")
+    refused(epoch(M_=4097), "num_minibatches 4097")
+    refused(epoch(E_=0), "num_epochs 0")
+    refused(epoch(E_=65), "num_epochs 65")
+    refused(epoch(E_=2, shuffle=0), "two epochs without device_shuffle")
+    for field in ("theta_dev", "adam_v_dev", "obs_dev", "old_logp_dev", "ret_dev", "perm_dev"):
+        refused(epoch(edit=lambda args, f=field: setattr(args[2], f, None)), "NULL " + field)
+    refused(epoch(edit=lambda args: setattr(args[1], "lr", -1e-4)), "negative lr")
+    refused(epoch(edit=lambda args: setattr(args[0], "lr", math.nan)), "NaN lr")
+    refused(lib.qr_ppo_population_epoch(None, None, B, M, 1, 1, None), "NULL population")
+    refused(lib.qr_ppo_population_epoch(pop._h, None, B, M, 1, 1, None), "NULL args")
+    refused(lib.qr_ppo_population_status(pop._h, None, None), "NULL status output")
+    # ... and the valid call runs: stats_dev may be NULL
+    assert epoch(edit=lambda args: setattr(args[1], "stats_dev", None)) == _lib.QR_OK
+    torch.cuda.synchronize()
+    assert [s[1] for s in pop.status()] == [M, M, M] and float(members[1].up.stats.abs().sum()) == 0.0 and float(members[0].up.stats[1]) > 0.0
+    odd_len.close(); odd_flags.close()
+    _close(members, twins, pop)
+
+
+def _trainer_env(n):
+    from test_gpu_rollout_conditions import _conditions, _handle
+
+    # The scenario's own time limit (250 steps): no episode is cut inside the 48 steps flown below.  Deliberate -- the sums over FINISHED
+    # episodes behind stats["ep_rew_mean"] leave ppo_gae_kernel as one float atomic per wave, whose order across a member's four waves is
+    # not fixed (seen once with max_steps = 20, 256 episodes ending per round: 0.00977849867 against 0.00977849960, every tensor
+    # equal).  That kernel is not part of the update and is the same in both populations; the comparison below keeps every statistic.
+    return _handle("e2e", n, 1, _conditions("e2e")[0], seed=21)
+
+
+def test_population_ppo_batched_update_equals_sequential_updates():
+    from optimal_quad_control_rl_amd import PopulationPPO
+
+    E = 256
+    shared = dict(n_steps=16, batch_size=1024, n_epochs=2, native_update=True)
+    kw = [dict(seed=3, learning_rate=3e-4), dict(seed=4, learning_rate=1e-3, target_kl=1e-4), dict(seed=5, learning_rate=1e-3, ent_coef=0.01)]
+    envs = [_trainer_env(3 * E) for _ in range(4)]
+    seq = PopulationPPO(envs[0], kw, envs_per_member=E, **shared)
+    bat = PopulationPPO(envs[1], kw, envs_per_member=E, batched_update=True, **shared)
+
+    def same(x, y, where):
+        for p, (a, b) in enumerate(zip(x.members, y.members)):
+            for name in ("theta", "m", "v"):
+                s, t = getattr(a._updater, name), getattr(b._updater, name)
+                assert torch.equal(s, t), (where, p, name, int((s != t).sum()))
+            for name in ("buf_obs", "buf_act", "buf_lp", "buf_rew", "buf_val", "buf_term_val"):
+                assert torch.equal(getattr(a, name), getattr(b, name)), (where, p, name)
+            assert repr(sorted(a.stats.items())) == repr(sorted(b.stats.items())), (where, p, a.stats, b.stats)
+            assert a._updater.shuffle_state() == b._updater.shuffle_state() and a._updater.step == b._updater.step, (where, p)
+
+    for r in range(2):
+        for q in (seq, bat):
+            q.collect()
+            q.train()
+        same(seq, bat, "round %d" % r)
+        print("round %d: early_stop %s, updates %s, episodes %s" % (r, [m.stats.get("early_stop") for m in bat.members],
+                                                                    [m.stats["updates"] for m in bat.members], [m.stats.get("episodes", 0) for m in bat.members]))
+    assert all(m.stats["updates"] >= 1 for m in bat.members)
+    # a state_dict of one kind loads into the other and the next round is equal again
+    seq2 = PopulationPPO(envs[2], kw, envs_per_member=E, **shared).load_state_dict(bat.state_dict())
+    bat2 = PopulationPPO(envs[3], kw, envs_per_member=E, batched_update=True, **shared).load_state_dict(seq.state_dict())
+    for q in (seq, bat, seq2, bat2):
+        q.collect()
+        q.train()
+    same(seq, bat, "round 2")
+    same(seq, seq2, "batched checkpoint -> sequential population")
+    same(seq, bat2, "sequential checkpoint -> batched population")
+    for q in (seq, bat, seq2, bat2):
+        q.close()
+    for e in envs:
+        e.close()
+    batched_update_refusals(_stub_env)     # the four ValueError cases of the constructor, on an env that must not be touched
+
+
+def test_population_epoch_is_no_slower_than_the_members_epochs_one_after_another():
+    """P = 8, obs_len 24, 100 000 rows per member, B = 5000, M = 20, one epoch per call, device_shuffle.  A: one qr_ppo_population_epoch;
+    B: eight qr_ppo_epoch calls one after another.  Alternating on the same buffers, one warm-up pair, medians of 9, host clock around
+    a stream synchronise.  The feature exists to be faster than what it replaces: A <= B is a condition."""
+    L, B, M, P = 24, 5000, 20, 8
+    members = [_Member(p, L, B * M, 5056) for p in range(P)]
+    from optimal_quad_control_rl_amd.ppo import MfmaPpoPopulationUpdater
+
+    pop = MfmaPpoPopulationUpdater([m.up for m in members])
+    batches = [m.batch() for m in members]
+
+    def run_a():
+        pop.epoch(batches, B, num_epochs=1, device_shuffle=True)
+
+    def run_b():
+        for m in members:
+            m.epoch_alone(B, 1, True)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.current_stream(DEV).synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    timed(run_a); timed(run_b)
+    ta, tb = [], []
+    for _ in range(9):
+        ta.append(timed(run_a))
+        tb.append(timed(run_b))
+    a, b = statistics.median(ta), statistics.median(tb)
+    print("population epoch %.3f ms, eight member epochs %.3f ms, ratio %.3f (P = 8, 100 000 rows, B = 5000, M = 20)" % (a, b, a / b))
+    assert all(m.up.status()[3] == 0 for m in members)
+    pop.close()
+    for m in members:
+        m.close()
+    assert a <= b, (a, b)
