@@ -54,7 +54,8 @@ extern "C" {
                              qr_policy_bank_* / qr_evaluate_policy_bank (round 10),
                              qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12),
                              qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14),
-                             qr_ppo_population_create / _destroy / _epoch / _status (round 15) */
+                             qr_ppo_population_create / _destroy / _epoch / _status (round 15),
+                             qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16) */
 
 enum {
     QR_OK = 0,
@@ -587,6 +588,60 @@ int qr_ppo_population_destroy(qr_ppo_population* pop);
 int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* args, int32_t B, int32_t num_minibatches,
                             int32_t num_epochs, int32_t device_shuffle, void* stream);
 int qr_ppo_population_status(qr_ppo_population* pop, int32_t* out, void* stream);
+
+/* ---- the rest of a population round on the device: bank load, values, sanitising, GAE (csrc/quadrace_population_prepare.hip) ------------
+ * Everything between the collect launch (qr_rollout_policy_population) and qr_ppo_population_epoch, for all P members of `pop`, in a fixed
+ * number of launches whatever P is, with ONE blocking host read per round.
+ * qr_ppo_population_load_bank: ONE launch, grid (ceil(image / 256), P).  Slot first_slot + p of `bank` receives BOTH images of member p's
+ * actor -- the f16 image and the low pieces f16(w - f16(clamp w)), saturated to the f16 range, 0 for a NaN weight -- packed on the device
+ * from theta_dev[p] (a HOST array [P] of device pointers to the members' flat parameter vectors; the actor is the block at offset 0 of the
+ * layout qr_ppo_num_params defines).  CONTRACT: the slot is bit for bit what qr_policy_bank_set writes when given the same eight float
+ * arrays.  The slots are marked as set.  No host packing, no copy, no synchronisation: the launch is ordered on `stream` like any other.
+ * Refused before anything is launched (QR_E_INVALID): a NULL argument or a NULL entry of theta_dev, a bank whose obs_len or device
+ * differs from the population's, first_slot < 0 or first_slot + P > capacity.
+ * qr_policy_bank_read: one image of one slot to host memory (which: 0 = the f16 image, 1 = the low pieces; bytes = the image's size, 16
+ * bytes per half8 element).  Blocks.  QR_E_INVALID on an unset slot or a wrong byte count.
+ * qr_ppo_population_prepare: `sh` describes the outputs of the ONE collect launch, [K][N][...] as qr_rollout_policy_population wrote them;
+ * members is a HOST array [P]: member p owns columns [first_env, first_env + E) and its own contiguous [K][E][...] buffers.  Four launches
+ * with the member index in the grid -- values (the member's value image, the one qr_ppo_forward(members[p], 1, ...) uses, over its K E
+ * rollout rows, its E last_obs rows and, when both term_obs and term_val are given, its K E term_obs rows, read in place), gather +
+ * sanitise, GAE + episode state, report -- then one blocking copy of report_host [P][8]: non-finite rows, truncations, sum ep_ret d,
+ * sum ep_len d, sum ep_gates d, episodes, sum of the sanitised rewards, 0.  The counts are exact; the sums are double sums of the float
+ * per-step terms in a fixed order (lane, wave, workgroup, workgroups in index order): two identical calls report identical bits.
+ * CONTRACT: every member buffer ends bit for bit where the composition of the existing calls leaves it: the member's columns copied
+ * (done as 0 / 1 float), val = qr_ppo_forward(net 1) of its rows, a row with a non-finite observation, action, log-prob, reward or value
+ * written as +0.0 in obs, act, old_logp, rew and val, last_val and term_val = (trunc ? V(term_obs) : 0) with non-finite values replaced by
+ * 0, qr_ppo_gae on the sanitised buffers with the member's gamma and lam (term_val NULL: no time-limit bootstrap for this member), adv =
+ * ret = 0 on the zeroed rows, ep_ret / ep_len / ep_gates updated by qr_ppo_gae's expressions (all three or none).
+ * Plain launches on `stream`: no graph, no atomic, no flag, no workgroup that waits for another.  The member table is device-resident and
+ * uploaded with a stream-ordered copy when it changes; the bad-row mask and the workgroup partials live in scratch the population object
+ * owns, allocated on first use and regrown when (K, E) ask for more.
+ * Refused before anything is launched (QR_E_INVALID, qr_last_error set, all buffers untouched): NULL pop, sh, members or report_host; K < 1;
+ * E < 256, E not a multiple of 256, N not a multiple of E; a NULL shared array other than term_obs; a first_env that is not a multiple of E
+ * inside [0, N); two members with the same first_env; any NULL member pointer other than term_val, or the three ep_* pointers given only in
+ * part; term_val given without sh->term_obs; non-finite gamma or lam; and a `stream` that is being captured by the caller (the call
+ * allocates, uploads and blocks on its report: it cannot become nodes of another graph).
+ * The f32-class forward has no form here. */
+typedef struct {   /* the ONE collect launch's outputs, [K][N][...] as qr_rollout_policy_population wrote them */
+    int32_t K, N, E;                       /* E = envs per member, a multiple of 256 */
+    const float *obs, *act, *logp, *rew;   /* [K][N][L], [K][N][4], [K][N], [K][N] */
+    const uint8_t *done, *trunc;           /* [K][N] */
+    const float *last_obs;                 /* [N][L] */
+    const float *term_obs;                 /* [K][N][L] or NULL */
+} qr_ppo_prepare_shared;
+typedef struct {   /* member p: its envs are columns [first_env, first_env + E) of the shared arrays */
+    int32_t first_env;
+    float gamma, lam;
+    float *obs, *act, *old_logp, *rew, *done, *val;   /* the member's own contiguous [K][E][...] buffers (done as 0/1 float) */
+    float *term_val;                                   /* [K][E], or NULL: no time-limit bootstrap for this member */
+    float *last_val;                                   /* [E] */
+    float *adv, *ret;                                  /* [K][E] */
+    float *ep_ret, *ep_len, *ep_gates;                 /* [E] running episode state, updated in place (all three or none) */
+} qr_ppo_prepare_member;
+int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* theta_dev, qr_policy_bank* bank, int32_t first_slot, void* stream);
+int qr_policy_bank_read(const qr_policy_bank* bank, int32_t slot, int32_t which, void* out_host, size_t bytes);
+int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_shared* sh, const qr_ppo_prepare_member* members,
+                              double* report_host, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

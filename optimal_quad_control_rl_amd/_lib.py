@@ -28,6 +28,18 @@ class QrPpoMemberArgs(C.Structure):
                 [(n, C.c_float) for n in ("clip", "vf_coef", "ent_coef", "max_grad_norm", "lr", "beta1", "beta2", "eps")] + [("stats_dev", _vp)])
 
 
+class QrPpoPrepareShared(C.Structure):
+    """qr_ppo_prepare_shared of include/quadrace.h: the one collect launch's outputs, [K][N][...]."""
+    _fields_ = ([(n, C.c_int32) for n in ("K", "N", "E")] +
+                [(n, _vp) for n in ("obs", "act", "logp", "rew", "done", "trunc", "last_obs", "term_obs")])
+
+
+class QrPpoPrepareMember(C.Structure):
+    """qr_ppo_prepare_member of include/quadrace.h: one member's columns, hyper-parameters and own buffers for qr_ppo_population_prepare."""
+    _fields_ = ([("first_env", C.c_int32), ("gamma", C.c_float), ("lam", C.c_float)] +
+                [(n, _vp) for n in ("obs", "act", "old_logp", "rew", "done", "val", "term_val", "last_val", "adv", "ret", "ep_ret", "ep_len", "ep_gates")])
+
+
 # name -> (restype, argtypes); must list every symbol of include/quadrace.h and include/quad3d.h
 SIGNATURES = {
     "qr_abi_version": (C.c_int, []),
@@ -108,6 +120,9 @@ SIGNATURES = {
     "qr_ppo_population_destroy": (C.c_int, [_vp]),
     "qr_ppo_population_epoch": (C.c_int, [_vp, C.POINTER(QrPpoMemberArgs), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "qr_ppo_population_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
+    "qr_ppo_population_load_bank": (C.c_int, [_vp, C.POINTER(_vp), _vp, C.c_int32, _vp]),
+    "qr_policy_bank_read": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t]),
+    "qr_ppo_population_prepare": (C.c_int, [_vp, C.POINTER(QrPpoPrepareShared), C.POINTER(QrPpoPrepareMember), C.POINTER(C.c_double), _vp]),
     # include/quad3d.h (predecessor environments of "3D quad.ipynb")
     "q3_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)]),
     "q3_destroy": (C.c_int, [_vp]),
@@ -137,7 +152,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_condition_bank_capacity", "qr_condition_bank_set", "qr_evaluate_policy_grid",
                     "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
                     "q3_evaluate_policy_bank", "qr_rollout_policy_population", "qr_ppo_population_create", "qr_ppo_population_destroy",
-                    "qr_ppo_population_epoch", "qr_ppo_population_status")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_ppo_population_epoch", "qr_ppo_population_status", "qr_ppo_population_load_bank", "qr_policy_bank_read",
+                    "qr_ppo_population_prepare")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

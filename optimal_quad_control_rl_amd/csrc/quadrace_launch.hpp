@@ -177,5 +177,8 @@ int bank_device(const qr_policy_bank* b);
 int bank_capacity(const qr_policy_bank* b);
 int bank_first_unset(const qr_policy_bank* b, int num_policies);
 bool bank_slot_set(const qr_policy_bank* b, int slot);   // slot in [0, capacity) and filled (qr_evaluate_policy_grid)
+half8* bank_weights_mut(qr_policy_bank* b);              // for qr_ppo_population_load_bank: the slots are packed on the device ...
+half8* bank_weights_lo_mut(qr_policy_bank* b);
+void bank_mark_set(qr_policy_bank* b, int first_slot, int count);   // ... and marked as set on the host
 
 }  // namespace qr

@@ -130,6 +130,13 @@ int bank_first_unset(const qr_policy_bank* b, int num_policies) {   // first slo
     return -1;
 }
 bool bank_slot_set(const qr_policy_bank* b, int slot) { return b && slot >= 0 && slot < b->capacity && b->is_set[(size_t)slot]; }
+// mutable access for qr_ppo_population_load_bank (quadrace_population_prepare.hip), which packs slots on the device
+half8* bank_weights_mut(qr_policy_bank* b) { return b ? b->d_weights : nullptr; }
+half8* bank_weights_lo_mut(qr_policy_bank* b) { return b ? b->d_weights_lo : nullptr; }
+void bank_mark_set(qr_policy_bank* b, int first_slot, int count) {
+    for (int s = first_slot; s < first_slot + count && s < b->capacity; ++s)
+        if (s >= 0) b->is_set[(size_t)s] = 1;
+}
 }  // namespace qr
 
 namespace {
@@ -322,6 +329,18 @@ int qr_policy_bank_set(qr_policy_bank* b, int32_t slot, const float* w1, const f
         return pfail(QR_E_HIP, "qr_policy_bank_set: upload failed");
     }
     b->is_set[(size_t)slot] = 1;
+    return QR_OK;
+}
+
+int qr_policy_bank_read(const qr_policy_bank* b, int32_t slot, int32_t which, void* out_host, size_t bytes) {
+    if (!b || !out_host) return pfail(QR_E_INVALID, "qr_policy_bank_read: null argument");
+    if (slot < 0 || slot >= b->capacity || !b->is_set[(size_t)slot]) return pfail(QR_E_INVALID, "qr_policy_bank_read: slot must be a set slot in [0, capacity)");
+    if (which < 0 || which > 1) return pfail(QR_E_INVALID, "qr_policy_bank_read: which must be 0 (f16 image) or 1 (low pieces)");
+    if (bytes != b->total_half8 * 16) return pfail(QR_E_INVALID, "qr_policy_bank_read: bytes must be the size of one image");
+    if (hipSetDevice(b->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");   // a load launch may still write the slot
+    const qr::half8* src = (which == 0 ? b->d_weights : b->d_weights_lo) + (size_t)slot * b->total_half8;
+    if (hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return pfail(QR_E_HIP, "qr_policy_bank_read: download failed");
     return QR_OK;
 }
 

@@ -943,4 +943,12 @@ namespace qr {
 // perm_dev[k B .. (k + 1) B) (which also bumps the device-resident shuffle count) -- with the handle's host-side epoch cursor left disarmed
 int ppo_epoch_prologue(qr_ppo* p, const float* adv_dev, int32_t* perm_dev, int32_t B, int32_t num_minibatches, int32_t device_shuffle,
                        hipStream_t s);
+// quadrace_ppo_population.hip, for quadrace_population_prepare.hip: the borrowed members of a population object, and the slot in which it
+// keeps what qr_ppo_population_prepare allocates (released by qr_ppo_population_destroy through population_prepare_release)
+int population_size(const qr_ppo_population* pop);
+int population_obs_len(const qr_ppo_population* pop);
+int population_device(const qr_ppo_population* pop);
+qr_ppo* population_member(const qr_ppo_population* pop, int p);
+void*& population_prepare_slot(qr_ppo_population* pop);
+void population_prepare_release(void* state);   // quadrace_population_prepare.hip
 }  // namespace qr

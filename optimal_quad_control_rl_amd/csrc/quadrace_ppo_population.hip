@@ -484,7 +484,16 @@ struct qr_ppo_population {
     std::vector<unsigned long long> g_seeds;
     int g_B = 0, g_M = 0, g_E = 0, g_shuffle = 0;
     hipStream_t capture_stream = nullptr;
+    void* prepare = nullptr;        // what qr_ppo_population_prepare owns (quadrace_population_prepare.hip), released with the object
 };
+
+namespace qr {   // what quadrace_population_prepare.hip needs of the object
+int population_size(const qr_ppo_population* pop) { return pop ? (int)pop->members.size() : 0; }
+int population_obs_len(const qr_ppo_population* pop) { return pop ? pop->L : -1; }
+int population_device(const qr_ppo_population* pop) { return pop ? pop->device : -1; }
+qr_ppo* population_member(const qr_ppo_population* pop, int p) { return pop->members[(size_t)p]; }
+void*& population_prepare_slot(qr_ppo_population* pop) { return pop->prepare; }
+}  // namespace qr
 
 namespace {
 
@@ -578,6 +587,7 @@ int qr_ppo_population_destroy(qr_ppo_population* pop) {
     if (pop->capture_stream) (void)hipStreamDestroy(pop->capture_stream);
     (void)hipFree(pop->d_table);
     (void)hipFree(pop->d_scratch);
+    qr::population_prepare_release(pop->prepare);
     delete pop;
     return QR_OK;
 }

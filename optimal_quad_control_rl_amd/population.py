@@ -12,7 +12,10 @@ does not know it is one of many.  The kernel's contract (include/quadrace.h) mak
 handle with env_id_base + p E.  With `batched_update=False` (the default) the P updates still run one after another, each through its
 member's own updater; with `batched_update=True` they run as ONE launch sequence for all members (`qr_ppo_population_epoch`,
 csrc/quadrace_ppo_population.hip: three launches per minibatch of the whole population), and every member ends bit for bit where its own
-update would have left it.
+update would have left it.  `batched_prepare=True` (with `batched_update=True`) moves the rest of the round to the device as well: the
+bank is loaded in one launch from the members' parameter vectors, and the members' value forwards, slice copies, buffer sanitising and GAE
+run as four launches and ONE blocking read for the whole population (`qr_ppo_population_prepare`, csrc/quadrace_population_prepare.hip);
+`batched_prepare=False` (the default) is the path described above, unchanged.
 
 Selection and mutation schedules are not here: `.members` are the learners, `.bank` holds their current actors for
 `evaluate_policies` / `rank_policies`, and `state_dict` / `load_state_dict` nest the members', so a user can write them."""
@@ -96,9 +99,14 @@ class PopulationPPO:
     The env is reset once here (condition_reset with `conditions`), which is every member's start.
     batched_update: train() runs the members' updates through one `ppo.MfmaPpoPopulationUpdater` instead of one after another.  Needs
     native_update=True for every member, the f16-operand kernels (no policy_forward="f32class", no update_precision="f32"), one batch_size and
-    one n_epochs for all, and a single process (no data-parallel process group): anything else is a ValueError."""
+    one n_epochs for all, and a single process (no data-parallel process group): anything else is a ValueError.
+    batched_prepare: collect() fills the bank with ONE device launch (`MfmaPpoPopulationUpdater.load_bank`) and train() replaces the members'
+    collect_fused() + buffer sanitising + GAE by ONE `MfmaPpoPopulationUpdater.prepare` for all members; every tensor ends bit for bit where
+    the members' own steps leave it, and a member's own MfmaPolicy is no longer loaded.  Needs batched_update=True and the race envs (a
+    ValueError otherwise); truncation_bootstrap may differ between members (a member without it passes no term_val)."""
 
-    def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, batched_update=False, **shared_hyper):
+    def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, batched_update=False, batched_prepare=False,
+                 **shared_hyper):
         from .conditions import Condition, ConditionBank
         from .policy import MfmaPolicyBank
 
@@ -117,7 +125,12 @@ class PopulationPPO:
             raise ValueError("a population collects in the closed-loop kernel: fused_collect=False is not available")
         if any(h.get("conditions") is not None for h in hyper):
             raise ValueError("give `conditions` to PopulationPPO itself, with condition_of_member")
-        self.batched_update = bool(batched_update)
+        self.batched_update, self.batched_prepare = bool(batched_update), bool(batched_prepare)
+        if self.batched_prepare:
+            if not self.batched_update:
+                raise ValueError("batched_prepare needs batched_update=True: it prepares the buffers of the batched update")
+            if hasattr(env, "KIND") and hasattr(env, "trainer_state"):
+                raise ValueError("batched_prepare is built for the race envs: the predecessor envs keep the members' own prepare steps")
         if self.batched_update:
             from .ppo import MfmaPpoUpdater
 
@@ -166,6 +179,8 @@ class PopulationPPO:
     # ---------------------------------------------------------------------------------------------------------------- rounds
     def load_bank(self):
         """Slot p of `.bank` <- member p's current actor: done by collect(); call it yourself before ranking after a train()."""
+        if self.batched_prepare:   # one launch, packed on the device from the members' parameter vectors
+            return self._pop_updater.load_bank(self.bank, 0)
         for p, m in enumerate(self.members):
             self.bank.load_torch(p, m.policy.pi)
         return self.bank
@@ -205,11 +220,50 @@ class PopulationPPO:
         self._launch = None
         return self
 
+    def _prepare_batched(self):
+        """What every member's collect_fused() + _train_prepare() does, for all members at once: the host bookkeeping of each member, ONE
+        `prepare` (values, slices, sanitising, GAE, episode state on the device) and the statistics from its report -> per member what
+        _train_prepare returns."""
+        launch, K, E = self._launch, self.n_steps, self.envs_per_member
+        out, args = launch["out"], []
+        for p, m in enumerate(self.members):
+            if p in launch["taken"]:
+                raise RuntimeError("member %d has already taken its rollout of this launch" % p)
+            if (int(m.noise_step), int(m.noise_seed)) != (launch["first_step"], launch["seeds"][p]):
+                raise RuntimeError("member %d asks for another rollout than the population launched" % p)
+            launch["taken"].add(p)
+            m.noise_step += K
+            m.num_timesteps += K * E
+            if getattr(m, "_adv_ret", None) is None:   # persistent: the epoch graph's nodes address these buffers
+                m._adv_ret = (torch.empty_like(m.buf_rew), torch.empty_like(m.buf_rew))
+            if getattr(m, "_last_val_buf", None) is None:
+                m._last_val_buf = torch.empty(E, dtype=torch.float32, device=m.dev)
+            m.last_val = m._last_val_buf
+            args.append(dict(first_env=p * E, gamma=m.gamma, lam=m.lam, obs=m.buf_obs, act=m.buf_act, old_logp=m.buf_lp, rew=m.buf_rew,
+                             done=m.buf_done, val=m.buf_val, term_val=m.buf_term_val, last_val=m.last_val, adv=m._adv_ret[0], ret=m._adv_ret[1],
+                             ep_ret=m.ep_ret, ep_len=m.ep_len, ep_gates=m.ep_gates))
+        shared = dict(E=E, obs=out[0], act=out[1], logp=out[2], rew=out[3], done=out[4], trunc=out[5], last_obs=out[6], term_obs=self._term_obs)
+        views = []
+        for m, r in zip(self.members, self._pop_updater.prepare(shared, args)):
+            if m.truncation_bootstrap:
+                m.stats["truncations"] = int(r[1])
+            m.stats["non_finite_rows"] = int(r[0])
+            m._stats_pending = False
+            if r[5] > 0:
+                m.stats.update({"ep_rew_mean": r[2] / r[5], "ep_len_mean": r[3] / r[5], m._gates_key: r[4] / r[5], "episodes": r[5]})
+            m.stats["reward_per_step"] = r[6] / float(K * E)
+            views.append(m._train_views(*m._adv_ret))
+        return views
+
     def _train_batched(self):
         batches, kl = [], []
-        for m in self.members:   # slice, values, GAE, sanitising, learning-rate schedule: exactly ppo.PPO.train's own steps
-            m.collect_fused()
-            obs, act, old_lp, adv, ret, rows = m._train_prepare()
+        prepared = self._prepare_batched() if self.batched_prepare else None
+        for p, m in enumerate(self.members):   # slice, values, GAE, sanitising, learning-rate schedule: exactly ppo.PPO.train's own steps
+            if prepared is None:
+                m.collect_fused()
+                obs, act, old_lp, adv, ret, rows = m._train_prepare()
+            else:
+                obs, act, old_lp, adv, ret, rows = prepared[p]
             lr, kl_stop, perm = m._native_begin(rows)
             kl.append(kl_stop)
             batches.append(dict(obs=obs, act=act, old_lp=old_lp.contiguous(), adv=adv.contiguous(), ret=ret.contiguous(), perm=perm, lr=lr,

@@ -350,6 +350,56 @@ class MfmaPpoPopulationUpdater:
         self._lib.check(self._L.qr_ppo_population_status(self._h, out, self._stream()))
         return [(bool(out[4 * p]), int(out[4 * p + 1]), int(out[4 * p + 2]), int(out[4 * p + 3])) for p in range(n)]
 
+    def load_bank(self, bank, first_slot=0):
+        """Slots first_slot .. first_slot + P - 1 of `bank` (a policy.MfmaPolicyBank) <- the members' current actors, both images packed on
+        the device from each updater's theta in ONE launch (qr_ppo_population_load_bank): bit for bit what bank.load_torch writes, without
+        host packing, copy or synchronisation."""
+        C = self._C
+        thetas = (C.c_void_p * len(self.updaters))(*[u.theta.data_ptr() for u in self.updaters])
+        self._lib.check(self._lib.require(self._L, "qr_ppo_population_load_bank")(self._h, thetas, bank._h, int(first_slot), self._stream()))
+        return bank
+
+    PREPARE_SHARED = ("obs", "act", "logp", "rew", "done", "trunc", "last_obs")
+    PREPARE_MEMBER = ("obs", "act", "old_logp", "rew", "done", "val", "last_val", "adv", "ret")
+
+    def prepare(self, shared, members):
+        """Everything between the collect launch and the update launches for all members (qr_ppo_population_prepare): four launches and one
+        blocking read.  shared: dict of the collect launch's outputs -- obs [K, N, L], act [K, N, 4], logp, rew [K, N] float32, done, trunc
+        [K, N] uint8, last_obs [N, L], term_obs [K, N, L] or None -- and E (envs per member).  members: per member a dict with first_env,
+        gamma, lam and its own contiguous float32 buffers obs [K, E, L], act [K, E, 4], old_logp, rew, done, val, adv, ret [K, E],
+        last_val [E], term_val [K, E] or None, ep_ret / ep_len / ep_gates [E] (all three or none).
+        -> per member [non-finite rows, truncations, sum ep_ret d, sum ep_len d, sum ep_gates d, episodes, sum reward, 0] as floats."""
+        C, lib = self._C, self._lib
+        if len(members) != len(self.updaters):
+            raise ValueError("one dict of arguments per member")
+        K, N = (int(x) for x in shared["rew"].shape)
+        E, Lo = int(shared["E"]), int(shared["obs"].shape[-1])
+        want = dict(obs=(K, N, Lo), act=(K, N, 4), logp=(K, N), rew=(K, N), done=(K, N), trunc=(K, N), last_obs=(N, Lo), term_obs=(K, N, Lo))
+        sh = lib.QrPpoPrepareShared()
+        sh.K, sh.N, sh.E = K, N, E
+        for name in self.PREPARE_SHARED + ("term_obs",):
+            t = shared.get(name)
+            if t is None and name == "term_obs":
+                continue
+            dt = torch.uint8 if name in ("done", "trunc") else torch.float32
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == want[name]):
+                raise ValueError("shared[%r] must be a contiguous %s CUDA tensor of shape %s" % (name, dt, want[name]))
+            setattr(sh, name, t.data_ptr())
+        shapes = dict(obs=(K, E, Lo), act=(K, E, 4), last_val=(E,), ep_ret=(E,), ep_len=(E,), ep_gates=(E,))
+        args = (lib.QrPpoPrepareMember * len(members))()
+        for a, m in zip(args, members):
+            a.first_env, a.gamma, a.lam = int(m["first_env"]), float(m["gamma"]), float(m["lam"])
+            for name in self.PREPARE_MEMBER + ("term_val", "ep_ret", "ep_len", "ep_gates"):
+                t = m.get(name)
+                if t is None and name not in self.PREPARE_MEMBER:
+                    continue
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shapes.get(name, (K, E))):
+                    raise ValueError("a member's %r must be a contiguous float32 CUDA tensor of shape %s" % (name, shapes.get(name, (K, E))))
+                setattr(a, name, t.data_ptr())
+        report = (C.c_double * (8 * len(members)))()
+        lib.check(lib.require(self._L, "qr_ppo_population_prepare")(self._h, C.byref(sh), args, report, self._stream()))
+        return [[float(report[8 * p + q]) for q in range(8)] for p in range(len(members))]
+
 
 class PPO:
     def __init__(self, env, n_steps=32, batch_size=None, n_epochs=5, gamma=0.999, gae_lambda=0.95, clip_range=0.2,
@@ -683,6 +733,11 @@ class PPO:
         if self.stats["non_finite_rows"]:
             adv = adv.masked_fill(self._bad, 0.0)
             ret = torch.where(self._bad, self.buf_val, ret)
+        return self._train_views(adv, ret)
+
+    def _train_views(self, adv, ret):
+        """The second half of _train_prepare, for advantages / returns that are already sanitised (PopulationPPO(batched_prepare=True)
+        gets them from qr_ppo_population_prepare): the flat views and this round's learning rate."""
         B = self.n_steps * self.n_envs
         obs = self.buf_obs.view(B, -1)
         act = self.buf_act.view(B, 4)

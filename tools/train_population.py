@@ -3,13 +3,15 @@
 qr_rollout_policy_population), ranked on shared starts (GPU box).
 
     python tools/train_population.py --seeds 0-9 [--envs-per-member 256] [--variant indi|e2e] [--track square|zigzag]
-        [--steps 3e6] [--n-steps 32] [--epochs 5] [--minibatches 4] [--lr 3e-4] [--target-kl 0.02] [--curve 20] [--batched-update]
+        [--steps 3e6] [--n-steps 32] [--epochs 5] [--minibatches 4] [--lr 3e-4] [--target-kl 0.02] [--curve 20] [--batched-update [--batched-prepare]]
 
 --steps counts env steps PER MEMBER.  Member p owns envs [p E, (p + 1) E) of a P x E env and differs from the others in its seed only
 (network initialisation, minibatch permutations, action noise); the env's own seed is 1, as for tools/train_ppo.py --seed 0.  Every
 --curve rounds (training clock stopped) and at the end all members are evaluated in one bank launch on shared starts
 (evaluate_policies): one line per member, then the rank_policies table.  --batched-update: the members' updates run as one launch
-sequence (PopulationPPO(batched_update=True) -> qr_ppo_population_epoch) instead of one after another; same results, bit for bit.  The JSON
+sequence (PopulationPPO(batched_update=True) -> qr_ppo_population_epoch) instead of one after another; same results, bit for bit.  --batched-prepare (needs --batched-update, implies nothing else): the bank
+load, the members' value forwards, slice copies, sanitising and GAE run on the device for all members at once
+(PopulationPPO(batched_prepare=True) -> qr_ppo_population_load_bank / qr_ppo_population_prepare); same tensors, bit for bit.  The JSON
 line carries round_ms, the mean wall time of a round (collect + train) after the first one (which captures graphs and allocates)."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,6 +50,8 @@ def parser():
     ap.add_argument("--no-trunc-bootstrap", action="store_true")
     ap.add_argument("--torch-update", action="store_true", help="update with torch autograd instead of the matrix-core kernels")
     ap.add_argument("--batched-update", action="store_true", help="update all members in one launch sequence (matrix-core update, f16 operands)")
+    ap.add_argument("--batched-prepare", action="store_true",
+                    help="bank load, values, sanitising and GAE of all members on the device in a fixed number of launches (needs --batched-update)")
     ap.add_argument("--curve", type=int, default=0, help="evaluate every member every this many rounds (training clock stopped)")
     ap.add_argument("--eval-envs-per-member", type=int, default=256)
     ap.add_argument("--out", default="")
@@ -69,7 +73,10 @@ def main():
     from optimal_quad_control_rl_amd import (PopulationPPO, Quadcopter3DGates, Quadcopter3DGatesINDI, TRAIN_DISTURBANCE_RANGES, evaluate_policies,
                                              rank_policies, square_track, zigzag_track)
 
-    a = parser().parse_args()
+    ap = parser()
+    a = ap.parse_args()
+    if a.batched_prepare and not a.batched_update:
+        ap.error("--batched-prepare needs --batched-update")
     seeds = parse_seeds(a.seeds)
     P, E = len(seeds), a.envs_per_member
     trk = square_track() if a.track == "square" else zigzag_track()
@@ -86,7 +93,8 @@ def main():
                         n_epochs=a.epochs, batch_size=E * a.n_steps // a.minibatches, learning_rate=a.lr, target_kl=a.target_kl,
                         lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps), native_update=not a.torch_update,
                         truncation_bootstrap=not a.no_trunc_bootstrap, policy_forward="f32class" if a.precision != "f16-operands" else "torch",
-                        update_precision="f32" if a.precision == "f32" else "f16-operands", batched_update=a.batched_update)
+                        update_precision="f32" if a.precision == "f32" else "f16-operands", batched_update=a.batched_update,
+                        batched_prepare=a.batched_prepare)
     # evaluation on a separate env, every member on the same starts: 2000 steps = 20 s of flight, crashes restart the lap count
     ev = make_env(P * a.eval_envs_per_member, 99)
     ev.max_steps = 10 ** 6
@@ -128,7 +136,7 @@ def main():
     for place, i in enumerate(order):
         print("%3d   %s" % (place + 1, member_line(seeds[i], res[i])), flush=True)
     out = dict(seeds=seeds, envs_per_member=E, variant=a.variant, track=a.track, n_steps=a.n_steps, epochs=a.epochs, minibatches=a.minibatches,
-               lr=a.lr, target_kl=a.target_kl, batched_update=bool(a.batched_update), rounds=rounds[0], round_ms=1e3 * (train_s - first[0]) / (rounds[0] - 1) if rounds[0] > 1 else None, train_steps_per_member=pop.num_timesteps, train_seconds=train_s,
+               lr=a.lr, target_kl=a.target_kl, batched_update=bool(a.batched_update), batched_prepare=bool(a.batched_prepare), rounds=rounds[0], round_ms=1e3 * (train_s - first[0]) / (rounds[0] - 1) if rounds[0] > 1 else None, train_steps_per_member=pop.num_timesteps, train_seconds=train_s,
                train_Msteps_per_s=pop.num_timesteps * P / train_s / 1e6, ranking=[seeds[i] for i in order],
                flying_lap_seconds=[r["total"]["flying_lap_seconds"] for r in res],
                crashes_per_12s=[r["window"]["crashes_per_window"] for r in res], curve=curve)
