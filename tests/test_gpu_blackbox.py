@@ -206,6 +206,8 @@ def _trigger_facts(trig, w, m, what):
 # 293 none does, so the E2E cases that must hold such an env fly 1 024; INDI: 683 of 1 024 and 206 of 293)
 _CASES = [("e2e", 1, 1024, "f16-operands", False), ("e2e", 0, 1024, "f16-operands", True), ("indi", 0, 1024, "f16-operands", True),
           ("indi", 1, 256 + 37, "f16-operands", False), ("indi", 1, 256 + 37, "f32", True)]
+# every other instantiation of blackbox_policy_kernel<variant, gates_ahead, f32class> (and, for the twin's rows, of the recorder's)
+_CASES += [(v, g, 1024 if v == "e2e" else 256 + 37, p, True) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 _IDS = ["%s-ga%d-n%d-%s-%s" % (c[0], c[1], c[2], c[3], "stoch" if c[4] else "det") for c in _CASES]
 
 

@@ -140,6 +140,8 @@ def _grid_against_twins(variant, gates_ahead, E, precision, pol, cog, K=SC["step
 
 
 _CASES = [(v, g, e, p) for v in ("e2e", "indi") for g in (0, 1) for e in (256, 1024) for p in ("f16-operands", "f32")]
+# every other instantiation of eval_policy_grid_kernel<variant, gates_ahead, f32class>, one workgroup per cell
+_CASES += [(v, g, 256, p) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 
 
 @pytest.mark.parametrize("variant,gates_ahead,E,precision", _CASES, ids=["%s-ga%d-E%d-%s" % c for c in _CASES])

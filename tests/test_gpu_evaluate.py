@@ -84,6 +84,8 @@ def test_records_equal_the_spec(variant, gates_ahead, n, precision):
 
 
 _CLOSED = [("indi", 0, 4096 + 37, "f32"), ("e2e", 1, 4096 + 37, "f32"), ("indi", 1, 4096, "f16-operands"), ("e2e", 0, 4096, "f16-operands")]
+# every other instantiation of eval_policy_kernel<variant, gates_ahead, f32class>, at the ragged size
+_CLOSED += [(v, g, 4096 + 37, p) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 
 
 @pytest.mark.parametrize("variant,gates_ahead,n,precision", _CLOSED, ids=["%s-ga%d-n%d-%s" % c for c in _CLOSED])

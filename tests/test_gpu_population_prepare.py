@@ -8,7 +8,12 @@ does and adds them in float64, within n * 2^-52 * sum |terms| (n terms): the bou
 
 A note on the planted 3e38 rows of last_obs / term_obs: the forward saturates its inputs and activations to the f16 range, so with finite
 weights these values come out finite; the nan_to_num of last_val / term_val is reached through a member whose value net carries an
-infinite output bias (every one of its values is +inf, so every one of its rows is zeroed)."""
+infinite output bias (every one of its values is +inf, so every one of its rows is zeroed).
+
+Shapes: the older cases give every workgroup of the value and the gather launch one tile.  test_prepare_with_many_tiles_per_workgroup flies
+the two shapes of test_population_prepare_host.MANY_TILE_SHAPES (P = 256 and E = 512), where a workgroup walks rollout, last_obs and
+term_obs tiles in turn and gathers three tiles, with plants in tiles it reaches late; every obs_len of dispatch_L is run once by the bank
+load and once by the prepare."""
 import ctypes as C
 import math
 import statistics
@@ -18,11 +23,12 @@ import numpy as np
 import pytest
 import torch
 
-from test_population_prepare_host import _stub_env, batched_prepare_refusals
+from test_population_prepare_host import MANY_TILE_SHAPES, _stub_env, batched_prepare_refusals, late_plants, prepare_grids
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
+OBS_LENS = (24, 17, 16, 13, 20, 21, 25, 28, 29, 32, 36)     # every length dispatch_L instantiates
 GAMMA = (0.999, 0.99, 0.95, 0.9)
 LAM = (0.95, 0.9, 1.0, 0.8)
 H = 120
@@ -81,7 +87,7 @@ def _plant(theta, L):
         theta[b2 + 9] = math.nan
 
 
-@pytest.mark.parametrize("L", [24, 17, 16])
+@pytest.mark.parametrize("L", OBS_LENS)
 def test_bank_load_equals_bank_set(L):
     from optimal_quad_control_rl_amd import _lib
     from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
@@ -132,25 +138,77 @@ def test_bank_load_equals_bank_set(L):
     _close(ups, pop, ref, got, wide, other)
 
 
+@pytest.fixture(scope="module")
+def members_256():
+    """256 members of obs_len 13 and their population object, made once for the tests that need the largest population"""
+    t0 = time.perf_counter()
+    ups, pop = _members(13, 256)
+    torch.cuda.synchronize()
+    print("256 members and their population object: %.2f s" % (time.perf_counter() - t0))
+    yield ups, pop
+    _close(ups, pop)
+
+
+def test_bank_load_of_256_members_behind_a_first_slot(members_256):
+    """the 2 KB of parameter-vector pointers in the kernel arguments and blockIdx.y up to 255, into slots 37 .. 292 of a 300-slot bank"""
+    from optimal_quad_control_rl_amd import _lib
+    from optimal_quad_control_rl_amd.policy import MfmaPolicyBank
+
+    L, P, first = 13, 256, 37
+    ups, pop = members_256
+    lib = ups[0]._L
+    kept = ups[200].theta.clone()
+    _plant(ups[200].theta, L)
+    ref, got = MfmaPolicyBank(L, P, 0), MfmaPolicyBank(L, 300, 0)
+    for p, u in enumerate(ups):
+        ref.load_torch(p, u.policy.pi)
+    pop.load_bank(got, first_slot=first)
+    images = {}
+    for p in range(P):
+        for which in (0, 1):
+            (rc_r, r), (rc_g, g) = _read(lib, ref, p, which, L), _read(lib, got, first + p, which, L)
+            assert rc_r == rc_g == _lib.QR_OK
+            assert np.array_equal(r, g), (p, which, int((r != g).sum()))
+            images[p] = images.get(p, b"") + g.tobytes()
+    assert len(set(images.values())) == P                                   # 256 different members: a slot filled from another member fails above
+    planted = _read(lib, got, first + 200, 0, L)[1]
+    assert (planted == 0x7C00).any() and (planted == 0xFC00).any() and (planted == 0x7E00).any() and (planted == 0x0001).any()
+    for slot in (0, first - 1, first + P, 299):                             # outside [first, first + P): still unset
+        assert _read(lib, got, slot, 0, L)[0] == _lib.QR_E_INVALID
+    with torch.no_grad():
+        ups[200].theta.copy_(kept)                                          # the members are shared with other tests of this module
+    ref.close(); got.close()
+
+
 # --------------------------------------------------------------------------------------------------------------------------- prepare
 class _Case:
     """Synthetic outputs of one collect launch and P members on it."""
 
-    def __init__(self, L, N, E, K, firsts, term_obs=True, no_term_member=None, inf_value_member=None, seed=0):
+    def __init__(self, L, N, E, K, firsts, term_obs=True, no_term_member=None, inf_value_member=None, seed=0, members=None, on_device=False,
+                 late=None):
+        """members: (ups, pop) made elsewhere (and closed there); on_device: the big arrays come from a seeded generator on the GPU (the
+        CPU's randn dominates the time of the large cases); late: test_population_prepare_host.late_plants(P, E, K)"""
         self.L, self.N, self.E, self.K, self.firsts = L, N, E, K, list(firsts)
         P = len(firsts)
-        self.ups, self.pop = _members(L, P)
+        self.own_members = members is None
+        self.ups, self.pop = _members(L, P) if members is None else members
         if inf_value_member is not None:     # the value net's output bias: the last parameter before log_std
             with torch.no_grad():
                 self.ups[inf_value_member].theta[-5] = math.inf
             self.ups[inf_value_member].pack()
         g = torch.Generator(device="cpu").manual_seed(1234 + seed)
-        r = lambda *s: torch.randn(s, generator=g)
+        if on_device:
+            gd = torch.Generator(device=DEV).manual_seed(1234 + seed)
+            r = lambda *s: torch.randn(s, generator=gd, device=DEV)
+            u = lambda *s: torch.rand(s, generator=gd, device=DEV)
+        else:
+            r = lambda *s: torch.randn(s, generator=g)
+            u = lambda *s: torch.rand(s, generator=g)
         obs, act, logp, rew = r(K, N, L), r(K, N, 4), r(K, N), 3.0 * r(K, N)
-        done = torch.rand((K, N), generator=g) < 0.125
+        done = u(K, N) < 0.125
         done[0, ::5] = True
         done[K - 1, 1::7] = True
-        trunc = done & (torch.rand((K, N), generator=g) < 0.5)
+        trunc = done & (u(K, N) < 0.5)
         last_obs, term = r(N, L), r(K, N, L)
         f = self.firsts
         t1 = min(1, K - 1)
@@ -161,6 +219,18 @@ class _Case:
         last_obs[f[0] + 5] = 3e38
         trunc[t1, f[0] + 13] = done[t1, f[0] + 13] = True
         term[t1, f[0] + 13] = 3e38                            # a truncated row
+        if late is not None:                                  # plants a workgroup meets on its second or a later tile
+            ga, te, la = late["gather"], late["term"], late["last"]
+            (t, c), fm = ga["tile"], f[ga["member"]]
+            obs[t, fm + c * 256 + ga["obs_row"], ga["obs_col"]] = math.nan
+            act[t, fm + c * 256 + ga["act_row"], ga["act_col"]] = math.inf
+            (t, c), fm = te["empty_tile"], f[te["member"]]
+            trunc[t, fm + c * 256:fm + (c + 1) * 256] = False  # done stays: an episode end that is no time limit
+            (t, c) = te["tile"]
+            row = fm + c * 256 + te["row"]
+            trunc[t, row] = done[t, row] = True
+            term[t, row] = 3e38
+            last_obs[f[la["member"]] + la["row"]] = 3e38
         term[~trunc] = math.nan                               # must not leak
         self.shared = dict(E=E, obs=obs.to(DEV), act=act.to(DEV), logp=logp.to(DEV), rew=rew.to(DEV), done=done.to(torch.uint8).to(DEV),
                            trunc=trunc.to(torch.uint8).to(DEV), last_obs=last_obs.to(DEV), term_obs=term.to(DEV) if term_obs else None)
@@ -251,7 +321,8 @@ class _Case:
         return args, report
 
     def close(self):
-        _close(self.ups, self.pop)
+        if self.own_members:
+            _close(self.ups, self.pop)
 
 
 def test_prepare_equals_the_composition():
@@ -285,6 +356,60 @@ def test_prepare_corollaries(kw):
         m = args[1]
         assert report[1][0] == c.K * c.E and float(m["val"].abs().sum()) == 0.0 and float(m["last_val"].abs().sum()) == 0.0
         assert float(m["term_val"].abs().sum()) == 0.0 and float(m["adv"].abs().sum()) == 0.0 and report[0][0] < c.K * c.E
+    c.close()
+
+
+@pytest.mark.parametrize("L", OBS_LENS)
+def test_prepare_at_every_obs_len(L):
+    """every instantiation of dispatch_L: the float4 path (L % 4 == 0) and the scalar one, badrow[(k 256 + tid) / L], the image of each size"""
+    c = _Case(L, 512, 256, 3, (256, 0), seed=L)
+    _, report = c.check("L %d" % L)
+    assert sum(r[0] for r in report) >= 4 and all(r[5] > 0 and r[1] > 0 for r in report)
+    c.close()
+
+
+@pytest.mark.parametrize("shape", MANY_TILE_SHAPES, ids=["P%(P)d-E%(E)d-K%(K)d-L%(L)d" % s for s in MANY_TILE_SHAPES])
+def test_prepare_with_many_tiles_per_workgroup(shape, members_256):
+    """The tile loops of the value and the gather launch walked several times by one workgroup (the conditions are asserted on the CPU:
+    test_population_prepare_host.test_many_tile_shapes_walk_several_tiles_per_workgroup), with non-finite values in tiles a workgroup
+    reaches on its second or a later iteration.  The members' columns lie in the shared arrays in reverse order."""
+    L, P, E, K = shape["L"], shape["P"], shape["E"], shape["K"]
+    g, late = prepare_grids(P, E, K), late_plants(P, E, K)
+    firsts = [(P - 1 - p) * E for p in range(P)]
+    t0 = time.perf_counter()
+    c = _Case(L, P * E, E, K, firsts, members=members_256 if (L, P) == (13, 256) else None, on_device=True, late=late)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    sh = c.shared
+    ga, te, la = late["gather"], late["term"], late["last"]
+    tile_of = lambda name, m, tc: sh[name][tc[0], firsts[m] + tc[1] * 256:firsts[m] + (tc[1] + 1) * 256]
+    # the inputs are what the plan says: a term_obs tile without a truncation before a tile with one, in one workgroup of the value launch
+    assert int(tile_of("trunc", te["member"], te["empty_tile"]).sum()) == 0 and int(tile_of("done", te["member"], te["empty_tile"]).sum()) > 0
+    assert int(tile_of("trunc", te["member"], te["tile"])[te["row"]]) == 1
+    assert (g["roll"] + g["cpe"] + te["q"][0]) % g["vgrid"] == (g["roll"] + g["cpe"] + te["q"][1]) % g["vgrid"]
+    src_next = tile_of("obs", ga["member"], ga["next_tile"]).clone()
+    assert bool(torch.isfinite(src_next).all()) and bool(torch.isfinite(tile_of("act", ga["member"], ga["next_tile"])).all())
+    args, report = c.check(repr(shape))
+    t2 = time.perf_counter()
+    print("%r: grids %r, inputs %.2f s, prepare + %d compositions %.2f s" % (shape, g, t1 - t0, P, t2 - t1))
+    member_tile = lambda name, m, tc: args[m][name][tc[0], tc[1] * 256:(tc[1] + 1) * 256]
+    # gather: exactly the two planted rows of the late tile are zeroed, and the tile the same workgroup does next comes out as it went in
+    m = ga["member"]
+    bad = member_tile("obs", m, ga["tile"]).eq(0.0).all(-1).nonzero().flatten().tolist()
+    assert bad == sorted((ga["obs_row"], ga["act_row"])), bad
+    assert float(member_tile("act", m, ga["tile"])[bad].abs().sum()) == 0.0 and float(member_tile("adv", m, ga["tile"])[bad].abs().sum()) == 0.0
+    _same(member_tile("obs", m, ga["next_tile"]), src_next, "the clean tile after the planted one")
+    assert int(member_tile("obs", m, ga["next_tile"]).eq(0.0).all(-1).sum()) == 0
+    assert report[m][0] == 2.0                                      # the member's non-finite rows: the two late plants and nothing else
+    # term: the tile without a truncation is all zero, the planted row of the next one was evaluated
+    m = te["member"]
+    assert float(member_tile("term_val", m, te["empty_tile"]).abs().sum()) == 0.0
+    v = float(member_tile("term_val", m, te["tile"])[te["row"]])
+    assert math.isfinite(v) and v != 0.0
+    # last_obs: the planted row of a member other than member 0 went through the saturating forward
+    m = la["member"]
+    assert m != 0 and float(sh["last_obs"][firsts[m] + la["row"], 0]) > 1e38 and math.isfinite(float(args[m]["last_val"][la["row"]]))
+    assert all(r[5] > 0 and r[1] > 0 for r in report)
     c.close()
 
 

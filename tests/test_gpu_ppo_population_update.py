@@ -6,7 +6,10 @@ Adam step count, the status quadruple, the shuffle state, the permutation buffer
 tolerance anywhere.
 
 Inputs: seeded N(0, 1) obs / act / adv / ret, old_logp from each member's own initial policy; the members differ in their initial
-parameters (torch.manual_seed(p)), lr, clip, ent_coef, vf_coef, max_grad_norm and shuffle seed."""
+parameters (torch.manual_seed(p)), lr, clip, ent_coef, vf_coef, max_grad_norm and shuffle seed.
+
+Every obs_len of dispatch_L is run in both partial forms at P = 2; P = 65 and P = 256 (the limit of qr_ppo_population_create) are run at
+obs_len 13 with a learning rate of its own per member."""
 import ctypes as C
 import math
 import statistics
@@ -120,6 +123,59 @@ def test_every_member_equals_its_twin(L, B, M, P):
         x.hyper["lr"] = x.hyper["lr"] * 0.5 + 1e-4
     _both(members, twins, pop, B, 2, True, "second call (replay, changed lr)")
     assert all(m.up.step == 4 * M for m in members)
+    _close(members, twins, pop)
+
+
+OBS_LENS = (13, 16, 17, 20, 21, 24, 25, 28, 29, 32, 36)     # every length dispatch_L instantiates
+
+
+@pytest.mark.parametrize("flags", [0, PARTIAL_F32], ids=["bf16-partials", "f32-partials"])
+@pytest.mark.parametrize("L", OBS_LENS)
+def test_every_obs_len_in_both_partial_forms(L, flags):
+    """every instantiation of the grad / reduce / step kernels, at the smallest shape with more than one group and minibatch"""
+    B, M, P = 128, 2, 2
+    members, twins, pop = _population(L, B * M, B, P, flags)
+    before = [m.up.theta.clone() for m in members]
+    _both(members, twins, pop, B, 2, True, "L %d, flags %d" % (L, flags))
+    for p, m in enumerate(members):
+        assert m.up.status() == (False, 2 * M, 0, 0) and m.up.shuffle_state() == (1000 + 17 * p, 2), (p, m.up.status())
+        assert sorted(m.perm.tolist()) == list(range(B * M)) and not torch.equal(m.up.theta, before[p])
+    _close(members, twins, pop)
+
+
+def _lr_of(p):
+    """a learning rate of its own for every member; 0 (nothing may move) for every fifth, never for members 63, 64 and 255"""
+    return 0.0 if p % 5 == 2 else 1e-4 * (1 + p % 7) + 1e-6 * p
+
+
+@pytest.mark.parametrize("P", [65, 256])
+def test_large_populations_every_member_equals_its_twin(P):
+    """ppo_population_lr_kernel (one thread per member), the 1 KB of learning rates in its arguments and the member tables behind
+    blockIdx.z at the largest member counts: past one wave (65) and the limit (256)."""
+    L, B, M = 13, 64, 2
+    t0 = time.perf_counter()
+    members, twins, pop = _population(L, B * M, B, P)
+    for x in members + twins:
+        x.hyper["lr"] = _lr_of(x.p)
+    moving = [p for p in range(P) if _lr_of(p) != 0.0]
+    assert {63, 64, P - 1} <= set(moving) and len(moving) < P and len({_lr_of(p) for p in moving}) == len(moving)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    before = [m.up.theta.clone() for m in members]
+    _both(members, twins, pop, B, 1, True, "first call")
+    first = [m.up.theta.clone() for m in members]
+    assert [p for p in range(P) if not torch.equal(first[p], before[p])] == moving      # each member's own lr reached the device
+    assert pop.status() == [(False, M, 0, 0)] * P
+    assert len({tuple(m.perm.tolist()) for m in members}) == P                         # every member under its own key
+    # the replay: only learning rates change -- those that were 0 stay 0, the others are halved.  A member that kept its old rate, or
+    # got a neighbour's, differs from its twin; a member with lr = 0 must not move at all
+    for x in members + twins:
+        x.hyper["lr"] = 0.5 * x.hyper["lr"]
+    _both(members, twins, pop, B, 1, True, "second call (replay, changed lr)")
+    assert [p for p in range(P) if not torch.equal(members[p].up.theta, first[p])] == moving
+    assert pop.status() == [(False, 2 * M, 0, 0)] * P
+    torch.cuda.synchronize()
+    print("P = %d: %d handles made in %.2f s, two calls with their twins compared in %.2f s" % (P, 2 * P, t1 - t0, time.perf_counter() - t1))
     _close(members, twins, pop)
 
 

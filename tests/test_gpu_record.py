@@ -110,7 +110,8 @@ def _assert_window_is_not_vacuous(rows, s, final_target, what):
 # ---------------------------------------------------------------------------------------------------------------------------------
 _CASES = [(v, g, n, p, st) for v in ("e2e", "indi") for g in (0, 1) for n in (4096, 4096 + 37, 65536) for p in ("f16-operands", "f32")
           for st in (False, True)]
-
+# every other instantiation of record_policy_kernel<variant, gates_ahead, f32class>, at the ragged size
+_CASES += [(v, g, 4096 + 37, p, True) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 
 @pytest.mark.parametrize("variant,gates_ahead,n,precision,stochastic", _CASES,
                          ids=["%s-ga%d-n%d-%s-%s" % (c[0], c[1], c[2], c[3], "stoch" if c[4] else "det") for c in _CASES])

@@ -142,6 +142,8 @@ def _against_twins(variant, gates_ahead, precision, cog):
 
 
 _CASES = [(v, g, p) for v in ("e2e", "indi") for g in (0, 1) for p in ("f16-operands", "f32")]
+# every other instantiation of rollout_policy_cond_kernel<variant, gates_ahead, f32class>
+_CASES += [(v, g, p) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 
 
 @pytest.mark.parametrize("variant,gates_ahead,precision", _CASES, ids=["%s-ga%d-%s" % c for c in _CASES])

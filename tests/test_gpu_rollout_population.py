@@ -8,7 +8,8 @@ Shapes: N = 768 = 3 groups x 256 with policy_of_group = [2, 0, 2] on a 3-slot ba
 kernel that read slot g, slot 0 or the wrong half of the map entry fails), three different log_std rows and seeds, K = 48 with
 max_steps = 20, so EVERY env is truncated and reset at least twice inside the call, and the forced rows of
 test_gpu_rollout_conditions.py add ground crashes and gate passes at the first step (the random weights alone crash nobody within 20
-steps); all of it asserted on the twins' own outputs.  One case with E = 512 (a group spans two workgroups).  PopulationPPO's members against standalone PPO learners
+steps); all of it asserted on the twins' own outputs.  One case with E = 512 (a group spans two workgroups), every <variant, gates_ahead, precision> once, and
+one launch of 256 groups on 256 slots of which four groups are compared.  PopulationPPO's members against standalone PPO learners
 on the twins, and the launch time against the parent's kernel on the same launch shape."""
 import ctypes as C
 import statistics
@@ -19,7 +20,7 @@ import torch
 
 import eval_spec as S
 from eval_helpers import SENTINEL, _closed_loop_layers, _group_equals, _policy_bank, _ptr
-from test_gpu_rollout_conditions import _bank, _conditions, _force_rows, _handle, _term_buffer
+from test_gpu_rollout_conditions import GATE_ROWS, GROUND_ROWS, _bank, _conditions, _force_rows, _handle, _term_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +93,60 @@ _CASES = [(v, g, d) for v in ("e2e", "indi") for g in (0, 1) for d in (False, Tr
 @pytest.mark.parametrize("variant,gates_ahead,deterministic", _CASES, ids=["%s-ga%d-%s" % (v, g, "det" if d else "stoch") for v, g, d in _CASES])
 def test_every_group_equals_its_twin(variant, gates_ahead, deterministic):
     _against_twins(variant, gates_ahead, deterministic, "f16-operands")
+
+
+_DEEP = [(v, g, p) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
+
+
+@pytest.mark.parametrize("variant,gates_ahead,precision", _DEEP, ids=["%s-ga%d-%s" % c for c in _DEEP])
+def test_every_group_equals_its_twin_with_more_gates_ahead(variant, gates_ahead, precision):
+    """the instantiations <variant, gates_ahead 2 .. 4, precision>: obs_len up to 36, the largest image and observation tile in LDS"""
+    _against_twins(variant, gates_ahead, False, precision)
+
+
+def test_256_groups_on_256_slots():
+    """One launch of 256 groups x 256 envs, every group on a slot of its own (a permutation that is not the identity), with its own
+    log_std and seed, K = 8 with max_steps = 5: every env is cut by the time limit inside the call.  Groups 0, 63, 64 and 255 against
+    their twins (a twin for every group would take a minute)."""
+    variant, groups, Kc, short = "indi", 256, 8, 5
+    cond = _conditions(variant)[0].replace(max_steps=short)
+    env = _handle(variant, groups * E, 0, cond)
+    layers = _layers(variant, env.state_len, groups)
+    pog = [(37 * g + 11) % groups for g in range(groups)]
+    assert sorted(pog) == list(range(groups)) and all(pog[g] != g for g in (0, 63, 64, 255))
+    rng = np.random.default_rng(5)
+    log_stds = rng.uniform(-2.0, 0.0, size=(groups, 4)).astype(np.float32)
+    seeds = [int(s) for s in rng.integers(0, 2 ** 63, size=groups)]
+    pbank, cbank = _policy_bank(env.state_len, layers), _bank(variant, [cond])
+    start = env.get_state_tensors()
+    checked = (0, 63, 64, 255)
+    world = env.get_state_tensors()[0]
+    for g in checked:       # _force_rows' starts, in the compared groups only
+        for r in GROUND_ROWS:
+            world[g * E + r, 2], world[g * E + r, 5] = -0.005, 2.0
+        for r in GATE_ROWS:
+            world[g * E + r, :6] = torch.tensor([-0.01, 0.0, -1.5, 3.0, 0.0, 0.0], device=world.device)
+    env.set_state_tensors(world=world)
+    tb = _term_buffer(env, Kc)
+    out = [t.clone() for t in env.rollout_policy_population_device(pbank, pog, cbank, [0] * groups, E, Kc, log_stds, seeds, first_step=7)]
+    after = env.get_state_tensors()
+    for g in checked:
+        lo, hi = g * E, (g + 1) * E
+        twin = _handle(variant, E, 0, cond, env_id_base=lo)
+        _group_equals(start, twin, lo, hi, "start, group %d" % g)
+        _force_rows(twin, 1)
+        pol = _mfma(env.state_len, layers[pog[g]])
+        ttb = _term_buffer(twin, Kc)
+        tout = twin.rollout_policy_device(pol, Kc, log_stds[g], noise_seed=seeds[g], first_step=7)
+        t_done, t_trunc = tout[4].bool(), tout[5].bool()
+        crashes, limits = int((t_done & ~t_trunc).sum()), int(t_trunc.sum())
+        print("group", g, "slot", pog[g], "crashes", crashes, "time limits", limits)
+        assert bool(t_done.any(0).all()) and limits >= 1 and crashes >= 3 and int((tout[3] > 5.0).sum()) >= 1
+        _compare_group(g, lo, hi, out, tb, after, twin, tout, ttb)
+        twin.close(); pol.close()
+    acts = [out[1][:, g * E:(g + 1) * E] for g in checked]
+    assert all(not torch.equal(acts[i], acts[j]) for i in range(4) for j in range(i))
+    env.close(); pbank.close(); cbank.close()
 
 
 def test_every_group_equals_its_twin_f32():
@@ -322,10 +377,32 @@ def _trainer_env(n, env_id_base=0):
     return _handle("e2e", n, 1, _conditions("e2e")[0].replace(max_steps=SHORT), env_id_base=env_id_base, seed=21)
 
 
+def _same_stats(a, b, abs_rewards, where):
+    """Two learners' statistics: the same keys, and every value equal (by repr, so NaN = NaN) -- but for ep_rew_mean.  That one is
+    fin[0] / fin[3], and fin[0] leaves ppo_gae_kernel as one float32 atomic per wave: with 256 envs four partial sums w_k whose order of
+    arrival is not fixed (seen with 256 episodes ending in a round: every tensor equal, the two means not; the same is noted in
+    test_gpu_ppo_population_update.py and test_gpu_population_prepare.py).  A float32
+    sum of n = 4 terms in any order is within gamma_3 sum |w_k| of the exact sum, gamma_3 = 3 u / (1 - 3 u), u = 2^-24, so two orders
+    are within twice that of each other.  sum |w_k| <= the finished episodes' |returns| <= `abs_rewards`, the sum of |reward| over
+    every step flown so far (added in float64), times 1 + 2^-18 for the float32 running returns of at most 20 steps (the time limit); the quotient in
+    double adds 2^-52 relative.  The other three sums are small whole numbers, exact in any order, and stay exact here."""
+    assert sorted(a) == sorted(b), (where, sorted(a), sorted(b))
+    u = 2.0 ** -24
+    gamma3 = 3.0 * u / (1.0 - 3.0 * u)
+    for key in a:
+        if key == "ep_rew_mean":
+            assert a["episodes"] == b["episodes"] > 0, where
+            bound = 2.0 * gamma3 * (1.0 + 2.0 ** -18) * abs_rewards / a["episodes"] + 2.0 ** -52 * abs(a[key])
+            print(where, "ep_rew_mean", a[key], b[key], "difference", abs(a[key] - b[key]), "bound", bound)
+            assert abs(a[key] - b[key]) <= bound, (where, a[key], b[key], bound)
+        else:
+            assert repr(a[key]) == repr(b[key]), (where, key, a[key], b[key])
+
+
 def test_population_members_equal_standalone_learners():
     """Two members (seeds 3 and 4, different learning rates) over two rounds against a standalone PPO each on the 256-env twin handle
-    with the same keywords: parameters, Adam moments and statistics bit-equal; then a state_dict round trip into a fresh population
-    continues the run bit for bit."""
+    with the same keywords: parameters, Adam moments and statistics bit-equal (ep_rew_mean, whose float atomics arrive in no fixed
+    order, within the bound of _same_stats); then a state_dict round trip into a fresh population continues the run bit for bit."""
     from optimal_quad_control_rl_amd import PopulationPPO
     from optimal_quad_control_rl_amd.ppo import PPO
 
@@ -336,9 +413,12 @@ def test_population_members_equal_standalone_learners():
     assert len(pop.members) == 2 and all(m.n_envs == E and m.fused_collect for m in pop.members)
     with pytest.raises(RuntimeError):
         pop.train()                                                                    # nothing collected yet
+    abs_rewards = [0.0, 0.0]                                                           # per member: sum |reward| of every step so far
     for _ in range(2):
         pop.collect()
         pop.train()
+        for p, m in enumerate(pop.members):
+            abs_rewards[p] += float(m.buf_rew.double().abs().sum())
     assert pop.num_timesteps == 2 * 16 * E
     twins = []
     for p, kw in enumerate(members):
@@ -356,7 +436,8 @@ def test_population_members_equal_standalone_learners():
             assert torch.equal(x, y)
         for name in ("buf_obs", "buf_act", "buf_lp", "buf_rew", "buf_val", "buf_term_val"):
             assert torch.equal(getattr(m, name), getattr(solo, name)), (p, name)
-        assert repr(sorted(m.stats.items())) == repr(sorted(solo.stats.items())), (p, m.stats, solo.stats)
+        assert "ep_rew_mean" in m.stats and m.stats["episodes"] >= 1
+        _same_stats(m.stats, solo.stats, abs_rewards[p], "member %d against its standalone learner" % p)
         _group_equals(env.get_state_tensors(), tenv, p * E, (p + 1) * E, "env state, member %d" % p)
         twins.append((tenv, solo))
     assert not torch.equal(pop.members[0]._updater.theta, pop.members[1]._updater.theta)
@@ -369,8 +450,8 @@ def test_population_members_equal_standalone_learners():
         q.train()
     for p, (x, y) in enumerate(zip(pop.members, pop2.members)):
         assert torch.equal(x._updater.theta, y._updater.theta) and torch.equal(x._updater.m, y._updater.m) and torch.equal(x._updater.v, y._updater.v), p
-        assert torch.equal(x.buf_obs, y.buf_obs) and torch.equal(x.buf_act, y.buf_act)
-        assert repr(sorted(x.stats.items())) == repr(sorted(y.stats.items()))
+        assert torch.equal(x.buf_obs, y.buf_obs) and torch.equal(x.buf_act, y.buf_act) and torch.equal(x.buf_rew, y.buf_rew)
+        _same_stats(x.stats, y.stats, abs_rewards[p] + float(x.buf_rew.double().abs().sum()), "member %d after the round trip" % p)
         tenv, solo = twins[p]
         solo.collect()
         solo.train()

@@ -116,6 +116,83 @@ def test_the_kernels_are_where_the_header_says_and_wait_for_nobody():
     assert "bank_mark_set" in policy and "qr_policy_bank_read" in policy
 
 
+def prepare_grids(P, E, K):
+    """The grid sizes of the value and the gather launch.  MIRRORS qr_ppo_population_prepare (csrc/quadrace_population_prepare.hip: cpe,
+    roll, vtiles, spread, vgrid, ggrid) and must change with it; test_many_tile_shapes_walk_several_tiles_per_workgroup holds the
+    source's three lines against this restatement."""
+    cpe = E // 256
+    roll = K * cpe                         # rollout tiles = gather tiles = term_obs tiles
+    vtiles = 2 * roll + cpe                # rollout, last_obs and term_obs tiles of the value launch
+    spread = max(1, 1024 // P)
+    return dict(cpe=cpe, roll=roll, vtiles=vtiles, vgrid=min(vtiles, spread), ggrid=min(roll, 4 * spread))
+
+
+def value_tile_kind(tile, g):
+    """0 = rollout rows, 1 = last_obs rows, 2 = term_obs rows: population_value_kernel's decoding of a tile index"""
+    return 0 if tile < g["roll"] else 1 if tile < g["roll"] + g["cpe"] else 2
+
+
+# The prepare cases at which a workgroup walks SEVERAL tiles (tests/test_gpu_population_prepare.py flies them).  N = P E.
+MANY_TILE_SHAPES = [dict(L=13, P=256, E=256, K=33), dict(L=36, P=64, E=512, K=70)]
+
+
+def late_plants(P, E, K):
+    """Where the non-finite values go so that a workgroup meets them on its second or a later tile, from the rule above.  Tiles are
+    (step t, chunk c of 256 rows); a workgroup w walks tiles w, w + grid, w + 2 grid, ...
+      gather: NaN observation element and an infinite action in gather tile ggrid (workgroup 0, second iteration); tile 2 ggrid (its
+              third) stays clean.
+      term:   term_obs tile q = 2 vgrid + 1 gets a truncated row with a plant; the same workgroup's tile before it, q - vgrid, is a
+              term_obs tile too and loses every truncation.
+      last:   a last_obs plant in another member than member 0.
+    Members P - 1, P - 2, P - 3: none of them carries one of _Case's early plants (members 0 .. 3)."""
+    g = prepare_grids(P, E, K)
+    cpe = g["cpe"]
+    tile = lambda q: (q // cpe, q % cpe)
+    q_term = 2 * g["vgrid"] + 1
+    return dict(gather=dict(member=P - 1, tile=tile(g["ggrid"]), next_tile=tile(2 * g["ggrid"]), obs_row=200, obs_col=-1, act_row=100, act_col=3),
+                term=dict(member=P - 2, empty_tile=tile(q_term - g["vgrid"]), tile=tile(q_term), row=77, q=(q_term - g["vgrid"], q_term)),
+                last=dict(member=P - 3, row=E - 5))
+
+
+def test_many_tile_shapes_walk_several_tiles_per_workgroup():
+    """The conditions under which the many-tile cases are many-tile cases, for the shapes the GPU test uses: a change of the launch rule
+    that turns them back into one-tile-per-workgroup cases fails here."""
+    from optimal_quad_control_rl_amd import build
+
+    text = open(os.path.join(build.CSRC, "quadrace_population_prepare.hip")).read()
+    for line in ("const long long roll = (long long)K * cpe, vtiles = 2 * roll + cpe;",
+                 "const int spread = 1024 / P > 1 ? 1024 / P : 1;",
+                 "const int vgrid = (int)(vtiles < spread ? vtiles : spread), ggrid = (int)(roll < 4 * spread ? roll : 4 * spread);"):
+        assert line in text, "the launch rule changed: restate it in prepare_grids and re-derive MANY_TILE_SHAPES\n" + line
+    assert text.count("tile += gridDim.x") == 2
+    assert prepare_grids(2, 256, 9) == dict(cpe=1, roll=9, vtiles=19, vgrid=19, ggrid=9)          # one tile per workgroup: the older cases
+    assert prepare_grids(8, 256, 256) == dict(cpe=1, roll=256, vtiles=513, vgrid=128, ggrid=256)  # a real round
+    for sh in MANY_TILE_SHAPES:
+        P, E, K = sh["P"], sh["E"], sh["K"]
+        g = prepare_grids(P, E, K)
+        print(sh, g, "value tiles per workgroup %.2f, gather tiles per workgroup %.2f" % (g["vtiles"] / g["vgrid"], g["roll"] / g["ggrid"]))
+        assert 1 <= P <= 256 and E % 256 == 0 and sh["L"] in (13, 16, 17, 20, 21, 24, 25, 28, 29, 32, 36)
+        assert g["vtiles"] >= 3 * g["vgrid"]                                                       # (a)
+        kinds = [{value_tile_kind(t, g) for t in range(w, g["vtiles"], g["vgrid"])} for w in range(g["vgrid"])]
+        assert any(k == {0, 1, 2} for k in kinds), "no value workgroup visits all three kinds of tile"
+        assert g["roll"] >= 2 * g["ggrid"] + 1                                                     # (b): workgroup 0 gathers three tiles
+        # the late plants land where they are meant to
+        lp = late_plants(P, E, K)
+        cpe, index = g["cpe"], lambda tc: tc[0] * g["cpe"] + tc[1]
+        ga = lp["gather"]
+        first, second = index(ga["tile"]), index(ga["next_tile"])
+        assert first >= g["ggrid"] and second == first + g["ggrid"] and second < g["roll"]
+        assert ga["tile"][0] not in (0, 1, K - 1) and ga["next_tile"][0] not in (0, 1) and ga["obs_row"] != ga["act_row"]
+        te = lp["term"]
+        q0, q1 = index(te["empty_tile"]), index(te["tile"])
+        assert (q0, q1) == te["q"] and 0 <= q0 < q1 < g["roll"] and q1 - q0 == g["vgrid"]
+        t0, t1 = g["roll"] + cpe + q0, g["roll"] + cpe + q1                                        # as tiles of the value launch
+        assert value_tile_kind(t0, g) == value_tile_kind(t1, g) == 2 and t0 % g["vgrid"] == t1 % g["vgrid"] and t0 // g["vgrid"] >= 1
+        assert len({ga["member"], te["member"], lp["last"]["member"]}) == 3 and min(ga["member"], te["member"], lp["last"]["member"]) >= 4
+    assert any(sh["E"] // 256 >= 2 for sh in MANY_TILE_SHAPES) and any(sh["P"] == 256 for sh in MANY_TILE_SHAPES)   # (c)
+    assert any(sh["L"] % 4 == 0 for sh in MANY_TILE_SHAPES) and any(sh["L"] % 4 != 0 for sh in MANY_TILE_SHAPES)    # both load paths
+
+
 def _stub_env(n):
     def touched(*a, **k):
         raise AssertionError("the argument checks come before the env is used")
