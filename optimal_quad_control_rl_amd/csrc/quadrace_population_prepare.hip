@@ -4,7 +4,7 @@
 //   qr_ppo_population_load_bank   ONE launch, grid (ceil(kTotalHalf8 / 256), P): slot first_slot + p of a policy bank <- both images of member p's
 //                                 actor, packed on the device from the member's flat parameter vector.  ppo_pack_kernel's index arithmetic for
 //                                 net 0 (quadrace_ppo.hip) restated, plus the low pieces with the rule of pack_policy_images (quadrace_policy.hip).
-//   qr_ppo_population_prepare     FOUR launches, a member index in the grid as in ppo_population_grad_kernel, then one blocking copy:
+//   qr_ppo_population_prepare     FOUR launches, a member index in the grid as in ppo_grad_kernel's member mode, then one blocking copy:
 //       value     population_value_kernel: policy_forward<L> with the member's VALUE image over its K E rollout rows, its E last_obs rows and
 //                 (time-limit bootstrap) its K E term_obs rows, read in place from the shared [K][N][..] arrays of the collect launch; a
 //                 256-row tile of term_obs without a truncation is not evaluated (term_val = 0 there)

@@ -1,9 +1,9 @@
 // quadrace_ppo_device.hpp -- what the PPO update kernels of more than one translation unit are built from: parameter / image / partial
 // layouts (NetOff, PpoDims, DenseMap), the device-resident control block, the gradient kernel's argument block and device functions
 // (MFMA layers, transposed LDS reads, exchange area, partial stores), the apply kernel's argument block, gradient reduction and image
-// scatter, and the host-side qr_ppo handle.  Moved here VERBATIM from quadrace_ppo.hip (which keeps every kernel and the C ABI) when
-// quadrace_ppo_population.hip needed them: device functions only, all inlined, so the existing code objects do not move
-// (tools/isa_digest.py).  No kernel lives here.
+// scatter, and the host-side qr_ppo handle.  Moved here VERBATIM from quadrace_ppo.hip (which keeps its other kernels and the C ABI) when
+// quadrace_ppo_population.hip needed them: device functions, all inlined, so the existing code objects do not move
+// (tools/isa_digest.py).  ONE kernel lives here, the one both units launch: ppo_grad_kernel (a template; each unit instantiates its mode).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -692,6 +692,405 @@ __device__ __forceinline__ void chain_stats_out(const PpoBatch& a, float (&wsum)
         wo[1] = make_float4(wsum[4], wsum[5], wsum[6], wsum[7]);
     }
 }
+
+// One member's entry of the device-resident table: everything its workgroups need, found from blockIdx alone.
+struct PopMember {
+    PpoBatch b;          // rollout arrays, B, G, clip, vf_coef, ent_coef, stop, theta, images, wave_out, stats as fill_batch() sets them;
+                         // idx = the member's WHOLE permutation, acc = its WHOLE advantage-sum table (the kernels add k B / 2 k)
+    void* partial;       // the member's partial buffer (bf16 or f32: the launch knows)
+    float *theta, *m, *v;
+    PpoCtrl* ctrl;
+    float max_norm, beta1, beta2, eps;
+    float kl_limit;      // 1.5 * target_kl * B; <= 0: no early stop
+    int pad_;
+    // scratch owned by the population object, rewritten by every minibatch's reduce launch and read by its step launch
+    float* grad;         // [workgroups * kApplyThreads] gradient element of thread j
+    float* sq;           // [workgroups] squared sums, as floats
+    float* mb;           // [0..3] the last block's red[4..7]; [4], [5] as int: PpoCtrl::stop / adam_t before this minibatch
+};
+
+// kMember = false (quadrace_ppo.hip, grid (wgs, 2)): the minibatch `a` and its `partial` are the kernel arguments; table = nullptr, k = 0.
+// kMember = true (quadrace_ppo_population.hip, grid (wgs, 2, P)): the workgroup takes both from ITS member's entry of the device-resident
+// table (the address derives from blockIdx.z alone: scalar loads, and what the other mode holds in kernel-argument registers sits in the
+// same kind of register here) at minibatch k, a launch argument; `a` and `partial` are passed empty.  The table is zero-filled before the
+// host sets its fields, so a profiling build stamps nothing in this mode (a.ticks == nullptr).
+// ONE template with real __restrict__ parameters and the mode's prologue under `if constexpr`: both modes' code objects are the ones the
+// two separate kernels had, up to kernel-argument offsets ("A variant of a pinned kernel without a copy").
+template <int L, typename PT, bool kMember>
+__global__ void __launch_bounds__(512, 1)
+ppo_grad_kernel(PpoBatch a, PT* __restrict__ partial, const PopMember* __restrict__ table, int k) {
+    using D = PpoDims<L>;
+    using P = PolicyDims<L>;
+    constexpr int KS1 = P::kSteps1;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half8* W = reinterpret_cast<half8*>(smem);
+    half8* E = W + D::kImage;
+    const unsigned lds_base = (unsigned)(size_t)smem;
+    if constexpr (kMember) {   // the member of this workgroup and its minibatch k, in the form the other mode receives as kernel arguments
+        const PopMember& M = table[blockIdx.z];
+        a = M.b;
+        a.idx += (size_t)k * a.B;
+        a.acc += 2 * k;
+        partial = reinterpret_cast<PT*>(M.partial);
+    }
+    const int net = blockIdx.y;
+    const int stop_flag = *a.stop;
+#if defined(QR_PHASE_TIMING) && defined(QR_TICK_PASS)
+    const int pass = QR_TICK_PASS;   // (shadowed by the pass loops' own counter)
+#undef QR_TICK_GATE
+#define QR_TICK_GATE (pass == QR_TICK_PASS)
+#endif
+    PPO_TICK(a, 0);
+#ifdef QR_PHASE_TIMING
+    PPO_WALL(a.ticks, (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (threadIdx.x >> 6)) * 16 + 14);
+#endif
+    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int role = wave8 >> 2;          // 0: chain wave, 1: dW wave (wave-uniform: every branch on it is whole-wave)
+    const int wave = wave8 & 3;           // chain: the wave's 32-sample tile; dW: its 2 x 2 block of weight tiles
+    const int et = wave & 1;
+    const int O = net == 0 ? 4 : 1;
+    PT* gn = partial + ((size_t)blockIdx.x * 2 + net) * D::kRawSlots;   // accumulator-order partial of (workgroup, net)
+    const float scale = 1.0f / (float)a.B;
+    const int pairs = (a.G + 1) / 2;   // passes of 2 sample groups = 128 samples
+    const f32x16p zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // The pass loop is written out per role (loop unswitching by hand): inside ONE loop the dW waves' persistent accumulators would be
+    // live through the chain waves' branch as well (the compiler does not know that a wave never changes its role) and spill.
+    if (role == 0) {
+    for (int pair = blockIdx.x, pass = 0; pair < pairs; pair += gridDim.x, ++pass) {
+        // Everything derived from the lane index is formed INSIDE the pass loop, behind an opaque copy: as loop invariants the image
+        // addresses, identity operands and lane constants were hoisted in front of the loop and kept alive through the whole kernel
+        // (89 spilled registers and a scratch segment, i.e. the runtime's scratch set-up on every launch).
+        int lane = (int)(threadIdx.x & 63), tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(lane), "+v"(tid));
+        const int c = lane & 31, h = lane >> 5;
+        float* stash = reinterpret_cast<float*>(E + kExHalf8) + wave * 32 + c;
+            // =========================================== chain waves ===========================================================
+            const int g = 2 * pair + (wave >> 1);
+            const bool live = g < a.G;   // whole wave; a wave without samples runs on row 0 with zero deltas (it shares the barriers)
+            // (Measured and dropped: under qr_ppo_epoch's device shuffle the row index is a computable bijection of the position, so
+            // the kernel could form it instead of loading it -- one dependent round trip less, 3.4 k of the prologue's 7.7 k cycles
+            // in a probe that skipped the index.  The 8-round Feistel + key derivation in front of the gather cost as much as the
+            // trip saved: epoch graph 38.4 -> 39.4 us per update at 16 384 rows, 70 -> 75 us at 65 536.  tools/exp_patches/ppo_noidx.patch keeps the probe.)
+            // a minibatch need not be a multiple of 64 rows (the reference's batch_size is 5000, R:792): positions past B in the last
+            // group read the minibatch's last row and carry zero loss gradients, like the rows of a wave without samples
+            const int pos = (live ? g : a.G - 1) * 64 + 32 * et + c;
+            const bool row_ok = pos < a.B;
+            const int b = a.idx[row_ok ? pos : a.B - 1];
+            float xin[KS1][8];
+            {
+                const float* row = a.obs + (size_t)b * L;
+#pragma unroll
+                for (int s = 0; s < KS1; ++s)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int k = 16 * s + 8 * h + j;
+                        xin[s][j] = row[k < L ? k : L - 1];
+                    }
+            }
+            const float4 act_v = net == 0 ? reinterpret_cast<const float4*>(a.act)[b] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const float old_logp_in = a.old_logp[b], adv_in = a.adv[b], ret_in = a.ret[b];
+            const double acc_s1 = a.acc[0], acc_s2 = a.acc[1];
+            float log_std_v[4];
+            {
+                const float* log_std = a.theta + net_off(L, 4).total + net_off(L, 1).total;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) log_std_v[k] = log_std[k];
+            }
+            // Pass 0: the dW waves stage the operand image layer by layer and release one barrier per layer ([A] W1, [B] W2, [C] W3,
+            // [S0] W4): the forward pass starts as soon as W1 is in LDS and runs while the other 72 KB arrive (staging the whole
+            // image before the first layer was the long pole of the prologue: 8.2 k of 9.7 k cycles).  Later passes: [S0] only.
+            __syncthreads();   // pass 0: [A] W1 staged / later passes: [S0] the dW waves have finished with the exchange area
+            if (stop_flag) return;   // uniform over the grid (member mode: over the member's workgroups)
+            PPO_TICK(a, 1);
+            if (h == 0) {
+                stash[0 * kStashRows] = act_v.x;
+                stash[1 * kStashRows] = act_v.y;
+                stash[2 * kStashRows] = act_v.z;
+                stash[3 * kStashRows] = act_v.w;
+                stash[4 * kStashRows] = old_logp_in;
+                stash[5 * kStashRows] = adv_in;
+                stash[6 * kStashRows] = ret_in;
+            }
+            half8 in[KS1];
+#pragma unroll
+            for (int s = 0; s < KS1; ++s) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = 16 * s + 8 * h + j;
+                    v[j] = k < L ? xin[s][j] : (k == L ? 1.0f : 0.0f);
+                }
+                in[s] = sat_pack(v);
+            }
+            const bool valid = h == 0 && live && row_ok;
+            // ---- forward: the activations stay in registers until they have been published for their layer's weight gradient
+            constexpr bool kHM = true;    // ReLU-derivative bits are taken from the published activations in the backward pass (see mlp_layer_bwd)
+            uint32_t m1[2] = {0u, 0u}, m2[2] = {0u, 0u}, m3[2] = {0u, 0u};
+            half8 h1[8], h2[8], h3[8];
+            // this wave's own packs in the h region of the exchange area, as this lane wrote them (packs_to_lds): even / odd pack index
+            const u32x4p* hm_e = reinterpret_cast<const u32x4p*>(E + 4 * 8 * 64 + wave * 8 * 64) + (lane ^ (h << 2));
+            const u32x4p* hm_o = reinterpret_cast<const u32x4p*>(E + 4 * 8 * 64 + wave * 8 * 64) + (lane ^ ((h | 2) << 2));
+            mlp_layer<KS1, false, true, kHM>(W, lane, in, h1, m1);
+            PPO_TICK(a, 2);
+            if (pass == 0) __syncthreads();   // [B] W2 staged
+            mlp_layer<8, false, true, kHM>(W + P::kOff2, lane, h1, h2, m2);
+            PPO_TICK(a, 3);
+            if (pass == 0) __syncthreads();   // [C] W3 staged
+            mlp_layer<8, false, true, kHM>(W + P::kOff3, lane, h2, h3, m3);
+            PPO_TICK(a, 4);
+            if (pass == 0) __syncthreads();   // [S0] W4 staged
+            half8 w4[8], w4t[4];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) w4[s] = W[P::kOff4 + s * 64 + (lane ^ ((h | ((s & 1) << 1)) << 2))];
+            {
+                const unsigned a40 = lds_base + tr_lane_out(lane, 0, true) + 16u * (unsigned)P::kOff4;
+                const unsigned a41 = lds_base + tr_lane_out(lane, 1, true) + 16u * (unsigned)P::kOff4;
+                w4t[0] = lds_tr_pair2<16 * 128 * 0>(a40, a41);
+                w4t[1] = lds_tr_pair2<16 * 128 * 1>(a40, a41);
+                w4t[2] = lds_tr_pair2<16 * 128 * 2>(a40, a41);
+                w4t[3] = lds_tr_pair2<16 * 128 * 3>(a40, a41);
+            }
+            float out4[4];
+            {
+                f32x16p acc = zero;
+#pragma unroll
+                for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w4[s], h3[s], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out4[r] = acc[r];
+            }
+            // ---- per-sample loss gradients (x B; the 1/B of the batch means is applied when the tiles are stored)
+            float wsum[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            const float* st_ = stash;
+            float dout[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (net == 0) {
+                const float act[4] = {st_[0 * kStashRows], st_[1 * kStashRows], st_[2 * kStashRows], st_[3 * kStashRows]};
+                const float old_logp_v = st_[4 * kStashRows], adv_v = st_[5 * kStashRows];
+                float z[4], inv_std[4], logp = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float ls = log_std_v[k];
+                    inv_std[k] = __expf(-ls);
+                    z[k] = (act[k] - out4[k]) * inv_std[k];
+                    logp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;
+                }
+                const float log_ratio = valid ? logp - old_logp_v : 0.0f;
+                const float ratio = __expf(log_ratio);
+                const double amean = acc_s1 / a.B;
+                const double avar = fmax((acc_s2 - a.B * amean * amean) / (a.B > 1 ? a.B - 1 : 1), 0.0);
+                const float A = valid ? (adv_v - (float)amean) * (float)(1.0 / (sqrt(avar) + 1e-8)) : 0.0f;
+                const bool flows = A >= 0.0f ? (ratio <= 1.0f + a.clip) : (ratio >= 1.0f - a.clip);
+                const float gl = (flows && valid) ? -A * ratio : 0.0f;
+                float dls[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    dout[k] = gl * z[k] * inv_std[k];
+                    dls[k] = gl * (z[k] * z[k] - 1.0f);
+                }
+                const float clipped_ratio = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
+                // per-lane terms of the minibatch statistics; their wave sums are formed AFTER d3 (below), where this wave would
+                // otherwise wait for the dW waves at [S2]: nothing downstream in the chain needs them
+#pragma unroll
+                for (int k = 0; k < 4; ++k) wsum[k] = dls[k];
+                wsum[4] = valid ? -fminf(A * ratio, A * clipped_ratio) : 0.0f;
+                wsum[5] = valid ? (ratio - 1.0f) - log_ratio : 0.0f;
+                wsum[6] = valid && fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
+            } else {
+                const float err = valid ? out4[0] - st_[6 * kStashRows] : 0.0f;
+                dout[0] = a.vf_coef * 2.0f * err;
+                wsum[4] = err * err;
+            }
+            PPO_TICK(a, 5);
+            // ---- layer 4 operands: d4 (k-slot (h, j) = output unit 8 h + j) transposed by the identity MFMA, h3 as natural packs
+            half8 d4;
+            {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (j < 4 && valid) ? dout[j < 4 ? j : 0] : 0.0f;
+                d4 = sat_pack(v);
+                half8 id;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) id[j] = (8 * h + j == c) ? (_Float16)1.0f : (_Float16)0.0f;
+                const f32x16p acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(d4, id, zero, 0, 0, 0);
+                E[(0 * 8 + 2 * wave) * 64 + lane] = plain_pack(acc, 0);
+                E[(0 * 8 + 2 * wave + 1) * 64 + lane] = plain_pack(acc, 1);
+            }
+            packs_to_lds(h3, E + 4 * 8 * 64, wave, lane);
+            __syncthreads();   // [S1] layer-4 operands published
+            PPO_TICK(a, 6);
+            // d3 = (W4^T d4) * relu'(z3) -- registers and the image only, while the dW waves form dW4
+            half8 dA[8], dB[8];
+            lds_tr_wait<0>(w4t[0], w4t[1]);
+            lds_tr_wait<0>(w4t[2], w4t[3]);
+            u32x4p hm3[2][4];   // h3 (published before [S1]) read back half a layer at a time: 16 registers, not 32
+            if constexpr (kHM) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hm3[0][k] = ((k & 1) ? hm_o : hm_e)[k * 64];
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const f32x16p acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w4t[t], d4, zero, 0, 0, 0);
+                if constexpr (kHM) {
+                    if (t == 1) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) hm3[1][k] = ((k & 1) ? hm_o : hm_e)[(4 + k) * 64];
+                    }
+                    dA[2 * t] = mask_pack_h(acc, 0, hm3[t >> 1][2 * (t & 1)]);
+                    dA[2 * t + 1] = mask_pack_h(acc, 1, hm3[t >> 1][2 * (t & 1) + 1]);
+                } else {
+                    dA[2 * t] = mask_pack(acc, m3[t >> 1], t, 0);
+                    dA[2 * t + 1] = mask_pack(acc, m3[t >> 1], t, 1);
+                }
+            }
+            chain_stats_out(a, wsum, net, live, lane, g, et, scale);
+            PPO_TICK(a, 7);
+            __syncthreads();   // [S2] the dW waves are done reading the layer-4 operands
+            packs_to_lds(dA, E, wave, lane);
+            packs_to_lds(h2, E + 4 * 8 * 64, wave, lane);
+            __syncthreads();   // [S3] layer-3 operands published
+            PPO_TICK(a, 8);
+            mlp_layer_bwd<P::kOff3, kHM>(lds_base + tr_lane_hidden(lane, 0, true), lds_base + tr_lane_hidden(lane, 1, true), dA, dB, m2, hm_e, hm_o);   // d2
+            PPO_TICK(a, 9);
+            __syncthreads();   // [S4]
+            packs_to_lds(dB, E, wave, lane);
+            packs_to_lds(h1, E + 4 * 8 * 64, wave, lane);
+            __syncthreads();   // [S5] layer-2 operands published
+            PPO_TICK(a, 10);
+            mlp_layer_bwd<P::kOff2, kHM>(lds_base + tr_lane_hidden(lane, 0, true), lds_base + tr_lane_hidden(lane, 1, true), dB, dA, m1, hm_e, hm_o);   // d1
+            PPO_TICK(a, 11);
+            __syncthreads();   // [S6]
+            // ---- layer 1 operands: d1 as natural packs, x0 transposed by the identity MFMA (column unit = input index)
+            packs_to_lds(dA, E, wave, lane);
+#pragma unroll
+            for (int ut = 0; ut < D::kIT; ++ut) {
+                f32x16p acc = zero;
+#pragma unroll
+                for (int s = 0; s < KS1; ++s) {
+                    half8 id;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) id[j] = (16 * s + 8 * h + j == 32 * ut + c) ? (_Float16)1.0f : (_Float16)0.0f;
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(in[s], id, acc, 0, 0, 0);
+                }
+                E[((4 + ut) * 8 + 2 * wave) * 64 + lane] = plain_pack(acc, 0);
+                E[((4 + ut) * 8 + 2 * wave + 1) * 64 + lane] = plain_pack(acc, 1);
+            }
+            __syncthreads();   // [S7] layer-1 operands published
+            PPO_TICK(a, 12);
+            // (a later pass: this wave's next gather is issued while the dW waves finish; [S0] keeps the exchange area and the stash)
+        }
+    } else {
+        // The operand image (80 KB) is staged by THESE four waves -- they have nothing else to do until the first operands are
+        // published and nothing else live in their registers -- while the chain waves' gather is in flight.  ALL loads are issued
+        // up front in layer order (one burst of kImgLoads x 16 bytes per thread; loads return in order), then each layer is written
+        // to LDS and released with its own barrier, so that the chain waves' forward pass overlaps the rest of the staging.
+        // Every workgroup walks a layer's chunks in a different rotation: all workgroups of a network read the SAME 80 KB, and in
+        // the same order they would all be queueing on one L2 channel at a time.
+        {
+            const f32x4p* src = reinterpret_cast<const f32x4p*>(a.images + (size_t)net * D::kImage);
+            f32x4p* dst = reinterpret_cast<f32x4p*>(W);
+            const int t256 = (int)(threadIdx.x & 255);
+            constexpr int n1 = P::kOff2 / 256, n2 = (P::kOff3 - P::kOff2) / 256, n3 = (P::kOff4 - P::kOff3) / 256, n4 = (D::kImage - P::kOff4) / 256;
+            static_assert(P::kOff2 % 256 == 0 && P::kOff3 % 256 == 0 && P::kOff4 % 256 == 0 && D::kImage % 256 == 0, "image layers are whole 256-chunk blocks");
+            const int rot = (int)blockIdx.x;
+            f32x4p i1[n1], i2[n2], i3[n3], i4[n4];
+#pragma unroll
+            for (int q = 0; q < n1; ++q) i1[q] = src[((q + rot) % n1) * 256 + t256];
+#pragma unroll
+            for (int q = 0; q < n2; ++q) i2[q] = src[P::kOff2 + ((q + rot) % n2) * 256 + t256];
+#pragma unroll
+            for (int q = 0; q < n3; ++q) i3[q] = src[P::kOff3 + ((q + rot) % n3) * 256 + t256];
+#pragma unroll
+            for (int q = 0; q < n4; ++q) i4[q] = src[P::kOff4 + ((q + rot) % n4) * 256 + t256];
+            auto put = [&](int i, const f32x4p& v) { dst[i ^ (((i >> 5) & 3) << 2)] = v; };   // chunk swizzle: conflict-free transposed reads
+#pragma unroll
+            for (int q = 0; q < n1; ++q) put(((q + rot) % n1) * 256 + t256, i1[q]);
+            __syncthreads();   // [A] W1 staged
+            if (stop_flag) return;   // uniform over the grid (the chain waves leave at the same barrier)
+#pragma unroll
+            for (int q = 0; q < n2; ++q) put(P::kOff2 + ((q + rot) % n2) * 256 + t256, i2[q]);
+            __syncthreads();   // [B] W2 staged
+#pragma unroll
+            for (int q = 0; q < n3; ++q) put(P::kOff3 + ((q + rot) % n3) * 256 + t256, i3[q]);
+            __syncthreads();   // [C] W3 staged
+#pragma unroll
+            for (int q = 0; q < n4; ++q) put(P::kOff4 + ((q + rot) % n4) * 256 + t256, i4[q]);
+        }
+        PPO_TICK(a, 1);   // (profiling build) image staged: compare with the chain waves' release from [S0]
+        // weight-gradient accumulators, live across the passes (initialised AFTER the staging burst: its 80 registers are free again)
+        f32x16p dw4 = zero, dw3[2][2] = {{zero, zero}, {zero, zero}}, dw2[2][2] = {{zero, zero}, {zero, zero}}, dw1[2][2] = {{zero, zero}, {zero, zero}};
+    for (int pair = blockIdx.x, pass = 0; pair < pairs; pair += gridDim.x, ++pass) {
+        // Everything derived from the lane index is formed INSIDE the pass loop, behind an opaque copy: as loop invariants the image
+        // addresses, identity operands and lane constants were hoisted in front of the loop and kept alive through the whole kernel
+        // (89 spilled registers and a scratch segment, i.e. the runtime's scratch set-up on every launch).
+        int lane = (int)(threadIdx.x & 63), tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(lane), "+v"(tid));
+        const unsigned ex_lane0 = lds_base + 16u * (unsigned)D::kImage + ex_lane_const(lane, 0);   // exchange area + lane
+        const unsigned ex_lane1 = lds_base + 16u * (unsigned)D::kImage + ex_lane_const(lane, 1);   // constants (two reads)
+            // ============================================= dW waves ============================================================
+            __syncthreads();   // [S0]
+            if (stop_flag) return;
+            // The weight-gradient accumulators of ALL four layers live in this wave's registers across the passes of a large
+            // minibatch (16 + 64 + 64 + 16 kIT VGPRs): a later pass accumulates on the matrix core instead of reading its partial
+            // back and adding (round 2: a read-modify-write of 126 KB per workgroup and pass), and the partial leaves ONCE, in the
+            // last pass: each layer as soon as it is complete, in accumulator order (16 stores of one contiguous run per lane and
+            // hidden layer -- as 64 row-segment stores per lane they queued for ~9 k cycles per layer and had to be deferred to the
+            // end), written through L2 (store_dw_tile_raw) so that they drain under the remaining layers.
+            const bool last = pair + (int)gridDim.x >= pairs;
+            const int to0 = 2 * (wave >> 1), ti0 = 2 * (wave & 1);
+            __syncthreads();   // [S1]
+            PPO_TICK(a, 6);
+            dw_tile_old_tr_half<0>(E, ex_lane0 + 2048u * (unsigned)wave, ex_lane1 + 2048u * (unsigned)wave, lane, dw4);   // tile (0, wave)
+            dw_tile_old_tr_half<4>(E, ex_lane0 + 2048u * (unsigned)wave, ex_lane1 + 2048u * (unsigned)wave, lane, dw4);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();   // [S2] operands consumed (the MFMAs have them in registers): the chain may overwrite them
+            PPO_TICK(a, 7);
+            __syncthreads();   // [S3]
+            PPO_TICK(a, 8);
+            dw_block_tr(ex_lane0 + 2048u * (unsigned)to0, ex_lane1 + 2048u * (unsigned)to0, ex_lane0 + 2048u * (unsigned)ti0, ex_lane1 + 2048u * (unsigned)ti0, dw3);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();   // [S4]
+            if (last) store_dw_tile_raw<PT>(dw4, gn + (D::kRawT4 + wave) * 1024, O, lane, scale);   // 1 tile: cheap
+            if (last) {   // dW3 is complete: its partial drains while dW2 / dW1 are formed
+#pragma unroll
+                for (int bt = 0; bt < 2; ++bt)
+#pragma unroll
+                    for (int bi = 0; bi < 2; ++bi) store_dw_tile_raw<PT, true>(dw3[bt][bi], gn + (D::kRawT3 + 4 * (to0 + bt) + ti0 + bi) * 1024, kH - 32 * (to0 + bt), lane, scale);
+            }
+            PPO_TICK(a, 9);
+            __syncthreads();   // [S5]
+            PPO_TICK(a, 10);
+            dw_block_tr(ex_lane0 + 2048u * (unsigned)to0, ex_lane1 + 2048u * (unsigned)to0, ex_lane0 + 2048u * (unsigned)ti0, ex_lane1 + 2048u * (unsigned)ti0, dw2);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();   // [S6]
+            PPO_TICK(a, 11);
+            __syncthreads();   // [S7] (arrive BEFORE the layer-2 stores: the chain waves are released to their next gather at once)
+            PPO_TICK(a, 12);
+            if (last) {   // likewise dW2 (the chain waves are past their last barrier of this pass)
+#pragma unroll
+                for (int bt = 0; bt < 2; ++bt)
+#pragma unroll
+                    for (int bi = 0; bi < 2; ++bi) store_dw_tile_raw<PT, true>(dw2[bt][bi], gn + (D::kRawT2 + 4 * (to0 + bt) + ti0 + bi) * 1024, kH - 32 * (to0 + bt), lane, scale);
+            }
+            dw_tiles_tr_old_half<D::kIT, 0>(ex_lane0 + 2048u * (unsigned)wave, ex_lane1 + 2048u * (unsigned)wave, E + 4 * 8 * 64, lane, dw1);   // tiles (wave, 0..kIT-1)
+            dw_tiles_tr_old_half<D::kIT, 4>(ex_lane0 + 2048u * (unsigned)wave, ex_lane1 + 2048u * (unsigned)wave, E + 4 * 8 * 64, lane, dw1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (last) {
+#pragma unroll
+                for (int bi = 0; bi < D::kIT; ++bi) store_dw_tile_raw<PT, true>(dw1[0][bi], gn + (D::kIT * wave + bi) * 1024, kH - 32 * wave, lane, scale);
+            }
+            PPO_TICK(a, 13);
+#ifdef QR_PHASE_TIMING
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            PPO_WALL(a.ticks, (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (threadIdx.x >> 6)) * 16 + 15);
+#endif
+            // ([S0] of the next pass separates these reads from the chain waves' next writes)
+        }
+    }
+}
+
+#if defined(QR_PHASE_TIMING) && defined(QR_TICK_PASS)
+#undef QR_TICK_GATE
+#define QR_TICK_GATE true
+#endif
 
 struct ApplyArgs {
     float *theta, *m, *v;     // parameters and Adam moments (flat, n floats)

@@ -1,0 +1,202 @@
+// quadrace_rollout_group.hpp -- the ONE kernel behind the two grouped closed-loop rollouts: qr_rollout_policy_conditions
+// (quadrace_rollout_cond.hip, kPop = false) and qr_rollout_policy_population (quadrace_rollout_population.hip, kPop = true).  Included by
+// those two units and by nothing else; each keeps its launch function, its checks and its instantiations.
+//
+// K x [obs -> MFMA policy -> a = mean + std * eps -> env.step(clip(a))] with the rollout rows, the terminal-observation rows, last_obs
+// and the end-of-kernel state write-back of rollout_policy_kernel (quadrace_env_kernels.hpp), and the inputs of eval_policy_grid_kernel
+// (quadrace_eval_grid.hip):
+//   * group map: the launch carries num_groups groups x E envs, E a multiple of kBlock, N = num_groups E exactly.  Workgroup b belongs
+//     to group g = b / (E / kBlock) and reads map[g] = (policy slot, condition slot) from an address that derives from blockIdx alone:
+//     a scalar load, and the bases built from it stay in scalar registers, as eval_policy_grid_kernel keeps them.  The host has
+//     validated every index it passes against the banks' capacities.
+//   * condition image: a slot of the condition bank is [CondHeader | reset table | gate rows] (quadrace_device.hpp).  A kernel-local
+//     copy of Params takes num_gates, max_steps, obs_lo and obs_inv from the header (scalar loads: uniform address, memory no store of
+//     this kernel touches), and the workgroup stages the slot's table image into its LDS where rollout_policy_kernel stages
+//     P.tables + kOffResetImage.  The header's gates_per_lap is not used (a rollout counts no laps).  The residual-MLP table, dt,
+//     flags and gates_ahead stay the handle's.
+// What the mode decides, in the prologue and nowhere else:
+//   kPop = false   one policy per launch: the weight image and its low pieces are A.weights / A.weights_lo, the sampling arguments are
+//                  A.std / A.logp_const / A.seed_*; only the condition half of the map entry is read (a 4-byte load); bank, bank_lo and
+//                  table are passed as null.
+//   kPop = true    both halves of the map entry are read (one 8-byte load): the workgroup stages image map[g].x of the policy bank
+//                  (bank + slot * PolicyDims<L>::kTotalHalf8), the f32-class forward reads that slot's low pieces from global memory as
+//                  eval_policy_bank_kernel does, and the sampling arguments are table[g], one 32-byte PopulationEntry
+//                  (quadrace_launch.hpp) read by one scalar load, which stays in scalar registers where the other mode's kernel
+//                  arguments sit.  A's weight pointers and per-launch sampling fields are not read; step_lo / step_hi, deterministic
+//                  and f32class stay launch-wide.
+// Unlike the grid evaluator the reset stream and the action noise are keyed by the handle's ORDINARY env ids (P.gid + i): training
+// wants independent envs, not common random numbers across groups.  Group g therefore computes what an E-env handle with
+// env_id_base + g E, configured with the group's condition, computes under qr_rollout_policy with the group's weights, log_std and seed
+// (tests/test_gpu_rollout_conditions.py and tests/test_gpu_rollout_population.py demand bit equality).
+//
+// The step loop RESTATES rollout_policy_kernel's, statement for statement, the way quadrace_record.hip does, instead of sharing a
+// body with it: that kernel's matrix-instruction schedule is pinned with sched_barriers and its code object must not move
+// (tools/isa_digest.py), so quadrace_env_kernels.hpp is left untouched.  What differs: there are no tail lanes (the host refuses
+// anything else), so every lane is an env, every wave is full, and the `active` / `full_wave` tests are gone.  The two modes, in
+// turn, are one template and not two restatements: a bool mode, real __restrict__ parameters, the mode's prologue under `if constexpr`
+// ("A variant of a pinned kernel without a copy").  The parameter list is the population mode's, the three pointers it alone
+// reads NOT last: of the two orders this is the one under which more of the 40 instantiations kept their code (DESIGN.md has the count).
+#pragma once
+#include "quadrace_env_kernels.hpp"
+#include "quadrace_launch.hpp"
+
+namespace qr {
+
+// conds: slot 0 of the condition bank; map[g] = (policy, condition) of group g; wgs_per_group = E / kBlock; kPop: bank / bank_lo = image 0
+// of the two policy arrays, table[g] = sampling arguments of group g
+template <int V, int GA, bool kF32, bool kPop>
+__global__ void __launch_bounds__(kBlock, 1)
+rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ bank, const half8* __restrict__ bank_lo,
+                            const float* __restrict__ conds, const int2* __restrict__ map, const PopulationEntry* __restrict__ table,
+                            int wgs_per_group, int K, float* __restrict__ obs_out, float4* __restrict__ act_out,
+                            float* __restrict__ logp_out, float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
+                            uint8_t* __restrict__ trunc_out, float* __restrict__ last_obs_out) {
+    constexpr int L = obs_len<V, GA>();
+    using D = PolicyDims<L>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half8* W = reinterpret_cast<half8*>(smem);                                   // policy weights (f16)
+    float* rtab = reinterpret_cast<float*>(smem + (size_t)D::kTotalHalf8 * 16);  // reset table | gate rows | obs tiles
+    float* gates = rtab + kResetTableFloats;
+    // workgroup-uniform (blockIdx only): the group of this workgroup, its map entry, its images, its sampling arguments, and the
+    // handle's Params with the condition's scalars
+    const int grp = (int)blockIdx.x / wgs_per_group;
+    const half8* __restrict__ img;
+    const half8* __restrict__ img_lo;
+    const float* __restrict__ cond;
+    PopulationEntry S;   // std, logp_const, seed_lo, seed_hi of the group
+    if constexpr (kPop) {
+        const int2 pc = map[grp];
+        img = bank + (size_t)pc.x * D::kTotalHalf8;
+        img_lo = bank_lo + (size_t)pc.x * D::kTotalHalf8;
+        cond = conds + (size_t)pc.y * kCondSlotFloats;
+        S = table[grp];
+    } else {
+        img = A.weights;
+        img_lo = A.weights_lo;
+        cond = conds + (size_t)map[grp].y * kCondSlotFloats;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) S.std[c] = A.std[c];
+        S.logp_const = A.logp_const;
+        S.seed_lo = A.seed_lo;
+        S.seed_hi = A.seed_hi;
+    }
+    const CondHeader* __restrict__ hdr = reinterpret_cast<const CondHeader*>(cond);
+    Params P = P0;
+    P.num_gates = hdr->num_gates;
+    P.max_steps = hdr->max_steps;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        P.obs_lo[c] = hdr->obs_lo[c];
+        P.obs_inv[c] = hdr->obs_inv[c];
+    }
+    const int i = blockIdx.x * kBlock + threadIdx.x;   // < P.n: the grid is exactly P.n / kBlock workgroups
+    const int lane = threadIdx.x & 63;
+    Env<V> e;
+    load_env<V>(P, i, e);
+    MlpRegs mlp;
+    const bool use_mlp = (V == kE2E) && (P.flags & kFlagResidual);
+    if (use_mlp) mlp_load_regs(P.tables, lane, mlp);
+    {
+        const float4* s4 = reinterpret_cast<const float4*>(img);
+        float4* d4 = reinterpret_cast<float4*>(W);
+        for (int j = threadIdx.x; j < D::kTotalHalf8; j += kBlock) d4[j] = s4[j];
+    }
+    {   // [reset table | gate rows] of the condition, as stage_tables copies the handle's (counts are multiples of 4)
+        const float4* s4 = reinterpret_cast<const float4*>(cond + kCondHeaderFloats);
+        float4* d4 = reinterpret_cast<float4*>(rtab);
+        const int count4 = (kResetTableFloats + P.num_gates * kGateStride) / 4;
+        for (int j = threadIdx.x; j < count4; j += kBlock) d4[j] = s4[j];
+    }
+    __syncthreads();
+    const uint32_t gid_lo = P.gid_lo + (uint32_t)i;   // ordinary ids: reset stream and noise of env i of the handle
+    const uint32_t gid_hi = P.gid_hi + (gid_lo < P.gid_lo ? 1u : 0u);
+    const size_t n = (size_t)P.n;
+    const int wave_first = i - lane;
+    float* tile = gates + kMaxGates * kGateStride + (threadIdx.x >> 6) * 64 * L;
+    bool any_reset = false;
+    float stash[reset_value_count<V>()];   // the lane's own next reset draws (reset_from_stash)
+    bool stash_ok = false;
+    float o[L];
+    observe<V, GA>(P, gates, e, o);
+    for (int k = 0; k < K; ++k) {
+        // ---- action noise: rollout_policy_kernel's slices, verbatim (drawn in deterministic mode too and then multiplied out); the
+        // Philox key is the group's
+        float mean[4];
+        float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t pc4[4];
+        float bm_u1a, bm_u2a, bm_u1b, bm_u2b, bm_ra, bm_rb, bm_sa, bm_ca, bm_sb, bm_cb;
+        auto pin_u = [](uint32_t& x) { asm volatile("" : "+v"(x)); };
+        auto pin_f = [](float& x) { asm volatile("" : "+v"(x)); };
+        auto noise_slice = [&](int slot) {
+            if (slot >= 1 && slot <= 11) { pin_u(pc4[0]); pin_u(pc4[1]); pin_u(pc4[2]); pin_u(pc4[3]); }
+            if (slot == 12) pin_f(bm_u1a);
+            if (slot == 13) pin_f(bm_u1b);
+            if (slot == 14) pin_f(bm_u2a);
+            if (slot == 15) pin_f(bm_u2b);
+            if (slot == 16) { pin_f(bm_ra); pin_f(bm_rb); pin_f(bm_sa); pin_f(bm_sb); }
+            if (slot == 0) {
+                const uint32_t s_lo = A.step_lo + (uint32_t)k;
+                pc4[0] = gid_lo; pc4[1] = gid_hi; pc4[2] = s_lo; pc4[3] = A.step_hi + (s_lo < A.step_lo ? 1u : 0u);
+            } else if (slot <= 10) {
+                philox4x32_round(pc4, S.seed_lo, S.seed_hi, slot - 1);
+            } else if (slot == 11) {  // Box-Muller: two pairs of normals from four uniforms (u1 in (0,1], u2 in [0,1))
+                bm_u1a = (float)((pc4[0] >> 8) + 1u) * 5.9604644775390625e-8f; bm_u2a = u01(pc4[1]);
+                bm_u1b = (float)((pc4[2] >> 8) + 1u) * 5.9604644775390625e-8f; bm_u2b = u01(pc4[3]);
+            } else if (slot == 12) {
+                bm_ra = fast_sqrt(-2.0f * __logf(bm_u1a));
+            } else if (slot == 13) {
+                bm_rb = fast_sqrt(-2.0f * __logf(bm_u1b));
+            } else if (slot == 14) {
+                qr_sincos(6.283185307179586f * bm_u2a, bm_sa, bm_ca);
+            } else if (slot == 15) {
+                qr_sincos(6.283185307179586f * bm_u2b, bm_sb, bm_cb);
+            } else if (slot == 16) {
+                eps[0] = bm_ra * bm_ca; eps[1] = bm_ra * bm_sa; eps[2] = bm_rb * bm_cb; eps[3] = bm_rb * bm_sb;
+            }
+        };
+        // The observation row of this step (the policy's input) is stored under the third layer's MFMAs: LDS transpose in slot 0,
+        // coalesced block store in slot 2 (every wave is full).
+        auto obs_slice = [&](int slot) {
+            if (slot == 0) obs_tile_write<V, GA>(tile, lane, o);
+            if (slot == 2) obs_tile_flush<V, GA>(tile, obs_out + (size_t)k * n * L, (size_t)wave_first, lane);
+        };
+        if constexpr (kF32) {
+#pragma unroll
+            for (int slot = 0; slot <= 16; ++slot) noise_slice(slot);
+            obs_slice(0);
+            obs_slice(2);
+            policy_forward_f32class<L>(W, img_lo, lane, o, mean);
+        } else {
+            policy_forward<L>(W, lane, o, mean, noise_slice, obs_slice);
+        }
+        float a[4] = {mean[0], mean[1], mean[2], mean[3]};
+        float logp = S.logp_const;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float en = A.deterministic ? 0.0f : eps[c];   // fmaf(std, 0, mean) = mean, fmaf(-0, 0, logp) = logp
+            a[c] = fmaf(S.std[c], en, mean[c]);
+            logp = fmaf(-0.5f * en, en, logp);
+        }
+        // rollout buffer row t: the observation the action was computed from (stored above), the unclipped action, its log-prob
+        stream_store(act_out + (size_t)k * n + i, make_float4(a[0], a[1], a[2], a[3]));
+        stream_store(logp_out + (size_t)k * n + i, logp);
+        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
+                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        bool done, trunc, did_reset;
+        const float reward = step_env<V>(P, gates, rtab, tile, mlp, lane, true, e, u, gid_lo, gid_hi, done, trunc, did_reset,
+                                         [&](bool fin) { store_terminal_obs<V, GA>(P, gates, e, (size_t)k * n, i, fin); },
+                                         [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); });
+        any_reset |= did_reset;
+        stream_store(rew_out + (size_t)k * n + i, reward);
+        stream_store(done_out + (size_t)k * n + i, (uint8_t)(done ? 1 : 0));
+        if (trunc_out) stream_store(trunc_out + (size_t)k * n + i, (uint8_t)(trunc ? 1 : 0));
+        observe<V, GA>(P, gates, e, o);
+    }
+    if (last_obs_out) store_obs_coalesced<V, GA>(tile, last_obs_out, (size_t)wave_first, lane, o);
+    define_exit_values<V>(e);
+    P.ts[i] = pack_ts<V>(e);
+    store_world<V>(P, i, e);
+    if (any_reset) store_dist<V>(P, i, e);
+}
+
+}  // namespace qr

@@ -1,4 +1,4 @@
-"""GPU: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions, rollout_policy_cond_kernel<V, GA, kF32>)
+"""GPU: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions, rollout_policy_group_kernel<V, GA, kF32, false>)
 against the closed-loop rollout itself (qr_rollout_policy), which the existing suite pins.  Group g of a launch must equal a 256-env
 twin handle that was configured with the group's condition through the ordinary Python setters, has env_id_base = g * 256, was seeded
 alike and flown by rollout_policy_device: start state, every output row, the terminal-observation rows, last_obs and the five state
@@ -142,7 +142,7 @@ def _against_twins(variant, gates_ahead, precision, cog):
 
 
 _CASES = [(v, g, p) for v in ("e2e", "indi") for g in (0, 1) for p in ("f16-operands", "f32")]
-# every other instantiation of rollout_policy_cond_kernel<variant, gates_ahead, f32class>
+# every other instantiation of rollout_policy_group_kernel<variant, gates_ahead, f32class, false>
 _CASES += [(v, g, p) for v in ("e2e", "indi") for g in (2, 3, 4) for p in ("f16-operands", "f32")]
 
 

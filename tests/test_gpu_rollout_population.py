@@ -1,4 +1,4 @@
-"""GPU: the closed-loop rollout for a population of policies (qr_rollout_policy_population, rollout_policy_population_kernel<V, GA, kF32>)
+"""GPU: the closed-loop rollout for a population of policies (qr_rollout_policy_population, rollout_policy_group_kernel<V, GA, kF32, true>)
 against the closed-loop rollout itself (qr_rollout_policy) and its condition-mix form (qr_rollout_policy_conditions), which the existing
 suite pins.  Group g of a launch must equal a twin handle of E envs with env_id_base = g E, configured with the group's condition, flown
 by rollout_policy_device with the weights of the group's bank slot in an MfmaPolicy, the group's log_std and the group's noise seed:

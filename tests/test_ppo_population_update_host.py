@@ -95,9 +95,13 @@ def test_the_device_table_entry_and_the_kernels_are_where_the_header_says():
     from optimal_quad_control_rl_amd import build
 
     text = open(os.path.join(build.CSRC, "quadrace_ppo_population.hip")).read()
-    for kernel in ("ppo_population_grad_kernel", "ppo_population_reduce_kernel", "ppo_population_step_kernel", "ppo_population_lr_kernel"):
+    for kernel in ("ppo_population_reduce_kernel", "ppo_population_step_kernel", "ppo_population_lr_kernel"):
         assert re.search(r"__global__[^;{]*\b%s\b" % kernel, text), kernel
+    # the gradient kernel is the one both PPO units share: a template with a member mode in the shared header, instantiated here
+    shared = open(os.path.join(build.CSRC, "quadrace_ppo_device.hpp")).read()
+    assert re.search(r"template\s*<[^>]*\bbool kMember\b[^>]*>\s*__global__[^;{]*\bppo_grad_kernel\b", shared)
     code = re.sub(r"//[^\n]*", "", text)
+    assert len(re.findall(r"ppo_grad_kernel<L, \w+, true>\), dim3\(wgs, 2, P\)", code)) == 2
     # no inter-workgroup wait of any kind in the new unit
     for word in ("atomic", "s_sleep", "Cooperative", "__threadfence", "arrive", "barrier_timeouts"):
         assert word not in code, word
