@@ -55,7 +55,8 @@ extern "C" {
                              qr_condition_bank_* / qr_evaluate_policy_grid (round 11), qr_rollout_policy_conditions (round 12),
                              qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14),
                              qr_ppo_population_create / _destroy / _epoch / _status (round 15),
-                             qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16) */
+                             qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16),
+                             qr_ppo_population_exploit (round 18) */
 
 enum {
     QR_OK = 0,
@@ -642,6 +643,32 @@ int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* thet
 int qr_policy_bank_read(const qr_policy_bank* bank, int32_t slot, int32_t which, void* out_host, size_t bytes);
 int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_shared* sh, const qr_ppo_prepare_member* members,
                               double* report_host, void* stream);
+
+/* ---- exploit: overwrite members of a population with copies of other members, in one launch (csrc/quadrace_ppo_population.hip) ---------
+ * The device half of population-based training.  theta_dev, adam_m_dev, adam_v_dev: HOST arrays [P] of device pointers to the members'
+ * flat parameter vectors and Adam moments (as qr_ppo_population_load_bank takes theta_dev).  src_of: HOST array [P]; src_of[p] == p leaves
+ * member p alone, any other value s makes p a DESTINATION and s its SOURCE.  log_std_shift: HOST array [P], or NULL for all zeros; only
+ * the destinations' entries are used.
+ * For every destination p with source s, in ONE launch for all destinations (grid (ceil(n / 256), destinations); no launch at all when
+ * there is none): theta[p] <- theta[s], m[p] <- m[s], v[p] <- v[s]; the four log_std entries of theta[p] become
+ * theta[s][n - 4 + i] + log_std_shift[p] (one float32 add, also when the shift is 0); both f16 operand images of handle p are rewritten
+ * from the new vector, element by element with qr_ppo_pack's gather (padding and the constant-1 bias unit included); PpoCtrl::adam_t of p
+ * <- that of s, copied on the device.  Everything else in p's handle stays p's own -- stop flag, applied / skipped counts, barrier words,
+ * lr, shuffle seed and count, target_kl, partial buffers, stats_dev -- and so do its rollout buffers and envs.  Members that are not
+ * destinations are not touched at all.
+ * CONTRACT: afterwards member p is bit for bit where this composition of existing calls leaves it: three hipMemcpy device-to-device copies
+ * from s, a float32 add of the shift into the last four entries of theta[p], qr_ppo_pack(p, theta[p]), qr_ppo_adam_step(p, &t_s, set) --
+ * theta, both Adam moments, the operand images, the Adam step count, and an untouched status quadruple, shuffle state and stats.  A later
+ * qr_ppo_population_epoch or qr_ppo_epoch on any member runs exactly as after the composition, and their cached graphs stay valid: no
+ * pointer moved.
+ * A plain launch on `stream`: no host read, no graph, no atomic, no flag, no workgroup that waits for another.  Which member takes whom and
+ * the shifts ride in the kernel arguments; the table of the members' pointers is device-resident, owned by the population object, and
+ * uploaded with a stream-ordered copy and one synchronisation of `stream` when a pointer moved -- in practice by the first call only.
+ * Refused before anything is launched (QR_E_INVALID, qr_last_error set, all buffers untouched): a NULL pop, pointer array, array entry
+ * or src_of; an index outside [0, P); a source that is itself a destination (src_of[src_of[p]] != src_of[p]: one launch may not read what
+ * it writes); a non-finite entry of log_std_shift; and a `stream` that is being captured by the caller. */
+int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, float* const* adam_m_dev, float* const* adam_v_dev,
+                              const int32_t* src_of, const float* log_std_shift, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

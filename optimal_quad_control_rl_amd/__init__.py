@@ -10,7 +10,7 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
-           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO"]
+           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -50,10 +50,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import policy
 
         return policy.MfmaPolicyBank
-    if name == "PopulationPPO":  # P PPO learners on one env, one collect launch per round (qr_rollout_policy_population)
+    if name in ("PopulationPPO", "PBT"):  # P PPO learners on one env, one collect launch per round (qr_rollout_policy_population); PBT: their selection schedule
         from . import population
 
-        return population.PopulationPPO
+        return getattr(population, name)
     if name == "ShardedRaceEnv":
         from . import sharded
 

@@ -123,6 +123,7 @@ SIGNATURES = {
     "qr_ppo_population_load_bank": (C.c_int, [_vp, C.POINTER(_vp), _vp, C.c_int32, _vp]),
     "qr_policy_bank_read": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t]),
     "qr_ppo_population_prepare": (C.c_int, [_vp, C.POINTER(QrPpoPrepareShared), C.POINTER(QrPpoPrepareMember), C.POINTER(C.c_double), _vp]),
+    "qr_ppo_population_exploit": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _f32p, _vp]),
     # include/quad3d.h (predecessor environments of "3D quad.ipynb")
     "q3_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)]),
     "q3_destroy": (C.c_int, [_vp]),
@@ -153,7 +154,7 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
                     "q3_evaluate_policy_bank", "qr_rollout_policy_population", "qr_ppo_population_create", "qr_ppo_population_destroy",
                     "qr_ppo_population_epoch", "qr_ppo_population_status", "qr_ppo_population_load_bank", "qr_policy_bank_read",
-                    "qr_ppo_population_prepare")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_ppo_population_prepare", "qr_ppo_population_exploit")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

@@ -45,39 +45,10 @@ namespace qr {
 template <int L>
 __global__ void __launch_bounds__(256) ppo_pack_kernel(const float* __restrict__ theta, half8* __restrict__ images) {
     using D = PpoDims<L>;
-    using P = PolicyDims<L>;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int net = blockIdx.y;
     if (e >= D::kImage) return;
-    const int O = net == 0 ? 4 : 1;
-    const float* th = theta + (net == 0 ? 0 : net_off(L, 4).total);
-    const NetOff o = net_off(L, O);
-    const int lane = e & 63, c = lane & 31, h = lane >> 5;
-    half8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float val = 0.0f;
-        if (e < P::kOff2) {  // layer 1: row = output unit, k = input index (natural order), input L = constant 1
-            const int t = e / (P::kSteps1 * 64), s = (e / 64) % P::kSteps1;
-            const int row = 32 * t + c, k = 16 * s + 8 * h + j;
-            if (row < kH) val = k < L ? th[o.w1 + row * L + k] : (k == L ? th[o.b1 + row] : 0.0f);
-            else val = (row == kPolBiasUnit && k == L) ? 1.0f : 0.0f;
-        } else if (e < P::kOff4) {  // layers 2, 3: k-slots named in accumulator-row order
-            const bool third = e >= P::kOff3;
-            const int e2 = e - (third ? P::kOff3 : P::kOff2);
-            const int t = e2 / 512, sp = (e2 / 64) % 8;
-            const int row = 32 * t + c, hid = 32 * (sp >> 1) + rho_(8 * (sp & 1) + j, h);
-            const int ow = third ? o.w3 : o.w2, ob = third ? o.b3 : o.b2;
-            if (row < kH) val = hid < kH ? th[ow + row * kH + hid] : (hid == kPolBiasUnit ? th[ob + row] : 0.0f);
-            else val = (row == kPolBiasUnit && hid == kPolBiasUnit) ? 1.0f : 0.0f;
-        } else {  // output layer: rows 0..O-1 of one 32-row tile
-            const int sp = (e - P::kOff4) / 64;
-            const int hid = 32 * (sp >> 1) + rho_(8 * (sp & 1) + j, h);
-            if (c < O) val = hid < kH ? th[o.w4 + c * kH + hid] : (hid == kPolBiasUnit ? th[o.b4 + c] : 0.0f);
-        }
-        v[j] = (_Float16)val;
-    }
-    images[(size_t)net * D::kImage + e] = v;
+    images[(size_t)net * D::kImage + e] = pack_gather<L>(theta, net, e);   // quadrace_ppo_device.hpp
 }
 
 // ---- adv_stats: sum and sum of squares of the advantages of minibatch mb = blockIdx.y, rows idx[mb * B + 0..B), into

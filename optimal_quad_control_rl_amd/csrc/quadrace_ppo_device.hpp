@@ -1253,8 +1253,44 @@ __device__ __forceinline__ float reduce_grad_element(const ApplyArgs& a, int i, 
     return g;
 }
 
+// half8 element e of net `net`'s f16 operand image, gathered from the flat parameter vector: ppo_pack_kernel's element, and
+// ppo_population_exploit_kernel's (padding zeros and the constant-1 bias unit included, which pack_scatter below never writes)
+template <int L>
+__device__ __forceinline__ half8 pack_gather(const float* __restrict__ theta, int net, int e) {
+    using P = PolicyDims<L>;
+    const int O = net == 0 ? 4 : 1;
+    const float* th = theta + (net == 0 ? 0 : net_off(L, 4).total);
+    const NetOff o = net_off(L, O);
+    const int lane = e & 63, c = lane & 31, h = lane >> 5;
+    half8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float val = 0.0f;
+        if (e < P::kOff2) {  // layer 1: row = output unit, k = input index (natural order), input L = constant 1
+            const int t = e / (P::kSteps1 * 64), s = (e / 64) % P::kSteps1;
+            const int row = 32 * t + c, k = 16 * s + 8 * h + j;
+            if (row < kH) val = k < L ? th[o.w1 + row * L + k] : (k == L ? th[o.b1 + row] : 0.0f);
+            else val = (row == kPolBiasUnit && k == L) ? 1.0f : 0.0f;
+        } else if (e < P::kOff4) {  // layers 2, 3: k-slots named in accumulator-row order
+            const bool third = e >= P::kOff3;
+            const int e2 = e - (third ? P::kOff3 : P::kOff2);
+            const int t = e2 / 512, sp = (e2 / 64) % 8;
+            const int row = 32 * t + c, hid = 32 * (sp >> 1) + rho_(8 * (sp & 1) + j, h);
+            const int ow = third ? o.w3 : o.w2, ob = third ? o.b3 : o.b2;
+            if (row < kH) val = hid < kH ? th[ow + row * kH + hid] : (hid == kPolBiasUnit ? th[ob + row] : 0.0f);
+            else val = (row == kPolBiasUnit && hid == kPolBiasUnit) ? 1.0f : 0.0f;
+        } else {  // output layer: rows 0..O-1 of one 32-row tile
+            const int sp = (e - P::kOff4) / 64;
+            const int hid = 32 * (sp >> 1) + rho_(8 * (sp & 1) + j, h);
+            if (c < O) val = hid < kH ? th[o.w4 + c * kH + hid] : (hid == kPolBiasUnit ? th[o.b4 + c] : 0.0f);
+        }
+        v[j] = (_Float16)val;
+    }
+    return v;
+}
+
 // f16 operand-image positions of parameter `local` (index inside one net's block of the flat vector): the inverse of
-// ppo_pack_kernel's gather.  Every weight sits once in the image.
+// pack_gather.  Every weight sits once in the image.
 template <int L>
 __device__ __forceinline__ void pack_scatter(_Float16* __restrict__ img, int O, int local, float val) {
     using P = PolicyDims<L>;

@@ -150,6 +150,45 @@ __global__ void __launch_bounds__(kApplyThreads, 2) ppo_population_step_kernel(c
     }
 }
 
+// ---- exploit: destination members become copies of source members (qr_ppo_population_exploit) ----------------------------------------
+// What a member is to this kernel: device-resident, one entry per member, uploaded when a pointer moves.  What a CALL says -- which
+// members are overwritten, from whom, with which log_std shift -- is 2 KB and rides in the kernel arguments like PopLr.
+struct ExploitMember {
+    float *theta, *m, *v;
+    half8* images;            // [2][kImage]
+    PpoCtrl* ctrl;
+};
+struct ExploitPlan {          // entry d of the launch's grid.y: member dst[d] <- member src[d], log_std + shift[d]
+    unsigned char dst[kMaxPopulation], src[kMaxPopulation];
+    float shift[kMaxPopulation];
+};
+constexpr int kExploitThreads = 256;
+
+// grid (ceil(n / 256), destinations).  Thread e copies parameter e (theta with the shift added to the four log_std entries, both Adam
+// moments) and, below 2 kImage, gathers half8 element e of the destination's images from the SOURCE's theta -- ppo_pack_kernel's element,
+// so the images are what qr_ppo_pack makes of the new vector (log_std is in no image, and a source is never a destination: nothing this
+// launch reads is written by it).  The last block copies the Adam step count.  Nothing waits for anything.
+template <int L>
+__global__ void __launch_bounds__(kExploitThreads) ppo_population_exploit_kernel(const ExploitMember* __restrict__ table, ExploitPlan plan) {
+    const ExploitMember& D = table[plan.dst[blockIdx.y]];
+    const ExploitMember& S = table[plan.src[blockIdx.y]];
+    const float shift = plan.shift[blockIdx.y];
+    const int n = ppo_num_params(L);
+    const int e = blockIdx.x * kExploitThreads + threadIdx.x;
+    if (e < n) {
+        const float th = S.theta[e];
+        D.theta[e] = e >= n - 4 ? th + shift : th;
+        D.m[e] = S.m[e];
+        D.v[e] = S.v[e];
+    }
+    constexpr int kImage = PpoDims<L>::kImage;
+    if (e < 2 * kImage) {
+        const int net = e >= kImage ? 1 : 0;
+        D.images[e] = pack_gather<L>(S.theta, net, e - net * kImage);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) D.ctrl->adam_t = S.ctrl->adam_t;
+}
+
 }  // namespace qr
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -169,6 +208,10 @@ struct qr_ppo_population {
     int g_B = 0, g_M = 0, g_E = 0, g_shuffle = 0;
     hipStream_t capture_stream = nullptr;
     void* prepare = nullptr;        // what qr_ppo_population_prepare owns (quadrace_population_prepare.hip), released with the object
+    // qr_ppo_population_exploit: the members as its kernel sees them, allocated on first use
+    qr::ExploitMember* d_exploit = nullptr;
+    std::vector<qr::ExploitMember> h_exploit;
+    bool exploit_valid = false;
 };
 
 namespace qr {   // what quadrace_population_prepare.hip needs of the object
@@ -274,6 +317,7 @@ int qr_ppo_population_destroy(qr_ppo_population* pop) {
     if (pop->capture_stream) (void)hipStreamDestroy(pop->capture_stream);
     (void)hipFree(pop->d_table);
     (void)hipFree(pop->d_scratch);
+    (void)hipFree(pop->d_exploit);
     qr::population_prepare_release(pop->prepare);
     delete pop;
     return QR_OK;
@@ -379,6 +423,67 @@ int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* ar
         pop->g_B = B; pop->g_M = num_minibatches; pop->g_E = num_epochs; pop->g_shuffle = device_shuffle; pop->g_seeds = seeds;
     }
     POP_HIP(hipGraphLaunch(pop->exec, st));
+    return QR_OK;
+}
+
+int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, float* const* adam_m_dev, float* const* adam_v_dev,
+                              const int32_t* src_of, const float* log_std_shift, void* stream) {
+    if (!pop || !theta_dev || !adam_m_dev || !adam_v_dev || !src_of) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: null argument");
+    const int P = (int)pop->members.size();
+    for (int p = 0; p < P; ++p) {
+        if (!theta_dev[p] || !adam_m_dev[p] || !adam_v_dev[p]) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a member's pointer is null");
+        if (src_of[p] < 0 || src_of[p] >= P) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: src_of holds an index outside [0, members)");
+        if (log_std_shift && !std::isfinite(log_std_shift[p])) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a log_std_shift is not finite");
+    }
+    qr::ExploitPlan plan;
+    std::memset(&plan, 0, sizeof(plan));
+    int destinations = 0;
+    for (int p = 0; p < P; ++p) {
+        const int s = src_of[p];
+        if (s == p) continue;
+        if (src_of[s] != s)
+            return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a source is itself a destination (one launch may not read what it writes)");
+        const float shift = log_std_shift ? log_std_shift[p] : 0.0f;
+        plan.dst[destinations] = (unsigned char)p;
+        plan.src[destinations] = (unsigned char)s;
+        plan.shift[destinations] = shift;
+        ++destinations;
+    }
+    POP_HIP(hipSetDevice(pop->device));
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return popfail(QR_E_INVALID, "qr_ppo_population_exploit: `stream` is being captured (the call may allocate and upload the member table)");
+    if (destinations == 0) return QR_OK;
+    // the members as the kernel sees them: uploaded when a pointer moved (in practice: by the first call)
+    std::vector<qr::ExploitMember> table((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        qr_ppo* h = pop->members[p];
+        table[(size_t)p] = qr::ExploitMember{theta_dev[p], adam_m_dev[p], adam_v_dev[p], h->d_images, h->d_ctrl};
+    }
+    static_assert(sizeof(qr::ExploitMember) == 5 * sizeof(void*), "no padding: the table is compared bytewise");
+    if (!pop->exploit_valid || std::memcmp(table.data(), pop->h_exploit.data(), sizeof(qr::ExploitMember) * (size_t)P) != 0) {
+        if (!pop->d_exploit) POP_HIP(hipMalloc((void**)&pop->d_exploit, sizeof(qr::ExploitMember) * (size_t)P));
+        // stream-ordered behind whatever earlier calls left on `st`; synchronised, so the host copy may go
+        pop->exploit_valid = false;
+        POP_HIP(hipMemcpyAsync(pop->d_exploit, table.data(), sizeof(qr::ExploitMember) * (size_t)P, hipMemcpyHostToDevice, st));
+        POP_HIP(hipStreamSynchronize(st));
+        pop->h_exploit = table;
+        pop->exploit_valid = true;
+    }
+    if (int rc = dispatch_L(pop->L, [&](auto Lc) {
+            constexpr int L = decltype(Lc)::value;
+            const int n = qr::ppo_num_params(L), images = 2 * qr::PpoDims<L>::kImage;
+            const int blocks = ((n > images ? n : images) + qr::kExploitThreads - 1) / qr::kExploitThreads;
+            hipLaunchKernelGGL(qr::ppo_population_exploit_kernel<L>, dim3(blocks, destinations), dim3(qr::kExploitThreads), 0, st,
+                               (const qr::ExploitMember*)pop->d_exploit, plan);
+            POP_HIP(hipGetLastError());
+            return (int)QR_OK;
+        }))
+        return rc;
+    for (int d = 0; d < destinations; ++d) {   // as qr_ppo_pack leaves the handle: its images belong to this vector
+        pop->members[plan.dst[d]]->packed_theta = theta_dev[plan.dst[d]];
+    }
     return QR_OK;
 }
 

@@ -17,12 +17,107 @@ bank is loaded in one launch from the members' parameter vectors, and the member
 run as four launches and ONE blocking read for the whole population (`qr_ppo_population_prepare`, csrc/quadrace_population_prepare.hip);
 `batched_prepare=False` (the default) is the path described above, unchanged.
 
-Selection and mutation schedules are not here: `.members` are the learners, `.bank` holds their current actors for
-`evaluate_policies` / `rank_policies`, and `state_dict` / `load_state_dict` nest the members', so a user can write them."""
+Selection and mutation: `PopulationPPO.exploit` overwrites members with copies of other members -- parameters, Adam state, operand images,
+one launch for all of them with `batched_update=True` (`qr_ppo_population_exploit`) -- and `PBT` is the schedule on top of it
+(population-based training: every `interval` rounds the worst quantile is replaced by perturbed copies of the best); pass it as
+`PopulationPPO(..., pbt=PBT(...))`.  Without `pbt=` a population is P independent runs, as before.  `.members` are the learners, `.bank`
+holds their current actors for `evaluate_policies` / `rank_policies`, and `state_dict` / `load_state_dict` nest the members', so a user
+can write another schedule on `exploit`."""
+import copy
+import math
+
+import numpy as np
 import torch
 
 from ._closed_loop import group_size
 from .ppo import PPO
+
+# what a destination of exploit() inherits from its source besides parameters and optimiser state (attributes of ppo.PPO) ...
+INHERITED = ("lr0", "_kl_lr_scale", "_kl_first_trips", "clip", "ent_coef", "target_kl")
+# ... and the ppo.PPO keyword names under which PBT perturbs three of them
+PERTURBABLE = {"learning_rate": "lr0", "clip_range": "clip", "ent_coef": "ent_coef"}
+
+
+def check_exploit(P, src_of, log_std_shift=None):
+    """The argument checks of qr_ppo_population_exploit, as ValueErrors -> (src_of as ints, shifts as floats)."""
+    src_of = [int(s) for s in src_of]
+    shift = [0.0] * P if log_std_shift is None else [float(x) for x in log_std_shift]
+    if len(src_of) != P or len(shift) != P:
+        raise ValueError("src_of (and log_std_shift) hold one entry per member")
+    if any(s < 0 or s >= P for s in src_of):
+        raise ValueError("src_of holds an index outside [0, %d)" % P)
+    if any(src_of[s] != s for s in src_of):
+        raise ValueError("a source is itself a destination: a member that is copied from keeps its own state in the same call")
+    if not all(math.isfinite(x) for x in shift):
+        raise ValueError("log_std_shift must be finite")
+    return src_of, shift
+
+
+class PBT:
+    """A population-based-training schedule: truncation selection every `interval` rounds.
+
+    interval: rounds (collect + train) between decisions; warmup_rounds: rounds before the first interval starts.
+    quantile: the bottom ceil(quantile * P) members are overwritten, each by a member drawn uniformly from the top ceil(quantile * P);
+    at most 0.5.  A member of the top set is never overwritten, a member without a fitness is never a source.
+    fitness: "ep_rew_mean" or "gates_per_episode" -- the episode-weighted mean of that training statistic over the rounds since the last
+    decision, counting only rounds in which the member finished episodes -- or a callable f(population) -> P floats (None / NaN: no
+    fitness), asked at decision time.  Higher is better.
+    perturb: {"learning_rate" | "clip_range" | "ent_coef": (factor, factor)}: each destination multiplies the value it inherits by one of
+    the two, drawn per name; the result is clamped to bounds[name] = (low, high).  log_std_shift = s: each destination's log_std is its
+    source's plus +s or -s.
+    seed: the draws of decision k come from numpy's default_rng((seed, k)) and from nothing else: `plan` is a pure function."""
+
+    def __init__(self, interval=10, quantile=0.25, fitness="ep_rew_mean", perturb=None, bounds=None, log_std_shift=0.0, seed=0, warmup_rounds=0):
+        if int(interval) != interval or interval < 1 or int(warmup_rounds) != warmup_rounds or warmup_rounds < 0:
+            raise ValueError("interval must be a whole number >= 1 and warmup_rounds one >= 0")
+        if not 0.0 < float(quantile) <= 0.5:
+            raise ValueError("quantile must lie in (0, 0.5]: above it the sources and the destinations would overlap")
+        if not (callable(fitness) or fitness in ("ep_rew_mean", "gates_per_episode")):
+            raise ValueError("fitness must be 'ep_rew_mean', 'gates_per_episode' or a callable f(population) -> P floats")
+        perturb, bounds = dict(perturb or {}), dict(bounds or {})
+        for name, pair in perturb.items():
+            if name not in PERTURBABLE or len(pair) != 2 or not all(math.isfinite(f) and f > 0.0 for f in pair):
+                raise ValueError("perturb maps %s to a pair of positive factors" % " / ".join(PERTURBABLE))
+        for name, (lo, hi) in bounds.items():
+            if name not in PERTURBABLE or not lo <= hi:
+                raise ValueError("bounds maps %s to (low, high)" % " / ".join(PERTURBABLE))
+        if not (math.isfinite(log_std_shift) and log_std_shift >= 0.0):
+            raise ValueError("log_std_shift must be finite and >= 0")
+        self.interval, self.quantile, self.fitness, self.warmup_rounds = int(interval), float(quantile), fitness, int(warmup_rounds)
+        self.perturb = {k: (float(a), float(b)) for k, (a, b) in perturb.items()}
+        self.bounds = {k: (float(a), float(b)) for k, (a, b) in bounds.items()}
+        self.log_std_shift, self.seed = float(log_std_shift), int(seed)
+
+    def due(self, rounds):
+        """Is a decision due after `rounds` rounds of training?"""
+        done = rounds - self.warmup_rounds
+        return done > 0 and done % self.interval == 0
+
+    def plan(self, fitness, decision_index):
+        """fitness: P values (None / NaN: none) -> (src_of, factors): src_of[p] == p leaves member p alone; factors[p] is None for such a
+        member and for a destination {name: factor for the names of `perturb`} plus "log_std_shift": +-s.  Ranking: higher fitness first,
+        ties by index, members without a fitness last (by index).  The destinations, in index order, each draw a source, then one factor
+        per name in sorted order, then (log_std_shift > 0 only) the sign of the shift."""
+        P = len(fitness)
+        valid = [p for p in range(P) if fitness[p] is not None and not math.isnan(float(fitness[p]))]
+        ranked = sorted(valid, key=lambda p: (-float(fitness[p]), p)) + [p for p in range(P) if p not in valid]
+        k = int(math.ceil(self.quantile * P))
+        top = ranked[:min(k, len(valid))]
+        src_of, factors = list(range(P)), [None] * P
+        if not top:
+            return src_of, factors
+        rng = np.random.default_rng((self.seed, int(decision_index)))
+        for p in sorted(q for q in ranked[P - k:] if q not in top):
+            src_of[p] = top[int(rng.integers(len(top)))]
+            f = {name: self.perturb[name][int(rng.integers(2))] for name in sorted(self.perturb)}
+            f["log_std_shift"] = (self.log_std_shift if int(rng.integers(2)) else -self.log_std_shift) if self.log_std_shift else 0.0
+            factors[p] = f
+        return src_of, factors
+
+    def perturbed(self, name, value, factor):
+        """value * factor, clamped to bounds[name]"""
+        lo, hi = self.bounds.get(name, (-math.inf, math.inf))
+        return min(max(float(value) * float(factor), lo), hi)
 
 
 class _MemberEnv:
@@ -103,16 +198,31 @@ class PopulationPPO:
     batched_prepare: collect() fills the bank with ONE device launch (`MfmaPpoPopulationUpdater.load_bank`) and train() replaces the members'
     collect_fused() + buffer sanitising + GAE by ONE `MfmaPpoPopulationUpdater.prepare` for all members; every tensor ends bit for bit where
     the members' own steps leave it, and a member's own MfmaPolicy is no longer loaded.  Needs batched_update=True and the race envs (a
-    ValueError otherwise); truncation_bootstrap may differ between members (a member without it passes no term_val)."""
+    ValueError otherwise); truncation_bootstrap may differ between members (a member without it passes no term_val).
+    pbt: a `PBT` schedule (None: none, and nothing below exists).  train() then ends with the schedule's bookkeeping (the round count and the
+    fitness accumulators), learn() applies a decision (`pbt_step`) whenever one is due, `.lineage` lists per replaced member
+    (round, dst, src, (fitness of dst, fitness of src), the destination's new hyper-parameters), and state_dict / load_state_dict carry
+    the schedule's position, the accumulators, the lineage and each member's clip / ent_coef / target_kl for a bit-for-bit resume.
+    A decision that changes a member's clip or ent_coef changes the argument set of `qr_ppo_population_epoch`: the next train() pays one
+    table upload and one graph re-capture, once per decision.  A changed learning rate costs nothing: it travels in the arguments of
+    ppo_population_lr_kernel every round anyway."""
 
     def __init__(self, env, members, envs_per_member=256, conditions=None, condition_of_member=None, batched_update=False, batched_prepare=False,
-                 **shared_hyper):
+                 pbt=None, **shared_hyper):
         from .conditions import Condition, ConditionBank
         from .policy import MfmaPolicyBank
 
         members = [dict(m) for m in members]
         if len(members) < 1:
             raise ValueError("members must hold at least one dict of PPO keywords")
+        if pbt is not None:
+            if not isinstance(pbt, PBT):
+                raise ValueError("pbt must be a population.PBT schedule")
+            if len(members) < 2:
+                raise ValueError("pbt needs at least two members: one to copy from and one to overwrite")
+        self.pbt, self.lineage = pbt, []
+        self._pbt_round, self._pbt_decisions = 0, 0
+        self._pbt_acc = [[0.0, 0.0] for _ in members]   # per member: episodes, sum of episodes x statistic since the last decision
         self.envs_per_member, slots = group_size(envs_per_member, env.num_envs, "envs_per_member", "member")
         if slots != len(members):
             raise ValueError("len(members) * envs_per_member must equal env.num_envs (%d * %d != %d)"
@@ -211,6 +321,8 @@ class PopulationPPO:
         batched_update, every member's part of train() before the launches, ONE update launch sequence for all, every member's part after."""
         if self._launch is None:
             raise RuntimeError("call collect() before train()")
+        if self.pbt is not None:   # "episodes" is written only in a round that finished some: taken out, it tells this round from an older one
+            held = [m.stats.pop("episodes", None) for m in self.members]
         if self.batched_update:
             self._train_batched()
         else:
@@ -218,7 +330,96 @@ class PopulationPPO:
                 m.collect_fused()
                 m.train()
         self._launch = None
+        if self.pbt is not None:
+            self._pbt_after_round(held)
         return self
+
+    # ------------------------------------------------------------------------------------------------- selection and mutation
+    @torch.no_grad()
+    def exploit(self, src_of, log_std_shift=None, hyper=None):
+        """Every member p with src_of[p] != p becomes a copy of member s = src_of[p]: parameters (log_std plus log_std_shift[p]), Adam
+        moments and step count, operand images -- with batched_update ONE device launch for all of them (`MfmaPpoPopulationUpdater.exploit`),
+        otherwise copies, `pack()` and the step write through each member's own updater (members without native_update: their torch
+        parameters and `opt` state); both leave the same bits.  p then inherits s's lr0, _kl_lr_scale, _kl_first_trips, clip, ent_coef and
+        target_kl; hyper[p] (a dict of those names) overrides them.  p keeps its own seed, noise and shuffle streams, envs, episode
+        accumulators, num_timesteps and condition.  The bank is reloaded by the next collect().
+        ValueError: what qr_ppo_population_exploit refuses (a wrong length, an index outside [0, P), a source that is itself a
+        destination, a non-finite shift) and an unknown name in `hyper`; RuntimeError: between collect() and train()."""
+        P = len(self.members)
+        src_of, shift = check_exploit(P, src_of, log_std_shift)
+        hyper = dict(hyper or {})
+        for p, h in hyper.items():
+            if not (isinstance(p, int) and 0 <= p < P) or any(name not in INHERITED for name in h):
+                raise ValueError("hyper maps a member index to a dict of %s" % ", ".join(INHERITED))
+        if self._launch is not None:
+            raise RuntimeError("a collected rollout is waiting for train(): exploit between rounds")
+        dst = [p for p in range(P) if src_of[p] != p]
+        if self._pop_updater is not None:
+            self._pop_updater.exploit(src_of, shift)
+        else:
+            for p in dst:
+                d, s = self.members[p], self.members[src_of[p]]
+                add = torch.tensor(shift[p], dtype=torch.float32, device=d.dev)   # one float32 add, also of 0: what the kernel does
+                if d._updater is not None and s._updater is not None:
+                    for name in ("theta", "m", "v"):
+                        getattr(d._updater, name).copy_(getattr(s._updater, name))
+                    d._updater.theta[-4:].add_(add)
+                    d._updater.pack()
+                    d._updater.step = s._updater.step
+                elif d._updater is None and s._updater is None:
+                    for pd, ps in zip(d.policy.parameters(), s.policy.parameters()):
+                        pd.data.copy_(ps.data)
+                    d.policy.log_std.data.add_(add)
+                    state = copy.deepcopy(s.opt.state_dict())
+                    state["param_groups"] = d.opt.state_dict()["param_groups"]
+                    d.opt.load_state_dict(state)
+                else:
+                    raise ValueError("members %d and %d differ in native_update: their optimiser states have no common form" % (p, src_of[p]))
+        for p in dst:
+            d, s = self.members[p], self.members[src_of[p]]
+            for name in INHERITED:
+                setattr(d, name, getattr(s, name))
+            for name, value in hyper.get(p, {}).items():
+                setattr(d, name, value)
+        return self
+
+    def _pbt_after_round(self, held):
+        """train()'s last step under a schedule: the round count and, past the warm-up, each member's episodes of THIS round."""
+        self._pbt_round += 1
+        key = self.pbt.fitness if isinstance(self.pbt.fitness, str) else None
+        for m, acc, old in zip(self.members, self._pbt_acc, held):
+            if "episodes" not in m.stats:
+                if old is not None:
+                    m.stats["episodes"] = old
+            elif key is not None and self._pbt_round > self.pbt.warmup_rounds:
+                n = float(m.stats["episodes"])
+                acc[0] += n
+                acc[1] += n * float(m.stats[m._gates_key if key == "gates_per_episode" else key])
+
+    def pbt_fitness(self):
+        """Per member the fitness the schedule would decide on now (None: none yet)."""
+        if callable(self.pbt.fitness):
+            return [None if f is None else float(f) for f in self.pbt.fitness(self)]
+        return [acc[1] / acc[0] if acc[0] > 0 else None for acc in self._pbt_acc]
+
+    def pbt_step(self):
+        """One decision of the schedule: rank, exploit, perturb, record; the accumulators start again.  learn() calls it when
+        `pbt.due(rounds)`; a loop of your own calls it between train() and the next collect().  -> the new lineage entries."""
+        pbt, fit = self.pbt, self.pbt_fitness()
+        src_of, factors = pbt.plan(fit, self._pbt_decisions)
+        hyper, entries = {}, []
+        for p, f in enumerate(factors):
+            if f is None:
+                continue
+            s = self.members[src_of[p]]
+            hyper[p] = {attr: pbt.perturbed(name, getattr(s, attr), f[name]) for name, attr in PERTURBABLE.items() if name in f}
+            new = {attr: hyper[p].get(attr, getattr(s, attr)) for attr in ("lr0", "clip", "ent_coef", "target_kl")}
+            entries.append((self._pbt_round, p, src_of[p], (fit[p], fit[src_of[p]]), dict(new, log_std_shift=f["log_std_shift"])))
+        self.exploit(src_of, [0.0 if f is None else f["log_std_shift"] for f in factors], hyper)
+        self.lineage += entries
+        self._pbt_decisions += 1
+        self._pbt_acc = [[0.0, 0.0] for _ in self.members]
+        return entries
 
     def _prepare_batched(self):
         """What every member's collect_fused() + _train_prepare() does, for all members at once: the host bookkeeping of each member, ONE
@@ -292,10 +493,12 @@ class PopulationPPO:
 
     def learn(self, total_timesteps_per_member, callback=None):
         """Rounds of collect() + train() until every member has seen `total_timesteps_per_member` env steps.  callback(self) after each
-        round; returning False stops."""
+        round; returning False stops.  Under a `pbt` schedule a due decision is applied after train() and before the callback."""
         while self.members[0].num_timesteps < total_timesteps_per_member:
             self.collect()
             self.train()
+            if self.pbt is not None and self.pbt.due(self._pbt_round):
+                self.pbt_step()
             if callback is not None and callback(self) is False:
                 break
         return self
@@ -310,19 +513,35 @@ class PopulationPPO:
         self.env._observe_under(self.conditions, self.condition_of_member, self.envs_per_member)
 
     def state_dict(self):
-        """The members' state_dicts (each with its rows of the env state) and their network parameters, nested."""
-        return dict(envs_per_member=int(self.envs_per_member), condition_of_member=list(self.condition_of_member),
-                    members=[dict(trainer=m.state_dict(), policy={k: v.detach().cpu().clone() for k, v in m.policy.state_dict().items()})
-                             for m in self.members])
+        """The members' state_dicts (each with its rows of the env state) and their network parameters, nested; under a `pbt` schedule also
+        its position, accumulators and lineage and the members' clip / ent_coef / target_kl (which exploit() moves and ppo.PPO does not save)."""
+        sd = dict(envs_per_member=int(self.envs_per_member), condition_of_member=list(self.condition_of_member),
+                  members=[dict(trainer=m.state_dict(), policy={k: v.detach().cpu().clone() for k, v in m.policy.state_dict().items()})
+                           for m in self.members])
+        if self.pbt is not None:
+            sd["pbt"] = dict(round=int(self._pbt_round), decisions=int(self._pbt_decisions), acc=[list(a) for a in self._pbt_acc],
+                             lineage=[(r, d, s, tuple(f), dict(h)) for r, d, s, f, h in self.lineage],
+                             hyper=[dict(clip=m.clip, ent_coef=m.ent_coef, target_kl=m.target_kl) for m in self.members])
+        return sd
 
     def load_state_dict(self, sd):
         if len(sd["members"]) != len(self.members) or int(sd["envs_per_member"]) != self.envs_per_member:
             raise ValueError("the checkpoint holds another population shape")
         if list(sd["condition_of_member"]) != list(self.condition_of_member):
             raise ValueError("the checkpoint flies another condition map: construct the population with it")
+        if (self.pbt is not None) != ("pbt" in sd):
+            raise ValueError("the checkpoint was written %s a pbt schedule and this population is built %s one"
+                             % (("with", "without") if "pbt" in sd else ("without", "with")))
         for m, part in zip(self.members, sd["members"]):
             m.policy.load_state_dict(part["policy"])
             m.load_state_dict(part["trainer"])
+        if self.pbt is not None:
+            st = sd["pbt"]
+            self._pbt_round, self._pbt_decisions = int(st["round"]), int(st["decisions"])
+            self._pbt_acc = [[float(a), float(b)] for a, b in st["acc"]]
+            self.lineage = [(r, d, s, tuple(f), dict(h)) for r, d, s, f, h in st["lineage"]]
+            for m, h in zip(self.members, st["hyper"]):
+                m.clip, m.ent_coef, m.target_kl = h["clip"], h["ent_coef"], h["target_kl"]
         self._launch = None
         self.load_bank()
         return self

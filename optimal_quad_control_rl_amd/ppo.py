@@ -359,6 +359,19 @@ class MfmaPpoPopulationUpdater:
         self._lib.check(self._lib.require(self._L, "qr_ppo_population_load_bank")(self._h, thetas, bank._h, int(first_slot), self._stream()))
         return bank
 
+    def exploit(self, src_of, log_std_shift=None):
+        """Members p with src_of[p] != p become copies of member src_of[p] in ONE launch (qr_ppo_population_exploit): theta (the four log_std
+        entries plus log_std_shift[p]), both Adam moments, the operand images and the Adam step count; everything else of p stays its own.
+        The members' torch parameters are views of `theta`: they follow.  No host read, no synchronisation after the first call."""
+        C, n = self._C, len(self.updaters)
+        src_of = [int(s) for s in src_of]
+        if len(src_of) != n or (log_std_shift is not None and len(log_std_shift) != n):
+            raise ValueError("src_of (and log_std_shift) hold one entry per member")
+        ptrs = lambda name: (C.c_void_p * n)(*[getattr(u, name).data_ptr() for u in self.updaters])
+        shift = None if log_std_shift is None else (C.c_float * n)(*[float(x) for x in log_std_shift])
+        self._lib.check(self._lib.require(self._L, "qr_ppo_population_exploit")(self._h, ptrs("theta"), ptrs("m"), ptrs("v"), (C.c_int32 * n)(*src_of),
+                                                                              shift, self._stream()))
+
     PREPARE_SHARED = ("obs", "act", "logp", "rew", "done", "trunc", "last_obs")
     PREPARE_MEMBER = ("obs", "act", "old_logp", "rew", "done", "val", "last_val", "adv", "ret")
 

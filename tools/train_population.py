@@ -4,6 +4,7 @@ qr_rollout_policy_population), ranked on shared starts (GPU box).
 
     python tools/train_population.py --seeds 0-9 [--envs-per-member 256] [--variant indi|e2e] [--track square|zigzag]
         [--steps 3e6] [--n-steps 32] [--epochs 5] [--minibatches 4] [--lr 3e-4] [--target-kl 0.02] [--curve 20] [--batched-update [--batched-prepare]]
+        [--pbt-interval R [--pbt-quantile 0.25] [--pbt-fitness ep_rew_mean|gates|eval] [--pbt-perturb-lr 0.8,1.25] [--pbt-log-std-shift s]]
 
 --steps counts env steps PER MEMBER.  Member p owns envs [p E, (p + 1) E) of a P x E env and differs from the others in its seed only
 (network initialisation, minibatch permutations, action noise); the env's own seed is 1, as for tools/train_ppo.py --seed 0.  Every
@@ -12,7 +13,11 @@ qr_rollout_policy_population), ranked on shared starts (GPU box).
 sequence (PopulationPPO(batched_update=True) -> qr_ppo_population_epoch) instead of one after another; same results, bit for bit.  --batched-prepare (needs --batched-update, implies nothing else): the bank
 load, the members' value forwards, slice copies, sanitising and GAE run on the device for all members at once
 (PopulationPPO(batched_prepare=True) -> qr_ppo_population_load_bank / qr_ppo_population_prepare); same tensors, bit for bit.  The JSON
-line carries round_ms, the mean wall time of a round (collect + train) after the first one (which captures graphs and allocates)."""
+line carries round_ms, the mean wall time of a round (collect + train) after the first one (which captures graphs and allocates).
+--pbt-interval R: population-based training (PopulationPPO(pbt=PBT(...))): every R rounds the worst --pbt-quantile of the members are
+overwritten by copies of the best, their learning rate multiplied by one of --pbt-perturb-lr and their log_std moved by +- --pbt-log-std-shift;
+the fitness is a training statistic (ep_rew_mean, gates = gates per episode) or eval = gates per 12 s of the bank evaluation above (training
+clock stopped).  The lineage goes into the JSON line.  Without --pbt-interval nothing changes."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -52,6 +57,11 @@ def parser():
     ap.add_argument("--batched-update", action="store_true", help="update all members in one launch sequence (matrix-core update, f16 operands)")
     ap.add_argument("--batched-prepare", action="store_true",
                     help="bank load, values, sanitising and GAE of all members on the device in a fixed number of launches (needs --batched-update)")
+    ap.add_argument("--pbt-interval", type=int, default=0, help="population-based training: rounds between decisions (0: off)")
+    ap.add_argument("--pbt-quantile", type=float, default=0.25, help="share of the members replaced (and copied from) per decision, at most 0.5")
+    ap.add_argument("--pbt-fitness", default="ep_rew_mean", choices=("ep_rew_mean", "gates", "eval"))
+    ap.add_argument("--pbt-perturb-lr", default="", help="two factors, e.g. 0.8,1.25: a copy's learning rate is multiplied by one of them")
+    ap.add_argument("--pbt-log-std-shift", type=float, default=0.0, help="a copy's log_std is its source's plus or minus this")
     ap.add_argument("--curve", type=int, default=0, help="evaluate every member every this many rounds (training clock stopped)")
     ap.add_argument("--eval-envs-per-member", type=int, default=256)
     ap.add_argument("--out", default="")
@@ -89,12 +99,31 @@ def main():
         return env
 
     env = make_env(P * E, 1)
+    paused, pbt = [0.0], None
+    if a.pbt_interval:
+        from optimal_quad_control_rl_amd.population import PBT
+
+        def eval_fitness(p):   # gates per 12 s on the shared starts of the bank evaluation; the training clock does not run
+            torch.cuda.synchronize()
+            e0 = time.perf_counter()
+            fit = [r["window"]["gates_per_window"] for r in evaluate()]
+            torch.cuda.synchronize()
+            paused[0] += time.perf_counter() - e0
+            return fit
+
+        try:
+            factors = tuple(float(x) for x in a.pbt_perturb_lr.split(",")) if a.pbt_perturb_lr else None
+            pbt = PBT(interval=a.pbt_interval, quantile=a.pbt_quantile,
+                      fitness={"ep_rew_mean": "ep_rew_mean", "gates": "gates_per_episode", "eval": eval_fitness}[a.pbt_fitness],
+                      perturb={"learning_rate": factors} if factors else None, log_std_shift=a.pbt_log_std_shift)
+        except ValueError as e:
+            ap.error("--pbt-*: %s" % e)
     pop = PopulationPPO(env, [dict(seed=s) for s in seeds], envs_per_member=E, ent_coef=a.ent_coef, gamma=a.gamma, n_steps=a.n_steps,
                         n_epochs=a.epochs, batch_size=E * a.n_steps // a.minibatches, learning_rate=a.lr, target_kl=a.target_kl,
                         lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps), native_update=not a.torch_update,
                         truncation_bootstrap=not a.no_trunc_bootstrap, policy_forward="f32class" if a.precision != "f16-operands" else "torch",
                         update_precision="f32" if a.precision == "f32" else "f16-operands", batched_update=a.batched_update,
-                        batched_prepare=a.batched_prepare)
+                        batched_prepare=a.batched_prepare, pbt=pbt)
     # evaluation on a separate env, every member on the same starts: 2000 steps = 20 s of flight, crashes restart the lap count
     ev = make_env(P * a.eval_envs_per_member, 99)
     ev.max_steps = 10 ** 6
@@ -102,7 +131,7 @@ def main():
     def evaluate():
         return evaluate_policies(pop.members, ev, envs_per_policy=a.eval_envs_per_member, n_eval_steps=2000, window_steps=1200, seed=99)
 
-    curve, paused, rounds, first = [], [0.0], [0], [0.0]
+    curve, rounds, first = [], [0], [0.0]
 
     def on_round(p):
         rounds[0] += 1
@@ -126,6 +155,19 @@ def main():
                               flying_lap=[r["total"]["flying_lap_seconds"] for r in res],
                               crashes_per_12s=[r["window"]["crashes_per_window"] for r in res]))
 
+    decision_ms = []
+    if pbt is not None:   # a decision's own wall time (exploit launch + host bookkeeping; an "eval" fitness is on the paused clock)
+        step = pop.pbt_step
+
+        def timed_step():
+            torch.cuda.synchronize()
+            d0, p0 = time.perf_counter(), paused[0]
+            entries = step()
+            torch.cuda.synchronize()
+            decision_ms.append(1e3 * (time.perf_counter() - d0 - (paused[0] - p0)))
+            return entries
+
+        pop.pbt_step = timed_step
     t0 = time.perf_counter()
     pop.learn(int(a.steps), callback=on_round)
     torch.cuda.synchronize()
@@ -140,6 +182,11 @@ def main():
                train_Msteps_per_s=pop.num_timesteps * P / train_s / 1e6, ranking=[seeds[i] for i in order],
                flying_lap_seconds=[r["total"]["flying_lap_seconds"] for r in res],
                crashes_per_12s=[r["window"]["crashes_per_window"] for r in res], curve=curve)
+    if pbt is not None:
+        out["pbt"] = dict(interval=a.pbt_interval, quantile=a.pbt_quantile, fitness=a.pbt_fitness, perturb_lr=a.pbt_perturb_lr,
+                          log_std_shift=a.pbt_log_std_shift, decisions=len(decision_ms),
+                          decision_ms=sum(decision_ms) / len(decision_ms) if decision_ms else None)
+        out["lineage"] = [dict(round=r, dst=seeds[d], src=seeds[s], fitness=list(f), hyper=h) for r, d, s, f, h in pop.lineage]
     print(json.dumps(out))
     if a.out:
         json.dump(out, open(a.out, "w"), indent=1)
