@@ -22,7 +22,7 @@
 #include "../../include/quad3d.h"
 #include "../../include/quadrace.h"
 #include "quadrace_device.hpp"
-#include "quadrace_launch.hpp"   // set_last_error, launch_dynamic_lds, the policy accessors; quadrace_policy.hpp (the MFMA forward)
+#include "quadrace_launch.hpp"   // the host support (quadrace_host.hpp), launch_dynamic_lds, the policy accessors and checks; quadrace_policy.hpp
 
 namespace {
 
@@ -835,14 +835,6 @@ q3_eval_policy_bank_kernel(Q3Params P, Q3Buffers<T> B, const qr::half8* __restri
     q3_eval_body<T, kF32, false>(P, img, img_lo, i, local0 + (int)threadIdx.x, K, rec, recf, B);
 }
 
-int q3fail(int code, const std::string& m) { return qr::set_last_error(code, m); }
-
-#define Q3_HIP(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) return q3fail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 }  // namespace
 
 struct q3_env {
@@ -859,9 +851,11 @@ struct q3_env {
 };
 
 namespace {
+const char* const kQ3LenRule = "must be 16 (the state row is the observation)";
+
 int q3_ready(const q3_env* e) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, "q3_set_track has not been called");
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    if (e->kind == Q3_KIND_GATES && !e->has_track) return qr::set_last_error(QR_E_STATE, "q3_set_track has not been called");
     return QR_OK;
 }
 
@@ -912,11 +906,11 @@ hipError_t q3_launch_eval_policy_bank(q3_env* e, const qr::half8* bank, const qr
 
 // what q3_evaluate_policy and q3_evaluate_policy_bank refuse alike (`who` names the entry point in the message)
 int q3_check_eval_args(const q3_env* e, int K, int flags, const int32_t* rec, const float* recf, const std::string& w) {
-    if (!e) return q3fail(QR_E_INVALID, w + "null q3_env handle");
-    if (!rec) return q3fail(QR_E_INVALID, w + "rec_dev is null");
-    if (K < 1) return q3fail(QR_E_INVALID, w + "num_steps must be >= 1");
-    if (flags != 0 && flags != QR_ROLLOUT_F32CLASS) return q3fail(QR_E_INVALID, w + "`flags` takes 0 or QR_ROLLOUT_F32CLASS");
-    if (((uintptr_t)rec | (uintptr_t)recf) & 15u) return q3fail(QR_E_INVALID, w + "rec_dev / recf_dev must be 16-byte aligned");
+    if (!e) return qr::set_last_error(QR_E_INVALID, w + "null q3_env handle");
+    if (!rec) return qr::set_last_error(QR_E_INVALID, w + "rec_dev is null");
+    if (K < 1) return qr::set_last_error(QR_E_INVALID, w + "num_steps must be >= 1");
+    if (flags != 0 && flags != QR_ROLLOUT_F32CLASS) return qr::set_last_error(QR_E_INVALID, w + "`flags` takes 0 or QR_ROLLOUT_F32CLASS");
+    if (((uintptr_t)rec | (uintptr_t)recf) & 15u) return qr::set_last_error(QR_E_INVALID, w + "rec_dev / recf_dev must be 16-byte aligned");
     return QR_OK;
 }
 
@@ -925,19 +919,19 @@ int q3_check_eval_args(const q3_env* e, int K, int flags, const int32_t* rec, co
 extern "C" {
 
 int q3_create(int kind, int num_envs, int device, uint64_t env_id_base, q3_env** out) {
-    if (!out) return q3fail(QR_E_INVALID, "out is null");
+    if (!out) return qr::set_last_error(QR_E_INVALID, "out is null");
     *out = nullptr;
-    if (kind != Q3_KIND_HOVER && kind != Q3_KIND_GATES) return q3fail(QR_E_INVALID, "kind must be Q3_KIND_HOVER or Q3_KIND_GATES");
-    if (num_envs < 1) return q3fail(QR_E_INVALID, "num_envs must be >= 1");
+    if (kind != Q3_KIND_HOVER && kind != Q3_KIND_GATES) return qr::set_last_error(QR_E_INVALID, "kind must be Q3_KIND_HOVER or Q3_KIND_GATES");
+    if (num_envs < 1) return qr::set_last_error(QR_E_INVALID, "num_envs must be >= 1");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return q3fail(QR_E_NO_DEVICE, "no HIP device visible: libquadrace has no CPU fallback");
-    if (device < 0 || device >= count) return q3fail(QR_E_INVALID, "device index out of range");
+        return qr::set_last_error(QR_E_NO_DEVICE, "no HIP device visible: libquadrace has no CPU fallback");
+    if (device < 0 || device >= count) return qr::set_last_error(QR_E_INVALID, "device index out of range");
     hipDeviceProp_t prop;
-    Q3_HIP(hipGetDeviceProperties(&prop, device));
+    QR_HIP(hipGetDeviceProperties(&prop, device));
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return q3fail(QR_E_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    Q3_HIP(hipSetDevice(device));
+        return qr::set_last_error(QR_E_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    QR_HIP(hipSetDevice(device));
     q3_env* e = new q3_env();
     e->kind = kind;
     e->device = device;
@@ -961,7 +955,7 @@ int q3_create(int kind, int num_envs, int device, uint64_t env_id_base, q3_env**
     if (err == hipSuccess) err = hipMemset(e->d_episode, 0, n * 4);
     if (err != hipSuccess) {
         q3_destroy(e);
-        return q3fail(QR_E_HIP, std::string("allocating env state: ") + hipGetErrorString(err));
+        return qr::set_last_error(QR_E_HIP, std::string("allocating env state: ") + hipGetErrorString(err));
     }
     *out = e;
     return QR_OK;
@@ -979,16 +973,16 @@ int q3_destroy(q3_env* e) {
     return QR_OK;
 }
 
-int q3_num_envs(const q3_env* e) { return e ? e->P.n : q3fail(QR_E_INVALID, "null q3_env handle"); }
+int q3_num_envs(const q3_env* e) { return e ? e->P.n : qr::set_last_error(QR_E_INVALID, "null q3_env handle"); }
 int q3_elem_size(const q3_env* e) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
     return e->kind == Q3_KIND_HOVER ? 8 : 4;
 }
 
 int q3_set_track(q3_env* e, const float* gate_pos, const float* gate_yaw, int G, const float start_pos[3]) {
-    if (!e || !gate_pos || !gate_yaw || !start_pos) return q3fail(QR_E_INVALID, "null argument");
-    if (e->kind != Q3_KIND_GATES) return q3fail(QR_E_STATE, "q3_set_track applies to Q3_KIND_GATES only");
-    if (G < 1 || G > kQ3MaxGates) return q3fail(QR_E_INVALID, "num_gates must be in 1..32");
+    if (!e || !gate_pos || !gate_yaw || !start_pos) return qr::set_last_error(QR_E_INVALID, "null argument");
+    if (e->kind != Q3_KIND_GATES) return qr::set_last_error(QR_E_STATE, "q3_set_track applies to Q3_KIND_GATES only");
+    if (G < 1 || G > kQ3MaxGates) return qr::set_last_error(QR_E_INVALID, "num_gates must be in 1..32");
     e->P.num_gates = G;
     for (int g = 0; g < G; ++g) {
         for (int k = 0; k < 3; ++k) e->P.gate[g][k] = gate_pos[3 * g + k];
@@ -1002,16 +996,16 @@ int q3_set_track(q3_env* e, const float* gate_pos, const float* gate_yaw, int G,
 }
 
 int q3_set_limits(q3_env* e, int max_steps, double dt) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    if (max_steps < 1 || !(dt > 0.0)) return q3fail(QR_E_INVALID, "max_steps must be >= 1 and dt > 0");
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    if (max_steps < 1 || !(dt > 0.0)) return qr::set_last_error(QR_E_INVALID, "max_steps must be >= 1 and dt > 0");
     e->P.max_steps = max_steps;
     e->P.dt = dt;
     return QR_OK;
 }
 
 int q3_set_thresholds(q3_env* e, double pos, double vel, double ang, double rat) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    if (e->kind != Q3_KIND_HOVER) return q3fail(QR_E_STATE, "q3_set_thresholds applies to Q3_KIND_HOVER only");
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    if (e->kind != Q3_KIND_HOVER) return qr::set_last_error(QR_E_STATE, "q3_set_thresholds applies to Q3_KIND_HOVER only");
     e->P.pos_thr = pos;
     e->P.vel_thr = vel;
     e->P.ang_thr = ang;
@@ -1020,32 +1014,32 @@ int q3_set_thresholds(q3_env* e, double pos, double vel, double ang, double rat)
 }
 
 int q3_seed(q3_env* e, uint64_t seed) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    QR_HIP(hipSetDevice(e->device));
     e->P.seed_lo = (uint32_t)seed;
     e->P.seed_hi = (uint32_t)(seed >> 32);
-    Q3_HIP(hipDeviceSynchronize());
-    Q3_HIP(hipMemset(e->d_episode, 0, (size_t)e->P.n * 4));
+    QR_HIP(hipDeviceSynchronize());
+    QR_HIP(hipMemset(e->d_episode, 0, (size_t)e->P.n * 4));
     return QR_OK;
 }
 
 int q3_reset(q3_env* e, const uint8_t* mask, void* states_out, void* stream) {
     if (int rc = q3_ready(e)) return rc;
-    Q3_HIP(hipSetDevice(e->device));
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
         q3_reset_kernel<double><<<e->grid(), kQ3Block, 0, st>>>(e->P, e->buffers<double>(), mask, static_cast<double*>(states_out));
     else
         q3_reset_kernel<float><<<e->grid(), kQ3Block, 0, st>>>(e->P, e->buffers<float>(), mask, static_cast<float*>(states_out));
-    Q3_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
 int q3_step(q3_env* e, const float* actions, void* states_out, void* rew_out, uint8_t* done_out, uint8_t* trunc_out,
             void* stream) {
     if (int rc = q3_ready(e)) return rc;
-    if (!actions) return q3fail(QR_E_INVALID, "actions_dev is null");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!actions) return qr::set_last_error(QR_E_INVALID, "actions_dev is null");
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float4* a = reinterpret_cast<const float4*>(actions);
     if (e->kind == Q3_KIND_HOVER)
@@ -1054,16 +1048,16 @@ int q3_step(q3_env* e, const float* actions, void* states_out, void* rew_out, ui
     else
         q3_step_kernel<float><<<e->grid(), kQ3Block, 0, st>>>(e->P, e->buffers<float>(), a, static_cast<float*>(states_out),
                                                              static_cast<float*>(rew_out), done_out, trunc_out);
-    Q3_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
 static int q3_launch_rollout(q3_env* e, const float* actions, int K, void* states_steps, void* rew_out, uint8_t* done_out,
                              uint8_t* trunc_out, void* states_out, void* stream) {
     if (int rc = q3_ready(e)) return rc;
-    if (!actions) return q3fail(QR_E_INVALID, "actions_dev is null");
-    if (K < 1) return q3fail(QR_E_INVALID, "num_steps must be >= 1");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!actions) return qr::set_last_error(QR_E_INVALID, "actions_dev is null");
+    if (K < 1) return qr::set_last_error(QR_E_INVALID, "num_steps must be >= 1");
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float4* a = reinterpret_cast<const float4*>(actions);
     if (e->kind == Q3_KIND_HOVER) {
@@ -1081,7 +1075,7 @@ static int q3_launch_rollout(q3_env* e, const float* actions, int K, void* state
             q3_rollout_kernel<float, false><<<e->grid(), kQ3Block, 0, st>>>(e->P, e->buffers<float>(), a, K, static_cast<float*>(rew_out), done_out,
                                                                            nullptr, nullptr, static_cast<float*>(states_out));
     }
-    Q3_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
@@ -1091,7 +1085,7 @@ int q3_step_many(q3_env* e, const float* actions, int K, void* rew_out, uint8_t*
 
 int q3_rollout(q3_env* e, const float* actions, int K, void* states_steps_out, void* rew_out, uint8_t* done_out, uint8_t* trunc_out,
                void* stream) {
-    if (!states_steps_out) return q3fail(QR_E_INVALID, "states_steps_out_dev is null (q3_step_many is the form without per-step rows)");
+    if (!states_steps_out) return qr::set_last_error(QR_E_INVALID, "states_steps_out_dev is null (q3_step_many is the form without per-step rows)");
     return q3_launch_rollout(e, actions, K, states_steps_out, rew_out, done_out, trunc_out, nullptr, stream);
 }
 
@@ -1099,95 +1093,81 @@ int q3_rollout(q3_env* e, const float* actions, int K, void* states_steps_out, v
 int q3_rollout_policy(q3_env* e, qr_policy* policy, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags,
                       float* obs_out, float* act_out, float* logp_out, float* rew_out, uint8_t* done_out, uint8_t* trunc_out, float* term_obs,
                       float* last_obs, void* states_out, void* stream) {
-    const std::string w = "q3_rollout_policy: ";
-    if (!e) return q3fail(QR_E_INVALID, w + "null q3_env handle");
-    if (!policy || !log_std) return q3fail(QR_E_INVALID, w + "null policy handle or log_std");
-    if (K < 1) return q3fail(QR_E_INVALID, w + "num_steps must be >= 1");
-    if (!obs_out || !act_out || !logp_out || !rew_out || !done_out) return q3fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
+    const char* who = "q3_rollout_policy";
+    const std::string w = std::string(who) + ": ";
+    if (!e) return qr::set_last_error(QR_E_INVALID, w + "null q3_env handle");
+    if (!policy || !log_std) return qr::set_last_error(QR_E_INVALID, w + "null policy handle or log_std");
+    if (K < 1) return qr::set_last_error(QR_E_INVALID, w + "num_steps must be >= 1");
+    if (!obs_out || !act_out || !logp_out || !rew_out || !done_out) return qr::set_last_error(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
     if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
-        return q3fail(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
-    if (qr::policy_obs_len(policy) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "policy obs_len must be 16 (the state row is the observation)");
-    if (qr::policy_device(policy) != e->device) return q3fail(QR_E_INVALID, w + "policy on another GPU");
+        return qr::set_last_error(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (int rc = qr::check_policy_handle(policy, kQ3ObsLen, e->device, who, kQ3LenRule)) return rc;
     if (((uintptr_t)obs_out | (uintptr_t)act_out | (uintptr_t)term_obs | (uintptr_t)last_obs | (uintptr_t)states_out) & 15u)
-        return q3fail(QR_E_INVALID, w + "obs_out / act_out / term_obs / last_obs / states_out must be 16-byte aligned");
-    const qr::half8* wt = qr::policy_weights(policy);
-    if (!wt) return q3fail(QR_E_STATE, w + "the policy has no weights");
-    if (int rc = q3_ready(e)) return rc;
+        return qr::set_last_error(QR_E_INVALID, w + "obs_out / act_out / term_obs / last_obs / states_out must be 16-byte aligned");
     qr::PolicyArgs A{};
-    A.weights = wt;
+    if (int rc = qr::fetch_policy_weights(policy, who, A.weights)) return rc;
+    if (int rc = q3_ready(e)) return rc;
     A.weights_lo = qr::policy_weights_lo(policy);
-    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
-    float sum_log_std = 0.0f;
-    for (int c = 0; c < 4; ++c) {
-        A.std[c] = expf(log_std[c]);
-        sum_log_std += log_std[c];
-    }
-    A.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
-    // the action-noise stream of qr_rollout_policy: Philox(counter = (env id, step), key = noise seed with the same fixed tweak)
-    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;
-    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
-    A.step_lo = (uint32_t)first_step;
-    A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
-    Q3_HIP(hipSetDevice(e->device));
+    qr::set_sampling(A, qr::sampling_entry(log_std, noise_seed), first_step, flags);   // the action-noise stream of qr_rollout_policy
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
-        Q3_HIP(q3_launch_rollout_policy<double>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
+        QR_HIP(q3_launch_rollout_policy<double>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
     else
-        Q3_HIP(q3_launch_rollout_policy<float>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
+        QR_HIP(q3_launch_rollout_policy<float>(e, A, K, obs_out, act_out, logp_out, rew_out, done_out, trunc_out, term_obs, last_obs, states_out, st));
     return QR_OK;
 }
 
 // Every refusal comes before anything is enqueued: a failed call leaves the env and the records untouched.
 int q3_evaluate_policy(q3_env* e, qr_policy* policy, int32_t K, int32_t flags, int32_t* rec, float* recf, void* stream) {
-    const std::string w = "q3_evaluate_policy: ";
-    if (!policy) return q3fail(QR_E_INVALID, w + "null policy handle");
+    const char* who = "q3_evaluate_policy";
+    const std::string w = std::string(who) + ": ";
+    if (!policy) return qr::set_last_error(QR_E_INVALID, w + "null policy handle");
     if (int rc = q3_check_eval_args(e, K, flags, rec, recf, w)) return rc;
-    if (qr::policy_obs_len(policy) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "policy obs_len must be 16 (the state row is the observation)");
-    if (qr::policy_device(policy) != e->device) return q3fail(QR_E_INVALID, w + "policy on another GPU");
-    const qr::half8* wt = qr::policy_weights(policy);
-    if (!wt) return q3fail(QR_E_STATE, w + "the policy has no weights");
-    if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, w + "q3_set_track has not been called");
+    if (int rc = qr::check_policy_handle(policy, kQ3ObsLen, e->device, who, kQ3LenRule)) return rc;
+    const qr::half8* wt = nullptr;
+    if (int rc = qr::fetch_policy_weights(policy, who, wt)) return rc;
+    if (e->kind == Q3_KIND_GATES && !e->has_track) return qr::set_last_error(QR_E_STATE, w + "q3_set_track has not been called");
     const bool f32class = (flags & QR_ROLLOUT_F32CLASS) != 0;
-    Q3_HIP(hipSetDevice(e->device));
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
-        Q3_HIP(q3_launch_eval_policy<double>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
+        QR_HIP(q3_launch_eval_policy<double>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
     else
-        Q3_HIP(q3_launch_eval_policy<float>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
+        QR_HIP(q3_launch_eval_policy<float>(e, wt, qr::policy_weights_lo(policy), f32class, K, rec, recf, st));
     return QR_OK;
 }
 
 int q3_evaluate_policy_bank(q3_env* e, qr_policy_bank* bank, int32_t num_policies, int32_t envs_per_policy, int32_t K, int32_t flags,
                             int32_t* rec, float* recf, void* stream) {
-    const std::string w = "q3_evaluate_policy_bank: ";
-    if (!bank) return q3fail(QR_E_INVALID, w + "null bank handle");
+    const char* who = "q3_evaluate_policy_bank";
+    const std::string w = std::string(who) + ": ";
+    if (!bank) return qr::set_last_error(QR_E_INVALID, w + "null bank handle");
     if (int rc = q3_check_eval_args(e, K, flags, rec, recf, w)) return rc;
-    if (qr::bank_obs_len(bank) != kQ3ObsLen) return q3fail(QR_E_INVALID, w + "bank obs_len must be 16 (the state row is the observation)");
-    if (qr::bank_device(bank) != e->device) return q3fail(QR_E_INVALID, w + "bank on another GPU");
-    if (num_policies < 1 || num_policies > qr::bank_capacity(bank)) return q3fail(QR_E_INVALID, w + "num_policies must be in 1..capacity");
+    if (int rc = qr::check_policy_bank(bank, kQ3ObsLen, e->device, who, "bank", kQ3LenRule)) return rc;
+    if (num_policies < 1 || num_policies > qr::bank_capacity(bank)) return qr::set_last_error(QR_E_INVALID, w + "num_policies must be in 1..capacity");
     if (envs_per_policy < kQ3Block || envs_per_policy % kQ3Block != 0)
-        return q3fail(QR_E_INVALID, w + "envs_per_policy must be a positive multiple of 256 (one workgroup serves one policy)");
+        return qr::set_last_error(QR_E_INVALID, w + "envs_per_policy must be a positive multiple of 256 (one workgroup serves one policy)");
     if ((long long)num_policies * envs_per_policy != (long long)e->P.n)
-        return q3fail(QR_E_INVALID, w + "num_policies * envs_per_policy must equal num_envs");
+        return qr::set_last_error(QR_E_INVALID, w + "num_policies * envs_per_policy must equal num_envs");
     const int unset = qr::bank_first_unset(bank, num_policies);
-    if (unset >= 0) return q3fail(QR_E_STATE, w + "slot " + std::to_string(unset) + " of the bank has no weights");
-    if (e->kind == Q3_KIND_GATES && !e->has_track) return q3fail(QR_E_STATE, w + "q3_set_track has not been called");
+    if (unset >= 0) return qr::set_last_error(QR_E_STATE, w + "slot " + std::to_string(unset) + " of the bank has no weights");
+    if (e->kind == Q3_KIND_GATES && !e->has_track) return qr::set_last_error(QR_E_STATE, w + "q3_set_track has not been called");
     const bool f32class = (flags & QR_ROLLOUT_F32CLASS) != 0;
-    Q3_HIP(hipSetDevice(e->device));
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
-        Q3_HIP(q3_launch_eval_policy_bank<double>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
+        QR_HIP(q3_launch_eval_policy_bank<double>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
                                                   rec, recf, st));
     else
-        Q3_HIP(q3_launch_eval_policy_bank<float>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
+        QR_HIP(q3_launch_eval_policy_bank<float>(e, qr::bank_weights(bank), qr::bank_weights_lo(bank), f32class, num_policies, envs_per_policy, K,
                                                  rec, recf, st));
     return QR_OK;
 }
 
 int q3_get_state(q3_env* e, void* states, int32_t* target, int32_t* steps, void* stream) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
         q3_copy_state_kernel<double><<<e->grid(), kQ3Block, 0, st>>>(e->P.n, e->buffers<double>(), static_cast<double*>(states),
@@ -1195,13 +1175,13 @@ int q3_get_state(q3_env* e, void* states, int32_t* target, int32_t* steps, void*
     else
         q3_copy_state_kernel<float><<<e->grid(), kQ3Block, 0, st>>>(e->P.n, e->buffers<float>(), static_cast<float*>(states),
                                                                    target, steps, nullptr, nullptr, nullptr);
-    Q3_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
 int q3_set_state(q3_env* e, const void* states, const int32_t* target, const int32_t* steps, void* stream) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (e->kind == Q3_KIND_HOVER)
         q3_copy_state_kernel<double><<<e->grid(), kQ3Block, 0, st>>>(e->P.n, e->buffers<double>(), nullptr, nullptr, nullptr,
@@ -1209,17 +1189,17 @@ int q3_set_state(q3_env* e, const void* states, const int32_t* target, const int
     else
         q3_copy_state_kernel<float><<<e->grid(), kQ3Block, 0, st>>>(e->P.n, e->buffers<float>(), nullptr, nullptr, nullptr,
                                                                    static_cast<const float*>(states), target, steps);
-    Q3_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
 int q3_episode_counts(q3_env* e, uint32_t* get_dev, const uint32_t* set_dev, void* stream) {
-    if (!e) return q3fail(QR_E_INVALID, "null q3_env handle");
-    Q3_HIP(hipSetDevice(e->device));
+    if (!e) return qr::set_last_error(QR_E_INVALID, "null q3_env handle");
+    QR_HIP(hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t bytes = (size_t)e->P.n * 4;
-    if (set_dev) Q3_HIP(hipMemcpyAsync(e->d_episode, set_dev, bytes, hipMemcpyDeviceToDevice, st));
-    if (get_dev) Q3_HIP(hipMemcpyAsync(get_dev, e->d_episode, bytes, hipMemcpyDeviceToDevice, st));
+    if (set_dev) QR_HIP(hipMemcpyAsync(e->d_episode, set_dev, bytes, hipMemcpyDeviceToDevice, st));
+    if (get_dev) QR_HIP(hipMemcpyAsync(get_dev, e->d_episode, bytes, hipMemcpyDeviceToDevice, st));
     return QR_OK;
 }
 

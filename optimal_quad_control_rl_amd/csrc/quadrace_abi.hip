@@ -41,14 +41,15 @@ struct qr_env {
         qr::Params P{};
     } sg;
     hipStream_t capture_stream = nullptr;
-    // qr_evaluate_policy_grid: the device copy of the last group map, [group_map_cap] (policy, condition), and its host mirror
-    int2* d_group_map = nullptr;
-    int group_map_cap = 0;
-    std::vector<int32_t> group_map_host;
-    // qr_rollout_policy_population: the device copy of the last per-group sampling table, [pop_table_cap] entries, and its host mirror
-    qr::PopulationEntry* d_pop_table = nullptr;
-    int pop_table_cap = 0;
-    std::vector<qr::PopulationEntry> pop_table_host;
+    // a per-group table of the last launch in a device array of the handle, [cap] entries, and its host mirror (upload_table)
+    template <typename T>
+    struct DeviceTable {
+        T* d = nullptr;
+        int cap = 0;
+        std::vector<T> host;
+    };
+    DeviceTable<int2> group_map;                  // qr_evaluate_policy_grid and the two group rollouts: (policy, condition) per group
+    DeviceTable<qr::PopulationEntry> pop_table;   // qr_rollout_policy_population: the sampling values per group
 };
 
 // A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
@@ -89,13 +90,6 @@ int set_last_error(int code, const std::string& msg) { return fail(code, msg); }
 }  // namespace qr
 
 namespace {
-
-#define QR_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return fail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
-    } while (0)
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -179,12 +173,7 @@ int check_ready(const qr_env* e) {
 }
 
 // hipEvent bracket of a K-step call: skipped when switched off (qr_set_timing) or while the caller captures `st` into a graph
-bool want_events(const qr_env* e, hipStream_t st) {
-    if (!e->timing) return false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return false;
-    return true;
-}
+bool want_events(const qr_env* e, hipStream_t st) { return e->timing && !qr::stream_is_capturing(st); }
 
 // K-step entry points write terminal observations to row [k][env]: the registered buffer must hold K rows of N envs
 int check_term_rows(const qr_env* e, int K, const char* who) {
@@ -222,53 +211,66 @@ int check_group_shape(const qr_env* e, int groups, int envs_per_group, const cha
     return QR_OK;
 }
 
-// The group map of qr_evaluate_policy_grid / qr_rollout_policy_conditions: interleaved (policy, condition) per group, in a device array
-// of the handle.  An equal map is already there; another one is copied after a device synchronisation, like the tables (an earlier
-// launch may still read the array), which a stream under capture does not allow.
-int upload_group_map(qr_env* e, const std::vector<int32_t>& map, int num_groups, hipStream_t st, const char* who) {
-    if (e->d_group_map && map == e->group_map_host) return QR_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(QR_E_STATE, std::string(who) + ": a new group map is uploaded after a device synchronisation, which a stream under "
-                                                   "capture does not allow; call once with this map outside the capture");
-    QR_HIP(hipDeviceSynchronize());
-    e->group_map_host.clear();   // nothing valid on the device until the copy below has succeeded
-    if (num_groups > e->group_map_cap) {
-        if (e->d_group_map) (void)hipFree(e->d_group_map);
-        e->d_group_map = nullptr;
-        e->group_map_cap = 0;
-        QR_HIP(hipMalloc((void**)&e->d_group_map, sizeof(int2) * (size_t)num_groups));
-        e->group_map_cap = num_groups;
+// What the three group entry points (qr_evaluate_policy_grid, qr_rollout_policy_conditions, qr_rollout_policy_population) refuse about
+// the condition bank and the group shape, in the order they all refuse it.
+int check_condition_groups(const qr_env* e, const qr_condition_bank* conditions, int num_groups, int envs_per_group, const char* who) {
+    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, std::string(who) + ": condition bank of another variant");
+    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, std::string(who) + ": condition bank on another GPU");
+    if (num_groups < 1) return fail(QR_E_INVALID, std::string(who) + ": num_groups must be >= 1");
+    return check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", who);
+}
+
+// The group maps of the same three: first every index against its bank, then every slot it names filled; within a pass group by group,
+// the policy before the condition.  No index reaches the device that has not passed here.  policy_of_group = nullptr: no policy bank
+// (qr_rollout_policy_conditions).
+int check_group_indices(const qr_policy_bank* policies, const int32_t* policy_of_group, const qr_condition_bank* conditions,
+                        const int32_t* condition_of_group, int num_groups, const char* who) {
+    const int pcap = policy_of_group ? qr::bank_capacity(policies) : 0;
+    const auto at = [who](const char* map, int g) { return std::string(who) + ": " + map + "[" + std::to_string(g) + "] is outside the "; };
+    const auto slot = [who](int s) { return std::string(who) + ": slot " + std::to_string(s) + " of the "; };
+    for (int g = 0; g < num_groups; ++g) {
+        if (policy_of_group && (policy_of_group[g] < 0 || policy_of_group[g] >= pcap))
+            return fail(QR_E_INVALID, at("policy_of_group", g) + "policy bank");
+        if (condition_of_group[g] < 0 || condition_of_group[g] >= conditions->capacity)
+            return fail(QR_E_INVALID, at("condition_of_group", g) + "condition bank");
     }
-    QR_HIP(hipMemcpy(e->d_group_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    e->group_map_host = map;
+    for (int g = 0; g < num_groups; ++g) {
+        if (policy_of_group && !qr::bank_slot_set(policies, policy_of_group[g]))
+            return fail(QR_E_STATE, slot(policy_of_group[g]) + "policy bank has no weights");
+        if (!conditions->is_set[(size_t)condition_of_group[g]])
+            return fail(QR_E_STATE, slot(condition_of_group[g]) + "condition bank was never set");
+    }
     return QR_OK;
 }
 
-// The per-group sampling table of qr_rollout_policy_population, in a device array of the handle under the rule of upload_group_map:
-// an equal table (byte for byte; the pad is zero) is already there, another one is copied after a device synchronisation, which a
-// stream under capture does not allow.
-int upload_population_table(qr_env* e, const std::vector<qr::PopulationEntry>& table, hipStream_t st, const char* who) {
-    const size_t bytes = table.size() * sizeof(qr::PopulationEntry);
-    if (e->d_pop_table && table.size() == e->pop_table_host.size() && std::memcmp(table.data(), e->pop_table_host.data(), bytes) == 0)
-        return QR_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(QR_E_STATE, std::string(who) + ": a new sampling table (log_std, noise_seed per group) is uploaded after a device "
-                                                   "synchronisation, which a stream under capture does not allow; call once with these "
-                                                   "values outside the capture");
+// A per-group table of a launch (the group map, the sampling table) in a device array of the handle.  An equal table (byte for byte; any
+// pad is zero) is already there; another one is copied after a device synchronisation, like the tables (an earlier launch may still
+// read the array), which a stream under capture does not allow.  `noun` / `these`: what the capture refusal calls the table.
+template <typename T>
+int upload_table(qr_env::DeviceTable<T>& t, const std::vector<T>& table, hipStream_t st, const char* who, const char* noun, const char* these) {
+    const size_t bytes = table.size() * sizeof(T);
+    if (t.d && table.size() == t.host.size() && std::memcmp(table.data(), t.host.data(), bytes) == 0) return QR_OK;
+    if (qr::stream_is_capturing(st))
+        return fail(QR_E_STATE, std::string(who) + ": a new " + noun + " is uploaded after a device synchronisation, which a stream under "
+                                                   "capture does not allow; call once with " + these + " outside the capture");
     QR_HIP(hipDeviceSynchronize());
-    e->pop_table_host.clear();   // nothing valid on the device until the copy below has succeeded
-    if ((int)table.size() > e->pop_table_cap) {
-        if (e->d_pop_table) (void)hipFree(e->d_pop_table);
-        e->d_pop_table = nullptr;
-        e->pop_table_cap = 0;
-        QR_HIP(hipMalloc((void**)&e->d_pop_table, bytes));
-        e->pop_table_cap = (int)table.size();
+    t.host.clear();   // nothing valid on the device until the copy below has succeeded
+    if ((int)table.size() > t.cap) {
+        if (t.d) (void)hipFree(t.d);
+        t.d = nullptr;
+        t.cap = 0;
+        QR_HIP(hipMalloc((void**)&t.d, bytes));
+        t.cap = (int)table.size();
     }
-    QR_HIP(hipMemcpy(e->d_pop_table, table.data(), bytes, hipMemcpyHostToDevice));
-    e->pop_table_host = table;
+    QR_HIP(hipMemcpy(t.d, table.data(), bytes, hipMemcpyHostToDevice));
+    t.host = table;
     return QR_OK;
+}
+// the (policy, condition) map of a launch; policy_of_group = nullptr: the policy half is zero
+int upload_group_map(qr_env* e, const int32_t* policy_of_group, const int32_t* condition_of_group, int num_groups, hipStream_t st, const char* who) {
+    std::vector<int2> map((size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g) map[(size_t)g] = make_int2(policy_of_group ? policy_of_group[g] : 0, condition_of_group[g]);
+    return upload_table(e->group_map, map, st, who, "group map", "this map");
 }
 
 // One launch on `st` inside the hipEvent bracket of want_events: QR_TIMED_LAUNCH(e, st, launcher call).  A failed launch reports the
@@ -281,6 +283,32 @@ int timed_launch(qr_env* e, hipStream_t st, const char* what, Launch&& launch) {
     if (hipError_t err = launch()) return fail(QR_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
     if (ev) QR_HIP(hipEventRecord(e->ev1, st));
     e->timing_valid = ev;
+    return QR_OK;
+}
+
+// the open-loop entry points (qr_step, qr_step_many, qr_step_launches, qr_profile_steps) need these four; trunc may be null
+int check_step_buffers(const float* actions, const float* obs, const float* rew, const uint8_t* done, const char* who) {
+    if (!actions || !obs || !rew || !done) return fail(QR_E_INVALID, std::string(who) + ": actions/obs/rew/done buffers are required");
+    return QR_OK;
+}
+
+// step k of a K-step call as one launch of the step kernel: row k of the [K][N][...] buffers and of the terminal-observation rows
+hipError_t launch_step_row(const qr_env* e, int k, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc, hipStream_t st) {
+    const size_t row = (size_t)k * (size_t)e->cfg.num_envs;
+    qr::Params Pk = e->P;
+    if (Pk.term_obs) Pk.term_obs += row * e->L;
+    return qr::launch_step(e->cfg.variant, Pk, actions + row * 4, obs + row * e->L, rew + row, done + row, trunc ? trunc + row : nullptr, st);
+}
+
+// What the closed-loop rollouts (qr_rollout_policy, _conditions, _population) refuse first, in one order: `required` = the entry
+// point's handles and arrays are all there.
+int check_rollout_common(const qr_env* e, int K, bool required, const float* obs, const float* act, const float* logp, const float* rew,
+                         const uint8_t* done, const char* who) {
+    if (K < 1 || !required) return fail(QR_E_INVALID, std::string(who) + ": bad argument");
+    if (int rc = check_term_rows(e, K, who)) return rc;
+    if (!obs || !act || !logp || !rew || !done) return fail(QR_E_INVALID, std::string(who) + ": obs/act/logp/rew/done buffers are required");
+    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
+        return fail(QR_E_STATE, std::string(who) + ": pause / pause_if_collision envs are evaluation modes; use qr_step");
     return QR_OK;
 }
 
@@ -368,8 +396,8 @@ int qr_destroy(qr_env* e) {
     if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
     if (e->slab) (void)hipFree(e->slab);
     if (e->d_tables) (void)hipFree(e->d_tables);
-    if (e->d_group_map) (void)hipFree(e->d_group_map);
-    if (e->d_pop_table) (void)hipFree(e->d_pop_table);
+    if (e->group_map.d) (void)hipFree(e->group_map.d);
+    if (e->pop_table.d) (void)hipFree(e->pop_table.d);
     delete e;
     return QR_OK;
 }
@@ -524,8 +552,7 @@ int qr_reset(qr_env* e, const uint8_t* mask_dev, float* obs_out_dev, void* strea
 int qr_step(qr_env* e, const float* actions_dev, float* obs_out_dev, float* rew_out_dev, uint8_t* done_out_dev,
             uint8_t* trunc_out_dev, void* stream) {
     if (int rc = check_ready(e)) return rc;
-    if (!actions_dev || !obs_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, "qr_step: actions/obs/rew/done buffers are required");
+    if (int rc = check_step_buffers(actions_dev, obs_out_dev, rew_out_dev, done_out_dev, "qr_step")) return rc;
     QR_HIP(qr::launch_step(e->cfg.variant, e->P, actions_dev, obs_out_dev, rew_out_dev, done_out_dev, trunc_out_dev,
                            (hipStream_t)stream));
     return QR_OK;
@@ -536,17 +563,11 @@ int qr_step_many(qr_env* e, int32_t K, const float* actions_dev, float* obs_out_
     if (int rc = check_ready(e)) return rc;
     if (K < 1) return fail(QR_E_INVALID, "qr_step_many: num_steps must be >= 1");
     if (int rc = check_term_rows(e, K, "qr_step_many")) return rc;
-    if (!actions_dev || !obs_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, "qr_step_many: actions/obs/rew/done buffers are required");
+    if (int rc = check_step_buffers(actions_dev, obs_out_dev, rew_out_dev, done_out_dev, "qr_step_many")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
     // one launch: the fused rollout kernel keeps the env state in registers across the K steps
-    QR_HIP(qr::launch_rollout(e->cfg.variant, e->P, e->rollout_form, K, actions_dev, obs_out_dev, rew_out_dev, done_out_dev,
-                              trunc_out_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout(e->cfg.variant, e->P, e->rollout_form, K, actions_dev, obs_out_dev, rew_out_dev, done_out_dev,
+                                                      trunc_out_dev, st));
 }
 
 int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_out_dev, float* rew_out_dev,
@@ -554,20 +575,11 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
     if (int rc = check_ready(e)) return rc;
     if (K < 1) return fail(QR_E_INVALID, "qr_step_launches: num_steps must be >= 1");
     if (int rc = check_term_rows(e, K, "qr_step_launches")) return rc;
-    if (!actions_dev || !obs_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, "qr_step_launches: actions/obs/rew/done buffers are required");
+    if (int rc = check_step_buffers(actions_dev, obs_out_dev, rew_out_dev, done_out_dev, "qr_step_launches")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)e->cfg.num_envs;
     // a caller that is itself capturing `stream` into a graph gets plain kernel nodes (a graph launch cannot be captured)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-        for (int k = 0; k < K; ++k) {
-            qr::Params Pk = e->P;
-            if (Pk.term_obs) Pk.term_obs += (size_t)k * n * e->L;
-            QR_HIP(qr::launch_step(e->cfg.variant, Pk, actions_dev + (size_t)k * n * 4, obs_out_dev + (size_t)k * n * e->L,
-                                   rew_out_dev + (size_t)k * n, done_out_dev + (size_t)k * n,
-                                   trunc_out_dev ? trunc_out_dev + (size_t)k * n : nullptr, st));
-        }
+    if (qr::stream_is_capturing(st)) {
+        for (int k = 0; k < K; ++k) QR_HIP(launch_step_row(e, k, actions_dev, obs_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, st));
         e->timing_valid = false;
         return QR_OK;
     }
@@ -580,13 +592,8 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
         hipGraph_t graph = nullptr;
         QR_HIP(hipStreamBeginCapture(e->capture_stream, hipStreamCaptureModeThreadLocal));
         hipError_t err = hipSuccess;
-        for (int k = 0; k < K && err == hipSuccess; ++k) {
-            qr::Params Pk = e->P;
-            if (Pk.term_obs) Pk.term_obs += (size_t)k * n * e->L;   // terminal-observation rows [k][env]
-            err = qr::launch_step(e->cfg.variant, Pk, actions_dev + (size_t)k * n * 4, obs_out_dev + (size_t)k * n * e->L,
-                                  rew_out_dev + (size_t)k * n, done_out_dev + (size_t)k * n,
-                                  trunc_out_dev ? trunc_out_dev + (size_t)k * n : nullptr, e->capture_stream);
-        }
+        for (int k = 0; k < K && err == hipSuccess; ++k)
+            err = launch_step_row(e, k, actions_dev, obs_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, e->capture_stream);
         const hipError_t end = hipStreamEndCapture(e->capture_stream, &graph);
         if (err != hipSuccess || end != hipSuccess) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -602,50 +609,22 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
         g.K = K; g.act = actions_dev; g.obs = obs_out_dev; g.rew = rew_out_dev; g.done = done_out_dev; g.trunc = trunc_out_dev;
         std::memcpy(&g.P, &e->P, sizeof(e->P));  // byte copy: compared with memcmp above
     }
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(hipGraphLaunch(g.exec, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
+    return QR_TIMED_LAUNCH(e, st, hipGraphLaunch(g.exec, st));
 }
 
 // What qr_rollout_policy and qr_rollout_policy_conditions refuse about their shared arguments and the handle's mode, in one order; on
-// success A holds the sampling arguments of the launch.
+// success A holds the weights and the sampling arguments of the launch.
 static int rollout_policy_args(const qr_env* e, qr_policy* policy, int K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
                                int flags, const float* obs_out_dev, const float* act_out_dev, const float* logp_out_dev,
                                const float* rew_out_dev, const uint8_t* done_out_dev, const char* who, qr::PolicyArgs& A) {
-    const std::string w = std::string(who) + ": ";
-    if (K < 1 || !policy || !log_std) return fail(QR_E_INVALID, w + "bad argument");
-    if (int rc = check_term_rows(e, K, who)) return rc;
-    if (!obs_out_dev || !act_out_dev || !logp_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
-    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, w + "pause / pause_if_collision envs are evaluation modes; use qr_step");
-    const qr::half8* wt = qr::policy_weights(policy);
-    if (!wt) return fail(QR_E_STATE, w + "the policy has no weights");
-    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, w + "policy obs_len != env obs_len");
-    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, w + "policy on another GPU");
-    if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
-        return fail(QR_E_INVALID, w + "`deterministic` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (int rc = check_rollout_common(e, K, policy && log_std, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, who)) return rc;
     A = qr::PolicyArgs{};
-    A.weights = wt;
+    if (int rc = qr::fetch_policy_weights(policy, who, A.weights)) return rc;
+    if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, who)) return rc;
+    if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
+        return fail(QR_E_INVALID, std::string(who) + ": `deterministic` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
     A.weights_lo = qr::policy_weights_lo(policy);
-    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
-    float sum_log_std = 0.0f;
-    for (int c = 0; c < 4; ++c) {
-        A.std[c] = expf(log_std[c]);
-        sum_log_std += log_std[c];
-    }
-    A.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
-    // Domain separation: the reset stream is Philox(counter = (env id, episode, block), key = env seed), the action
-    // noise Philox(counter = (env id, step), key = noise seed).  With equal seeds the two would share random bits
-    // whenever (episode, block) == (step lo, step hi); the noise key is therefore tweaked by a fixed odd constant.
-    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;
-    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
-    A.step_lo = (uint32_t)first_step;
-    A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    qr::set_sampling(A, qr::sampling_entry(log_std, noise_seed), first_step, flags);
     return QR_OK;
 }
 
@@ -659,13 +638,8 @@ int qr_rollout_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_
                                      rew_out_dev, done_out_dev, "qr_rollout_policy", A))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool ev = want_events(e, st);
-    if (ev) QR_HIP(hipEventRecord(e->ev0, st));
-    QR_HIP(qr::launch_rollout_policy(e->cfg.variant, e->P, A, K, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
-                                     done_out_dev, trunc_out_dev, last_obs_dev, st));
-    if (ev) QR_HIP(hipEventRecord(e->ev1, st));
-    e->timing_valid = ev;
-    return QR_OK;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy(e->cfg.variant, e->P, A, K, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
+                                                             done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
 int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_per_lap, int32_t flags, int32_t* rec_dev,
@@ -673,12 +647,9 @@ int qr_evaluate_policy(qr_env* e, qr_policy* policy, int32_t K, int32_t gates_pe
     if (int rc = check_ready(e)) return rc;
     if (!policy) return fail(QR_E_INVALID, "qr_evaluate_policy: null policy handle");
     if (int rc = check_eval_args(e, K, &gates_per_lap, flags, rec_dev, recf_dev, "qr_evaluate_policy")) return rc;
-    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy: policy obs_len != env obs_len");
-    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy: policy on another GPU");
-    const qr::half8* w = qr::policy_weights(policy);
-    if (!w) return fail(QR_E_STATE, "qr_evaluate_policy: the policy has no weights");
+    if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, "qr_evaluate_policy")) return rc;
     qr::PolicyArgs A{};   // no sampling: only the weight images are read
-    A.weights = w;
+    if (int rc = qr::fetch_policy_weights(policy, "qr_evaluate_policy", A.weights)) return rc;
     A.weights_lo = qr::policy_weights_lo(policy);
     A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
     A.deterministic = 1;
@@ -692,8 +663,7 @@ int qr_evaluate_policy_bank(qr_env* e, qr_policy_bank* bank, int32_t num_policie
     if (int rc = check_ready(e)) return rc;
     if (!bank) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: null bank handle");
     if (int rc = check_eval_args(e, K, &gates_per_lap, flags, rec_dev, recf_dev, "qr_evaluate_policy_bank")) return rc;
-    if (qr::bank_obs_len(bank) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank obs_len != env obs_len");
-    if (qr::bank_device(bank) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_bank: bank on another GPU");
+    if (int rc = qr::check_policy_bank(bank, e->L, e->cfg.device, "qr_evaluate_policy_bank", "bank")) return rc;
     if (num_policies < 1 || num_policies > qr::bank_capacity(bank))
         return fail(QR_E_INVALID, "qr_evaluate_policy_bank: num_policies must be in 1..capacity");
     if (int rc = check_group_shape(e, num_policies, envs_per_policy, "num_policies", "policy", "qr_evaluate_policy_bank")) return rc;
@@ -790,35 +760,14 @@ int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_ba
     if (!conditions) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: null condition bank handle");
     if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: the two group maps are required");
     if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, "qr_evaluate_policy_grid")) return rc;
-    if (qr::bank_obs_len(policies) != e->L) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: bank obs_len != env obs_len");
-    if (qr::bank_device(policies) != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: policy bank on another GPU");
-    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank of another variant");
-    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition bank on another GPU");
-    if (num_groups < 1) return fail(QR_E_INVALID, "qr_evaluate_policy_grid: num_groups must be >= 1");
-    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", "qr_evaluate_policy_grid")) return rc;
-    const int pcap = qr::bank_capacity(policies);
-    for (int g = 0; g < num_groups; ++g) {
-        const int p = policy_of_group[g], c = condition_of_group[g];
-        if (p < 0 || p >= pcap)
-            return fail(QR_E_INVALID, "qr_evaluate_policy_grid: policy_of_group[" + std::to_string(g) + "] is outside the policy bank");
-        if (c < 0 || c >= conditions->capacity)
-            return fail(QR_E_INVALID, "qr_evaluate_policy_grid: condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
-    }
-    for (int g = 0; g < num_groups; ++g) {
-        if (!qr::bank_slot_set(policies, policy_of_group[g]))
-            return fail(QR_E_STATE, "qr_evaluate_policy_grid: slot " + std::to_string(policy_of_group[g]) + " of the policy bank has no weights");
-        if (!conditions->is_set[(size_t)condition_of_group[g]])
-            return fail(QR_E_STATE, "qr_evaluate_policy_grid: slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
-    }
+    const char* who = "qr_evaluate_policy_grid";
+    if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (int rc = check_group_indices(policies, policy_of_group, conditions, condition_of_group, num_groups, who)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<int32_t> map(2 * (size_t)num_groups);
-    for (int g = 0; g < num_groups; ++g) {
-        map[2 * (size_t)g + 0] = policy_of_group[g];
-        map[2 * (size_t)g + 1] = condition_of_group[g];
-    }
-    if (int rc = upload_group_map(e, map, num_groups, st, "qr_evaluate_policy_grid")) return rc;
+    if (int rc = upload_group_map(e, policy_of_group, condition_of_group, num_groups, st, who)) return rc;
     return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
-                                       e->d_group_map, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
+                                       e->group_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
 }
 
 // The refusals come first and in full, as in qr_evaluate_policy_grid; the map travels in that call's (policy, condition) array with
@@ -835,91 +784,42 @@ int qr_rollout_policy_conditions(qr_env* e, qr_policy* policy, qr_condition_bank
         return rc;
     if (!conditions) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: null condition bank handle");
     if (!condition_of_group) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: the group map is required");
-    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition bank of another variant");
-    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition bank on another GPU");
-    if (num_groups < 1) return fail(QR_E_INVALID, "qr_rollout_policy_conditions: num_groups must be >= 1");
-    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", who)) return rc;
-    for (int g = 0; g < num_groups; ++g)
-        if (condition_of_group[g] < 0 || condition_of_group[g] >= conditions->capacity)
-            return fail(QR_E_INVALID, "qr_rollout_policy_conditions: condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
-    for (int g = 0; g < num_groups; ++g)
-        if (!conditions->is_set[(size_t)condition_of_group[g]])
-            return fail(QR_E_STATE, "qr_rollout_policy_conditions: slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (int rc = check_group_indices(nullptr, nullptr, conditions, condition_of_group, num_groups, who)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<int32_t> map(2 * (size_t)num_groups, 0);
-    for (int g = 0; g < num_groups; ++g) map[2 * (size_t)g + 1] = condition_of_group[g];
-    if (int rc = upload_group_map(e, map, num_groups, st, who)) return rc;
-    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_cond(e->cfg.variant, e->P, A, conditions->d_slots, e->d_group_map, num_groups, envs_per_group, K,
+    if (int rc = upload_group_map(e, nullptr, condition_of_group, num_groups, st, who)) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_cond(e->cfg.variant, e->P, A, conditions->d_slots, e->group_map.d, num_groups, envs_per_group, K,
                                        obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
 // The refusals come first and in full: what qr_rollout_policy_conditions refuses, what qr_evaluate_policy_grid refuses about its policy
-// bank, and the NULL arrays; nothing is enqueued or copied before the last of them.  The per-group sampling entries are computed with
-// the statements of rollout_policy_args, so that entry g holds the bits qr_rollout_policy would use for log_std[g] and noise_seed[g].
+// bank, and the NULL arrays; nothing is enqueued or copied before the last of them.  Entry g of the sampling table holds the bits
+// qr_rollout_policy would use for log_std[g] and noise_seed[g] (qr::sampling_entry).
 int qr_rollout_policy_population(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups, int32_t envs_per_group,
                                  const int32_t* policy_of_group, const int32_t* condition_of_group, int32_t K, const float* log_std,
                                  const uint64_t* noise_seed, uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev,
                                  float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev,
                                  void* stream) {
     const char* who = "qr_rollout_policy_population";
-    const std::string w = std::string(who) + ": ";
     if (int rc = check_ready(e)) return rc;
-    if (K < 1 || !policies || !log_std || !noise_seed) return fail(QR_E_INVALID, w + "bad argument");
-    if (int rc = check_term_rows(e, K, who)) return rc;
-    if (!obs_out_dev || !act_out_dev || !logp_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, w + "obs/act/logp/rew/done buffers are required");
-    if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
-        return fail(QR_E_STATE, w + "pause / pause_if_collision envs are evaluation modes; use qr_step");
-    if (qr::bank_obs_len(policies) != e->L) return fail(QR_E_INVALID, w + "bank obs_len != env obs_len");
-    if (qr::bank_device(policies) != e->cfg.device) return fail(QR_E_INVALID, w + "policy bank on another GPU");
+    if (int rc = check_rollout_common(e, K, policies && log_std && noise_seed, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, who))
+        return rc;
+    if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
     if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
-        return fail(QR_E_INVALID, w + "`flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
-    if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
-    if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, w + "the two group maps are required");
-    if (conditions->variant != e->cfg.variant) return fail(QR_E_INVALID, w + "condition bank of another variant");
-    if (conditions->device != e->cfg.device) return fail(QR_E_INVALID, w + "condition bank on another GPU");
-    if (num_groups < 1) return fail(QR_E_INVALID, w + "num_groups must be >= 1");
-    if (int rc = check_group_shape(e, num_groups, envs_per_group, "num_groups", "group", who)) return rc;
-    const int pcap = qr::bank_capacity(policies);
-    for (int g = 0; g < num_groups; ++g) {
-        const int p = policy_of_group[g], c = condition_of_group[g];
-        if (p < 0 || p >= pcap) return fail(QR_E_INVALID, w + "policy_of_group[" + std::to_string(g) + "] is outside the policy bank");
-        if (c < 0 || c >= conditions->capacity)
-            return fail(QR_E_INVALID, w + "condition_of_group[" + std::to_string(g) + "] is outside the condition bank");
-    }
-    for (int g = 0; g < num_groups; ++g) {
-        if (!qr::bank_slot_set(policies, policy_of_group[g]))
-            return fail(QR_E_STATE, w + "slot " + std::to_string(policy_of_group[g]) + " of the policy bank has no weights");
-        if (!conditions->is_set[(size_t)condition_of_group[g]])
-            return fail(QR_E_STATE, w + "slot " + std::to_string(condition_of_group[g]) + " of the condition bank was never set");
-    }
+        return fail(QR_E_INVALID, std::string(who) + ": `flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
+    if (!conditions) return fail(QR_E_INVALID, std::string(who) + ": null condition bank handle");
+    if (!policy_of_group || !condition_of_group) return fail(QR_E_INVALID, std::string(who) + ": the two group maps are required");
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (int rc = check_group_indices(policies, policy_of_group, conditions, condition_of_group, num_groups, who)) return rc;
     qr::PolicyArgs A{};   // launch-wide: the step counter and the two flags; weights and sampling values are per group
-    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
-    A.step_lo = (uint32_t)first_step;
-    A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
-    std::vector<int32_t> map(2 * (size_t)num_groups);
+    qr::set_sampling(A, qr::PopulationEntry{}, first_step, flags);
     std::vector<qr::PopulationEntry> table((size_t)num_groups);
-    for (int g = 0; g < num_groups; ++g) {
-        map[2 * (size_t)g + 0] = policy_of_group[g];
-        map[2 * (size_t)g + 1] = condition_of_group[g];
-        qr::PopulationEntry& t = table[(size_t)g];
-        std::memset(&t, 0, sizeof(t));
-        const float* ls = log_std + 4 * (size_t)g;
-        float sum_log_std = 0.0f;   // rollout_policy_args' statements, per group
-        for (int c = 0; c < 4; ++c) {
-            t.std[c] = expf(ls[c]);
-            sum_log_std += ls[c];
-        }
-        t.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
-        t.seed_lo = (uint32_t)noise_seed[g] ^ 0x9E3779B9u;         // the noise key's domain separation, as there
-        t.seed_hi = (uint32_t)(noise_seed[g] >> 32) ^ 0x85EBCA6Bu;
-    }
+    for (int g = 0; g < num_groups; ++g) table[(size_t)g] = qr::sampling_entry(log_std + 4 * (size_t)g, noise_seed[g]);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_group_map(e, map, num_groups, st, who)) return rc;
-    if (int rc = upload_population_table(e, table, st, who)) return rc;
+    if (int rc = upload_group_map(e, policy_of_group, condition_of_group, num_groups, st, who)) return rc;
+    if (int rc = upload_table(e->pop_table, table, st, who, "sampling table (log_std, noise_seed per group)", "these values")) return rc;
     return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_population(e->cfg.variant, e->P, A, qr::bank_weights(policies), qr::bank_weights_lo(policies),
-                                       conditions->d_slots, e->d_group_map, e->d_pop_table, num_groups, envs_per_group, K, obs_out_dev,
+                                       conditions->d_slots, e->group_map.d, e->pop_table.d, num_groups, envs_per_group, K, obs_out_dev,
                                        act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
@@ -938,20 +838,11 @@ int qr_record_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log_s
         return fail(QR_E_INVALID, "qr_record_policy: `flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
     if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
         return fail(QR_E_STATE, "qr_record_policy: pause / pause_if_collision envs are evaluation modes; use qr_step");
-    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_record_policy: policy obs_len != env obs_len");
-    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_record_policy: policy on another GPU");
-    const qr::half8* w = qr::policy_weights(policy);
-    if (!w) return fail(QR_E_STATE, "qr_record_policy: the policy has no weights");
-    qr::PolicyArgs A{};   // the sampling arguments of qr_rollout_policy (same noise stream); no log-prob is computed
-    A.weights = w;
+    if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, "qr_record_policy")) return rc;
+    qr::PolicyArgs A{};   // the sampling arguments of qr_rollout_policy (same noise stream); the kernel computes no log-prob
+    if (int rc = qr::fetch_policy_weights(policy, "qr_record_policy", A.weights)) return rc;
     A.weights_lo = qr::policy_weights_lo(policy);
-    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
-    for (int c = 0; c < 4; ++c) A.std[c] = expf(log_std[c]);
-    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;   // domain separation from the reset stream: see qr_rollout_policy
-    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
-    A.step_lo = (uint32_t)first_step;
-    A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    qr::set_sampling(A, qr::sampling_entry(log_std, noise_seed), first_step, flags);
     hipStream_t st = (hipStream_t)stream;
     return QR_TIMED_LAUNCH(e, st, qr::launch_record_policy(e->cfg.variant, e->P, A, K, rec_envs, rows_dev, st));
 }
@@ -974,20 +865,11 @@ int qr_blackbox_policy(qr_env* e, qr_policy* policy, int32_t K, const float* log
         return fail(QR_E_INVALID, "qr_blackbox_policy: `flags` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
     if (e->P.flags & (qr::kFlagPause | qr::kFlagPauseIfCollision))
         return fail(QR_E_STATE, "qr_blackbox_policy: pause / pause_if_collision envs are evaluation modes; use qr_step");
-    if (qr::policy_obs_len(policy) != e->L) return fail(QR_E_INVALID, "qr_blackbox_policy: policy obs_len != env obs_len");
-    if (qr::policy_device(policy) != e->cfg.device) return fail(QR_E_INVALID, "qr_blackbox_policy: policy on another GPU");
-    const qr::half8* w = qr::policy_weights(policy);
-    if (!w) return fail(QR_E_STATE, "qr_blackbox_policy: the policy has no weights");
+    if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, "qr_blackbox_policy")) return rc;
     qr::PolicyArgs A{};   // the sampling arguments of qr_record_policy / qr_rollout_policy (same noise stream)
-    A.weights = w;
+    if (int rc = qr::fetch_policy_weights(policy, "qr_blackbox_policy", A.weights)) return rc;
     A.weights_lo = qr::policy_weights_lo(policy);
-    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
-    for (int c = 0; c < 4; ++c) A.std[c] = expf(log_std[c]);
-    A.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;   // domain separation from the reset stream: see qr_rollout_policy
-    A.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
-    A.step_lo = (uint32_t)first_step;
-    A.step_hi = (uint32_t)(first_step >> 32);
-    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+    qr::set_sampling(A, qr::sampling_entry(log_std, noise_seed), first_step, flags);
     const int slot0 = (int)(first_step % (uint64_t)window);   // the ring slot of the call's first step
     hipStream_t st = (hipStream_t)stream;
     return QR_TIMED_LAUNCH(e, st, qr::launch_blackbox_policy(e->cfg.variant, e->P, A, K, rec_envs, trigger, window, slot0, ring_dev, st_dev, term_dev, st));
@@ -1059,19 +941,13 @@ int qr_profile_steps(qr_env* e, int32_t K, const float* actions_dev, float* obs_
     if (int rc = check_ready(e)) return rc;
     if (K < 1 || !mean_kernel_ms || !region_ms) return fail(QR_E_INVALID, "qr_profile_steps: bad argument");
     if (int rc = check_term_rows(e, K, "qr_profile_steps")) return rc;
-    if (!actions_dev || !obs_out_dev || !rew_out_dev || !done_out_dev)
-        return fail(QR_E_INVALID, "qr_profile_steps: actions/obs/rew/done buffers are required");
+    if (int rc = check_step_buffers(actions_dev, obs_out_dev, rew_out_dev, done_out_dev, "qr_profile_steps")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)e->cfg.num_envs;
     std::vector<hipEvent_t> ev(2 * (size_t)K);
     for (auto& x : ev) QR_HIP(hipEventCreate(&x));
     for (int k = 0; k < K; ++k) {
         QR_HIP(hipEventRecord(ev[2 * k], st));
-        qr::Params Pk = e->P;
-        if (Pk.term_obs) Pk.term_obs += (size_t)k * n * e->L;   // terminal-observation rows [k][env]
-        QR_HIP(qr::launch_step(e->cfg.variant, Pk, actions_dev + (size_t)k * n * 4, obs_out_dev + (size_t)k * n * e->L,
-                               rew_out_dev + (size_t)k * n, done_out_dev + (size_t)k * n,
-                               trunc_out_dev ? trunc_out_dev + (size_t)k * n : nullptr, st));
+        QR_HIP(launch_step_row(e, k, actions_dev, obs_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, st));
         QR_HIP(hipEventRecord(ev[2 * k + 1], st));
     }
     QR_HIP(hipEventSynchronize(ev[2 * K - 1]));

@@ -6,11 +6,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 #include <type_traits>
 
 #include "../../include/quadrace.h"
 #include "quadrace_device.hpp"
+#include "quadrace_host.hpp"   // set_last_error, QR_HIP, stream_is_capturing
 #include "quadrace_policy.hpp"
 
 namespace qr {
@@ -96,9 +98,6 @@ hipError_t launch_dynamic_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st,
 // ---------------------------------------------------------------------------------------------------
 // defined in one translation unit, called from another
 // ---------------------------------------------------------------------------------------------------
-// quadrace_abi.hip
-int set_last_error(int code, const std::string& msg);
-
 // quadrace_kernels.hip
 hipError_t launch_step(int variant, const Params& P, const float* actions, float* obs, float* rew, uint8_t* done,
                        uint8_t* trunc, hipStream_t st);
@@ -142,7 +141,7 @@ hipError_t launch_rollout_policy_cond(int variant, const Params& P, const Policy
 
 // quadrace_rollout_population.hip: the closed-loop rollout for a population of policies (qr_rollout_policy_population): the workgroups of
 // group g fly policy map[g].x under condition map[g].y and sample with table[g]; A carries the launch-wide step counter, deterministic
-// and f32class only.  One entry = what rollout_policy_args computes for one (log_std, noise seed): 32 bytes, read by one scalar load.
+// and f32class only.  One entry = the sampling values of one (log_std, noise seed): 32 bytes, read by one scalar load.
 struct PopulationEntry {
     float std[4];               // exp(log_std)
     float logp_const;           // -sum(log_std) - 2*log(2*pi)
@@ -150,6 +149,34 @@ struct PopulationEntry {
     uint32_t pad;
 };
 static_assert(sizeof(PopulationEntry) == 32, "PopulationEntry is the 32-byte device table entry");
+// The sampling values of every closed-loop entry point (rollout, condition mix, population, recorder, black box, q3 rollout), computed
+// HERE and nowhere else: the tests demand that they agree bit for bit.  The pad stays zero (the table is compared bytewise).
+inline PopulationEntry sampling_entry(const float log_std[4], uint64_t noise_seed) {
+    PopulationEntry t{};
+    float sum_log_std = 0.0f;
+    for (int c = 0; c < 4; ++c) {
+        t.std[c] = expf(log_std[c]);
+        sum_log_std += log_std[c];
+    }
+    t.logp_const = -sum_log_std - 2.0f * 1.8378770664093453f;  // 4 * 0.5 * log(2*pi)
+    // Domain separation: the reset stream is Philox(counter = (env id, episode, block), key = env seed), the action
+    // noise Philox(counter = (env id, step), key = noise seed).  With equal seeds the two would share random bits
+    // whenever (episode, block) == (step lo, step hi); the noise key is therefore tweaked by a fixed odd constant.
+    t.seed_lo = (uint32_t)noise_seed ^ 0x9E3779B9u;
+    t.seed_hi = (uint32_t)(noise_seed >> 32) ^ 0x85EBCA6Bu;
+    return t;
+}
+// the sampling fields of a launch's PolicyArgs: the entry, the call's first step and its flags (the weights are the caller's)
+inline void set_sampling(PolicyArgs& A, const PopulationEntry& t, uint64_t first_step, int flags) {
+    A.f32class = (flags & QR_ROLLOUT_F32CLASS) ? 1 : 0;
+    for (int c = 0; c < 4; ++c) A.std[c] = t.std[c];
+    A.logp_const = t.logp_const;
+    A.seed_lo = t.seed_lo;
+    A.seed_hi = t.seed_hi;
+    A.step_lo = (uint32_t)first_step;
+    A.step_hi = (uint32_t)(first_step >> 32);
+    A.deterministic = (flags & QR_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+}
 hipError_t launch_rollout_policy_population(int variant, const Params& P, const PolicyArgs& A, const half8* bank, const half8* bank_lo,
                                             const float* conds, const int2* map, const PopulationEntry* table, int num_groups, int envs_per_group,
                                             int K, float* obs, float* act, float* logp, float* rew, uint8_t* done, uint8_t* trunc, float* last_obs,
@@ -180,5 +207,27 @@ bool bank_slot_set(const qr_policy_bank* b, int slot);   // slot in [0, capacity
 half8* bank_weights_mut(qr_policy_bank* b);              // for qr_ppo_population_load_bank: the slots are packed on the device ...
 half8* bank_weights_lo_mut(qr_policy_bank* b);
 void bank_mark_set(qr_policy_bank* b, int first_slot, int count);   // ... and marked as set on the host
+
+// ---------------------------------------------------------------------------------------------------
+// what the entry points of quadrace_abi.hip and quad3d.hip refuse about a policy handle or a bank: observation length, then device.
+// `who` names the entry point; a message is built on the failing path only.  `len_rule` completes "policy obs_len " / "bank obs_len ",
+// `noun` is what the device message calls the bank.  The weights are fetched by a call of their own: the entry points place that
+// refusal differently (before these two in the rollouts, after them everywhere else).
+// ---------------------------------------------------------------------------------------------------
+inline int check_policy_handle(const qr_policy* p, int obs_len, int device, const char* who, const char* len_rule = "!= env obs_len") {
+    if (policy_obs_len(p) != obs_len) return set_last_error(QR_E_INVALID, std::string(who) + ": policy obs_len " + len_rule);
+    if (policy_device(p) != device) return set_last_error(QR_E_INVALID, std::string(who) + ": policy on another GPU");
+    return QR_OK;
+}
+inline int fetch_policy_weights(const qr_policy* p, const char* who, const half8*& w) {
+    w = policy_weights(p);
+    return w ? QR_OK : set_last_error(QR_E_STATE, std::string(who) + ": the policy has no weights");
+}
+inline int check_policy_bank(const qr_policy_bank* b, int obs_len, int device, const char* who, const char* noun = "policy bank",
+                             const char* len_rule = "!= env obs_len") {
+    if (bank_obs_len(b) != obs_len) return set_last_error(QR_E_INVALID, std::string(who) + ": bank obs_len " + len_rule);
+    if (bank_device(b) != device) return set_last_error(QR_E_INVALID, std::string(who) + ": " + noun + " on another GPU");
+    return QR_OK;
+}
 
 }  // namespace qr

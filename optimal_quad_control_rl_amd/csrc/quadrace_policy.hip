@@ -109,7 +109,6 @@ struct qr_policy_bank {
 };
 
 namespace {
-int pfail(int code, const std::string& m) { return qr::set_last_error(code, m); }
 inline int rho(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 }  // namespace
 
@@ -205,15 +204,15 @@ extern "C" {
 const char* qr_policy_last_error(void) { return qr_last_error(); }  // same thread-local message as the env calls
 
 int qr_policy_create(int32_t obs_len, int32_t device, qr_policy** out) {
-    if (!out) return pfail(QR_E_INVALID, "qr_policy_create: null output");
+    if (!out) return qr::set_last_error(QR_E_INVALID, "qr_policy_create: null output");
     *out = nullptr;
     if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
-        return pfail(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
+        return qr::set_last_error(QR_E_INVALID, "qr_policy_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return pfail(QR_E_NO_DEVICE, "qr_policy_create: no HIP device visible (no CPU fallback)");
-    if (device < 0 || device >= ndev) return pfail(QR_E_INVALID, "qr_policy_create: bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return pfail(QR_E_HIP, "qr_policy_create: hipSetDevice failed");
+        return qr::set_last_error(QR_E_NO_DEVICE, "qr_policy_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return qr::set_last_error(QR_E_INVALID, "qr_policy_create: bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return qr::set_last_error(QR_E_HIP, "qr_policy_create: hipSetDevice failed");
     qr_policy* p = new qr_policy();
     p->L = obs_len;
     p->device = device;
@@ -223,7 +222,7 @@ int qr_policy_create(int32_t obs_len, int32_t device, qr_policy** out) {
         hipMalloc((void**)&p->d_weights_lo, p->total_half8 * 16) != hipSuccess) {
         if (p->d_weights) (void)hipFree(p->d_weights);
         delete p;
-        return pfail(QR_E_HIP, "qr_policy_create: hipMalloc failed");
+        return qr::set_last_error(QR_E_HIP, "qr_policy_create: hipMalloc failed");
     }
     *out = p;
     return QR_OK;
@@ -243,47 +242,47 @@ int qr_policy_destroy(qr_policy* p) {
 int qr_policy_set_weights(qr_policy* p, const float* w1, const float* b1, const float* w2, const float* b2,
                           const float* w3, const float* b3, const float* w4, const float* b4) {
     if (!p || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4)
-        return pfail(QR_E_INVALID, "qr_policy_set_weights: null argument");
+        return qr::set_last_error(QR_E_INVALID, "qr_policy_set_weights: null argument");
     std::vector<__half> img, img_lo;
     const size_t e = pack_policy_images(p->L, p->steps1, p->total_half8, w1, b1, w2, b2, w3, b3, w4, b4, img, img_lo);
-    if (e != p->total_half8) return pfail(QR_E_STATE, "qr_policy_set_weights: internal packing size mismatch");
-    if (hipSetDevice(p->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
-    if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");
+    if (e != p->total_half8) return qr::set_last_error(QR_E_STATE, "qr_policy_set_weights: internal packing size mismatch");
+    if (hipSetDevice(p->device) != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipDeviceSynchronize failed");
     if (hipMemcpy(p->d_weights, img.data(), img.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(p->d_weights_lo, img_lo.data(), img_lo.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess)
-        return pfail(QR_E_HIP, "qr_policy_set_weights: upload failed");
+        return qr::set_last_error(QR_E_HIP, "qr_policy_set_weights: upload failed");
     p->has_weights = true;
     return QR_OK;
 }
 
 int qr_policy_forward(qr_policy* p, int32_t n, const float* obs_dev, float* mean_out_dev, void* stream) {
-    if (!p || !obs_dev || !mean_out_dev || n < 1) return pfail(QR_E_INVALID, "qr_policy_forward: bad argument");
-    if (!p->has_weights) return pfail(QR_E_STATE, "qr_policy_forward: qr_policy_set_weights has not been called");
+    if (!p || !obs_dev || !mean_out_dev || n < 1) return qr::set_last_error(QR_E_INVALID, "qr_policy_forward: bad argument");
+    if (!p->has_weights) return qr::set_last_error(QR_E_STATE, "qr_policy_forward: qr_policy_set_weights has not been called");
     hipError_t e = qr::launch_policy(p->L, p->d_weights, n, obs_dev, mean_out_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return pfail(QR_E_HIP, std::string("qr_policy_forward: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qr::set_last_error(QR_E_HIP, std::string("qr_policy_forward: ") + hipGetErrorString(e));
     return QR_OK;
 }
 
 int qr_policy_forward_f32class(qr_policy* p, int32_t n, const float* obs_dev, float* mean_out_dev, void* stream) {
-    if (!p || !obs_dev || !mean_out_dev || n < 1) return pfail(QR_E_INVALID, "qr_policy_forward_f32class: bad argument");
-    if (!p->has_weights) return pfail(QR_E_STATE, "qr_policy_forward_f32class: qr_policy_set_weights has not been called");
+    if (!p || !obs_dev || !mean_out_dev || n < 1) return qr::set_last_error(QR_E_INVALID, "qr_policy_forward_f32class: bad argument");
+    if (!p->has_weights) return qr::set_last_error(QR_E_STATE, "qr_policy_forward_f32class: qr_policy_set_weights has not been called");
     hipError_t e = qr::launch_policy_f32class(p->L, p->d_weights, p->d_weights_lo, n, obs_dev, mean_out_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return pfail(QR_E_HIP, std::string("qr_policy_forward_f32class: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qr::set_last_error(QR_E_HIP, std::string("qr_policy_forward_f32class: ") + hipGetErrorString(e));
     return QR_OK;
 }
 
 // ---- bank of policies (qr_evaluate_policy_bank) ----
 int qr_policy_bank_create(int32_t obs_len, int32_t device, int32_t capacity, qr_policy_bank** out) {
-    if (!out) return pfail(QR_E_INVALID, "qr_policy_bank_create: null output");
+    if (!out) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_create: null output");
     *out = nullptr;
     if (!qr::dispatch_L(obs_len, [](auto) { return true; }, [] { return false; }))
-        return pfail(QR_E_INVALID, "qr_policy_bank_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
-    if (capacity < 1) return pfail(QR_E_INVALID, "qr_policy_bank_create: capacity must be >= 1");
+        return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_create: obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)");
+    if (capacity < 1) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_create: capacity must be >= 1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return pfail(QR_E_NO_DEVICE, "qr_policy_bank_create: no HIP device visible (no CPU fallback)");
-    if (device < 0 || device >= ndev) return pfail(QR_E_INVALID, "qr_policy_bank_create: bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return pfail(QR_E_HIP, "qr_policy_bank_create: hipSetDevice failed");
+        return qr::set_last_error(QR_E_NO_DEVICE, "qr_policy_bank_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_create: bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return qr::set_last_error(QR_E_HIP, "qr_policy_bank_create: hipSetDevice failed");
     qr_policy_bank* b = new qr_policy_bank();
     b->L = obs_len;
     b->device = device;
@@ -295,7 +294,7 @@ int qr_policy_bank_create(int32_t obs_len, int32_t device, int32_t capacity, qr_
     if (hipMalloc((void**)&b->d_weights, bytes) != hipSuccess || hipMalloc((void**)&b->d_weights_lo, bytes) != hipSuccess) {
         if (b->d_weights) (void)hipFree(b->d_weights);
         delete b;
-        return pfail(QR_E_HIP, "qr_policy_bank_create: hipMalloc failed");
+        return qr::set_last_error(QR_E_HIP, "qr_policy_bank_create: hipMalloc failed");
     }
     *out = b;
     return QR_OK;
@@ -311,36 +310,36 @@ int qr_policy_bank_destroy(qr_policy_bank* b) {
     return QR_OK;
 }
 
-int qr_policy_bank_capacity(const qr_policy_bank* b) { return b ? b->capacity : pfail(QR_E_INVALID, "qr_policy_bank_capacity: null bank"); }
+int qr_policy_bank_capacity(const qr_policy_bank* b) { return b ? b->capacity : qr::set_last_error(QR_E_INVALID, "qr_policy_bank_capacity: null bank"); }
 
 int qr_policy_bank_set(qr_policy_bank* b, int32_t slot, const float* w1, const float* b1, const float* w2, const float* b2,
                        const float* w3, const float* b3, const float* w4, const float* b4) {
-    if (!b || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) return pfail(QR_E_INVALID, "qr_policy_bank_set: null argument");
-    if (slot < 0 || slot >= b->capacity) return pfail(QR_E_INVALID, "qr_policy_bank_set: slot must be in [0, capacity)");
+    if (!b || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_set: null argument");
+    if (slot < 0 || slot >= b->capacity) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_set: slot must be in [0, capacity)");
     std::vector<__half> img, img_lo;
     const size_t e = pack_policy_images(b->L, b->steps1, b->total_half8, w1, b1, w2, b2, w3, b3, w4, b4, img, img_lo);
-    if (e != b->total_half8) return pfail(QR_E_STATE, "qr_policy_bank_set: internal packing size mismatch");
-    if (hipSetDevice(b->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
-    if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");   // a launch may still read the slot
+    if (e != b->total_half8) return qr::set_last_error(QR_E_STATE, "qr_policy_bank_set: internal packing size mismatch");
+    if (hipSetDevice(b->device) != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipDeviceSynchronize failed");   // a launch may still read the slot
     const size_t off = (size_t)slot * b->total_half8;
     if (hipMemcpy(b->d_weights + off, img.data(), img.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(b->d_weights_lo + off, img_lo.data(), img_lo.size() * sizeof(__half), hipMemcpyHostToDevice) != hipSuccess) {
         b->is_set[(size_t)slot] = 0;
-        return pfail(QR_E_HIP, "qr_policy_bank_set: upload failed");
+        return qr::set_last_error(QR_E_HIP, "qr_policy_bank_set: upload failed");
     }
     b->is_set[(size_t)slot] = 1;
     return QR_OK;
 }
 
 int qr_policy_bank_read(const qr_policy_bank* b, int32_t slot, int32_t which, void* out_host, size_t bytes) {
-    if (!b || !out_host) return pfail(QR_E_INVALID, "qr_policy_bank_read: null argument");
-    if (slot < 0 || slot >= b->capacity || !b->is_set[(size_t)slot]) return pfail(QR_E_INVALID, "qr_policy_bank_read: slot must be a set slot in [0, capacity)");
-    if (which < 0 || which > 1) return pfail(QR_E_INVALID, "qr_policy_bank_read: which must be 0 (f16 image) or 1 (low pieces)");
-    if (bytes != b->total_half8 * 16) return pfail(QR_E_INVALID, "qr_policy_bank_read: bytes must be the size of one image");
-    if (hipSetDevice(b->device) != hipSuccess) return pfail(QR_E_HIP, "hipSetDevice failed");
-    if (hipDeviceSynchronize() != hipSuccess) return pfail(QR_E_HIP, "hipDeviceSynchronize failed");   // a load launch may still write the slot
+    if (!b || !out_host) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_read: null argument");
+    if (slot < 0 || slot >= b->capacity || !b->is_set[(size_t)slot]) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_read: slot must be a set slot in [0, capacity)");
+    if (which < 0 || which > 1) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_read: which must be 0 (f16 image) or 1 (low pieces)");
+    if (bytes != b->total_half8 * 16) return qr::set_last_error(QR_E_INVALID, "qr_policy_bank_read: bytes must be the size of one image");
+    if (hipSetDevice(b->device) != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return qr::set_last_error(QR_E_HIP, "hipDeviceSynchronize failed");   // a load launch may still write the slot
     const qr::half8* src = (which == 0 ? b->d_weights : b->d_weights_lo) + (size_t)slot * b->total_half8;
-    if (hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return pfail(QR_E_HIP, "qr_policy_bank_read: download failed");
+    if (hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return qr::set_last_error(QR_E_HIP, "qr_policy_bank_read: download failed");
     return QR_OK;
 }
 

@@ -291,17 +291,9 @@ void population_prepare_release(void* state) {
 
 namespace {
 
-int prepfail(int code, const std::string& m) { return qr::set_last_error(code, m); }
-
-#define PREP_HIP(expr)                                                                                       \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) return prepfail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
 template <typename F>
 int dispatch_L(int L, F&& f) {
-    return qr::dispatch_L(L, f, [] { return prepfail(QR_E_INVALID, "qr_ppo_population: the members' obs_len is not an observation length of the envs"); });
+    return qr::dispatch_L(L, f, [] { return qr::set_last_error(QR_E_INVALID, "qr_ppo_population: the members' obs_len is not an observation length of the envs"); });
 }
 
 bool finite_host(float v) {
@@ -315,15 +307,15 @@ bool finite_host(float v) {
 extern "C" {
 
 int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* theta_dev, qr_policy_bank* bank, int32_t first_slot, void* stream) {
-    if (!pop || !theta_dev || !bank) return prepfail(QR_E_INVALID, "qr_ppo_population_load_bank: null argument");
+    if (!pop || !theta_dev || !bank) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_load_bank: null argument");
     const int P = qr::population_size(pop);
     for (int p = 0; p < P; ++p)
-        if (!theta_dev[p]) return prepfail(QR_E_INVALID, "qr_ppo_population_load_bank: a member's theta_dev is null");
+        if (!theta_dev[p]) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_load_bank: a member's theta_dev is null");
     if (qr::bank_obs_len(bank) != qr::population_obs_len(pop) || qr::bank_device(bank) != qr::population_device(pop))
-        return prepfail(QR_E_INVALID, "qr_ppo_population_load_bank: the bank's obs_len or device differs from the population's");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_load_bank: the bank's obs_len or device differs from the population's");
     if (first_slot < 0 || (long long)first_slot + P > (long long)qr::bank_capacity(bank))
-        return prepfail(QR_E_INVALID, "qr_ppo_population_load_bank: slots [first_slot, first_slot + members) must lie in [0, capacity)");
-    PREP_HIP(hipSetDevice(qr::population_device(pop)));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_load_bank: slots [first_slot, first_slot + members) must lie in [0, capacity)");
+    QR_HIP(hipSetDevice(qr::population_device(pop)));
     qr::PrepThetas thetas;
     std::memset(&thetas, 0, sizeof(thetas));
     for (int p = 0; p < P; ++p) thetas.v[p] = theta_dev[p];
@@ -333,7 +325,7 @@ int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* thet
         static_assert(qr::PpoDims<L>::kImage == qr::PolicyDims<L>::kTotalHalf8, "the updater's actor image has the layout of a bank slot");
         hipLaunchKernelGGL(qr::population_load_bank_kernel<L>, dim3((qr::PolicyDims<L>::kTotalHalf8 + 255) / 256, P), dim3(256), 0, st, thetas,
                            qr::bank_weights_mut(bank), qr::bank_weights_lo_mut(bank), (int)first_slot);
-        PREP_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         return (int)QR_OK;
     });
     if (rc != QR_OK) return rc;
@@ -343,51 +335,50 @@ int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* thet
 
 int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_shared* sh, const qr_ppo_prepare_member* members, double* report_host,
                               void* stream) {
-    if (!pop || !sh || !members || !report_host) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: null argument");
+    if (!pop || !sh || !members || !report_host) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: null argument");
     const int P = qr::population_size(pop);
     const int K = sh->K, N = sh->N, E = sh->E;
-    if (K < 1) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: K must be >= 1");
+    if (K < 1) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: K must be >= 1");
     if (E < 256 || E % 256 != 0 || N < E || N % E != 0)
-        return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: E must be a multiple of 256 (>= 256) and N a multiple of E");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: E must be a multiple of 256 (>= 256) and N a multiple of E");
     if (!sh->obs || !sh->act || !sh->logp || !sh->rew || !sh->done || !sh->trunc || !sh->last_obs)
-        return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: a shared array other than term_obs is null");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: a shared array other than term_obs is null");
     if ((unsigned long long)K * (unsigned long long)N > 0x7FFFFFFFull)
-        return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: K * N is beyond 2^31 - 1 rows");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: K * N is beyond 2^31 - 1 rows");
     for (int p = 0; p < P; ++p) {
         const qr_ppo_prepare_member& m = members[p];
         if (m.first_env < 0 || m.first_env >= N || m.first_env % E != 0)
-            return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: first_env must be a multiple of E inside [0, N)");
+            return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: first_env must be a multiple of E inside [0, N)");
         for (int q = 0; q < p; ++q)
-            if (members[q].first_env == m.first_env) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: two members share a first_env");
+            if (members[q].first_env == m.first_env) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: two members share a first_env");
         if (!m.obs || !m.act || !m.old_logp || !m.rew || !m.done || !m.val || !m.last_val || !m.adv || !m.ret)
-            return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: a member's buffer other than term_val / ep_* is null");
+            return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: a member's buffer other than term_val / ep_* is null");
         const int eps = (m.ep_ret ? 1 : 0) + (m.ep_len ? 1 : 0) + (m.ep_gates ? 1 : 0);
-        if (eps != 0 && eps != 3) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: episode state needs all three arrays");
-        if (m.term_val && !sh->term_obs) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: term_val needs the shared term_obs");
-        if (!finite_host(m.gamma) || !finite_host(m.lam)) return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: gamma / lam must be finite");
+        if (eps != 0 && eps != 3) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: episode state needs all three arrays");
+        if (m.term_val && !sh->term_obs) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: term_val needs the shared term_obs");
+        if (!finite_host(m.gamma) || !finite_host(m.lam)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: gamma / lam must be finite");
     }
-    PREP_HIP(hipSetDevice(qr::population_device(pop)));
+    QR_HIP(hipSetDevice(qr::population_device(pop)));
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return prepfail(QR_E_INVALID, "qr_ppo_population_prepare: `stream` is being captured (the call allocates, uploads the member table and blocks on its report)");
+    if (qr::stream_is_capturing(st))
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_prepare: `stream` is being captured (the call allocates, uploads the member table and blocks on its report)");
     // the object's scratch: allocated on first use, regrown when (K, E) ask for more
     void*& slot = qr::population_prepare_slot(pop);
     if (!slot) slot = new qr::PrepState();
     qr::PrepState* S = static_cast<qr::PrepState*>(slot);
     const size_t rows = (size_t)K * (size_t)E, wgs = (size_t)(E / 256);
-    if (!S->d_table) PREP_HIP(hipMalloc((void**)&S->d_table, sizeof(qr::PrepMember) * (size_t)P));
-    if (!S->d_report) PREP_HIP(hipMalloc((void**)&S->d_report, sizeof(double) * 8 * (size_t)P));
+    if (!S->d_table) QR_HIP(hipMalloc((void**)&S->d_table, sizeof(qr::PrepMember) * (size_t)P));
+    if (!S->d_report) QR_HIP(hipMalloc((void**)&S->d_report, sizeof(double) * 8 * (size_t)P));
     if (rows > S->bad_rows) {
-        PREP_HIP(hipStreamSynchronize(st));   // an earlier call's launches may still use the old block
+        QR_HIP(hipStreamSynchronize(st));   // an earlier call's launches may still use the old block
         if (S->d_bad) { (void)hipFree(S->d_bad); S->d_bad = nullptr; S->bad_rows = 0; }
-        PREP_HIP(hipMalloc((void**)&S->d_bad, rows * (size_t)P));
+        QR_HIP(hipMalloc((void**)&S->d_bad, rows * (size_t)P));
         S->bad_rows = rows;
     }
     if (wgs > S->partial_wgs) {
-        PREP_HIP(hipStreamSynchronize(st));
+        QR_HIP(hipStreamSynchronize(st));
         if (S->d_partial) { (void)hipFree(S->d_partial); S->d_partial = nullptr; S->partial_wgs = 0; }
-        PREP_HIP(hipMalloc((void**)&S->d_partial, sizeof(double) * 8 * wgs * (size_t)P));
+        QR_HIP(hipMalloc((void**)&S->d_partial, sizeof(double) * 8 * wgs * (size_t)P));
         S->partial_wgs = wgs;
     }
     std::vector<qr::PrepMember> table((size_t)P);
@@ -409,7 +400,7 @@ int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_share
         // stream-ordered behind whatever earlier calls left on `st`; h_table stays untouched until this call's closing synchronisation
         S->h_table = table;
         S->table_valid = false;
-        PREP_HIP(hipMemcpyAsync(S->d_table, S->h_table.data(), sizeof(qr::PrepMember) * (size_t)P, hipMemcpyHostToDevice, st));
+        QR_HIP(hipMemcpyAsync(S->d_table, S->h_table.data(), sizeof(qr::PrepMember) * (size_t)P, hipMemcpyHostToDevice, st));
         S->table_valid = true;
     }
     qr::PrepShared s;
@@ -422,7 +413,7 @@ int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_share
     const int vgrid = (int)(vtiles < spread ? vtiles : spread), ggrid = (int)(roll < 4 * spread ? roll : 4 * spread);
     const int rc = dispatch_L(qr::population_obs_len(pop), [&](auto Lc) {
         constexpr int L = decltype(Lc)::value;
-        PREP_HIP((qr::launch_dynamic_lds<qr::population_value_kernel<L>>(dim3(vgrid, P), dim3(qr::kPrepBlock), (size_t)qr::PolicyDims<L>::kTotalHalf8 * 16, st,
+        QR_HIP((qr::launch_dynamic_lds<qr::population_value_kernel<L>>(dim3(vgrid, P), dim3(qr::kPrepBlock), (size_t)qr::PolicyDims<L>::kTotalHalf8 * 16, st,
                                                                          (const qr::PrepMember*)S->d_table, s)));
         hipLaunchKernelGGL(qr::population_gather_kernel<L>, dim3(ggrid, P), dim3(qr::kPrepBlock), 0, st, (const qr::PrepMember*)S->d_table, s);
         return (int)QR_OK;
@@ -430,9 +421,9 @@ int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_share
     if (rc != QR_OK) return rc;
     hipLaunchKernelGGL(qr::population_gae_kernel, dim3(cpe, P), dim3(qr::kPrepBlock), 0, st, (const qr::PrepMember*)S->d_table, s);
     hipLaunchKernelGGL(qr::population_report_kernel, dim3(P), dim3(64), 0, st, (const qr::PrepMember*)S->d_table, cpe);
-    PREP_HIP(hipGetLastError());
-    PREP_HIP(hipMemcpyAsync(report_host, S->d_report, sizeof(double) * 8 * (size_t)P, hipMemcpyDeviceToHost, st));
-    PREP_HIP(hipStreamSynchronize(st));   // the round's one blocking read
+    QR_HIP(hipGetLastError());
+    QR_HIP(hipMemcpyAsync(report_host, S->d_report, sizeof(double) * 8 * (size_t)P, hipMemcpyDeviceToHost, st));
+    QR_HIP(hipStreamSynchronize(st));   // the round's one blocking read
     return QR_OK;
 }
 

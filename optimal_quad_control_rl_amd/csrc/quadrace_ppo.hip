@@ -341,20 +341,12 @@ void ppo_f32_release_graphs(void* cache);   // quadrace_ppo_f32.hip
 
 namespace {
 
-int ppofail(int code, const std::string& m) { return qr::set_last_error(code, m); }
-
-#define PPO_HIP(expr)                                                                                        \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) return ppofail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-
 template <int L>
 struct PpoOps {
     using D = qr::PpoDims<L>;
     static int pack(qr_ppo* p, const float* theta, hipStream_t st) {
         hipLaunchKernelGGL(qr::ppo_pack_kernel<L>, dim3((D::kImage + 255) / 256, 2), dim3(256), 0, st, theta, p->d_images);
-        PPO_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         return QR_OK;
     }
     // advantage statistics of this minibatch: the epoch table when the rows were announced by qr_ppo_epoch_begin, else one launch
@@ -380,9 +372,9 @@ struct PpoOps {
     // before a graph capture instead of inside it)
     static int configure(qr_ppo* p) {
         if (p->partial_bf16) {
-            PPO_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, false>>(kLdsFused)));
+            QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, false>>(kLdsFused)));
         } else {
-            PPO_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float, false>>(kLdsFused)));
+            QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float, false>>(kLdsFused)));
         }
         return QR_OK;
     }
@@ -400,7 +392,7 @@ struct PpoOps {
                                reinterpret_cast<__bf16*>(p->d_partial), no_table, 0);
         else
             hipLaunchKernelGGL((qr::ppo_grad_kernel<L, float, false>), dim3(wgs, 2), dim3(512), lds_f, st, b, p->d_partial, no_table, 0);
-        PPO_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         *chunks_out = wgs;
         return QR_OK;
     }
@@ -423,23 +415,23 @@ struct PpoOps {
                       "grid barrier: arrive[512], two resident workgroups per CU");
         hipLaunchKernelGGL(qr::ppo_apply_kernel<L>, dim3((threads + qr::kApplyThreads - 1) / qr::kApplyThreads),
                            dim3(qr::kApplyThreads), 0, st, a);
-        PPO_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         return QR_OK;
     }
 };
 
 template <typename F>
 int dispatch_L(int L, F&& f) {   // qr::dispatch_L with this file's failure: the message goes to qr_last_error()
-    return qr::dispatch_L(L, f, [] { return ppofail(QR_E_INVALID, "obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)"); });
+    return qr::dispatch_L(L, f, [] { return qr::set_last_error(QR_E_INVALID, "obs_len must be an observation length of the race envs (13 + 4g, 20 + 4g) or 16 (the predecessor envs)"); });
 }
 
 int fill_batch(qr_ppo* p, qr::PpoBatch& b, const float* theta, const float* obs, const float* act, const float* old_logp,
                const float* adv, const float* ret, const int32_t* idx, int32_t B, float clip, float vf_coef, float ent_coef,
                float* stats) {
-    if (!p || !theta || !obs || !act || !old_logp || !adv || !ret || !idx) return ppofail(QR_E_INVALID, "qr_ppo: null argument");
+    if (!p || !theta || !obs || !act || !old_logp || !adv || !ret || !idx) return qr::set_last_error(QR_E_INVALID, "qr_ppo: null argument");
     // (the gradient kernel masks the tail of a last, partial group of 64 rows)
     if (B < 64 || B > p->max_B)
-        return ppofail(QR_E_INVALID, "qr_ppo: minibatch size must be >= 64 and <= max_minibatch");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo: minibatch size must be >= 64 and <= max_minibatch");
     b.obs = obs; b.act = act; b.old_logp = old_logp; b.adv = adv; b.ret = ret; b.idx = idx;
     b.B = B; b.G = (B + 63) / 64;
     b.clip = clip; b.vf_coef = vf_coef; b.ent_coef = ent_coef;
@@ -476,15 +468,15 @@ int qr_ppo_create(int32_t obs_len, int32_t device, int32_t max_minibatch, qr_ppo
 }
 
 int qr_ppo_create_ex(int32_t obs_len, int32_t device, int32_t max_minibatch, int32_t flags, qr_ppo** out) {
-    if (!out) return ppofail(QR_E_INVALID, "qr_ppo_create: null output");
+    if (!out) return qr::set_last_error(QR_E_INVALID, "qr_ppo_create: null output");
     if (flags < 0 || (flags & ~(QR_PPO_PARTIAL_F32 | QR_PPO_NO_EPOCH_GRAPH)))
-        return ppofail(QR_E_INVALID, "qr_ppo_create_ex: unknown flag");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_create_ex: unknown flag");
     *out = nullptr;
-    if (max_minibatch < 64 || max_minibatch % 64 != 0) return ppofail(QR_E_INVALID, "qr_ppo_create: max_minibatch must be a multiple of 64");
+    if (max_minibatch < 64 || max_minibatch % 64 != 0) return qr::set_last_error(QR_E_INVALID, "qr_ppo_create: max_minibatch must be a multiple of 64");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ppofail(QR_E_NO_DEVICE, "qr_ppo_create: no HIP device visible (no CPU fallback)");
-    if (device < 0 || device >= ndev) return ppofail(QR_E_INVALID, "qr_ppo_create: bad device ordinal");
+        return qr::set_last_error(QR_E_NO_DEVICE, "qr_ppo_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_create: bad device ordinal");
     qr_ppo* p = new qr_ppo();
     p->L = obs_len;
     p->device = device;
@@ -500,7 +492,7 @@ int qr_ppo_create_ex(int32_t obs_len, int32_t device, int32_t max_minibatch, int
     // which forms of the kernels this handle uses: explicit flags (the library reads no environment variable)
     p->partial_bf16 = !(flags & QR_PPO_PARTIAL_F32);
     p->epoch_graph = !(flags & QR_PPO_NO_EPOCH_GRAPH);
-    PPO_HIP(hipSetDevice(device));
+    QR_HIP(hipSetDevice(device));
     const size_t mbbytes = (size_t)(qr_ppo::kMaxEpochMinibatches + 1) * 2 * sizeof(double);
     hipError_t e = hipMalloc((void**)&p->d_images, (size_t)2 * p->image_half8 * 16);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_partial, (size_t)qr_ppo::kFusedChunks * (p->raw_slots > p->num_params ? p->raw_slots : p->num_params) * 4);
@@ -511,7 +503,7 @@ int qr_ppo_create_ex(int32_t obs_len, int32_t device, int32_t max_minibatch, int
     if (e == hipSuccess) e = hipMemset(p->d_mbstats, 0, mbbytes);
     if (e != hipSuccess) {
         qr_ppo_destroy(p);
-        return ppofail(QR_E_HIP, std::string("qr_ppo_create: ") + hipGetErrorString(e));
+        return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_create: ") + hipGetErrorString(e));
     }
     *out = p;
     return QR_OK;
@@ -539,30 +531,30 @@ __attribute__((visibility("default"))) int qr_ppo_debug_set_ticks(qr_ppo* p, uns
 __attribute__((visibility("default"))) int qr_ppo_debug_set_apply_ticks(qr_ppo* p, unsigned long long* ticks_dev) { p->apply_ticks = ticks_dev; return QR_OK; }
 #endif
 
-int qr_ppo_num_params(const qr_ppo* p) { return p ? p->num_params : ppofail(QR_E_INVALID, "qr_ppo_num_params: null handle"); }
+int qr_ppo_num_params(const qr_ppo* p) { return p ? p->num_params : qr::set_last_error(QR_E_INVALID, "qr_ppo_num_params: null handle"); }
 
 int qr_ppo_pack(qr_ppo* p, const float* theta_dev, void* stream) {
-    if (!p || !theta_dev) return ppofail(QR_E_INVALID, "qr_ppo_pack: null argument");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!p || !theta_dev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_pack: null argument");
+    QR_HIP(hipSetDevice(p->device));
     p->packed_theta = theta_dev;
     return dispatch_L(p->L, [&](auto Lc) { return PpoOps<decltype(Lc)::value>::pack(p, theta_dev, (hipStream_t)stream); });
 }
 
 int qr_ppo_control(qr_ppo* p, float target_kl, int32_t clear, void* stream) {
-    if (!p) return ppofail(QR_E_INVALID, "qr_ppo_control: null handle");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!p) return qr::set_last_error(QR_E_INVALID, "qr_ppo_control: null handle");
+    QR_HIP(hipSetDevice(p->device));
     p->target_kl = target_kl;
     if (clear) {  // stop flag and counters (the barrier counters that follow them in PpoCtrl keep running)
-        PPO_HIP(hipMemsetAsync(&p->d_ctrl->stop, 0, 4 * sizeof(int), (hipStream_t)stream));
+        QR_HIP(hipMemsetAsync(&p->d_ctrl->stop, 0, 4 * sizeof(int), (hipStream_t)stream));
     }
     return QR_OK;
 }
 
 int qr_ppo_status(qr_ppo* p, int32_t* out4, void* stream) {
-    if (!p || !out4) return ppofail(QR_E_INVALID, "qr_ppo_status: null argument");
-    PPO_HIP(hipSetDevice(p->device));
-    PPO_HIP(hipMemcpyAsync(out4, &p->d_ctrl->stop, 4 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    PPO_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (!p || !out4) return qr::set_last_error(QR_E_INVALID, "qr_ppo_status: null argument");
+    QR_HIP(hipSetDevice(p->device));
+    QR_HIP(hipMemcpyAsync(out4, &p->d_ctrl->stop, 4 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    QR_HIP(hipStreamSynchronize((hipStream_t)stream));
     return QR_OK;
 }
 
@@ -573,15 +565,15 @@ int qr_ppo_epoch_begin(qr_ppo* p, const float* adv_dev, const int32_t* idx_dev, 
 }
 static int epoch_begin_impl(qr_ppo* p, const float* adv_dev, const int32_t* idx_dev, int32_t B, int32_t num_minibatches, void* stream,
                             unsigned long long* bump) {
-    if (!p || !adv_dev || !idx_dev) return ppofail(QR_E_INVALID, "qr_ppo_epoch_begin: null argument");
+    if (!p || !adv_dev || !idx_dev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch_begin: null argument");
     if (B < 64 || B > p->max_B || num_minibatches < 1 || num_minibatches > qr_ppo::kMaxEpochMinibatches)
-        return ppofail(QR_E_INVALID, "qr_ppo_epoch_begin: bad minibatch size / count");
-    PPO_HIP(hipSetDevice(p->device));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch_begin: bad minibatch size / count");
+    QR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(qr::ppo_zero_table_kernel, dim3((2 * num_minibatches + 255) / 256), dim3(256), 0, st, p->d_mbstats, 2 * num_minibatches);
     hipLaunchKernelGGL(qr::ppo_adv_stats_kernel, dim3((B + 1023) / 1024, num_minibatches), dim3(1024), 0, st, adv_dev, idx_dev, B,
                        p->d_mbstats, bump);
-    PPO_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     p->epoch_idx = idx_dev;
     p->epoch_B = B;
     p->epoch_count = num_minibatches;
@@ -595,8 +587,8 @@ int qr_ppo_grad(qr_ppo* p, const float* theta_dev, const float* obs_dev, const f
     qr::PpoBatch b;
     if (int rc = fill_batch(p, b, theta_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, stats_dev))
         return rc;
-    if (!grad_out_dev) return ppofail(QR_E_INVALID, "qr_ppo_grad: null grad_out");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!grad_out_dev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad: null grad_out");
+    QR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     return dispatch_L(p->L, [&](auto Lc) {
         constexpr int L = decltype(Lc)::value;
@@ -626,8 +618,8 @@ static int ppo_minibatch_impl(qr_ppo* p, float* theta_dev, float* adam_m_dev, fl
     qr::PpoBatch b;
     if (int rc = fill_batch(p, b, theta_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, stats_dev))
         return rc;
-    if (!adam_m_dev || !adam_v_dev || adam_step < 0) return ppofail(QR_E_INVALID, "qr_ppo_minibatch: bad Adam state");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!adam_m_dev || !adam_v_dev || adam_step < 0) return qr::set_last_error(QR_E_INVALID, "qr_ppo_minibatch: bad Adam state");
+    QR_HIP(hipSetDevice(p->device));
     p->packed_theta = theta_dev;   // the apply kernel keeps the images in step with this vector
     hipStream_t st = (hipStream_t)stream;
     return dispatch_L(p->L, [&](auto Lc) {
@@ -651,7 +643,7 @@ int qr_ppo_minibatch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam
                      const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B,
                      float clip, float vf_coef, float ent_coef, float max_grad_norm, float lr, float beta1, float beta2, float eps,
                      int32_t adam_step, float* stats_dev, void* stream) {
-    if (!(lr >= 0.0f)) return ppofail(QR_E_INVALID, "qr_ppo_minibatch: the learning rate must be >= 0");
+    if (!(lr >= 0.0f)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_minibatch: the learning rate must be >= 0");
     return ppo_minibatch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip,
                               vf_coef, ent_coef, max_grad_norm, lr, false, beta1, beta2, eps, adam_step, stats_dev, stream);
 }
@@ -662,8 +654,8 @@ int qr_ppo_minibatch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam
 int qr_ppo_apply(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, float* grad_dev, int32_t B, float max_grad_norm,
                  float lr, float beta1, float beta2, float eps, int32_t adam_step, float* stats_dev, void* stream) {
     if (!p || !theta_dev || !adam_m_dev || !adam_v_dev || !grad_dev || adam_step < 0 || B < 1 || !(lr >= 0.0f))
-        return ppofail(QR_E_INVALID, "qr_ppo_apply: bad argument (null pointer, adam_step < 0, B < 1 or a learning rate below 0)");
-    PPO_HIP(hipSetDevice(p->device));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_apply: bad argument (null pointer, adam_step < 0, B < 1 or a learning rate below 0)");
+    QR_HIP(hipSetDevice(p->device));
     p->packed_theta = theta_dev;
     hipStream_t st = (hipStream_t)stream;
     return dispatch_L(p->L, [&](auto Lc) {
@@ -681,30 +673,30 @@ int qr_ppo_apply(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
 
 // Device-resident optimiser step count (see PpoCtrl::adam_t): read it for a checkpoint, set it when one is loaded.
 int qr_ppo_adam_step(qr_ppo* p, int32_t* value, int32_t set, void* stream) {
-    if (!p || !value) return ppofail(QR_E_INVALID, "qr_ppo_adam_step: null argument");
-    if (set && *value < 0) return ppofail(QR_E_INVALID, "qr_ppo_adam_step: negative step count");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!p || !value) return qr::set_last_error(QR_E_INVALID, "qr_ppo_adam_step: null argument");
+    if (set && *value < 0) return qr::set_last_error(QR_E_INVALID, "qr_ppo_adam_step: negative step count");
+    QR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    if (set) PPO_HIP(hipMemcpyAsync(&p->d_ctrl->adam_t, value, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    else PPO_HIP(hipMemcpyAsync(value, &p->d_ctrl->adam_t, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PPO_HIP(hipStreamSynchronize(st));
+    if (set) QR_HIP(hipMemcpyAsync(&p->d_ctrl->adam_t, value, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    else QR_HIP(hipMemcpyAsync(value, &p->d_ctrl->adam_t, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    QR_HIP(hipStreamSynchronize(st));
     return QR_OK;
 }
 
 // On-device epoch permutations (qr_ppo_epoch with device_shuffle): state[0] = seed, state[1] = epochs shuffled so far.
 // set == 0 reads both (for a checkpoint), set != 0 writes both.  Blocks.
 int qr_ppo_shuffle_state(qr_ppo* p, uint64_t* state2, int32_t set, void* stream) {
-    if (!p || !state2) return ppofail(QR_E_INVALID, "qr_ppo_shuffle_state: null argument");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!p || !state2) return qr::set_last_error(QR_E_INVALID, "qr_ppo_shuffle_state: null argument");
+    QR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     if (set) {
         p->shuffle_seed = state2[0];
-        PPO_HIP(hipMemcpyAsync(&p->d_ctrl->shuffle_count, &state2[1], sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        QR_HIP(hipMemcpyAsync(&p->d_ctrl->shuffle_count, &state2[1], sizeof(uint64_t), hipMemcpyHostToDevice, st));
     } else {
         state2[0] = p->shuffle_seed;
-        PPO_HIP(hipMemcpyAsync(&state2[1], &p->d_ctrl->shuffle_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        QR_HIP(hipMemcpyAsync(&state2[1], &p->d_ctrl->shuffle_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-    PPO_HIP(hipStreamSynchronize(st));
+    QR_HIP(hipStreamSynchronize(st));
     return QR_OK;
 }
 
@@ -719,20 +711,19 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
                  int32_t num_minibatches, int32_t num_epochs, int32_t device_shuffle, float clip, float vf_coef, float ent_coef,
                  float max_grad_norm, float lr, float beta1, float beta2, float eps, float* stats_dev, void* stream) {
     if (!p || !theta_dev || !adam_m_dev || !adam_v_dev || !obs_dev || !act_dev || !old_logp_dev || !adv_dev || !ret_dev || !perm_dev)
-        return ppofail(QR_E_INVALID, "qr_ppo_epoch: null argument");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch: null argument");
     if (B < 64 || B > p->max_B || num_minibatches < 1 || num_minibatches > qr_ppo::kMaxEpochMinibatches || !(lr >= 0.0f))
-        return ppofail(QR_E_INVALID, "qr_ppo_epoch: bad minibatch size / count / learning rate");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch: bad minibatch size / count / learning rate");
     if (num_epochs < 1 || num_epochs > 64 || (num_epochs > 1 && !device_shuffle))
-        return ppofail(QR_E_INVALID, "qr_ppo_epoch: num_epochs > 1 needs device_shuffle (the caller cannot rewrite the permutation in between)");
-    PPO_HIP(hipSetDevice(p->device));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch: num_epochs > 1 needs device_shuffle (the caller cannot rewrite the permutation in between)");
+    QR_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool caller_captures = st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    const bool caller_captures = qr::stream_is_capturing(st);
     // the learning rate travels through device memory (it may follow a schedule; the epoch graph's nodes read PpoCtrl::lr).  Written by
     // a one-thread kernel: when the CALLER captures `st`, this node carries the value of the capturing call (lr is frozen into that
     // graph, like every other scalar argument of the call).
     hipLaunchKernelGGL(qr::ppo_set_lr_kernel, dim3(1), dim3(1), 0, st, &p->d_ctrl->lr, lr);
-    PPO_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     p->packed_theta = theta_dev;
     // per-device kernel attributes are set outside the capture (not a stream operation)
     if (int rc = dispatch_L(p->L, [&](auto Lc) { return PpoOps<decltype(Lc)::value>::configure(p); })) return rc;
@@ -742,7 +733,7 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
             if (device_shuffle) {   // perm = keyed bijection of [0, rows) for (seed, device-resident epoch count)
                 hipLaunchKernelGGL(qr::ppo_shuffle_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, perm_dev, rows, p->shuffle_seed,
                                    &p->d_ctrl->shuffle_count);
-                PPO_HIP(hipGetLastError());
+                QR_HIP(hipGetLastError());
             }
             if (int rc = epoch_begin_impl(p, adv_dev, perm_dev, B, num_minibatches, s, device_shuffle ? &p->d_ctrl->shuffle_count : nullptr))
                 return rc;
@@ -763,20 +754,20 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
                      g.max_grad_norm == max_grad_norm && g.beta1 == beta1 && g.beta2 == beta2 && g.eps == eps && g.target_kl == p->target_kl;
     if (!hit) {
         if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-        if (!p->capture_stream) PPO_HIP(hipStreamCreateWithFlags(&p->capture_stream, hipStreamNonBlocking));
+        if (!p->capture_stream) QR_HIP(hipStreamCreateWithFlags(&p->capture_stream, hipStreamNonBlocking));
         hipGraph_t graph = nullptr;
-        PPO_HIP(hipStreamBeginCapture(p->capture_stream, hipStreamCaptureModeRelaxed));
+        QR_HIP(hipStreamBeginCapture(p->capture_stream, hipStreamCaptureModeRelaxed));
         const int rc = enqueue(p->capture_stream);
         const hipError_t end = hipStreamEndCapture(p->capture_stream, &graph);
         if (rc != QR_OK || end != hipSuccess) {
             if (graph) (void)hipGraphDestroy(graph);
-            return rc != QR_OK ? rc : ppofail(QR_E_HIP, std::string("qr_ppo_epoch: graph capture failed: ") + hipGetErrorString(end));
+            return rc != QR_OK ? rc : qr::set_last_error(QR_E_HIP, std::string("qr_ppo_epoch: graph capture failed: ") + hipGetErrorString(end));
         }
         const hipError_t inst = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (inst != hipSuccess) {
             g.exec = nullptr;
-            return ppofail(QR_E_HIP, std::string("qr_ppo_epoch: hipGraphInstantiate: ") + hipGetErrorString(inst));
+            return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_epoch: hipGraphInstantiate: ") + hipGetErrorString(inst));
         }
         g.theta = theta_dev; g.m = adam_m_dev; g.v = adam_v_dev; g.obs = obs_dev; g.act = act_dev; g.old_logp = old_logp_dev;
         g.adv = adv_dev; g.ret = ret_dev; g.perm = perm_dev; g.stats = stats_dev; g.B = B; g.M = num_minibatches;
@@ -786,17 +777,17 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
     }
     // the capture consumed the epoch table's host-side cursor; a replay does not run that host code, so leave it disarmed
     p->epoch_idx = nullptr;
-    PPO_HIP(hipGraphLaunch(g.exec, st));
+    QR_HIP(hipGraphLaunch(g.exec, st));
     return QR_OK;
 }
 
 // Forward pass of one of the two networks with the operand images of the last pack (0 = policy means, 1 = value in column 0):
 // out_dev [n][4].  Same kernel as qr_policy_forward.
 int qr_ppo_forward(qr_ppo* p, int32_t net, int32_t n, const float* obs_dev, float* out_dev, void* stream) {
-    if (!p || !obs_dev || !out_dev || n < 1 || net < 0 || net > 1) return ppofail(QR_E_INVALID, "qr_ppo_forward: bad argument");
-    PPO_HIP(hipSetDevice(p->device));
+    if (!p || !obs_dev || !out_dev || n < 1 || net < 0 || net > 1) return qr::set_last_error(QR_E_INVALID, "qr_ppo_forward: bad argument");
+    QR_HIP(hipSetDevice(p->device));
     const hipError_t e = qr::launch_policy(p->L, p->d_images + (size_t)net * p->image_half8, n, obs_dev, out_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return ppofail(QR_E_HIP, std::string("qr_ppo_forward: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_forward: ") + hipGetErrorString(e));
     return QR_OK;
 }
 
@@ -805,12 +796,12 @@ int qr_ppo_gae(qr_ppo* p, int32_t T, int32_t N, const float* rew_dev, const floa
                const float* last_val_dev, const float* term_val_dev, float gamma, float lam, float* adv_out_dev, float* ret_out_dev,
                float* ep_ret_dev, float* ep_len_dev, float* ep_gates_dev, float* fin_dev, void* stream) {
     if (!p || !rew_dev || !done_dev || !val_dev || !last_val_dev || !adv_out_dev || !ret_out_dev || T < 1 || N < 1)
-        return ppofail(QR_E_INVALID, "qr_ppo_gae: bad argument");
-    if (ep_ret_dev && (!ep_len_dev || !ep_gates_dev)) return ppofail(QR_E_INVALID, "qr_ppo_gae: episode state needs all three arrays");
-    PPO_HIP(hipSetDevice(p->device));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_gae: bad argument");
+    if (ep_ret_dev && (!ep_len_dev || !ep_gates_dev)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_gae: episode state needs all three arrays");
+    QR_HIP(hipSetDevice(p->device));
     hipLaunchKernelGGL(qr::ppo_gae_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, N, rew_dev, done_dev, val_dev,
                        last_val_dev, term_val_dev, gamma, lam, adv_out_dev, ret_out_dev, ep_ret_dev, ep_len_dev, ep_gates_dev, fin_dev);
-    PPO_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     return QR_OK;
 }
 
@@ -822,7 +813,7 @@ int ppo_epoch_prologue(qr_ppo* p, const float* adv_dev, int32_t* perm_dev, int32
     if (device_shuffle) {
         const unsigned int rows = (unsigned int)B * (unsigned int)num_minibatches;
         hipLaunchKernelGGL(ppo_shuffle_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, perm_dev, rows, p->shuffle_seed, &p->d_ctrl->shuffle_count);
-        PPO_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
     }
     const int rc = epoch_begin_impl(p, adv_dev, perm_dev, B, num_minibatches, s, device_shuffle ? &p->d_ctrl->shuffle_count : nullptr);
     p->epoch_idx = nullptr;   // the population's kernels address the table themselves

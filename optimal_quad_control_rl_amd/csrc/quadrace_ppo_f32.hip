@@ -26,11 +26,11 @@
 #include <vector>
 
 #include "../../include/quadrace.h"
+#include "quadrace_host.hpp"
 #include "quadrace_policy.hpp"
 
 struct qr_ppo;
 namespace qr {
-int set_last_error(int code, const std::string& msg);                                   // quadrace_abi.hip
 int ppo_handle_info(const qr_ppo* p, int* L, int* device, int* max_B, int* num_params);  // quadrace_ppo.hip
 void** ppo_f32_scratch_slot(qr_ppo* p);                                                  // quadrace_ppo.hip: one hipMalloc'ed block, freed by qr_ppo_destroy
 size_t* ppo_f32_scratch_bytes(qr_ppo* p);
@@ -279,13 +279,6 @@ __global__ void __launch_bounds__(256) f32_dw_reduce_kernel(ReduceArgs a) {
 
 namespace {
 
-int f32fail(int code, const std::string& m) { return qr::set_last_error(code, m); }
-#define F32_HIP(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t _e = (expr);                                                                                \
-        if (_e != hipSuccess) return f32fail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-    } while (0)
-
 struct NetOff32 { int w[4], b[4], total; };
 NetOff32 net_off32(int L, int O) {   // = net_off() of quadrace_ppo.hip: [w1 b1 w2 b2 w3 b3 w4 b4]
     NetOff32 o;
@@ -426,14 +419,14 @@ int qr_ppo_grad_f32class(qr_ppo* p, const float* theta_dev, const float* obs_dev
                          const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip, float vf_coef,
                          float ent_coef, float* grad_out_dev, float* stats_dev, void* stream) {
     int L = 0, device = 0, max_B = 0, np = 0;
-    if (!p || qr::ppo_handle_info(p, &L, &device, &max_B, &np) != QR_OK) return f32fail(QR_E_INVALID, "qr_ppo_grad_f32class: null handle");
+    if (!p || qr::ppo_handle_info(p, &L, &device, &max_B, &np) != QR_OK) return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad_f32class: null handle");
     if (!theta_dev || !obs_dev || !act_dev || !old_logp_dev || !adv_dev || !ret_dev || !idx_dev || !grad_out_dev)
-        return f32fail(QR_E_INVALID, "qr_ppo_grad_f32class: null argument");
-    if (B < 2 || B > max_B) return f32fail(QR_E_INVALID, "qr_ppo_grad_f32class: minibatch size must be >= 2 and <= max_minibatch");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad_f32class: null argument");
+    if (B < 2 || B > max_B) return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad_f32class: minibatch size must be >= 2 and <= max_minibatch");
     if ((B + 31) / 32 > 65535)   // the layer GEMMs put the 32-row tiles on grid.y
-        return f32fail(QR_E_INVALID, "qr_ppo_grad_f32class: at most 2 097 120 rows per minibatch");
-    if (net_off32(L, 4).total + net_off32(L, 1).total + 4 != np) return f32fail(QR_E_STATE, "qr_ppo_grad_f32class: parameter layout mismatch");
-    F32_HIP(hipSetDevice(device));
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad_f32class: at most 2 097 120 rows per minibatch");
+    if (net_off32(L, 4).total + net_off32(L, 1).total + 4 != np) return qr::set_last_error(QR_E_STATE, "qr_ppo_grad_f32class: parameter layout mismatch");
+    QR_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const int H = qr::kHid;
     // ---- scratch (one block per handle, sized for max_minibatch), per net: H1 H2 H3 [R][120], OUT [R][4], deltas DA DB [R][120], D4 [R][4],
@@ -443,16 +436,17 @@ int qr_ppo_grad_f32class(qr_ppo* p, const float* theta_dev, const float* obs_dev
     void** slot = qr::ppo_f32_scratch_slot(p);
     size_t* have = qr::ppo_f32_scratch_bytes(p);
     if (*slot == nullptr || *have < floats * sizeof(float)) {
-        if (*slot) { F32_HIP(hipDeviceSynchronize()); (void)hipFree(*slot); *slot = nullptr; }
-        F32_HIP(hipMalloc(slot, floats * sizeof(float)));
+        if (*slot) { QR_HIP(hipDeviceSynchronize()); (void)hipFree(*slot); *slot = nullptr; }
+        QR_HIP(hipMalloc(slot, floats * sizeof(float)));
         *have = floats * sizeof(float);
     }
     const GradCall call{theta_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, grad_out_dev, stats_dev};
+    // not qr::stream_is_capturing: no NULL-stream test and `== Active`, which differs for an invalidated capture
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool caller_captures = hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
     if (caller_captures || !qr::ppo_uses_graphs(p)) {   // a graph launch cannot be captured: plain nodes into the caller's graph
         enqueue_grad(call, L, max_B, np, static_cast<float*>(*slot), st);
-        F32_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         return QR_OK;
     }
     // ~20 dependent launches of microseconds each: replayed as one graph per distinct argument set (a training loop's minibatch
@@ -465,28 +459,28 @@ int qr_ppo_grad_f32class(qr_ppo* p, const float* theta_dev, const float* obs_dev
         if (e.first == call) { exec = e.second; break; }
     if (!exec) {
         hipStream_t* cap = qr::ppo_capture_stream_slot(p);
-        if (!*cap) F32_HIP(hipStreamCreateWithFlags(cap, hipStreamNonBlocking));
+        if (!*cap) QR_HIP(hipStreamCreateWithFlags(cap, hipStreamNonBlocking));
         hipGraph_t graph = nullptr;
-        F32_HIP(hipStreamBeginCapture(*cap, hipStreamCaptureModeRelaxed));
+        QR_HIP(hipStreamBeginCapture(*cap, hipStreamCaptureModeRelaxed));
         enqueue_grad(call, L, max_B, np, static_cast<float*>(*slot), *cap);
         const hipError_t end = hipStreamEndCapture(*cap, &graph);
         if (end != hipSuccess) {
             if (graph) (void)hipGraphDestroy(graph);
-            return f32fail(QR_E_HIP, std::string("qr_ppo_grad_f32class: graph capture failed: ") + hipGetErrorString(end));
+            return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_grad_f32class: graph capture failed: ") + hipGetErrorString(end));
         }
         const hipError_t inst = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
-        if (inst != hipSuccess) return f32fail(QR_E_HIP, std::string("qr_ppo_grad_f32class: hipGraphInstantiate: ") + hipGetErrorString(inst));
+        if (inst != hipSuccess) return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_grad_f32class: hipGraphInstantiate: ") + hipGetErrorString(inst));
         if (gc.entries.size() < GraphCache::kMax) {
             gc.entries.emplace_back(call, exec);
         } else {   // the replaced graph may still be running on the caller's stream
-            F32_HIP(hipDeviceSynchronize());
+            QR_HIP(hipDeviceSynchronize());
             (void)hipGraphExecDestroy(gc.entries[gc.next_victim].second);
             gc.entries[gc.next_victim] = std::make_pair(call, exec);
             gc.next_victim = (gc.next_victim + 1) % GraphCache::kMax;
         }
     }
-    F32_HIP(hipGraphLaunch(exec, st));
+    QR_HIP(hipGraphLaunch(exec, st));
     return QR_OK;
 }
 

@@ -224,17 +224,9 @@ void*& population_prepare_slot(qr_ppo_population* pop) { return pop->prepare; }
 
 namespace {
 
-int popfail(int code, const std::string& m) { return qr::set_last_error(code, m); }
-
-#define POP_HIP(expr)                                                                                        \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) return popfail(QR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-
 template <typename F>
 int dispatch_L(int L, F&& f) {
-    return qr::dispatch_L(L, f, [] { return popfail(QR_E_INVALID, "qr_ppo_population: the members' obs_len is not an observation length of the envs"); });
+    return qr::dispatch_L(L, f, [] { return qr::set_last_error(QR_E_INVALID, "qr_ppo_population: the members' obs_len is not an observation length of the envs"); });
 }
 
 template <int L>
@@ -244,8 +236,8 @@ struct PopOps {
     static constexpr int kThreads = 2 * qr::DenseMap<L>::kDenseThreads + 4;
     static constexpr int kWorkgroups = (kThreads + qr::kApplyThreads - 1) / qr::kApplyThreads;
     static int configure(const qr_ppo_population* pop) {
-        if (pop->partial_bf16) POP_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, true>>(kLdsFused)));
-        else POP_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float, true>>(kLdsFused)));
+        if (pop->partial_bf16) QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, true>>(kLdsFused)));
+        else QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float, true>>(kLdsFused)));
         return QR_OK;
     }
     // minibatch k of every member: three launches
@@ -263,7 +255,7 @@ struct PopOps {
         hipLaunchKernelGGL(qr::ppo_population_reduce_kernel<L>, dim3(kWorkgroups, P), dim3(qr::kApplyThreads), 0, st, pop->d_table, wgs, 2 * G,
                            pop->partial_bf16 ? 1 : 0);
         hipLaunchKernelGGL(qr::ppo_population_step_kernel<L>, dim3(kWorkgroups, P), dim3(qr::kApplyThreads), 0, st, pop->d_table);
-        POP_HIP(hipGetLastError());
+        QR_HIP(hipGetLastError());
         return QR_OK;
     }
 };
@@ -273,17 +265,17 @@ struct PopOps {
 extern "C" {
 
 int qr_ppo_population_create(qr_ppo* const* members, int32_t num_members, qr_ppo_population** out) {
-    if (!out) return popfail(QR_E_INVALID, "qr_ppo_population_create: null output");
+    if (!out) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_create: null output");
     *out = nullptr;
     if (!members || num_members < 1 || num_members > qr::kMaxPopulation)
-        return popfail(QR_E_INVALID, "qr_ppo_population_create: num_members must be 1..256 and members non-null");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_create: num_members must be 1..256 and members non-null");
     for (int p = 0; p < num_members; ++p) {
-        if (!members[p]) return popfail(QR_E_INVALID, "qr_ppo_population_create: null member handle");
+        if (!members[p]) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_create: null member handle");
         for (int q = 0; q < p; ++q)
-            if (members[q] == members[p]) return popfail(QR_E_INVALID, "qr_ppo_population_create: a handle is listed twice");
+            if (members[q] == members[p]) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_create: a handle is listed twice");
         const qr_ppo *a = members[0], *b = members[p];
         if (a->L != b->L || a->device != b->device || a->partial_bf16 != b->partial_bf16 || a->epoch_graph != b->epoch_graph)
-            return popfail(QR_E_INVALID, "qr_ppo_population_create: the members must share obs_len, device and flags");
+            return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_create: the members must share obs_len, device and flags");
     }
     qr_ppo_population* pop = new qr_ppo_population();
     pop->members.assign(members, members + num_members);
@@ -303,7 +295,7 @@ int qr_ppo_population_create(qr_ppo* const* members, int32_t num_members, qr_ppo
     if (e == hipSuccess) e = hipMemset(pop->d_scratch, 0, sizeof(float) * pop->scratch_floats * (size_t)num_members);
     if (e != hipSuccess) {
         qr_ppo_population_destroy(pop);
-        return popfail(QR_E_HIP, std::string("qr_ppo_population_create: ") + hipGetErrorString(e));
+        return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_population_create: ") + hipGetErrorString(e));
     }
     *out = pop;
     return QR_OK;
@@ -325,24 +317,23 @@ int qr_ppo_population_destroy(qr_ppo_population* pop) {
 
 int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* args, int32_t B, int32_t num_minibatches, int32_t num_epochs,
                             int32_t device_shuffle, void* stream) {
-    if (!pop || !args) return popfail(QR_E_INVALID, "qr_ppo_population_epoch: null argument");
+    if (!pop || !args) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: null argument");
     const int P = (int)pop->members.size();
     if (B < 64 || num_minibatches < 1 || num_minibatches > qr_ppo::kMaxEpochMinibatches)
-        return popfail(QR_E_INVALID, "qr_ppo_population_epoch: bad minibatch size / count");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: bad minibatch size / count");
     if (num_epochs < 1 || num_epochs > 64 || (num_epochs > 1 && !device_shuffle))
-        return popfail(QR_E_INVALID, "qr_ppo_population_epoch: num_epochs > 1 needs device_shuffle (the caller cannot rewrite the permutations in between)");
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: num_epochs > 1 needs device_shuffle (the caller cannot rewrite the permutations in between)");
     for (int p = 0; p < P; ++p) {
         const qr_ppo_member_args& a = args[p];
-        if (B > pop->members[p]->max_B) return popfail(QR_E_INVALID, "qr_ppo_population_epoch: B is above a member's max_minibatch");
+        if (B > pop->members[p]->max_B) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: B is above a member's max_minibatch");
         if (!a.theta_dev || !a.adam_m_dev || !a.adam_v_dev || !a.obs_dev || !a.act_dev || !a.old_logp_dev || !a.adv_dev || !a.ret_dev || !a.perm_dev)
-            return popfail(QR_E_INVALID, "qr_ppo_population_epoch: a member's argument is null");
-        if (!(a.lr >= 0.0f)) return popfail(QR_E_INVALID, "qr_ppo_population_epoch: a member's learning rate is negative or NaN");
+            return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: a member's argument is null");
+        if (!(a.lr >= 0.0f)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: a member's learning rate is negative or NaN");
     }
-    POP_HIP(hipSetDevice(pop->device));
+    QR_HIP(hipSetDevice(pop->device));
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return popfail(QR_E_INVALID, "qr_ppo_population_epoch: `stream` is being captured (the call uploads the member table and launches a graph of its own)");
+    if (qr::stream_is_capturing(st))
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_epoch: `stream` is being captured (the call uploads the member table and launches a graph of its own)");
     // the member table this call needs
     std::vector<qr::PopMember> table((size_t)P);
     std::memset(table.data(), 0, sizeof(qr::PopMember) * (size_t)P);   // padding included: the table is compared bytewise below
@@ -378,13 +369,13 @@ int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* ar
     const bool same_table = pop->table_valid && std::memcmp(table.data(), pop->h_table.data(), sizeof(qr::PopMember) * (size_t)P) == 0;
     if (!same_table) {
         // stream-ordered behind whatever earlier calls left on `st`; synchronised, so the host copy may go
-        POP_HIP(hipMemcpyAsync(pop->d_table, table.data(), sizeof(qr::PopMember) * (size_t)P, hipMemcpyHostToDevice, st));
-        POP_HIP(hipStreamSynchronize(st));
+        QR_HIP(hipMemcpyAsync(pop->d_table, table.data(), sizeof(qr::PopMember) * (size_t)P, hipMemcpyHostToDevice, st));
+        QR_HIP(hipStreamSynchronize(st));
         pop->h_table = table;
         pop->table_valid = true;
     }
     hipLaunchKernelGGL(qr::ppo_population_lr_kernel, dim3(1), dim3(qr::kMaxPopulation), 0, st, pop->d_table, P, lrs);
-    POP_HIP(hipGetLastError());
+    QR_HIP(hipGetLastError());
     for (int p = 0; p < P; ++p) {   // the step kernel keeps each member's images in step with its vector; its own epoch table is not armed
         pop->members[p]->packed_theta = args[p].theta_dev;
         pop->members[p]->epoch_idx = nullptr;
@@ -405,35 +396,35 @@ int qr_ppo_population_epoch(qr_ppo_population* pop, const qr_ppo_member_args* ar
                      pop->g_shuffle == device_shuffle && pop->g_seeds == seeds;
     if (!hit) {
         if (pop->exec) { (void)hipGraphExecDestroy(pop->exec); pop->exec = nullptr; }
-        if (!pop->capture_stream) POP_HIP(hipStreamCreateWithFlags(&pop->capture_stream, hipStreamNonBlocking));
+        if (!pop->capture_stream) QR_HIP(hipStreamCreateWithFlags(&pop->capture_stream, hipStreamNonBlocking));
         hipGraph_t graph = nullptr;
-        POP_HIP(hipStreamBeginCapture(pop->capture_stream, hipStreamCaptureModeRelaxed));
+        QR_HIP(hipStreamBeginCapture(pop->capture_stream, hipStreamCaptureModeRelaxed));
         const int rc = enqueue(pop->capture_stream);
         const hipError_t end = hipStreamEndCapture(pop->capture_stream, &graph);
         if (rc != QR_OK || end != hipSuccess) {
             if (graph) (void)hipGraphDestroy(graph);
-            return rc != QR_OK ? rc : popfail(QR_E_HIP, std::string("qr_ppo_population_epoch: graph capture failed: ") + hipGetErrorString(end));
+            return rc != QR_OK ? rc : qr::set_last_error(QR_E_HIP, std::string("qr_ppo_population_epoch: graph capture failed: ") + hipGetErrorString(end));
         }
         const hipError_t inst = hipGraphInstantiate(&pop->exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (inst != hipSuccess) {
             pop->exec = nullptr;
-            return popfail(QR_E_HIP, std::string("qr_ppo_population_epoch: hipGraphInstantiate: ") + hipGetErrorString(inst));
+            return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_population_epoch: hipGraphInstantiate: ") + hipGetErrorString(inst));
         }
         pop->g_B = B; pop->g_M = num_minibatches; pop->g_E = num_epochs; pop->g_shuffle = device_shuffle; pop->g_seeds = seeds;
     }
-    POP_HIP(hipGraphLaunch(pop->exec, st));
+    QR_HIP(hipGraphLaunch(pop->exec, st));
     return QR_OK;
 }
 
 int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, float* const* adam_m_dev, float* const* adam_v_dev,
                               const int32_t* src_of, const float* log_std_shift, void* stream) {
-    if (!pop || !theta_dev || !adam_m_dev || !adam_v_dev || !src_of) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: null argument");
+    if (!pop || !theta_dev || !adam_m_dev || !adam_v_dev || !src_of) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: null argument");
     const int P = (int)pop->members.size();
     for (int p = 0; p < P; ++p) {
-        if (!theta_dev[p] || !adam_m_dev[p] || !adam_v_dev[p]) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a member's pointer is null");
-        if (src_of[p] < 0 || src_of[p] >= P) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: src_of holds an index outside [0, members)");
-        if (log_std_shift && !std::isfinite(log_std_shift[p])) return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a log_std_shift is not finite");
+        if (!theta_dev[p] || !adam_m_dev[p] || !adam_v_dev[p]) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: a member's pointer is null");
+        if (src_of[p] < 0 || src_of[p] >= P) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: src_of holds an index outside [0, members)");
+        if (log_std_shift && !std::isfinite(log_std_shift[p])) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: a log_std_shift is not finite");
     }
     qr::ExploitPlan plan;
     std::memset(&plan, 0, sizeof(plan));
@@ -442,18 +433,17 @@ int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, f
         const int s = src_of[p];
         if (s == p) continue;
         if (src_of[s] != s)
-            return popfail(QR_E_INVALID, "qr_ppo_population_exploit: a source is itself a destination (one launch may not read what it writes)");
+            return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: a source is itself a destination (one launch may not read what it writes)");
         const float shift = log_std_shift ? log_std_shift[p] : 0.0f;
         plan.dst[destinations] = (unsigned char)p;
         plan.src[destinations] = (unsigned char)s;
         plan.shift[destinations] = shift;
         ++destinations;
     }
-    POP_HIP(hipSetDevice(pop->device));
+    QR_HIP(hipSetDevice(pop->device));
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return popfail(QR_E_INVALID, "qr_ppo_population_exploit: `stream` is being captured (the call may allocate and upload the member table)");
+    if (qr::stream_is_capturing(st))
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_exploit: `stream` is being captured (the call may allocate and upload the member table)");
     if (destinations == 0) return QR_OK;
     // the members as the kernel sees them: uploaded when a pointer moved (in practice: by the first call)
     std::vector<qr::ExploitMember> table((size_t)P);
@@ -463,11 +453,11 @@ int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, f
     }
     static_assert(sizeof(qr::ExploitMember) == 5 * sizeof(void*), "no padding: the table is compared bytewise");
     if (!pop->exploit_valid || std::memcmp(table.data(), pop->h_exploit.data(), sizeof(qr::ExploitMember) * (size_t)P) != 0) {
-        if (!pop->d_exploit) POP_HIP(hipMalloc((void**)&pop->d_exploit, sizeof(qr::ExploitMember) * (size_t)P));
+        if (!pop->d_exploit) QR_HIP(hipMalloc((void**)&pop->d_exploit, sizeof(qr::ExploitMember) * (size_t)P));
         // stream-ordered behind whatever earlier calls left on `st`; synchronised, so the host copy may go
         pop->exploit_valid = false;
-        POP_HIP(hipMemcpyAsync(pop->d_exploit, table.data(), sizeof(qr::ExploitMember) * (size_t)P, hipMemcpyHostToDevice, st));
-        POP_HIP(hipStreamSynchronize(st));
+        QR_HIP(hipMemcpyAsync(pop->d_exploit, table.data(), sizeof(qr::ExploitMember) * (size_t)P, hipMemcpyHostToDevice, st));
+        QR_HIP(hipStreamSynchronize(st));
         pop->h_exploit = table;
         pop->exploit_valid = true;
     }
@@ -477,7 +467,7 @@ int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, f
             const int blocks = ((n > images ? n : images) + qr::kExploitThreads - 1) / qr::kExploitThreads;
             hipLaunchKernelGGL(qr::ppo_population_exploit_kernel<L>, dim3(blocks, destinations), dim3(qr::kExploitThreads), 0, st,
                                (const qr::ExploitMember*)pop->d_exploit, plan);
-            POP_HIP(hipGetLastError());
+            QR_HIP(hipGetLastError());
             return (int)QR_OK;
         }))
         return rc;
@@ -488,12 +478,12 @@ int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, f
 }
 
 int qr_ppo_population_status(qr_ppo_population* pop, int32_t* out, void* stream) {
-    if (!pop || !out) return popfail(QR_E_INVALID, "qr_ppo_population_status: null argument");
-    POP_HIP(hipSetDevice(pop->device));
+    if (!pop || !out) return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_status: null argument");
+    QR_HIP(hipSetDevice(pop->device));
     hipStream_t st = (hipStream_t)stream;
     for (size_t p = 0; p < pop->members.size(); ++p)
-        POP_HIP(hipMemcpyAsync(out + 4 * p, &pop->members[p]->d_ctrl->stop, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    POP_HIP(hipStreamSynchronize(st));
+        QR_HIP(hipMemcpyAsync(out + 4 * p, &pop->members[p]->d_ctrl->stop, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    QR_HIP(hipStreamSynchronize(st));
     return QR_OK;
 }
 
