@@ -40,7 +40,8 @@ class QrPpoPrepareMember(C.Structure):
                 [(n, _vp) for n in ("obs", "act", "old_logp", "rew", "done", "val", "term_val", "last_val", "adv", "ret", "ep_ret", "ep_len", "ep_gates")])
 
 
-# name -> (restype, argtypes); must list every symbol of include/quadrace.h and include/quad3d.h
+# name -> (restype, argtypes); must list every symbol of include/quadrace.h and include/quad3d.h, each bound compatibly with its
+# declaration: tests/test_abi_host.py::test_every_declared_function_is_bound_compatibly holds every row against the headers
 SIGNATURES = {
     "qr_abi_version": (C.c_int, []),
     "qr_last_error": (C.c_char_p, []),

@@ -1,6 +1,7 @@
 """CPU-side checks (no GPU needed): the C-ABI library builds, loads and exports every symbol that
-include/quadrace.h declares; the ctypes table matches the header; host-side helpers behave like the
-reference's; and -- on a box without a GPU -- the product fails loudly instead of falling back."""
+include/quadrace.h and include/quad3d.h declare; every row of the ctypes table binds its declaration compatibly
+(tests/abi_decl.py reads the headers); what is pinned about single entry points (tests/abi_table.py) holds; host-side helpers
+behave like the reference's; and -- on a box without a GPU -- the product fails loudly instead of falling back."""
 import ctypes as C
 import os
 import re
@@ -8,16 +9,103 @@ import re
 import numpy as np
 import pytest
 
+import abi_decl
+import abi_table
+from optimal_quad_control_rl_amd import _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DECLARED = {f[0]: f for name, prefix in (("quadrace.h", "qr_"), ("quad3d.h", "q3_")) for f in abi_decl.functions(abi_decl.header(name)[1], prefix)}
 
 
 def header_functions():
-    names = set()
-    for header, prefix in (("quadrace.h", "qr_"), ("quad3d.h", "q3_")):
-        src = open(os.path.join(ROOT, "include", header)).read()
-        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-        names |= set(re.findall(r"\b(" + prefix + r"[a-z_0-9]+)\s*\(", src))
-    return sorted(names)
+    return sorted(DECLARED)
+
+
+@pytest.fixture(scope="module")
+def exported():
+    """the built library as the dynamic loader sees it: no argtypes, nothing from _lib.py"""
+    from optimal_quad_control_rl_amd import build
+
+    build.build_native()
+    return C.CDLL(build.LIB)
+
+
+@pytest.mark.parametrize("name", sorted(DECLARED))
+def test_every_declared_function_is_bound_compatibly(name, exported):
+    """A wrong width or a dropped argument in a row of _lib.SIGNATURES loads and runs: this is what stops it."""
+    _, ret, _, types_ = DECLARED[name]
+    restype, argtypes = _lib.SIGNATURES[name]
+    assert abi_decl.binding_matches(ret, restype), (ret, restype)
+    assert len(argtypes) == len(types_), (types_, argtypes)
+    for k, (c_type, ctype) in enumerate(zip(types_, argtypes)):
+        assert abi_decl.binding_matches(c_type, ctype), "argument %d: %s bound as %s" % (k, c_type, ctype)
+    assert hasattr(exported, name), "%s declared in include/*.h but not exported" % name
+    fn = getattr(_lib.load(), name)
+    assert fn.restype is restype and list(fn.argtypes) == list(argtypes)
+
+
+def _part(seq, span):
+    return seq[span[0]:span[1]]
+
+
+@pytest.mark.parametrize("row", abi_table.ROWS, ids=lambda r: r["name"])
+def test_pinned_entry_points(row):
+    from optimal_quad_control_rl_amd import build
+
+    name = row["name"]
+    text, code = abi_decl.header_of(name)
+    _, ret, names, types_ = abi_decl.declaration(code, name)
+    restype, argtypes = _lib.SIGNATURES[name]
+    assert names == row["args"] and ret == "int" and restype is C.c_int and len(argtypes) == len(names)
+    for column, actual in (("types", types_), ("bound", argtypes)):
+        pinned = row.get(column, {})
+        for k, want in pinned.items() if isinstance(pinned, dict) else enumerate(pinned):
+            assert actual[k] == want, (column, k, actual[k], want)
+        assert isinstance(pinned, dict) or len(pinned) == len(actual), column
+    if row.get("optional"):
+        assert name in _lib.OPTIONAL_SYMBOLS
+    exports = open(os.path.join(build.CSRC, "exports.map")).read()
+    assert name[:3] + "*;" in exports and row.get("in_exports", "") in exports
+    if "in_version_comment" in row:
+        assert row["in_version_comment"] in abi_decl.version_comment(text)
+    if "source" in row:
+        assert row["source"] in build.SOURCES and os.path.exists(os.path.join(build.CSRC, row["source"]))
+        assert not (row.get("default_flags") and row["source"] in build.PER_SOURCE_FLAGS)
+        assert not (row.get("vgpr_form") and row["source"] in build.NO_VGPR_FORM)
+    for define, value in row.get("defines", {}).items():
+        assert abi_decl.define(code, define) == value, define
+    for pattern in row.get("patterns", []):
+        assert re.search(pattern, code), pattern
+    anchor, words = row.get("contract", (None, []))
+    comment = text if anchor is None else text.split(anchor)[0].rsplit("/*", 1)[1]
+    for word in words:
+        assert word in comment, word
+    for mine, other, theirs in row.get("same_as", []):
+        assert _part(names, mine) == _part(abi_decl.declaration(abi_decl.header_of(other)[1], other)[2], theirs), other
+
+
+@pytest.mark.parametrize("row", [r for r in abi_table.ROWS if "null_call" in r], ids=lambda r: r["name"])
+def test_null_handles_are_refused_without_a_device(row):
+    """A NULL handle is refused, not dereferenced -- before the library asks for a device."""
+    L = _lib.load()
+    args, code, message = row["null_call"]
+    rc = getattr(L, row["name"])(*args)
+    assert rc != _lib.QR_OK and code in (None, rc), rc
+    assert message is None or message in L.qr_last_error()
+
+
+def test_every_optional_symbol_is_a_signature():
+    assert set(_lib.OPTIONAL_SYMBOLS) <= set(_lib.SIGNATURES) and len(set(_lib.OPTIONAL_SYMBOLS)) == len(_lib.OPTIONAL_SYMBOLS)
+
+
+@pytest.mark.parametrize("name", _lib.OPTIONAL_SYMBOLS)
+def test_a_library_without_an_optional_symbol_is_reported_by_name(name):
+    class Old:   # a library built from older sources: no such attribute
+        pass
+
+    with pytest.raises(_lib.QuadraceError, match=name):
+        _lib.require(Old(), name)
+    assert _lib.require(_lib.load(), name) is not None
 
 
 def test_library_builds_and_exports_every_header_symbol():

@@ -1,15 +1,11 @@
 """CPU: the black box's bookkeeping specification (tests/blackbox_spec.py) on hand-made rows, CrashLog's unrolling and tables against
-it, and the entry point at every layer (header, library, ctypes table, package) without an ABI bump."""
-import ctypes as C
-import os
-import re
-
+it, the Python binding on a library without the entry point, and the package surface (the C entry point itself is pinned in
+tests/abi_table.py)."""
 import numpy as np
 import pytest
 
 import blackbox_spec as B
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S_LEN = 13
 R = S_LEN + 8
 
@@ -174,41 +170,8 @@ def test_cause_counts_and_by_gate_on_synthetic_status():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the entry point at every layer
+# the binding and the package surface
 # ---------------------------------------------------------------------------------------------------------------------------------
-_CTYPE = {"qr_env*": C.c_void_p, "qr_policy*": C.c_void_p, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "const float*": C.POINTER(C.c_float),
-          "float*": C.c_void_p, "int32_t*": C.c_void_p, "void*": C.c_void_p}   # device pointers travel as void*
-
-
-def test_blackbox_policy_is_declared_exported_and_listed():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, value in (("QR_BLACKBOX_ST_INTS", 4), ("QR_ABI_VERSION", 3), ("QR_RECORD_EXTRA", 8)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), code), name
-    assert re.search(r"QR_BLACKBOX_ON_CRASH\s*=\s*1\s*,\s*QR_BLACKBOX_ON_TIME_LIMIT\s*=\s*2", code)
-    m = re.search(r"int\s+qr_blackbox_policy\s*\(([^)]*)\)", code)
-    assert m, "include/quadrace.h does not declare qr_blackbox_policy"
-    decl = []
-    for a in m.group(1).split(","):
-        typ, name_ = a.strip().rsplit(None, 1)
-        stars = len(name_) - len(name_.lstrip("*"))
-        decl.append((re.sub(r"\s*\*", "*", typ + "*" * stars), name_.lstrip("*")))
-    assert [n for _, n in decl] == ["env", "policy", "num_steps", "log_std", "noise_seed", "first_step", "flags", "trigger", "window", "rec_envs",
-                                    "ring_dev", "st_dev", "term_dev", "stream"]
-    assert "qr_blackbox_policy" in hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]                  # the "additive since 3" comment names it
-    assert "quadrace_blackbox.hip" in build.SOURCES
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    assert hasattr(L, "qr_blackbox_policy"), "libquadrace.so does not export qr_blackbox_policy"
-    rt, at = _lib.SIGNATURES["qr_blackbox_policy"]
-    assert rt is C.c_int and [_CTYPE[t] for t, _ in decl] == list(at)
-    assert "qr_blackbox_policy" in _lib.OPTIONAL_SYMBOLS
-    assert _lib.load().qr_abi_version() == 3
-    assert L.qr_blackbox_policy(None, None, 1, None, 0, 0, 0, 1, 8, 1, None, None, None, None) != _lib.QR_OK   # a NULL handle is refused, not dereferenced
-
-
 def test_a_library_without_the_black_box_is_reported_by_symbol_name():
     from optimal_quad_control_rl_amd import _lib
     from optimal_quad_control_rl_amd.vec_env import Quadcopter3DGates
@@ -216,8 +179,6 @@ def test_a_library_without_the_black_box_is_reported_by_symbol_name():
     class Old:   # a library built from older sources: no such attribute
         pass
 
-    with pytest.raises(_lib.QuadraceError, match="qr_blackbox_policy"):
-        _lib.require(Old(), "qr_blackbox_policy")
     env = Quadcopter3DGates.__new__(Quadcopter3DGates)   # the binding asks for the symbol before it touches anything else
     env._L = Old()
     env._h = None                                        # (nothing to release)

@@ -1,52 +1,9 @@
-"""CPU: the policy bank and its evaluation entry point exist at every layer (header, library, ctypes table, package) without an ABI
-bump; rank_policies orders hand-made results as documented; the batching arithmetic of evaluate_policies is a pure function."""
-import ctypes as C
+"""CPU: the policy bank and its evaluation in the package (the C entry points are pinned in tests/abi_table.py); rank_policies orders hand-made results as documented; the batching arithmetic of evaluate_policies is a pure function."""
 import os
-import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-WEIGHTS = ["w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4"]
-ENTRY_POINTS = {
-    "qr_policy_bank_create": ["obs_len", "device", "capacity", "out"],
-    "qr_policy_bank_destroy": ["bank"],
-    "qr_policy_bank_capacity": ["bank"],
-    "qr_policy_bank_set": ["bank", "slot"] + WEIGHTS,
-    "qr_evaluate_policy_bank": ["env", "bank", "num_policies", "envs_per_policy", "num_steps", "gates_per_lap", "flags", "rec_dev", "recf_dev",
-                                "stream"],
-}
-
-
-def _declared_args(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    return [a.strip().split()[-1].lstrip("*") for a in m.group(1).split(",")]
-
-
-def test_bank_entry_points_are_declared_exported_and_listed():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"typedef\s+struct\s+qr_policy_bank\s+qr_policy_bank\s*;", code)
-    assert re.search(r"#define\s+QR_ABI_VERSION\s+3\b", code)
-    for name, args in ENTRY_POINTS.items():
-        assert _declared_args(code, name) == args, name
-    # the weight arguments are those of qr_policy_set_weights, in its order
-    assert _declared_args(code, "qr_policy_bank_set")[2:] == _declared_args(code, "qr_policy_set_weights")[1:]
-    assert "group-local reset stream" in hdr.lower()          # documented as a property of the call
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    for name, args in ENTRY_POINTS.items():
-        assert hasattr(L, name), "libquadrace.so does not export %s" % name
-        rt, at = _lib.SIGNATURES[name]
-        assert rt is C.c_int and len(at) == len(args), name
-        assert name in _lib.OPTIONAL_SYMBOLS, name
-    assert _lib.load().qr_abi_version() == 3
-    assert "quadrace_eval_bank.hip" in build.SOURCES          # a translation unit of its own, through the same rewrite and lint
-
 
 def test_package_exports_the_bank_names_lazily():
     import optimal_quad_control_rl_amd as pkg

@@ -1,56 +1,13 @@
-"""CPU: the condition bank and the grid evaluation entry point exist at every layer (header, library, ctypes table, package) without
-an ABI bump; the batching arithmetic of evaluate_grid is a pure function; Condition / disturbance_sweep / robustness_table and the
+"""CPU: the condition bank and the grid evaluation in the package (the C entry points are pinned in tests/abi_table.py); the batching arithmetic of evaluate_grid is a pure function; Condition / disturbance_sweep / robustness_table and the
 argument handling of tools/robustness_sweep.py work on hand-made data."""
-import ctypes as C
 import importlib.util
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-ENTRY_POINTS = {
-    "qr_condition_bank_create": ["variant", "device", "capacity", "out"],
-    "qr_condition_bank_destroy": ["bank"],
-    "qr_condition_bank_capacity": ["bank"],
-    "qr_condition_bank_set": ["bank", "slot", "gate_pos", "gate_yaw", "num_gates", "start_pos", "dist_ranges", "dist_scale", "max_steps",
-                              "gates_per_lap"],
-    "qr_evaluate_policy_grid": ["env", "policies", "conditions", "num_groups", "envs_per_group", "policy_of_group", "condition_of_group",
-                                "num_steps", "flags", "rec_dev", "recf_dev", "stream"],
-}
-
-
-def _declared_args(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    return [a.strip().split()[-1].lstrip("*") for a in m.group(1).split(",")]
-
-
-def test_grid_entry_points_are_declared_exported_and_listed():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"typedef\s+struct\s+qr_condition_bank\s+qr_condition_bank\s*;", code)
-    assert re.search(r"#define\s+QR_ABI_VERSION\s+3\b", code)
-    for name, args in ENTRY_POINTS.items():
-        assert _declared_args(code, name) == args, name
-    # the track arguments are those of qr_set_track, in its order
-    assert _declared_args(code, "qr_condition_bank_set")[2:6] == _declared_args(code, "qr_set_track")[1:]
-    assert "bit for bit" in hdr and "qr_condition_bank_" in hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]   # contract + version comment
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    for name, args in ENTRY_POINTS.items():
-        assert hasattr(L, name), "libquadrace.so does not export %s" % name
-        rt, at = _lib.SIGNATURES[name]
-        assert rt is C.c_int and len(at) == len(args), name
-        assert name in _lib.OPTIONAL_SYMBOLS, name
-    assert _lib.load().qr_abi_version() == 3
-    assert "quadrace_eval_grid.hip" in build.SOURCES          # a translation unit of its own, through the same rewrite and lint
-
 
 def test_package_exports_the_grid_names_lazily():
     import optimal_quad_control_rl_amd as pkg

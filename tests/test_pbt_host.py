@@ -1,8 +1,7 @@
 """CPU: population-based training above the device -- `PBT.plan` (truncation selection: exact sources and destinations on hand-written
-fitness lists), the refusals of `PopulationPPO(pbt=...)` and `PopulationPPO.exploit` before anything touches a GPU, and
-qr_ppo_population_exploit at every layer that needs no device: header, ctypes table, optional-symbol list, and the one refusal of the
-C call that a box without a GPU can reach (a population object needs a device; a NULL one does not)."""
-import ctypes as C
+fitness lists), the refusals of `PopulationPPO(pbt=...)` and `PopulationPPO.exploit` before anything touches a GPU, and where the
+exploit kernel lives (qr_ppo_population_exploit itself, with the one refusal of the C call that a box without a GPU can reach, is
+pinned in tests/abi_table.py)."""
 import math
 import os
 import re
@@ -11,7 +10,7 @@ import numpy as np
 import pytest
 
 from optimal_quad_control_rl_amd.population import INHERITED, PBT, PERTURBABLE, PopulationPPO, check_exploit
-from test_ppo_population_update_host import _stub_env
+from abi_decl import stub_env as _stub_env
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -161,48 +160,14 @@ def test_exploit_refusals_come_before_anything_is_touched():
     assert check_exploit(4, (0, 0, 3, 3)) == ([0, 0, 3, 3], [0.0] * 4)
 
 
-def _declaration(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    parts = [a.replace("*", " * ").split() for a in m.group(1).split(",")]
-    return [p[-1] for p in parts], [" ".join(p[:-1]) for p in parts]
+def test_the_exploit_kernel_shares_the_gather_of_qr_ppo_pack():
+    from optimal_quad_control_rl_amd import build, ppo
 
-
-def test_the_entry_point_is_declared_exported_and_bound():
-    from optimal_quad_control_rl_amd import _lib, build, ppo
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"#define\s+QR_ABI_VERSION\s+3\b", code)
-    assert "qr_ppo_population_exploit" in hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]
-    assert _declaration(code, "qr_ppo_population_exploit") == (
-        ["pop", "theta_dev", "adam_m_dev", "adam_v_dev", "src_of", "log_std_shift", "stream"],
-        ["qr_ppo_population *", "float * const *", "float * const *", "float * const *", "const int32_t *", "const float *", "void *"])
-    contract = hdr.split("int qr_ppo_population_exploit")[0].rsplit("/*", 1)[1]
-    for word in ("CONTRACT", "bit for bit", "Refused before anything is launched", "captured", "no host read", "no atomic", "qr_ppo_pack",
-                 "qr_ppo_adam_step", "itself a destination"):
-        assert word in contract, word
-    rt, at = _lib.SIGNATURES["qr_ppo_population_exploit"]
-    vpp = C.POINTER(C.c_void_p)
-    assert rt is C.c_int and at == [C.c_void_p, vpp, vpp, vpp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p]
-    assert "qr_ppo_population_exploit" in _lib.OPTIONAL_SYMBOLS
     assert callable(ppo.MfmaPpoPopulationUpdater.exploit)
     text = open(os.path.join(build.CSRC, "quadrace_ppo_population.hip")).read()
     assert re.search(r"__global__[^;{]*\bppo_population_exploit_kernel\b", text)
     # one gather for qr_ppo_pack and for the exploit kernel: the images cannot drift apart
     assert "pack_gather<L>" in text and "pack_gather<L>" in open(os.path.join(build.CSRC, "quadrace_ppo.hip")).read()
-
-
-def test_the_c_call_refuses_a_null_population_without_a_device():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    build.build_native()
-    L = _lib.load()
-    assert hasattr(L, "qr_ppo_population_exploit")
-    one = (C.c_void_p * 1)(None)
-    src = (C.c_int32 * 1)(0)
-    assert L.qr_ppo_population_exploit(None, one, one, one, src, None, None) == _lib.QR_E_INVALID
-    assert b"qr_ppo_population_exploit" in L.qr_last_error()
 
 
 def test_tool_flags():

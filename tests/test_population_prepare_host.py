@@ -1,92 +1,30 @@
-"""CPU: the device-side prepare of a population round (qr_ppo_population_load_bank, qr_policy_bank_read, qr_ppo_population_prepare) exists
-at every layer -- header, library, ctypes table, build, package, tool -- without an ABI bump; the two structs of _lib.py have the header's
+"""CPU: the device-side prepare of a population round in the build, the package and the tool (qr_ppo_population_load_bank,
+qr_policy_bank_read and qr_ppo_population_prepare themselves are pinned in tests/abi_table.py); the two structs of _lib.py have the header's
 field order and layout; the Python-side refusals come before anything touches a GPU."""
 import ctypes as C
 import os
 import re
-import types
 
 import pytest
 
+import abi_decl
+from abi_decl import stub_env as _stub_env   # the GPU tests import it from here
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-ENTRY_POINTS = {
-    "qr_ppo_population_load_bank": (["pop", "theta_dev", "bank", "first_slot", "stream"],
-                                    ["qr_ppo_population *", "const float * const *", "qr_policy_bank *", "int32_t", "void *"]),
-    "qr_policy_bank_read": (["bank", "slot", "which", "out_host", "bytes"], ["const qr_policy_bank *", "int32_t", "int32_t", "void *", "size_t"]),
-    "qr_ppo_population_prepare": (["pop", "sh", "members", "report_host", "stream"],
-                                  ["qr_ppo_population *", "const qr_ppo_prepare_shared *", "const qr_ppo_prepare_member *", "double *", "void *"]),
-}
 SHARED_FIELDS = [("int32_t", ["K", "N", "E"]), ("const float *", ["obs", "act", "logp", "rew"]), ("const uint8_t *", ["done", "trunc"]),
                  ("const float *", ["last_obs"]), ("const float *", ["term_obs"])]
 MEMBER_FIELDS = [("int32_t", ["first_env"]), ("float", ["gamma", "lam"]), ("float *", ["obs", "act", "old_logp", "rew", "done", "val"]),
                  ("float *", ["term_val"]), ("float *", ["last_val"]), ("float *", ["adv", "ret"]), ("float *", ["ep_ret", "ep_len", "ep_gates"])]
 
 
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    return hdr, re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _declaration(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    parts = [a.replace("*", " * ").split() for a in m.group(1).split(",")]
-    return [p[-1] for p in parts], [" ".join(p[:-1]) for p in parts]
-
-
-def _struct_fields(code, name):
-    body = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*%s\s*;" % name, code)
-    assert body, "include/quadrace.h does not define %s" % name
-    declared = []
-    for stmt in body.group(1).split(";"):
-        if stmt.strip():
-            base = re.match(r"\s*((?:const\s+)?\w+)", stmt)
-            for item in stmt[base.end():].split(","):
-                item = item.strip()
-                declared.append((base.group(1) + (" *" if item.startswith("*") else ""), item.lstrip("* ")))
-    return declared
-
-
-def test_entry_points_are_declared_exported_bound_and_built():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr, code = _header()
-    assert re.search(r"#define\s+QR_ABI_VERSION\s+3\b", code)
-    version_comment = hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]
-    for name in ENTRY_POINTS:
-        assert name in version_comment, name                                                  # the version comment names it
-    contract = hdr.split("typedef struct {   /* the ONE collect launch's outputs")[0].rsplit("/*", 1)[1]
-    for word in ("CONTRACT", "bit for bit", "Refused before anything is launched", "captured", "ONE blocking", "qr_policy_bank_set", "no atomic"):
-        assert word in contract, word
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    exports = open(os.path.join(build.CSRC, "exports.map")).read()
-    assert "qr_*;" in exports
-    ctype_of = {"int32_t": C.c_int32, "void *": C.c_void_p, "size_t": C.c_size_t, "double *": C.POINTER(C.c_double),
-                "qr_ppo_population *": C.c_void_p, "qr_policy_bank *": C.c_void_p, "const qr_policy_bank *": C.c_void_p,
-                "const float * const *": C.POINTER(C.c_void_p), "const qr_ppo_prepare_shared *": C.POINTER(_lib.QrPpoPrepareShared),
-                "const qr_ppo_prepare_member *": C.POINTER(_lib.QrPpoPrepareMember)}
-    for name, (args, types_) in ENTRY_POINTS.items():
-        assert _declaration(code, name) == (args, types_), name
-        assert hasattr(L, name), "libquadrace.so does not export %s" % name
-        rt, at = _lib.SIGNATURES[name]
-        assert rt is C.c_int and at == [ctype_of[t] for t in types_], name
-        assert name in _lib.OPTIONAL_SYMBOLS
-    assert _lib.load().qr_abi_version() == 3
-    # a translation unit of its own with the default flags, through the same rewrite and lint
-    src = "quadrace_population_prepare.hip"
-    assert src in build.SOURCES and os.path.exists(os.path.join(build.CSRC, src))
-    assert src not in build.PER_SOURCE_FLAGS and src not in build.NO_VGPR_FORM
-
-
 def test_structs_match_the_header():
     from optimal_quad_control_rl_amd import _lib
 
-    _, code = _header()
+    _, code = abi_decl.header()
     for cname, expected, ctype in (("qr_ppo_prepare_shared", SHARED_FIELDS, _lib.QrPpoPrepareShared),
                                    ("qr_ppo_prepare_member", MEMBER_FIELDS, _lib.QrPpoPrepareMember)):
-        declared = _struct_fields(code, cname)
+        declared = abi_decl.struct_fields(code, cname)
         assert declared == [(t, n) for t, names in expected for n in names], cname
         fields = ctype._fields_
         assert [n for n, _ in fields] == [n for _, n in declared], cname
@@ -191,14 +129,6 @@ def test_many_tile_shapes_walk_several_tiles_per_workgroup():
         assert len({ga["member"], te["member"], lp["last"]["member"]}) == 3 and min(ga["member"], te["member"], lp["last"]["member"]) >= 4
     assert any(sh["E"] // 256 >= 2 for sh in MANY_TILE_SHAPES) and any(sh["P"] == 256 for sh in MANY_TILE_SHAPES)   # (c)
     assert any(sh["L"] % 4 == 0 for sh in MANY_TILE_SHAPES) and any(sh["L"] % 4 != 0 for sh in MANY_TILE_SHAPES)    # both load paths
-
-
-def _stub_env(n):
-    def touched(*a, **k):
-        raise AssertionError("the argument checks come before the env is used")
-
-    return types.SimpleNamespace(num_envs=n, state_len=24, device=None, VARIANT=0, reset_device=touched, condition_reset=touched,
-                                 set_terminal_obs_buffer=touched)
 
 
 def batched_prepare_refusals(env_factory):

@@ -1,5 +1,6 @@
 """No GPU: the q3 evaluators' accounting as restated in tests/q3_eval_spec.py on hand-written step tables, summarize_q3_eval on
-hand-written records, the ctypes signatures, the stale-library error, and the argument checks that need no device."""
+hand-written records, the ctypes signatures (the header side is pinned in tests/abi_table.py), the stale-library error, and the
+argument checks that need no device."""
 import ctypes as C
 import types
 
@@ -123,22 +124,6 @@ def test_signatures_and_exports():
     assert "q3_evaluate_policy" in _lib.OPTIONAL_SYMBOLS and "q3_evaluate_policy_bank" in _lib.OPTIONAL_SYMBOLS
     for name in ("evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval"):
         assert name in pkg.__all__ and getattr(pkg, name) is getattr(evaluation, name), name
-
-
-def test_header_declares_what_the_binding_lists():
-    import os
-    import re
-
-    from optimal_quad_control_rl_amd import _lib
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "include", "quad3d.h")) as f:
-        text = f.read()
-    assert re.search(r"#define Q3_EVAL_REC_INTS 12\b", text) and re.search(r"#define Q3_EVAL_REC_FLOATS 4\b", text)
-    for name in ("q3_evaluate_policy", "q3_evaluate_policy_bank"):
-        m = re.search(r"\bint %s\(([^;]*)\);" % name, text)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
 
 
 @pytest.mark.parametrize("name", ["q3_evaluate_policy", "q3_evaluate_policy_bank"])

@@ -1,6 +1,6 @@
-"""CPU-side checks of the predecessor envs' closed-loop rollout (no GPU needed): the library exports q3_rollout_policy and the ctypes
-table binds it; the policy / PPO kernels know the observation length 16 (on a box without a GPU the create calls get as far as the
-device check instead of refusing the length); and a null env is refused with a message."""
+"""CPU-side checks of the predecessor envs' closed-loop rollout (no GPU needed; q3_rollout_policy's declaration and binding are pinned
+in tests/abi_table.py and tests/test_abi_host.py): the policy / PPO kernels know the observation length 16 (on a box without a GPU
+the create calls get as far as the device check instead of refusing the length); and a null env is refused with a message."""
 import ctypes as C
 
 
@@ -9,19 +9,6 @@ def _lib_and_handle():
 
     build.build_native()
     return _lib, _lib.load()
-
-
-def test_library_exports_and_binds_the_entry_point():
-    from optimal_quad_control_rl_amd import build
-
-    _lib, L = _lib_and_handle()
-    raw = C.CDLL(build.LIB)
-    for name in ("q3_rollout_policy", "q3_episode_counts"):
-        assert hasattr(raw, name), name
-        assert name in _lib.SIGNATURES
-    restype, argtypes = _lib.SIGNATURES["q3_rollout_policy"]
-    assert restype is C.c_int and len(argtypes) == 17
-    assert L.q3_rollout_policy.argtypes is not None and len(L.q3_rollout_policy.argtypes) == 17
 
 
 def test_obs_len_16_is_a_legal_length_and_23_is_not():

@@ -1,62 +1,7 @@
-"""CPU: the flight recorder exists at every layer (header, library, ctypes table, package) without an ABI bump, its code object is
-among the linted ones, and FlightRecord turns a synthetic [K][M][R] array into what a plain NumPy restatement gives."""
-import ctypes as C
-import os
-import re
-
+"""CPU: the flight recorder in the package (its C entry points are pinned in tests/abi_table.py), its code object among the linted
+ones, and FlightRecord turns a synthetic [K][M][R] array into what a plain NumPy restatement gives."""
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-_CTYPE = {"qr_env*": C.c_void_p, "const qr_env*": C.c_void_p, "qr_policy*": C.c_void_p, "int32_t": C.c_int32, "uint64_t": C.c_uint64,
-          "const float*": C.POINTER(C.c_float), "float*": C.c_void_p, "void*": C.c_void_p}   # device pointers travel as void*
-
-
-def _declaration(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    out = []
-    for a in m.group(1).split(","):
-        typ, name_ = a.strip().rsplit(None, 1)
-        stars = len(name_) - len(name_.lstrip("*"))
-        out.append((re.sub(r"\s*\*", "*", typ + "*" * stars), name_.lstrip("*")))   # (type, name), e.g. ("const float*", "log_std")
-    return out
-
-
-def test_record_policy_is_declared_exported_and_listed():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, value in (("QR_RECORD_EXTRA", 8), ("QR_ABI_VERSION", 3)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), code), name
-    rec = _declaration(code, "qr_record_policy")
-    assert [n for _, n in rec] == ["env", "policy", "num_steps", "log_std", "noise_seed", "first_step", "flags", "rec_envs", "rows_dev", "stream"]
-    row = _declaration(code, "qr_record_row_len")
-    assert [n for _, n in row] == ["env"]
-    assert "qr_record_policy" in hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]     # the "additive since 3" comment names it
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    for name, decl in (("qr_record_policy", rec), ("qr_record_row_len", row)):
-        assert hasattr(L, name), "libquadrace.so does not export %s" % name
-        rt, at = _lib.SIGNATURES[name]
-        assert rt is C.c_int and len(at) == len(decl)
-        assert [_CTYPE[t] for t, _ in decl] == list(at), (name, decl, at)
-        assert name in _lib.OPTIONAL_SYMBOLS
-    assert _lib.load().qr_abi_version() == 3
-    assert L.qr_record_row_len(None) == _lib.QR_E_INVALID                                  # a NULL handle is refused, not dereferenced
-
-
-def test_a_library_without_the_recorder_is_reported_by_symbol_name():
-    from optimal_quad_control_rl_amd import _lib
-
-    class Old:   # a library built from older sources: no such attribute
-        pass
-
-    with pytest.raises(_lib.QuadraceError, match="qr_record_policy"):
-        _lib.require(Old(), "qr_record_policy")
-    assert _lib.require(_lib.load(), "qr_record_policy") is not None
 
 
 def test_package_exports_the_recorder_lazily():

@@ -1,52 +1,16 @@
-"""CPU: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions) exists at every layer (header,
-library, ctypes table, build, package) without an ABI bump; plan_condition_groups is a pure function checked on hand-made sizes; the
+"""CPU: the closed-loop rollout across a mix of flight conditions in the package (qr_rollout_policy_conditions itself is pinned in
+tests/abi_table.py); plan_condition_groups is a pure function checked on hand-made sizes; the
 --train-scales / --train-tracks arguments of tools/train_ppo.py expand to the expected conditions on a stub env."""
-import ctypes as C
 import importlib.util
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 
+from abi_decl import stub_env
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-NAME = "qr_rollout_policy_conditions"
-ARGS = ["env", "policy", "conditions", "num_groups", "envs_per_group", "condition_of_group", "num_steps", "log_std", "noise_seed", "first_step",
-        "flags", "obs_out_dev", "act_out_dev", "logp_out_dev", "rew_out_dev", "done_out_dev", "trunc_out_dev", "last_obs_dev", "stream"]
-
-
-def _declared_args(code, name):
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-    assert m, "include/quadrace.h does not declare %s" % name
-    return [a.strip().split()[-1].lstrip("*") for a in m.group(1).split(",")]
-
-
-def test_entry_point_is_declared_exported_and_listed():
-    from optimal_quad_control_rl_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "quadrace.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"#define\s+QR_ABI_VERSION\s+3\b", code)
-    assert _declared_args(code, NAME) == ARGS
-    # the tail of the argument list is qr_rollout_policy's, in its order
-    assert _declared_args(code, NAME)[6:10] == _declared_args(code, "qr_rollout_policy")[2:6]
-    assert _declared_args(code, NAME)[11:] == _declared_args(code, "qr_rollout_policy")[7:]
-    assert NAME in hdr.split("#define QR_ABI_VERSION")[1].split("*/")[0]          # the version comment names it
-    contract = hdr.split("int " + NAME)[0].rsplit("/*", 1)[1]
-    assert "CONTRACT" in contract and "bit for bit" in contract and "COROLLARY" in contract
-    build.build_native()
-    L = C.CDLL(build.LIB)
-    assert hasattr(L, NAME), "libquadrace.so does not export %s" % NAME
-    rt, at = _lib.SIGNATURES[NAME]
-    assert rt is C.c_int and len(at) == len(ARGS)
-    assert at[5] == C.POINTER(C.c_int32) and at[8] is C.c_uint64 and at[9] is C.c_uint64
-    assert NAME in _lib.OPTIONAL_SYMBOLS
-    assert _lib.load().qr_abi_version() == 3
-    assert "quadrace_rollout_cond.hip" in build.SOURCES          # a translation unit of its own, through the same rewrite and lint
-    assert os.path.exists(os.path.join(build.CSRC, "quadrace_rollout_cond.hip"))
-
 
 def test_package_surface():
     import optimal_quad_control_rl_amd as pkg
@@ -124,9 +88,8 @@ def _stub_env(variant=0):
     from optimal_quad_control_rl_amd import square_track
 
     gp, gy, sp = square_track()
-    return types.SimpleNamespace(VARIANT=variant, gate_pos=np.asarray(gp, np.float32), gate_yaw=np.asarray(gy, np.float32), num_gates=len(gy),
-                                 start_pos=np.asarray(sp, np.float32), disturbance_ranges=np.array([[-0.03, 0.03]] * 6), disturbance_scale=1,
-                                 max_steps=1200)
+    return stub_env(0, VARIANT=variant, gate_pos=np.asarray(gp, np.float32), gate_yaw=np.asarray(gy, np.float32), num_gates=len(gy),
+                    start_pos=np.asarray(sp, np.float32), disturbance_ranges=np.array([[-0.03, 0.03]] * 6), disturbance_scale=1, max_steps=1200)
 
 
 def _tool():
