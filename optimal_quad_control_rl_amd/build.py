@@ -18,7 +18,7 @@ SOURCES = ["quadrace_kernels.hip", "quadrace_kernels_mlp.hip", "quadrace_abi.hip
            "quadrace_rollout_cond.hip", "quadrace_blackbox.hip", "quadrace_rollout_population.hip", "quadrace_ppo_population.hip",
            "quadrace_population_prepare.hip"]
 HEADERS = ["quadrace_device.hpp", "quadrace_policy.hpp", "quadrace_env_kernels.hpp", "quadrace_eval_body.hpp", "quadrace_launch.hpp", "quadrace_ppo_device.hpp",
-           "quadrace_rollout_group.hpp", "quadrace_host.hpp", os.path.join("..", "..", "include", "quadrace.h"), os.path.join("..", "..", "include", "quad3d.h")]
+           "quadrace_rollout_group.hpp", "quadrace_record_tiles.hpp", "quadrace_host.hpp", os.path.join("..", "..", "include", "quadrace.h"), os.path.join("..", "..", "include", "quad3d.h")]
 # quadrace_kernels_mlp.hip = the launcher, and with it the instantiations, of the two fused E2E + residual-MLP rollout kernels: compiled
 # without the SLP vectoriser (reasons and measurements at the top of that file); every other kernel keeps it
 # (quadrace_rollout_cond.hip and quadrace_rollout_population.hip inline the same residual-MLP step but take the flags of quadrace_kernels.hip, where their twin

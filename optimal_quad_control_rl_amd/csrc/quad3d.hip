@@ -656,8 +656,8 @@ q3_rollout_policy_kernel(Q3Params P, Q3Buffers<T> B, qr::PolicyArgs A, int K, fl
             stream_store(act_out + (size_t)k * n + i, make_float4(a[0], a[1], a[2], a[3]));
             stream_store(logp_out + (size_t)k * n + i, logp);
         }
-        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
-                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(a, u);
         bool done, trunc;
         const T reward = q3_step_env(P, ii, e, u, done, trunc, [&]() {
             if (term_obs == nullptr || !active) return;   // the final state of the episode, before the auto-reset replaces it
@@ -750,8 +750,8 @@ __device__ __forceinline__ void q3_eval_body(const Q3Params& P, const qr::half8*
         } else {
             policy_forward<L>(W, lane, o, mean);
         }
-        const float u[4] = {fminf(fmaxf(mean[0], -1.0f), 1.0f), fminf(fmaxf(mean[1], -1.0f), 1.0f),
-                            fminf(fmaxf(mean[2], -1.0f), 1.0f), fminf(fmaxf(mean[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(mean, u);
         const int target_before = e.target;
         bool pre_ground = false, pre_oob = false;
         if constexpr (kGates) {                 // the reference tests the PRE-step state for these two

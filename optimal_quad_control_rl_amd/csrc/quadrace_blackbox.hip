@@ -4,9 +4,9 @@
 // recorder's.  What an env looked like in the seconds before it crashed is then in the ring, oldest to newest ending at the trigger row,
 // together with the terminal world state (after the integration, before the auto-reset) and the cause of the end.
 //
-// The step loop RESTATES record_policy_kernel's, statement for statement, the way quadrace_rollout_cond.hip restates its twin: that
-// kernel's matrix-instruction schedule is pinned and its code object must not move when this unit is added (tools/isa_digest.py), so
-// quadrace_record.hip is left untouched and its three tile helpers are restated below.  Policy forward, noise slices, clip, step_env
+// The step loop RESTATES record_policy_kernel's, statement for statement, the way quadrace_rollout_group.hpp restates the rollout
+// kernel's: that kernel's matrix-instruction schedule is pinned, and a body shared with it moves its code.  The three
+// tile helpers are not restated: both units take them from quadrace_record_tiles.hpp.  Policy forward, noise slices, clip, step_env
 // with reset_from_stash, observe, the end-of-kernel write-back and the row layout R = S + QR_RECORD_EXTRA are the recorder's: the env
 // state after the call is bit-identical to qr_record_policy / qr_rollout_policy, whatever trigger, window and rec_envs are.
 //
@@ -26,56 +26,11 @@
 //     the end, so a call can be continued (consecutive first_step, same window, same buffers).
 #include "quadrace_env_kernels.hpp"
 #include "quadrace_launch.hpp"
+#include "quadrace_record_tiles.hpp"
 
 namespace qr {
 
 static_assert(QR_RECORD_EXTRA == 8 && QR_BLACKBOX_ST_INTS == 4, "row and status layout of include/quadrace.h");
-
-// the recorder's tile helpers (quadrace_record.hip, which explains the LDS traffic): columns [C0, C0 + NV) of this lane's tile row
-template <int R, int C0, int NV>
-__device__ __forceinline__ void bb_tile_write(float* __restrict__ row, const float (&v)[NV]) {
-    if constexpr (R % 4 == 0 && C0 % 4 == 0 && NV % 4 == 0) {
-        float4* r4 = reinterpret_cast<float4*>(row + C0);
-#pragma unroll
-        for (int q = 0; q < NV / 4; ++q) r4[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) row[C0 + q] = v[q];   // odd row stride: conflict-free ds_write_b32
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// the wave's 64 finished rows -> block[0 .. 64 R): every round with the whole wave, the last, partial round clamps its index
-template <int R>
-__device__ __forceinline__ void bb_tile_flush(const float* __restrict__ tile, float* __restrict__ block, int lane) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    constexpr int kVec = 16 * R;
-    const float4* t4 = reinterpret_cast<const float4*>(tile);
-    float4* g4 = reinterpret_cast<float4*>(block);
-#pragma unroll
-    for (int t = 0; t < (kVec + 63) / 64; ++t) {
-        const int e = t * 64 + lane;
-        const int ec = (t + 1) * 64 <= kVec || e < kVec ? e : kVec - 1;
-        stream_store(g4 + ec, t4[ec]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// one lane's own row: tile row -> dst[0 .. R)
-template <int R>
-__device__ __forceinline__ void bb_row_flush(const float* __restrict__ row, float* __restrict__ dst) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (R % 4 == 0) {   // rows of 96 bytes in a 16-byte aligned buffer
-#pragma unroll
-        for (int q = 0; q < R / 4; ++q) stream_store(reinterpret_cast<float4*>(dst) + q, reinterpret_cast<const float4*>(row)[q]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < R; ++q) stream_store(dst + q, row[q]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
 
 enum : int { kFlushNone = 0, kFlushBlock = 1, kFlushLanes = 2 };
 
@@ -133,7 +88,7 @@ blackbox_policy_kernel(Params P, PolicyArgs A, int K, int M, int trigger, int wi
     observe<V, GA>(P, gates, e, o);
     for (int k = 0; k < K; ++k) {
         // a lane-masked store block stays outside the forward's pinned schedule: the rows of step k - 1 of a wave without a block
-        if (flush_prev == kFlushLanes && was_armed) bb_row_flush<R>(trow, ring + (size_t)slot * slot_floats + row_off);
+        if (flush_prev == kFlushLanes && was_armed) rec_row_flush<R>(trow, ring + (size_t)slot * slot_floats + row_off);
         // ---- action noise: rollout_policy_kernel's slices, verbatim (drawn in deterministic mode too and then multiplied out)
         float mean[4];
         float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -172,8 +127,8 @@ blackbox_policy_kernel(Params P, PolicyArgs A, int K, int M, int trigger, int wi
         // world columns of step k into the tile (LDS operations of one wave execute in order: the flush's reads come first).  Both
         // conditions are scalars.
         auto rec_slice = [&](int rs) {
-            if (rs == 0 && flush_prev == kFlushBlock) bb_tile_flush<R>(tile, ring + (size_t)slot * slot_floats + block_off, lane);
-            if (rs == 2 && live) bb_tile_write<R, 0, S>(trow, e.s);
+            if (rs == 0 && flush_prev == kFlushBlock) rec_tile_flush<R>(tile, ring + (size_t)slot * slot_floats + block_off, lane);
+            if (rs == 2 && live) rec_tile_write<R, 0, S>(trow, e.s);
         };
         if constexpr (kF32) {
 #pragma unroll
@@ -191,8 +146,8 @@ blackbox_policy_kernel(Params P, PolicyArgs A, int K, int M, int trigger, int wi
             const float en = A.deterministic ? 0.0f : eps[c];   // fmaf(std, 0, mean) = mean
             a[c] = fmaf(A.std[c], en, mean[c]);
         }
-        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
-                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(a, u);
         const int target_before = e.target, steps_before = e.steps;
         bool done, trunc, did_reset;
         bool hit = false;
@@ -216,7 +171,7 @@ blackbox_policy_kernel(Params P, PolicyArgs A, int K, int M, int trigger, int wi
         any_reset |= did_reset;
         if (live) {
             const float tail[8] = {u[0], u[1], u[2], u[3], reward, done ? (trunc ? 2.0f : 1.0f) : 0.0f, (float)target_before, (float)steps_before};
-            bb_tile_write<R, S, 8>(trow, tail);
+            rec_tile_write<R, S, 8>(trow, tail);
         }
         // the row of this step is stored iff the lane was armed at its start; how it leaves is decided for the whole wave
         was_armed = armed;
@@ -228,8 +183,8 @@ blackbox_policy_kernel(Params P, PolicyArgs A, int K, int M, int trigger, int wi
         observe<V, GA>(P, gates, e, o);
     }
     // the rows of the last step
-    if (flush_prev == kFlushBlock) bb_tile_flush<R>(tile, ring + (size_t)slot * slot_floats + block_off, lane);
-    else if (flush_prev == kFlushLanes && was_armed) bb_row_flush<R>(trow, ring + (size_t)slot * slot_floats + row_off);
+    if (flush_prev == kFlushBlock) rec_tile_flush<R>(tile, ring + (size_t)slot * slot_floats + block_off, lane);
+    else if (flush_prev == kFlushLanes && was_armed) rec_row_flush<R>(trow, ring + (size_t)slot * slot_floats + row_off);
     if (!active) return;
     if (rec_env) st[i] = status;
     define_exit_values<V>(e);

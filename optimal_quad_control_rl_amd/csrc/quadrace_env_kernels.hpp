@@ -865,8 +865,8 @@ rollout_policy_kernel(Params P, PolicyArgs A, int K, float* __restrict__ obs_out
             stream_store(logp_out + (size_t)k * n + i, logp);
         }
         QR_TICK(P, 11);
-        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
-                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(a, u);
         bool done, trunc, did_reset;
         const float reward = step_env<V>(P, gates, rtab, tile, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc,
                                          did_reset, [&](bool fin) {

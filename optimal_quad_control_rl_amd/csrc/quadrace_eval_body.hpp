@@ -96,8 +96,8 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
         float mean[4];
         if constexpr (kF32) policy_forward_f32class<L>(W, img_lo, lane, o, mean);
         else policy_forward<L>(W, lane, o, mean);
-        const float u[4] = {fminf(fmaxf(mean[0], -1.0f), 1.0f), fminf(fmaxf(mean[1], -1.0f), 1.0f),
-                            fminf(fmaxf(mean[2], -1.0f), 1.0f), fminf(fmaxf(mean[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(mean, u);
         const int target_before = e.target;
         bool done, trunc, did_reset;
         const float reward = step_env<V>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,

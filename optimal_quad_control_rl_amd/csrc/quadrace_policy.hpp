@@ -307,4 +307,10 @@ struct PolicyArgs {
     int deterministic;          // 1: action = mean (no noise)
 };
 
+// what the env receives from a closed-loop kernel: the action clipped to the Box [-1, 1] (what SB3 does, R:785)
+__device__ __forceinline__ void clip_action(const float (&a)[4], float (&u)[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) u[c] = fminf(fmaxf(a[c], -1.0f), 1.0f);
+}
+
 }  // namespace qr

@@ -6,7 +6,8 @@
 //
 // Noise draws, env arithmetic, reset stream and the end-of-kernel state write-back are rollout_policy_kernel's, statement for statement
 // (tests/test_gpu_record.py demands bit equality with it); what that kernel stores (observation, unclipped action, log-prob, reward, done,
-// trunc, terminal observations: six streams) is not stored here, and the log-prob is not computed.
+// trunc, terminal observations: six streams) is not stored here, and the log-prob is not computed.  The three tile helpers are in
+// quadrace_record_tiles.hpp, which the black box includes too.
 //
 // Write shape: the rows [k][wave_first .. wave_first + 64) of a full wave are one contiguous block of 64 R floats.  Each lane assembles its
 // row in a wave-private LDS tile (the pre-step world columns go there BEFORE the step, so that no copy of the state is held in registers
@@ -19,57 +20,11 @@
 //   The flush reads the tile linearly (ds_read_b128, consecutive lanes on consecutive 16-byte slots: conflict-free).
 #include "quadrace_env_kernels.hpp"
 #include "quadrace_launch.hpp"
+#include "quadrace_record_tiles.hpp"
 
 namespace qr {
 
 static_assert(QR_RECORD_EXTRA == 8, "row layout of include/quadrace.h");
-
-// columns [C0, C0 + NV) of this lane's tile row
-template <int R, int C0, int NV>
-__device__ __forceinline__ void rec_tile_write(float* __restrict__ row, const float (&v)[NV]) {
-    if constexpr (R % 4 == 0 && C0 % 4 == 0 && NV % 4 == 0) {
-        float4* r4 = reinterpret_cast<float4*>(row + C0);
-#pragma unroll
-        for (int q = 0; q < NV / 4; ++q) r4[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) row[C0 + q] = v[q];   // odd row stride: conflict-free ds_write_b32
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// the wave's 64 finished rows -> block[0 .. 64 R): every round with the whole wave (see obs_tile_flush on why the last, partial round
-// clamps its index instead of masking lanes off)
-template <int R>
-__device__ __forceinline__ void rec_tile_flush(const float* __restrict__ tile, float* __restrict__ block, int lane) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    constexpr int kVec = 16 * R;
-    const float4* t4 = reinterpret_cast<const float4*>(tile);
-    float4* g4 = reinterpret_cast<float4*>(block);
-#pragma unroll
-    for (int t = 0; t < (kVec + 63) / 64; ++t) {
-        const int e = t * 64 + lane;
-        const int ec = (t + 1) * 64 <= kVec || e < kVec ? e : kVec - 1;
-        stream_store(g4 + ec, t4[ec]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// one lane's own row (ragged tail wave, a wave cut by rec_envs, a block that is not 16-byte aligned): tile row -> dst[0 .. R)
-template <int R>
-__device__ __forceinline__ void rec_row_flush(const float* __restrict__ row, float* __restrict__ dst) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (R % 4 == 0) {   // rows of 96 bytes in a 16-byte aligned buffer
-#pragma unroll
-        for (int q = 0; q < R / 4; ++q) stream_store(reinterpret_cast<float4*>(dst) + q, reinterpret_cast<const float4*>(row)[q]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < R; ++q) stream_store(dst + q, row[q]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
 
 template <int V, int GA, bool kF32>
 __global__ void __launch_bounds__(kBlock, 1)
@@ -173,8 +128,8 @@ record_policy_kernel(Params P, PolicyArgs A, int K, int M, float* __restrict__ r
             const float en = A.deterministic ? 0.0f : eps[c];   // fmaf(std, 0, mean) = mean
             a[c] = fmaf(A.std[c], en, mean[c]);
         }
-        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
-                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(a, u);
         const int target_before = e.target, steps_before = e.steps;
         bool done, trunc, did_reset;
         const float reward = step_env<V>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,

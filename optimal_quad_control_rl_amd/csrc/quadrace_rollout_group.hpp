@@ -180,8 +180,8 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         // rollout buffer row t: the observation the action was computed from (stored above), the unclipped action, its log-prob
         stream_store(act_out + (size_t)k * n + i, make_float4(a[0], a[1], a[2], a[3]));
         stream_store(logp_out + (size_t)k * n + i, logp);
-        const float u[4] = {fminf(fmaxf(a[0], -1.0f), 1.0f), fminf(fmaxf(a[1], -1.0f), 1.0f),
-                            fminf(fmaxf(a[2], -1.0f), 1.0f), fminf(fmaxf(a[3], -1.0f), 1.0f)};
+        float u[4];
+        clip_action(a, u);
         bool done, trunc, did_reset;
         const float reward = step_env<V>(P, gates, rtab, tile, mlp, lane, true, e, u, gid_lo, gid_hi, done, trunc, did_reset,
                                          [&](bool fin) { store_terminal_obs<V, GA>(P, gates, e, (size_t)k * n, i, fin); },
