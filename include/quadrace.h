@@ -56,7 +56,7 @@ extern "C" {
                              qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14),
                              qr_ppo_population_create / _destroy / _epoch / _status (round 15),
                              qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16),
-                             qr_ppo_population_exploit (round 18) */
+                             qr_ppo_population_exploit (round 18), qr_es_* (round 19) */
 
 enum {
     QR_OK = 0,
@@ -669,6 +669,72 @@ int qr_ppo_population_prepare(qr_ppo_population* pop, const qr_ppo_prepare_share
  * it writes); a non-finite entry of log_std_shift; and a `stream` that is being captured by the caller. */
 int qr_ppo_population_exploit(qr_ppo_population* pop, float* const* theta_dev, float* const* adam_m_dev, float* const* adam_v_dev,
                               const int32_t* src_of, const float* log_std_shift, void* stream);
+
+/* ---- evolution strategies on the policy bank: optimise what the evaluator measures (csrc/quadrace_es.hip) --------------------------------
+ * What it replaces: nothing in the reference -- its user trains on the shaped reward and then MEASURES lap time and crash rate.  The
+ * integers qr_evaluate_policy_bank counts are not differentiable; ES climbs them directly.  One generation is P = 2 num_pairs antithetic
+ * members of ONE actor parameter vector in bank slots, flown by qr_evaluate_policy_bank on common random numbers (its group-local reset
+ * stream), scored, and turned into an update -- a fixed number of launches whatever P is.  1 <= num_pairs <= 128 is a DELIBERATE limit:
+ * P = 256 is the pointer table of the one bank-load launch, and 256 policies x 256 envs is the 65 536-env launch the evaluators are tuned for.
+ * PARAMETER VECTOR: the actor block only, pi: w1 b1 w2 b2 w3 b3 w4 b4 in torch Linear layout, n = qr_es_num_params = 120 L + 29 644
+ * floats (a multiple of 4 for every L) -- layout and offset of the first n floats of a qr_ppo parameter vector, so theta_dev may point
+ * into a trainer's own vector.  obs_len: what qr_policy_bank_create accepts.
+ * THE NOISE (one device function, used by all three kernels): parameters 4q .. 4q + 3 of pair i in generation g come from ONE
+ * Philox4x32-10 block x = Philox(counter = (q, i, g lo, g hi), key = (seed lo ^ 0x2545F491, seed hi ^ 0x4F6CDD1D)).  The two tweak
+ * constants differ from the reset stream's key (the env seed itself) and from the action noise's 0x9E3779B9 / 0x85EBCA6B, so the three
+ * streams never share bits.  Uniforms and Box-Muller are the action noise's: u1 = ((x >> 8) + 1) 2^-24, u2 = (x >> 8) 2^-24,
+ * r = fast_sqrt(-2 __logf(u1)), (sin, cos) = qr_sincos(6.283185307179586f * u2); (x0, x1) -> eps[4q] = r cos, eps[4q + 1] = r sin,
+ * (x2, x3) -> eps[4q + 2], eps[4q + 3].  Member 2i is theta[j] + (sigma * eps_ij), member 2i + 1 is theta[j] - (sigma * eps_ij): the
+ * product and the sum are two separately rounded float32 operations.
+ * qr_es_noise: a diagnostic that is also the hook of this spec: eps_dev [num_pairs][n] receives the raw eps.  ONE launch.
+ * qr_es_perturb: TWO launches.  theta_pop [P][n] is written (to theta_pop_dev when given, else to scratch the handle owns), then slot
+ * first_slot + p of `bank` receives BOTH images of member p, packed by the kernel of qr_ppo_population_load_bank with its table pointed at
+ * the rows of theta_pop.  CONTRACT: the slot is bit for bit what qr_policy_bank_set writes when handed member p's float32 parameters --
+ * the f16 image (inf beyond the f16 range) and the low pieces f16(w - f16(clamp w)), saturated, 0 for a NaN weight.  The slots are marked
+ * as set.  No host packing, no copy, no synchronisation.
+ * qr_es_fitness: ONE launch, one workgroup per policy.  Policy p owns rows [p E, (p + 1) E), E = envs_per_policy, of records laid out as
+ * qr_evaluate_policy_bank writes them.  summary_dev [P][8] (may be NULL): s0 gate passes, s1 crashes, s2 time-limit ends, s3 lap-1 count,
+ * s4 lap-1 steps, s5 flying-lap count (laps 2..8), s6 flying-lap steps -- int64 sums, hence exact in any order, stored as double -- and
+ * s7 = the sum over the policy's envs of (double)recf[., 1] + (double)recf[., 0] (0 when recf_dev is NULL), added in ONE fixed order:
+ * chunks of 256 envs; inside a chunk a halving tree over x[0..255] (x[t] += x[t + 128], then + 64, ..., + 1, for t below the stride);
+ * the chunks' x[0] added in ascending order to a sum that starts at 0.  The score, in double, in the order written, every multiply and
+ * add rounded on its own:  F_p = (w_gate s0 + w_crash s1 + w_timeout s2 + w_return s7) / E + w_lap * (s5 > 0 ? s6 / s5 : no_lap_steps).
+ * qr_es_update: ONE launch over n / 4 threads; every thread regenerates its num_pairs noise blocks, nothing of size [pairs][n] is read.
+ * Utilities u_p from fitness_dev [P]: QR_ES_SHAPE_CENTERED_RANK: rank_p = #{q : F_q < F_p} + #{q < p : F_q == F_p}, where a NaN score
+ * ranks below everything and NaNs among themselves by index (ranks by counting: a permutation of 0 .. P - 1),
+ * u_p = (float)rank_p / (float)(P - 1) - 0.5f;  QR_ES_SHAPE_NONE: u_p = (float)F_p.  util_dev [P] (may be NULL) receives u.
+ * Per pair d_i = u_{2i} - u_{2i+1}; per parameter j, all in float32 and each operation rounded on its own:
+ *   g = 0; for i ascending: g = g + d_i * eps_ij;   g = g * (1.0f / ((float)P * sigma));   g = g - weight_decay * theta[j];
+ *   m = beta1 * m + (1.0f - beta1) * g;   v = beta2 * v + ((1.0f - beta2) * g) * g;
+ *   theta = theta + div_rn(lr * (m * c1), sqrt_rn(v * c2) + eps)                                                        (Adam ASCENT)
+ * where div_rn and sqrt_rn are the correctly rounded (IEEE round-to-nearest) float32 quotient and square root -- __fdiv_rn and sqrtf in
+ * the kernel; not the __fsqrt_rn of the HIP headers, which expands to the native 1-ulp instruction -- and the bias corrections c1 = 1 / (1 - beta1^t), c2 = 1 / (1 - beta2^t), t = adam_step >= 1 counted by the caller, computed on the
+ * host in double from the float32 betas and passed as float.  CONTRACT: theta, m, v and u end bit for bit where a NumPy float32
+ * restatement of these lines, fed with qr_es_noise's eps, leaves them.
+ * Plain launches on `stream`: no graph, no atomic, no flag, no workgroup that waits for another, no host read.
+ * Refused before anything is launched (QR_E_INVALID, qr_last_error set, all buffers and the bank untouched): a NULL handle or required
+ * pointer; num_pairs outside 1..128; an obs_len the bank does not accept; sigma not finite or <= 0; lr negative or NaN; adam_step < 1;
+ * an unknown shaping; envs_per_policy < 256 or not a multiple of 256; a bank whose obs_len or device differs from the handle's;
+ * first_slot < 0 or first_slot + P > capacity; a rec_dev, eps_dev, theta, moment or theta_pop pointer that is not 16-byte aligned.
+ * QR_E_NO_DEVICE from qr_es_create where no gfx950 is visible (no CPU fallback). */
+typedef struct qr_es qr_es;
+enum { QR_ES_SHAPE_CENTERED_RANK = 0, QR_ES_SHAPE_NONE = 1 };
+typedef struct {
+    double w_gate, w_crash, w_timeout, w_return, w_lap;   /* weights of s0, s1, s2, s7 (per env) and of the mean flying-lap steps */
+    double no_lap_steps;                                   /* stands for the mean flying-lap steps of a policy without a flying lap */
+    int32_t reserved[2];                                   /* 0 */
+} qr_es_fitness_weights;
+int qr_es_create(int32_t obs_len, int32_t device, int32_t num_pairs, qr_es** out);
+int qr_es_destroy(qr_es* es);
+int qr_es_num_params(const qr_es* es);
+int qr_es_noise(qr_es* es, uint64_t seed, uint64_t generation, float* eps_dev, void* stream);
+int qr_es_perturb(qr_es* es, const float* theta_dev, float sigma, uint64_t seed, uint64_t generation, qr_policy_bank* bank,
+                  int32_t first_slot, float* theta_pop_dev, void* stream);
+int qr_es_fitness(qr_es* es, const int32_t* rec_dev, const float* recf_dev, int32_t envs_per_policy, const qr_es_fitness_weights* w,
+                  double* summary_dev, double* fitness_dev, void* stream);
+int qr_es_update(qr_es* es, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const double* fitness_dev, float sigma, uint64_t seed,
+                 uint64_t generation, int32_t shaping, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t adam_step,
+                 float* util_dev, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -10,7 +10,7 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
-           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT"]
+           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -54,6 +54,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import population
 
         return getattr(population, name)
+    if name == "EvolutionStrategy":  # evolution strategies on the policy bank: optimise measured lap time and crash rate (qr_es_*)
+        from . import es
+
+        return es.EvolutionStrategy
     if name == "ShardedRaceEnv":
         from . import sharded
 

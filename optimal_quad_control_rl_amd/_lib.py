@@ -40,6 +40,13 @@ class QrPpoPrepareMember(C.Structure):
                 [(n, _vp) for n in ("obs", "act", "old_logp", "rew", "done", "val", "term_val", "last_val", "adv", "ret", "ep_ret", "ep_len", "ep_gates")])
 
 
+class QrEsFitnessWeights(C.Structure):
+    """qr_es_fitness_weights of include/quadrace.h: the weights of qr_es_fitness's score (passed by reference)."""
+    _fields_ = [(n, C.c_double) for n in ("w_gate", "w_crash", "w_timeout", "w_return", "w_lap", "no_lap_steps")] + [("reserved", C.c_int32 * 2)]
+
+
+QR_ES_SHAPE_CENTERED_RANK, QR_ES_SHAPE_NONE = 0, 1
+
 # name -> (restype, argtypes); must list every symbol of include/quadrace.h and include/quad3d.h, each bound compatibly with its
 # declaration: tests/test_abi_host.py::test_every_declared_function_is_bound_compatibly holds every row against the headers
 SIGNATURES = {
@@ -125,6 +132,13 @@ SIGNATURES = {
     "qr_policy_bank_read": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t]),
     "qr_ppo_population_prepare": (C.c_int, [_vp, C.POINTER(QrPpoPrepareShared), C.POINTER(QrPpoPrepareMember), C.POINTER(C.c_double), _vp]),
     "qr_ppo_population_exploit": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _f32p, _vp]),
+    "qr_es_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
+    "qr_es_destroy": (C.c_int, [_vp]),
+    "qr_es_num_params": (C.c_int, [_vp]),
+    "qr_es_noise": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "qr_es_perturb": (C.c_int, [_vp, _vp, C.c_float, C.c_uint64, C.c_uint64, _vp, C.c_int32, _vp, _vp]),
+    "qr_es_fitness": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),   # w: byref(QrEsFitnessWeights)
+    "qr_es_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_float, C.c_uint64, C.c_uint64, C.c_int32] + [C.c_float] * 5 + [C.c_int32, _vp, _vp]),
     # include/quad3d.h (predecessor environments of "3D quad.ipynb")
     "q3_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)]),
     "q3_destroy": (C.c_int, [_vp]),
@@ -155,7 +169,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_rollout_policy_conditions", "qr_blackbox_policy", "q3_evaluate_policy",
                     "q3_evaluate_policy_bank", "qr_rollout_policy_population", "qr_ppo_population_create", "qr_ppo_population_destroy",
                     "qr_ppo_population_epoch", "qr_ppo_population_status", "qr_ppo_population_load_bank", "qr_policy_bank_read",
-                    "qr_ppo_population_prepare", "qr_ppo_population_exploit")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_ppo_population_prepare", "qr_ppo_population_exploit", "qr_es_create", "qr_es_destroy", "qr_es_num_params", "qr_es_noise",
+                    "qr_es_perturb", "qr_es_fitness", "qr_es_update")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

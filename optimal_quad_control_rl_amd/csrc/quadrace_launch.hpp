@@ -208,6 +208,10 @@ half8* bank_weights_mut(qr_policy_bank* b);              // for qr_ppo_populatio
 half8* bank_weights_lo_mut(qr_policy_bank* b);
 void bank_mark_set(qr_policy_bank* b, int first_slot, int count);   // ... and marked as set on the host
 
+// quadrace_population_prepare.hip: the one launch of the bank-load kernel (qr_ppo_population_load_bank, and qr_es_perturb of quadrace_es.hip):
+// slot first_slot + p of (bank, bank_lo) <- both images of the actor block at theta[p], p < P <= 256; a QR_* code, qr_last_error set
+int launch_population_load_bank(int L, const float* const* theta, int P, half8* bank, half8* bank_lo, int first_slot, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------------------
 // what the entry points of quadrace_abi.hip and quad3d.hip refuse about a policy handle or a bank: observation length, then device.
 // `who` names the entry point; a message is built on the failing path only.  `len_rule` completes "policy obs_len " / "bank obs_len ",

@@ -304,6 +304,26 @@ bool finite_host(float v) {
 
 }  // namespace
 
+namespace qr {
+// the ONE launch of population_load_bank_kernel, for qr_ppo_population_load_bank and for qr_es_perturb (quadrace_es.hip), which points the
+// table at the rows of its population matrix: slot first_slot + p <- both images of the actor block at theta[p], p < P <= kPrepMaxMembers.
+// The caller has checked the bank and made its device current.  Returns a QR_* code (qr_last_error set).
+int launch_population_load_bank(int L, const float* const* theta, int P, half8* bank, half8* bank_lo, int first_slot, hipStream_t st) {
+    if (P < 1 || P > kPrepMaxMembers) return set_last_error(QR_E_INVALID, "the bank load takes 1..256 parameter vectors per launch");
+    PrepThetas thetas;
+    std::memset(&thetas, 0, sizeof(thetas));
+    for (int p = 0; p < P; ++p) thetas.v[p] = theta[p];
+    return ::dispatch_L(L, [&](auto Lc) {   // this file's failure message
+        constexpr int kL = decltype(Lc)::value;
+        static_assert(PpoDims<kL>::kImage == PolicyDims<kL>::kTotalHalf8, "the updater's actor image has the layout of a bank slot");
+        hipLaunchKernelGGL(population_load_bank_kernel<kL>, dim3((PolicyDims<kL>::kTotalHalf8 + 255) / 256, P), dim3(256), 0, st, thetas, bank, bank_lo,
+                           first_slot);
+        QR_HIP(hipGetLastError());
+        return (int)QR_OK;
+    });
+}
+}  // namespace qr
+
 extern "C" {
 
 int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* theta_dev, qr_policy_bank* bank, int32_t first_slot, void* stream) {
@@ -316,18 +336,8 @@ int qr_ppo_population_load_bank(qr_ppo_population* pop, const float* const* thet
     if (first_slot < 0 || (long long)first_slot + P > (long long)qr::bank_capacity(bank))
         return qr::set_last_error(QR_E_INVALID, "qr_ppo_population_load_bank: slots [first_slot, first_slot + members) must lie in [0, capacity)");
     QR_HIP(hipSetDevice(qr::population_device(pop)));
-    qr::PrepThetas thetas;
-    std::memset(&thetas, 0, sizeof(thetas));
-    for (int p = 0; p < P; ++p) thetas.v[p] = theta_dev[p];
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = dispatch_L(qr::population_obs_len(pop), [&](auto Lc) {
-        constexpr int L = decltype(Lc)::value;
-        static_assert(qr::PpoDims<L>::kImage == qr::PolicyDims<L>::kTotalHalf8, "the updater's actor image has the layout of a bank slot");
-        hipLaunchKernelGGL(qr::population_load_bank_kernel<L>, dim3((qr::PolicyDims<L>::kTotalHalf8 + 255) / 256, P), dim3(256), 0, st, thetas,
-                           qr::bank_weights_mut(bank), qr::bank_weights_lo_mut(bank), (int)first_slot);
-        QR_HIP(hipGetLastError());
-        return (int)QR_OK;
-    });
+    const int rc = qr::launch_population_load_bank(qr::population_obs_len(pop), theta_dev, P, qr::bank_weights_mut(bank), qr::bank_weights_lo_mut(bank),
+                                                   (int)first_slot, (hipStream_t)stream);
     if (rc != QR_OK) return rc;
     qr::bank_mark_set(bank, first_slot, P);
     return QR_OK;
