@@ -56,7 +56,8 @@ extern "C" {
                              qr_blackbox_policy (round 13), qr_rollout_policy_population (round 14),
                              qr_ppo_population_create / _destroy / _epoch / _status (round 15),
                              qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16),
-                             qr_ppo_population_exploit (round 18), qr_es_* (round 19) */
+                             qr_ppo_population_exploit (round 18), qr_es_* (round 19),
+                             qr_dynamics_* / qr_evaluate_policy_dynamics_grid (round 20) */
 
 enum {
     QR_OK = 0,
@@ -324,6 +325,82 @@ int qr_condition_bank_set(qr_condition_bank* bank, int32_t slot, const float* ga
 int qr_evaluate_policy_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, int32_t num_groups,
                             int32_t envs_per_group, const int32_t* policy_of_group, const int32_t* condition_of_group,
                             int32_t num_steps, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Evaluation of a grid of policies x flight conditions x VEHICLES in one launch: "which parameter error breaks this policy first, and by
+ * how much may the real vehicle differ before lap time or crash rate moves?" (thrust coefficient, drag, motor time constant, inertia, the
+ * INDI rate lags) is one call instead of one edited literal and one rebuild per vehicle.  A constant external disturbance of a condition
+ * does not cover it: a force offset is not a 15 % error of the thrust coefficient.
+ * A vehicle is the coefficient TABLE of the variant's equations of motion, each entry in the form and with the sign in which it enters the
+ * arithmetic (the reference's identified parameters, pre-folded; R = "3D quad race.ipynb", I = "3D quad race INDI inner loop.ipynb").
+ * E2E, 22 entries (W_i = rotor speed in rpm, w_i = normalised speed, u_i = command, vb = body velocity):
+ *    0  motor map gain (w_max - w_min)/2 = 4000                 W_i = [0] w_i + [1]                       R:92-93, 106-109
+ *    1  motor map offset (w_max + w_min)/2 = 7000                                                         R:92-93, 106-109
+ *    2  -k_x                                                    Fx = [2] vbx sum(W) + F_ext_x             R:78, 125
+ *    3  -k_y                                                    Fy = [3] vby sum(W) + F_ext_y             R:79, 126
+ *    4  -k_w                                                    T  = [4] sum(W^2) + F_ext_z               R:81, 124
+ *    5  -k_z                                                         + [5] vbz sum(W)                     R:80, 124
+ *    6  -k_h                                                         + [6] (vbx^2 + vby^2)                R:82, 124
+ *    7  g                                                       v' = R (Fx, Fy, T) + (0, 0, [7])          R:73, 138
+ *    8  1/Ixx                                                   p' = [8] M_ext_x                          R:74, 144
+ *    9  (Iyy - Izz)/Ixx                                              + [9] q r                            R:74-76, 144
+ *   10  k_pv/Ixx                                                     + [10] vby                           R:84, 129, 144
+ *   11  k_p/Ixx                                                      + [11] (W1^2 - W2^2 - W3^2 + W4^2)   R:83, 129, 144
+ *   12  1/Iyy                                                   q' = [12] M_ext_y                         R:75, 145
+ *   13  (Izz - Ixx)/Iyy                                              + [13] p r                           R:74-76, 145
+ *   14  k_qv/Iyy                                                     + [14] vbx                           R:86, 130, 145
+ *   15  k_q/Iyy                                                      + [15] (W1^2 + W2^2 - W3^2 - W4^2)   R:85, 130, 145
+ *   16  1/Izz                                                   r' = [16] M_ext_z                         R:76, 146
+ *   17  (Ixx - Iyy)/Izz                                              + [17] p q                           R:74-76, 146
+ *   18  -k_rr/Izz                                                    + [18] r                             R:89, 131, 146
+ *   19  -k_r2 [0] / (tau Izz)                                        + [19] (u1 - u2 + u3 - u4)           R:88, 91, 117-121, 131, 146
+ *   20  (k_r2/tau - k_r1) [0] / Izz                                  + [20] (w1 - w2 + w3 - w4)           R:87-88, 91, 131, 146
+ *   21  1/tau                                                   w_i' = [21] (u_i - w_i)                   R:91, 112-115
+ * INDI, 12 entries:
+ *    0  -k_x                                                    Dx = [0] vbx                              I:73, 86
+ *    1  -k_y                                                    Dy = [1] vby                              I:74, 87
+ *    2  -(T_max - T_min)/2 = -8                                 -T = [2] T_norm + [3]                     I:69-70, 94
+ *    3  -(T_max + T_min)/2 = -8                                                                           I:69-70, 94
+ *    4  g                                                       v' = R (Dx, Dy, -T) + (0, 0, [4])         I:55, 95
+ *    5, 6   -1/tau_p, p_max/tau_p                               p' = [5] p + [6] p_cmd                    I:58, 63-64, 101
+ *    7, 8   -1/tau_q, q_max/tau_q                               q' = [7] q + [8] q_cmd                    I:59, 65-66, 102
+ *    9, 10  -1/tau_r, r_max/tau_r                               r' = [9] r + [10] r_cmd                   I:60, 67-68, 103
+ *   11  1/tau_T                                                 T_norm' = [11] (T_cmd - T_norm)           I:61, 104
+ * (the INDI table has no constant term in the rate equations: symmetric rate ranges only.)
+ * qr_dynamics_count(variant) = 22 / 12 (QR_E_INVALID for an unknown variant).  qr_dynamics_nominal writes the nominal table -- the very
+ * constexpr arrays every kernel of the library is compiled from -- to `out` [count]; host only, no device needed; count must equal
+ * qr_dynamics_count(variant).  A dynamics bank owns one device array [capacity][32 floats] (a slot is 128 bytes: the table, then zeros);
+ * qr_dynamics_bank_set fills slot `slot` in [0, capacity) from the HOST array coeffs [count], or with the nominal table where coeffs is
+ * NULL, after synchronising the device like the other setters; QR_E_INVALID: NULL bank, slot outside the bank, a count other than the
+ * variant's, a coefficient that is not finite.  qr_dynamics_bank_read copies a slot's table back to the host (QR_E_STATE: slot never set).
+ * qr_evaluate_policy_dynamics_grid is qr_evaluate_policy_grid with the third bank and the third HOST map: group g flies slot
+ * policy_of_group[g] of `policies` under slot condition_of_group[g] of `conditions` as the vehicle in slot dynamics_of_group[g] of
+ * `dynamics`.  A 256-env workgroup loads its 32-float slot once, ahead of the step loop, through uniform-address loads, and keeps the
+ * coefficients in scalar registers: no load of a coefficient inside the loop, no LDS for them.  Everything else -- policy image, condition
+ * image, GROUP-LOCAL RESET STREAM, records, continue-a-call behaviour, the copy of the maps to a device array of the handle -- is
+ * qr_evaluate_policy_grid's.
+ * CONTRACT: (1) a group whose slot holds the nominal table (set from NULL, or from the values qr_dynamics_nominal returns) flies bit for
+ * bit what qr_evaluate_policy_grid flies for the same policy and condition from the same state: records, float records, the env state and
+ * the observation afterwards.  The runtime form performs the floating-point operations of the literal form in the same order, with every
+ * sign in the table.  (2) A group depends on its (policy, condition, dynamics) triple only: the same triple at another group index, or in
+ * other slots of the three banks, flies bit for bit the same from the same group-local state; and K steps in one call equal K calls of one
+ * step through the same record buffers.
+ * NOT modelled: the residual thrust / moment MLPs and the observation are the handle's -- a perturbed vehicle adds the same learned
+ * residual and is observed in the same units; there is no scale on the residual, no actuator delay and no observation noise.
+ * Refused before anything is launched or copied (qr_last_error set, records and state untouched): everything qr_evaluate_policy_grid
+ * refuses, in its order; and next to the condition bank's refusals the dynamics bank's -- QR_E_INVALID: NULL dynamics bank or map, a
+ * dynamics bank of another variant or device, an index outside the bank; QR_E_STATE: a referenced slot that was never set. */
+typedef struct qr_dynamics_bank qr_dynamics_bank;
+int qr_dynamics_count(int32_t variant);
+int qr_dynamics_nominal(int32_t variant, float* out, int32_t count);
+int qr_dynamics_bank_create(int32_t variant, int32_t device, int32_t capacity, qr_dynamics_bank** out);
+int qr_dynamics_bank_destroy(qr_dynamics_bank* bank);
+int qr_dynamics_bank_capacity(const qr_dynamics_bank* bank);
+int qr_dynamics_bank_set(qr_dynamics_bank* bank, int32_t slot, const float* coeffs, int32_t count);
+int qr_dynamics_bank_read(const qr_dynamics_bank* bank, int32_t slot, float* out, int32_t count);
+int qr_evaluate_policy_dynamics_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                     int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                     const int32_t* condition_of_group, const int32_t* dynamics_of_group, int32_t num_steps, int32_t flags,
+                                     int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* Closed-loop rollout across a MIX of flight conditions in one launch: PPO's collect phase (qr_rollout_policy: same policy forward, same
  * action noise, same rows, terminal-observation rows, last_obs and state write-back) with the group map and the condition bank of

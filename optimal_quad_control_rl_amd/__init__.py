@@ -10,7 +10,8 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "default_residual_blob", "ShardedRaceEnv", "Quadcopter3DVec", "Quadcopter3DVecGates", "PPO", "VecMonitor",
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
-           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy"]
+           "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy",
+           "evaluate_dynamics_grid", "DynamicsParams", "DynamicsBank", "physical_sweep"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -26,7 +27,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import sb3
 
         return getattr(sb3, name)
-    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
+    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid", "evaluate_dynamics_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
         from . import evaluation
 
         return getattr(evaluation, name)
@@ -46,6 +47,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import conditions
 
         return getattr(conditions, name)
+    if name in ("DynamicsParams", "DynamicsBank", "physical_sweep"):  # vehicles of the dynamics-grid evaluator (qr_dynamics_*)
+        from . import dynamics
+
+        return getattr(dynamics, name)
     if name == "MfmaPolicyBank":  # a bank of policies for one-launch evaluation (qr_policy_bank_*, qr_evaluate_policy_bank)
         from . import policy
 

@@ -98,6 +98,15 @@ SIGNATURES = {
     "qr_condition_bank_set": (C.c_int, [_vp, C.c_int32, _f32p, _f32p, C.c_int32, _f32p, _f32p, C.c_float, C.c_int32, C.c_int32]),
     "qr_evaluate_policy_grid": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                           _vp, _vp, _vp]),
+    "qr_dynamics_count": (C.c_int, [C.c_int32]),
+    "qr_dynamics_nominal": (C.c_int, [C.c_int32, _f32p, C.c_int32]),
+    "qr_dynamics_bank_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
+    "qr_dynamics_bank_destroy": (C.c_int, [_vp]),
+    "qr_dynamics_bank_capacity": (C.c_int, [_vp]),
+    "qr_dynamics_bank_set": (C.c_int, [_vp, C.c_int32, _f32p, C.c_int32]),
+    "qr_dynamics_bank_read": (C.c_int, [_vp, C.c_int32, _f32p, C.c_int32]),
+    "qr_evaluate_policy_dynamics_grid": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "qr_rollout_policy_conditions": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _f32p, C.c_uint64, C.c_uint64,
                                                C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qr_rollout_policy_population": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _f32p,
@@ -170,7 +179,9 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "q3_evaluate_policy_bank", "qr_rollout_policy_population", "qr_ppo_population_create", "qr_ppo_population_destroy",
                     "qr_ppo_population_epoch", "qr_ppo_population_status", "qr_ppo_population_load_bank", "qr_policy_bank_read",
                     "qr_ppo_population_prepare", "qr_ppo_population_exploit", "qr_es_create", "qr_es_destroy", "qr_es_num_params", "qr_es_noise",
-                    "qr_es_perturb", "qr_es_fitness", "qr_es_update")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_es_perturb", "qr_es_fitness", "qr_es_update", "qr_dynamics_count", "qr_dynamics_nominal", "qr_dynamics_bank_create",
+                    "qr_dynamics_bank_destroy", "qr_dynamics_bank_capacity", "qr_dynamics_bank_set", "qr_dynamics_bank_read",
+                    "qr_evaluate_policy_dynamics_grid")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

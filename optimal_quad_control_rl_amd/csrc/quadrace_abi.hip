@@ -50,6 +50,7 @@ struct qr_env {
     };
     DeviceTable<int2> group_map;                  // qr_evaluate_policy_grid and the two group rollouts: (policy, condition) per group
     DeviceTable<qr::PopulationEntry> pop_table;   // qr_rollout_policy_population: the sampling values per group
+    DeviceTable<int4> dyn_map;                    // qr_evaluate_policy_dynamics_grid: (policy, condition, dynamics, 0) per group
 };
 
 // A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
@@ -59,6 +60,14 @@ struct qr_condition_bank {
     int variant = 0, device = 0, capacity = 0;
     float* d_slots = nullptr;
     std::vector<uint8_t> is_set;   // per slot: qr_condition_bank_set has succeeded
+};
+
+// A bank of vehicles for qr_evaluate_policy_dynamics_grid: [capacity][qr::kDynSlotFloats] floats on the device, slot s = the variant's
+// coefficient table of quadrace_device.hpp followed by zeros.
+struct qr_dynamics_bank {
+    int variant = 0, device = 0, capacity = 0;
+    float* d_slots = nullptr;
+    std::vector<uint8_t> is_set;   // per slot: qr_dynamics_bank_set has succeeded
 };
 
 namespace {
@@ -398,6 +407,7 @@ int qr_destroy(qr_env* e) {
     if (e->d_tables) (void)hipFree(e->d_tables);
     if (e->group_map.d) (void)hipFree(e->group_map.d);
     if (e->pop_table.d) (void)hipFree(e->pop_table.d);
+    if (e->dyn_map.d) (void)hipFree(e->dyn_map.d);
     delete e;
     return QR_OK;
 }
@@ -768,6 +778,127 @@ int qr_evaluate_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_ba
     if (int rc = upload_group_map(e, policy_of_group, condition_of_group, num_groups, st, who)) return rc;
     return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies), conditions->d_slots,
                                        e->group_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, rec_dev, recf_dev, st));
+}
+
+// ---- bank of vehicles (qr_evaluate_policy_dynamics_grid) ----
+int qr_dynamics_count(int32_t variant) {
+    int count = 0;
+    if (!qr::dynamics_nominal(variant, &count)) return fail(QR_E_INVALID, "qr_dynamics_count: unknown variant");
+    return count;
+}
+
+int qr_dynamics_nominal(int32_t variant, float* out, int32_t count) {
+    int n = 0;
+    const float* table = qr::dynamics_nominal(variant, &n);
+    if (!table) return fail(QR_E_INVALID, "qr_dynamics_nominal: unknown variant");
+    if (!out) return fail(QR_E_INVALID, "qr_dynamics_nominal: null output");
+    if (count != n) return fail(QR_E_INVALID, "qr_dynamics_nominal: count must equal qr_dynamics_count(variant)");
+    std::memcpy(out, table, (size_t)n * sizeof(float));
+    return QR_OK;
+}
+
+int qr_dynamics_bank_create(int32_t variant, int32_t device, int32_t capacity, qr_dynamics_bank** out) {
+    if (!out) return fail(QR_E_INVALID, "qr_dynamics_bank_create: null output");
+    *out = nullptr;
+    if (variant != QR_VARIANT_E2E && variant != QR_VARIANT_INDI) return fail(QR_E_INVALID, "qr_dynamics_bank_create: unknown variant");
+    if (capacity < 1) return fail(QR_E_INVALID, "qr_dynamics_bank_create: capacity must be >= 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(QR_E_NO_DEVICE, "qr_dynamics_bank_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(QR_E_INVALID, "qr_dynamics_bank_create: bad device ordinal");
+    QR_HIP(hipSetDevice(device));
+    qr_dynamics_bank* b = new qr_dynamics_bank();
+    b->variant = variant;
+    b->device = device;
+    b->capacity = capacity;
+    b->is_set.assign((size_t)capacity, 0);
+    const size_t bytes = (size_t)capacity * qr::kDynSlotFloats * sizeof(float);
+    if (hipMalloc((void**)&b->d_slots, bytes) != hipSuccess) {
+        delete b;
+        return fail(QR_E_HIP, "qr_dynamics_bank_create: hipMalloc failed");
+    }
+    (void)hipMemset(b->d_slots, 0, bytes);
+    *out = b;
+    return QR_OK;
+}
+
+int qr_dynamics_bank_destroy(qr_dynamics_bank* b) {
+    if (!b) return QR_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    if (b->d_slots) (void)hipFree(b->d_slots);
+    delete b;
+    return QR_OK;
+}
+
+int qr_dynamics_bank_capacity(const qr_dynamics_bank* b) { return b ? b->capacity : fail(QR_E_INVALID, "qr_dynamics_bank_capacity: null bank"); }
+
+int qr_dynamics_bank_set(qr_dynamics_bank* b, int32_t slot, const float* coeffs, int32_t count) {
+    if (!b) return fail(QR_E_INVALID, "qr_dynamics_bank_set: null bank");
+    if (slot < 0 || slot >= b->capacity) return fail(QR_E_INVALID, "qr_dynamics_bank_set: slot must be in [0, capacity)");
+    int n = 0;
+    const float* nominal = qr::dynamics_nominal(b->variant, &n);
+    if (count != n) return fail(QR_E_INVALID, "qr_dynamics_bank_set: count must equal qr_dynamics_count of the bank's variant");
+    const float* src = coeffs ? coeffs : nominal;   // NULL = the nominal vehicle
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(src[k])) return fail(QR_E_INVALID, "qr_dynamics_bank_set: coefficient " + std::to_string(k) + " is not finite");
+    float host[qr::kDynSlotFloats] = {};
+    std::memcpy(host, src, (size_t)n * sizeof(float));
+    QR_HIP(hipSetDevice(b->device));
+    QR_HIP(hipDeviceSynchronize());   // a launch may still read the slot
+    if (hipMemcpy(b->d_slots + (size_t)slot * qr::kDynSlotFloats, host, sizeof(host), hipMemcpyHostToDevice) != hipSuccess) {
+        b->is_set[(size_t)slot] = 0;
+        return fail(QR_E_HIP, "qr_dynamics_bank_set: upload failed");
+    }
+    b->is_set[(size_t)slot] = 1;
+    return QR_OK;
+}
+
+int qr_dynamics_bank_read(const qr_dynamics_bank* b, int32_t slot, float* out, int32_t count) {
+    if (!b) return fail(QR_E_INVALID, "qr_dynamics_bank_read: null bank");
+    if (!out) return fail(QR_E_INVALID, "qr_dynamics_bank_read: null output");
+    if (slot < 0 || slot >= b->capacity) return fail(QR_E_INVALID, "qr_dynamics_bank_read: slot must be in [0, capacity)");
+    int n = 0;
+    (void)qr::dynamics_nominal(b->variant, &n);
+    if (count != n) return fail(QR_E_INVALID, "qr_dynamics_bank_read: count must equal qr_dynamics_count of the bank's variant");
+    if (!b->is_set[(size_t)slot]) return fail(QR_E_STATE, "qr_dynamics_bank_read: slot " + std::to_string(slot) + " of the dynamics bank was never set");
+    QR_HIP(hipSetDevice(b->device));
+    QR_HIP(hipDeviceSynchronize());
+    QR_HIP(hipMemcpy(out, b->d_slots + (size_t)slot * qr::kDynSlotFloats, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return QR_OK;
+}
+
+// qr_evaluate_policy_grid with a third bank and a third map: the same refusals in the same order, the dynamics bank's next to the
+// condition bank's.  Nothing is enqueued or copied unless every argument is valid.
+int qr_evaluate_policy_dynamics_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, int32_t num_groups,
+                                     int32_t envs_per_group, const int32_t* policy_of_group, const int32_t* condition_of_group,
+                                     const int32_t* dynamics_of_group, int32_t K, int32_t flags, int32_t* rec_dev, float* recf_dev, void* stream) {
+    const char* who = "qr_evaluate_policy_dynamics_grid";
+    const std::string w = std::string(who) + ": ";
+    if (int rc = check_ready(e)) return rc;
+    if (!policies) return fail(QR_E_INVALID, w + "null policy bank handle");
+    if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
+    if (!dynamics) return fail(QR_E_INVALID, w + "null dynamics bank handle");
+    if (!policy_of_group || !condition_of_group || !dynamics_of_group) return fail(QR_E_INVALID, w + "the three group maps are required");
+    if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, who)) return rc;
+    if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (dynamics->variant != e->cfg.variant) return fail(QR_E_INVALID, w + "dynamics bank of another variant");
+    if (dynamics->device != e->cfg.device) return fail(QR_E_INVALID, w + "dynamics bank on another GPU");
+    if (int rc = check_group_indices(policies, policy_of_group, conditions, condition_of_group, num_groups, who)) return rc;
+    for (int g = 0; g < num_groups; ++g)
+        if (dynamics_of_group[g] < 0 || dynamics_of_group[g] >= dynamics->capacity)
+            return fail(QR_E_INVALID, w + "dynamics_of_group[" + std::to_string(g) + "] is outside the dynamics bank");
+    for (int g = 0; g < num_groups; ++g)
+        if (!dynamics->is_set[(size_t)dynamics_of_group[g]])
+            return fail(QR_E_STATE, w + "slot " + std::to_string(dynamics_of_group[g]) + " of the dynamics bank was never set");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int4> map((size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g) map[(size_t)g] = make_int4(policy_of_group[g], condition_of_group[g], dynamics_of_group[g], 0);
+    if (int rc = upload_table(e->dyn_map, map, st, who, "group map", "this map")) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_dynamics_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
+                                       conditions->d_slots, dynamics->d_slots, e->dyn_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups,
+                                       envs_per_group, K, rec_dev, recf_dev, st));
 }
 
 // The refusals come first and in full, as in qr_evaluate_policy_grid; the map travels in that call's (policy, condition) array with

@@ -827,10 +827,79 @@ __device__ __forceinline__ float fast_sqrt(float x) {
 // -------------------------------------------------------------------------------------------------
 // Equations of motion: ds = f(s, u, d)
 // -------------------------------------------------------------------------------------------------
-// E2E Bebop model (R:57-152; constants pre-folded as in SURVEY Appendix A)
-template <bool kPk = false>
+// The coefficients of both models, named ONCE, in the form and with the sign in which they enter the arithmetic below (the reference's
+// identified parameters R:72-93 / I:58-74, pre-folded as in SURVEY Appendix A).  A kernel takes them either from these tables
+// (NominalDyn: every entry is a literal of the instruction stream, as before the tables existed) or from a per-workgroup register set
+// (RuntimeDyn: quadrace_eval_dynamics.hip loads one slot of a qr_dynamics_bank into scalar registers).  Both forms run the SAME explicit
+// fmaf nesting in the same order, and a sign lives in the table, never in a negation of the source: a RuntimeDyn that holds these values
+// reproduces NominalDyn bit for bit.  The kPk packed forms belong to the one-wave fused rollout and are nominal-only: their packed
+// instructions keep their own literals (eom_e2e refuses kPk with any other source).
+constexpr int kDynE2ECount = 22, kDynINDICount = 12, kDynSlotFloats = 32;   // a bank slot: 128 bytes, entries past the count are zero
+enum : int {   // E2E
+    kEMotorGain = 0, kEMotorOffset,                 // W = gain w + offset: (w_max - w_min) / 2, (w_max + w_min) / 2          R:106-109
+    kENegKx, kENegKy,                               // -k_x, -k_y                                                            R:125-126
+    kENegKw, kENegKz, kENegKh,                      // -k_w, -k_z, -k_h                                                      R:124
+    kEG,                                            // g                                                                     R:138
+    kEPM, kEPQR, kEPVby, kEPW,                      // p': 1/Ixx, (Iyy - Izz)/Ixx, k_pv/Ixx, k_p/Ixx                         R:144,129
+    kEQM, kEQPR, kEQVbx, kEQW,                      // q': 1/Iyy, (Izz - Ixx)/Iyy, k_qv/Iyy, k_q/Iyy                         R:145,130
+    kERM, kERPQ, kERR, kERCmd, kERMotor,            // r': 1/Izz, (Ixx - Iyy)/Izz, -k_rr/Izz, command mix, motor mix         R:146,131
+    kEMotorLag                                      // 1/tau                                                                 R:112-115
+};
+enum : int {   // INDI
+    kINegKx = 0, kINegKy,                           // -k_x, -k_y                                                            I:73-74,86-87
+    kIThrustGain, kIThrustOffset,                   // -T = gain T_norm + offset: -(T_max - T_min)/2 twice (T_min = 0)       I:94
+    kIG,                                            // g                                                                     I:95
+    kIPLag, kIPCmd, kIQLag, kIQCmd, kIRLag, kIRCmd, // -1/tau, max/tau of p, q, r                                            I:101-103
+    kITLag                                          // 1/tau_T                                                               I:104
+};
+constexpr float kDynE2ENominal[kDynE2ECount] = {
+    4000.0f, 7000.0f,
+    -1.07933887e-5f, -9.65250793e-6f,
+    -4.36301076e-8f, -2.7862899e-5f, -0.0625501332f,
+    9.81f,
+    1103.7527593819f, -0.896247240618101f, -8.79803364238411f, 1.55842505518764e-6f,
+    805.152979066023f, 0.924315619967794f, 10.4077084541063f, 9.79081191626409e-7f,
+    486.854917234664f, -0.163583252190847f, -0.395780237098345f, -13.3373373580007f, 8.33177659850698f,
+    16.6666666666667f};
+constexpr float kDynINDINominal[kDynINDICount] = {
+    -0.33915248f, -0.4314916f,
+    -8.0f, -8.0f,
+    9.81f,
+    -33.3333333333333f, 100.0f, -33.3333333333333f, 100.0f, -33.3333333333333f, 66.6666666666667f,
+    33.3333333333333f};
+template <int V>
+constexpr int dyn_count() { return V == kE2E ? kDynE2ECount : kDynINDICount; }
+
+// C::at<I>(arg) = entry I of variant V's table: a compile-time constant here (arg is a dummy: nothing travels through the call chain) ...
+template <int V>
+struct NominalDyn {
+    using Arg = int;
+    template <int I>
+    static __device__ __forceinline__ float at(Arg) {
+        static_assert(I >= 0 && I < dyn_count<V>(), "coefficient index");
+        constexpr float v = (V == kE2E) ? kDynE2ENominal[I < kDynE2ECount ? I : 0] : kDynINDINominal[I < kDynINDICount ? I : 0];
+        return v;
+    }
+};
+// ... and a register there: arg points at the kernel's own set, one value per entry, uniform over the workgroup (the kernel keeps them in
+// scalar registers; everything that takes the pointer is inlined, so no entry ever sits in memory)
+template <int V>
+struct RuntimeDyn {
+    using Arg = const RuntimeDyn*;
+    float c[dyn_count<V>()];
+    template <int I>
+    static __device__ __forceinline__ float at(Arg d) {
+        static_assert(I >= 0 && I < dyn_count<V>(), "coefficient index");
+        return d->c[I];
+    }
+};
+#define QR_DYN(I) C::template at<I>(dyn)
+
+// E2E Bebop model (R:57-152; coefficients: kDynE2ENominal or the caller's register set)
+template <bool kPk = false, class C = NominalDyn<kE2E>>
 __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const float vb[3], const float u[4],
-                                        const float M[3], const float F[3], float* ds) {
+                                        const float M[3], const float F[3], float* ds, typename C::Arg dyn = typename C::Arg()) {
+    static_assert(!kPk || __is_same(C, NominalDyn<kE2E>), "the packed forms are literal-only");
     const float p = s[9], q = s[10], r = s[11];
     const float w1 = s[12], w2 = s[13], w3 = s[14], w4 = s[15];
     float W1, W2, W3, W4, S, W1s, W2s, W3s, W4s;
@@ -841,16 +910,17 @@ __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const floa
         S = (W1 + W2) + (W3 + W4);
         W1s = Q12.x; W2s = Q12.y; W3s = Q34.x; W4s = Q34.y;
     } else {
-        W1 = fmaf(4000.0f, w1, 7000.0f); W2 = fmaf(4000.0f, w2, 7000.0f);   // R:106-109
-        W3 = fmaf(4000.0f, w3, 7000.0f); W4 = fmaf(4000.0f, w4, 7000.0f);
+        const float gain = QR_DYN(kEMotorGain), offset = QR_DYN(kEMotorOffset);
+        W1 = fmaf(gain, w1, offset); W2 = fmaf(gain, w2, offset);                     // R:106-109
+        W3 = fmaf(gain, w3, offset); W4 = fmaf(gain, w4, offset);
         S = (W1 + W2) + (W3 + W4);
         W1s = W1 * W1; W2s = W2 * W2; W3s = W3 * W3; W4s = W4 * W4;
     }
-    const float Fx = fmaf(-1.07933887e-5f * vb[0], S, F[0]);                          // R:125
-    const float Fy = fmaf(-9.65250793e-6f * vb[1], S, F[1]);                          // R:126
-    float T = fmaf(-4.36301076e-8f, (W1s + W2s) + (W3s + W4s), F[2]);                 // R:124
-    T = fmaf(-2.7862899e-5f * vb[2], S, T);
-    T = fmaf(-0.0625501332f, fmaf(vb[0], vb[0], vb[1] * vb[1]), T);
+    const float Fx = fmaf(QR_DYN(kENegKx) * vb[0], S, F[0]);                 // R:125
+    const float Fy = fmaf(QR_DYN(kENegKy) * vb[1], S, F[1]);                 // R:126
+    float T = fmaf(QR_DYN(kENegKw), (W1s + W2s) + (W3s + W4s), F[2]);        // R:124
+    T = fmaf(QR_DYN(kENegKz) * vb[2], S, T);
+    T = fmaf(QR_DYN(kENegKh), fmaf(vb[0], vb[0], vb[1] * vb[1]), T);
     ds[0] = s[3];
     ds[1] = s[4];
     ds[2] = s[5];
@@ -862,59 +932,62 @@ __device__ __forceinline__ void eom_e2e(const float* s, const Rot& R, const floa
         ds[3] = fmaf(R.r00, Fx, fmaf(R.r01, Fy, R.r02 * T));                          // R:138
         ds[4] = fmaf(R.r10, Fx, fmaf(R.r11, Fy, R.r12 * T));
     }
-    ds[5] = fmaf(R.r20, Fx, fmaf(R.r21, Fy, fmaf(R.r22, T, 9.81f)));
+    ds[5] = fmaf(R.r20, Fx, fmaf(R.r21, Fy, fmaf(R.r22, T, QR_DYN(kEG))));
     const float inv_cth = fast_rcp(R.cth);
     const float tth = R.sth * inv_cth;
     const float qr_mix = fmaf(q, R.sph, r * R.cph);
     ds[6] = fmaf(qr_mix, tth, p);                                                     // R:140
     ds[7] = fmaf(q, R.cph, -(r * R.sph));                                             // R:141
     ds[8] = qr_mix * inv_cth;                                                         // R:142
-    ds[9] = fmaf(1103.7527593819f, M[0],
-                 fmaf(-0.896247240618101f * q, r,
-                      fmaf(-8.79803364238411f, vb[1], 1.55842505518764e-6f * ((W1s - W2s) - (W3s - W4s)))));  // R:144
-    ds[10] = fmaf(805.152979066023f, M[1],
-                  fmaf(0.924315619967794f * p, r,
-                       fmaf(10.4077084541063f, vb[0], 9.79081191626409e-7f * ((W1s + W2s) - (W3s + W4s)))));  // R:145
-    ds[11] = fmaf(486.854917234664f, M[2],
-                  fmaf(-0.163583252190847f * p, q,
-                       fmaf(-0.395780237098345f, r,
-                            fmaf(-13.3373373580007f, (u[0] - u[1]) + (u[2] - u[3]),
-                                 8.33177659850698f * ((w1 - w2) + (w3 - w4))))));                            // R:146,131
+    ds[9] = fmaf(QR_DYN(kEPM), M[0],
+                 fmaf(QR_DYN(kEPQR) * q, r,
+                      fmaf(QR_DYN(kEPVby), vb[1], QR_DYN(kEPW) * ((W1s - W2s) - (W3s - W4s)))));  // R:144
+    ds[10] = fmaf(QR_DYN(kEQM), M[1],
+                  fmaf(QR_DYN(kEQPR) * p, r,
+                       fmaf(QR_DYN(kEQVbx), vb[0], QR_DYN(kEQW) * ((W1s + W2s) - (W3s + W4s)))));  // R:145
+    ds[11] = fmaf(QR_DYN(kERM), M[2],
+                  fmaf(QR_DYN(kERPQ) * p, q,
+                       fmaf(QR_DYN(kERR), r,
+                            fmaf(QR_DYN(kERCmd), (u[0] - u[1]) + (u[2] - u[3]),
+                                 QR_DYN(kERMotor) * ((w1 - w2) + (w3 - w4))))));                            // R:146,131
     if constexpr (kPk) {
         const f32x2p d12 = pk1(16.6666666666667f) * pk_keep(pk2(u[0], u[1]) - pk2(w1, w2));
         const f32x2p d34 = pk1(16.6666666666667f) * pk_keep(pk2(u[2], u[3]) - pk2(w3, w4));
         ds[12] = d12.x; ds[13] = d12.y; ds[14] = d34.x; ds[15] = d34.y;
     } else {
-        ds[12] = 16.6666666666667f * (u[0] - w1);                                     // R:112-115
-        ds[13] = 16.6666666666667f * (u[1] - w2);
-        ds[14] = 16.6666666666667f * (u[2] - w3);
-        ds[15] = 16.6666666666667f * (u[3] - w4);
+        const float lag = QR_DYN(kEMotorLag);
+        ds[12] = lag * (u[0] - w1);                                                   // R:112-115
+        ds[13] = lag * (u[1] - w2);
+        ds[14] = lag * (u[2] - w3);
+        ds[15] = lag * (u[3] - w4);
     }
 }
 
-// INDI inner-loop model (I:43-110)
+// INDI inner-loop model (I:43-110; coefficients: kDynINDINominal or the caller's register set)
+template <class C = NominalDyn<kINDI>>
 __device__ __forceinline__ void eom_indi(const float* s, const Rot& R, const float vb[3], const float u[4],
-                                         float* ds) {
+                                         float* ds, typename C::Arg dyn = typename C::Arg()) {
     const float p = s[9], q = s[10], r = s[11], Tn = s[12];
-    const float Dx = -0.33915248f * vb[0], Dy = -0.4314916f * vb[1];                      // I:73-74,86-87
-    const float mT = fmaf(-8.0f, Tn, -8.0f);                                              // I:94, T_max = 16
+    const float Dx = QR_DYN(kINegKx) * vb[0], Dy = QR_DYN(kINegKy) * vb[1];    // I:73-74,86-87
+    const float mT = fmaf(QR_DYN(kIThrustGain), Tn, QR_DYN(kIThrustOffset));   // I:94, T_max = 16
     ds[0] = s[3];
     ds[1] = s[4];
     ds[2] = s[5];
     ds[3] = fmaf(R.r00, Dx, fmaf(R.r01, Dy, R.r02 * mT));                                 // I:95
     ds[4] = fmaf(R.r10, Dx, fmaf(R.r11, Dy, R.r12 * mT));
-    ds[5] = fmaf(R.r20, Dx, fmaf(R.r21, Dy, fmaf(R.r22, mT, 9.81f)));
+    ds[5] = fmaf(R.r20, Dx, fmaf(R.r21, Dy, fmaf(R.r22, mT, QR_DYN(kIG))));
     const float inv_cth = fast_rcp(R.cth);
     const float tth = R.sth * inv_cth;
     const float qr_mix = fmaf(q, R.sph, r * R.cph);
     ds[6] = fmaf(qr_mix, tth, p);                                                         // I:97-99
     ds[7] = fmaf(q, R.cph, -(r * R.sph));
     ds[8] = qr_mix * inv_cth;
-    ds[9] = fmaf(-33.3333333333333f, p, 100.0f * u[0]);                                   // I:101-104
-    ds[10] = fmaf(-33.3333333333333f, q, 100.0f * u[1]);
-    ds[11] = fmaf(-33.3333333333333f, r, 66.6666666666667f * u[2]);
-    ds[12] = 33.3333333333333f * (u[3] - Tn);
+    ds[9] = fmaf(QR_DYN(kIPLag), p, QR_DYN(kIPCmd) * u[0]);             // I:101-104
+    ds[10] = fmaf(QR_DYN(kIQLag), q, QR_DYN(kIQCmd) * u[1]);
+    ds[11] = fmaf(QR_DYN(kIRLag), r, QR_DYN(kIRCmd) * u[2]);
+    ds[12] = QR_DYN(kITLag) * (u[3] - Tn);
 }
+#undef QR_DYN
 
 // -------------------------------------------------------------------------------------------------
 // Gate-frame observation of one env (update_states_gate, R:365-450 / I:218-265) into o[obs_len]
@@ -1026,10 +1099,11 @@ __device__ __forceinline__ void observe(const Params& P, const float* __restrict
 // for the terminal observation SB3 bootstraps time-limit truncations from (R:589-594).
 // `do_reset(need)` performs the auto-reset of the lanes with `need` (all lanes call it); the default is reset_done_lanes().
 // the arithmetic of one step from the pre-step state: new state `nw`, reward, flags, the target after the step
-template <int V, int kMode = 0, bool kPk = false>
+// C, `dyn`: the coefficients of the equations of motion (NominalDyn<V>: the literals, dyn a dummy; RuntimeDyn<V>: the caller's registers)
+template <int V, int kMode = 0, bool kPk = false, class C = NominalDyn<V>>
 __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& gate, const MlpRegs& mlp, bool use_mlp, int lane,
                                                const Env<V>& e, const float u[4], float* nw, int& new_target, bool& done,
-                                               bool& trunc) {
+                                               bool& trunc, typename C::Arg dyn = typename C::Arg()) {
     constexpr int S = Env<V>::S;
     const Rot R = make_rot<kPk>(e.s[6], e.s[7], e.s[8]);
     QR_TICK(P, 3);
@@ -1053,9 +1127,9 @@ __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& g
             }
         }
         QR_TICK(P, 4);
-        eom_e2e<kPk>(e.s, R, vb, u, M, F, ds);
+        eom_e2e<kPk, C>(e.s, R, vb, u, M, F, ds, dyn);
     } else {
-        eom_indi(e.s, R, vb, u, ds);
+        eom_indi<C>(e.s, R, vb, u, ds, dyn);
     }
     if constexpr (kPk && V == kE2E) {   // Euler step of the neighbours (phi, theta), (q, r), (w1, w2), (w3, w4) as pairs
 #pragma unroll
@@ -1119,17 +1193,17 @@ __device__ __forceinline__ float step_dynamics(const Params& P, const GateRow& g
     return reward;
 }
 
-template <int V, int kMode = 0, class BeforeReset, class DoReset>
+template <int V, int kMode = 0, class C = NominalDyn<V>, class BeforeReset, class DoReset>
 __device__ __forceinline__ float step_env(const Params& P, const float* __restrict__ gates,
                                           const float* __restrict__ rtab, float* __restrict__ tile, const MlpRegs& mlp,
                                           int lane, bool active, Env<V>& e, const float u[4], uint32_t gid_lo,
                                           uint32_t gid_hi, bool& done, bool& trunc, bool& did_reset,
-                                          BeforeReset&& before_reset, DoReset&& do_reset) {
+                                          BeforeReset&& before_reset, DoReset&& do_reset, typename C::Arg dyn = typename C::Arg()) {
     constexpr int S = Env<V>::S;
     float nw[S];
     int new_target;
     const GateRow gate = read_gate_row(gates, e.target);
-    const float reward = step_dynamics<V, kMode>(P, gate, mlp, (V == kE2E) && (P.flags & kFlagResidual), lane, e, u, nw, new_target, done, trunc);
+    const float reward = step_dynamics<V, kMode, false, C>(P, gate, mlp, (V == kE2E) && (P.flags & kFlagResidual), lane, e, u, nw, new_target, done, trunc, dyn);
     e.target = new_target;
     e.steps = e.steps + 1;
     did_reset = false;

@@ -34,12 +34,14 @@ constexpr size_t eval_lds_bytes() {
 //   i              the lane's env: state planes, rec and recf are indexed by it
 //   rid            the lane's id in the reset stream: the Philox counter's env id is P.gid + rid (64-bit carry as everywhere)
 //   gates_per_lap  passes that make a lap
+//   C, dyn         the coefficients of the equations of motion: NominalDyn<V> (the literals; the default, dyn a dummy) or RuntimeDyn<V> with
+//                  dyn = the set the kernel has loaded into workgroup-uniform registers (quadrace_eval_dynamics.hip)
 // kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
 // for every lane, every lane is an env and every lane stores.
-template <int V, int GA, bool kF32, bool kTail>
+template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>>
 __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
                                                  const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,
-                                                 int4* __restrict__ rec, float4* __restrict__ recf) {
+                                                 int4* __restrict__ rec, float4* __restrict__ recf, typename C::Arg dyn = typename C::Arg()) {
     constexpr int L = obs_len<V, GA>();
     using D = PolicyDims<L>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -100,8 +102,8 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
         clip_action(mean, u);
         const int target_before = e.target;
         bool done, trunc, did_reset;
-        const float reward = step_env<V>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,
-                                         [](bool) {}, [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); });
+        const float reward = step_env<V, 0, C>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,
+                                               [](bool) {}, [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); }, dyn);
         any_reset |= did_reset;
         // ---- accounting (tests/eval_spec.py, same order).  A pass on the step that ends the episode is not counted: the reset has
         // replaced the target, and that episode's lap count is void anyway.

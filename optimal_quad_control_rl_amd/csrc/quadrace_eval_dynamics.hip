@@ -1,0 +1,104 @@
+// quadrace_eval_dynamics.hip -- closed-loop evaluation of a grid of policies x flight conditions x VEHICLES in one launch
+// (qr_evaluate_policy_dynamics_grid): eval_policy_grid_kernel (quadrace_eval_grid.hip) with a third map entry and a third bank, the
+// coefficients of the equations of motion.  "Which parameter error breaks this policy first?" -- a thrust coefficient 15 % off, another
+// motor time constant, another inertia -- is one launch instead of one edited literal and one rebuild per vehicle.
+//   * per-workgroup (policy, condition, dynamics) from a group map: one 16-byte load from an address that derives from blockIdx alone,
+//     so a scalar load; the host has validated all three indices against the banks before the launch.
+//   * per-workgroup coefficients: a slot of the dynamics bank is kDynSlotFloats floats (128 bytes, 16-byte aligned), the variant's table
+//     of quadrace_device.hpp (22 entries for E2E, 12 for INDI) followed by zeros.  The workgroup loads its slot ONCE, ahead of the step
+//     loop, through uniform-address loads (memory no store of this kernel touches), and every entry is pinned to a scalar register from
+//     there on: the values are the same for all 256 lanes for all K steps, so they cost no vector register, no LDS and no load inside
+//     the loop.  A VALU instruction reads one scalar operand, so an FMA with two coefficients (the motor map, the INDI thrust map) takes
+//     one of them through a v_mov; everything else reads its coefficient where the literal stood.
+//   * the step is step_dynamics<.., RuntimeDyn<V>>: the explicit fmaf nesting of the literal form in the same order with the sign in the
+//     table, so a slot that holds the nominal table flies bit for bit what eval_policy_grid_kernel flies.
+// The policy image, the condition image, the group-local reset stream, the accounting and the record layout are eval_policy_body's.  No
+// tail lanes, no atomics, no workgroup that waits for another, no store inside the step loop.  A translation unit of its own: the code
+// objects of the other sources do not change when this one does.  Also here: the nominal tables as the host sees them
+// (qr_dynamics_nominal reads the constexpr arrays the kernels are compiled from).
+#include "quadrace_eval_body.hpp"
+#include "quadrace_launch.hpp"
+
+namespace qr {
+
+// one slot of the dynamics bank -> the register set of the step, every entry pinned to a scalar register
+template <int V>
+__device__ __forceinline__ RuntimeDyn<V> load_dynamics(const float* __restrict__ slot) {
+    RuntimeDyn<V> d;
+#pragma unroll
+    for (int k = 0; k < dyn_count<V>(); ++k) d.c[k] = slot[k];
+#pragma unroll
+    for (int k = 0; k < dyn_count<V>(); ++k) asm volatile("" : "+s"(d.c[k]));   // loaded here, once; never re-read, never a vector register
+    return d;
+}
+
+// bank / bank_lo: image 0 of the two policy arrays; conds: slot 0 of the condition bank; dyns: slot 0 of the dynamics bank;
+// map[g] = (policy, condition, dynamics, 0) of group g; wgs_per_group = E / kBlock
+template <int V, int GA, bool kF32>
+__global__ void __launch_bounds__(kBlock, 1)
+eval_policy_dynamics_grid_kernel(Params P0, const half8* __restrict__ bank, const half8* __restrict__ bank_lo, const float* __restrict__ conds,
+                                 const float* __restrict__ dyns, const int4* __restrict__ map, int wgs_per_group, int K, int4* __restrict__ rec,
+                                 float4* __restrict__ recf) {
+    using D = PolicyDims<obs_len<V, GA>()>;
+    // workgroup-uniform (blockIdx only): the group of this workgroup, its map entry, its images, and the workgroup's first env within its group
+    const int grp = (int)blockIdx.x / wgs_per_group;
+    const int local0 = ((int)blockIdx.x - grp * wgs_per_group) * kBlock;
+    const int4 pcd = map[grp];
+    const half8* __restrict__ img = bank + (size_t)pcd.x * D::kTotalHalf8;
+    const half8* __restrict__ img_lo = bank_lo + (size_t)pcd.x * D::kTotalHalf8;
+    const float* __restrict__ cond = conds + (size_t)pcd.y * kCondSlotFloats;
+    const RuntimeDyn<V> dyn = load_dynamics<V>(dyns + (size_t)pcd.z * kDynSlotFloats);
+    const CondHeader* __restrict__ hdr = reinterpret_cast<const CondHeader*>(cond);
+    Params P = P0;   // the handle's, with the condition's scalars
+    P.num_gates = hdr->num_gates;
+    P.max_steps = hdr->max_steps;
+    const int gates_per_lap = hdr->gates_per_lap;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        P.obs_lo[c] = hdr->obs_lo[c];
+        P.obs_inv[c] = hdr->obs_inv[c];
+    }
+    const int i = blockIdx.x * kBlock + threadIdx.x;   // < P.n: the grid is exactly P.n / kBlock workgroups
+    eval_policy_body<V, GA, kF32, false, RuntimeDyn<V>>(P, img, img_lo, cond + kCondHeaderFloats, i, local0 + (int)threadIdx.x, K, gates_per_lap, rec, recf, &dyn);
+}
+
+// bank / bank_lo: [capacity][PolicyDims<L>::kTotalHalf8] half8; conds: [capacity][kCondSlotFloats] floats; dyns: [capacity][kDynSlotFloats]
+// floats; map: [num_groups] (policy, condition, dynamics, 0), every index already checked against its bank by the caller.
+// envs_per_group % kBlock == 0 and num_groups * envs_per_group == P.n are checked again here: a grid that does not match P.n would read
+// and write out of bounds.
+hipError_t launch_eval_policy_dynamics_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
+                                            const int4* map, bool f32class, int num_groups, int envs_per_group, int K, int32_t* rec, float* recf,
+                                            hipStream_t st) {
+    if (num_groups < 1 || envs_per_group < kBlock || envs_per_group % kBlock != 0 || (long long)num_groups * envs_per_group != (long long)P.n ||
+        !bank || !bank_lo || !conds || !dyns || !map)
+        return hipErrorInvalidValue;
+    return dispatch_vg(variant, P.gates_ahead, [&](auto v, auto ga) {
+        constexpr int V = decltype(v)::value, GA = decltype(ga)::value;
+        constexpr size_t lds = eval_lds_bytes<obs_len<V, GA>()>();
+        int4* rec4 = reinterpret_cast<int4*>(rec);
+        float4* recf4 = reinterpret_cast<float4*>(recf);
+        const dim3 grid((unsigned)(P.n / kBlock));
+        const int wgs = envs_per_group / kBlock;
+        if (f32class)
+            return launch_dynamic_lds<eval_policy_dynamics_grid_kernel<V, GA, true>>(grid, dim3(kBlock), lds, st, P, bank, bank_lo, conds, dyns, map, wgs, K,
+                                                                                     rec4, recf4);
+        return launch_dynamic_lds<eval_policy_dynamics_grid_kernel<V, GA, false>>(grid, dim3(kBlock), lds, st, P, bank, bank_lo, conds, dyns, map, wgs, K,
+                                                                                  rec4, recf4);
+    });
+}
+
+// the nominal table of a variant as the kernels are compiled from it; nullptr for an unknown variant
+const float* dynamics_nominal(int variant, int* count) {
+    if (variant == kE2E) {
+        *count = kDynE2ECount;
+        return kDynE2ENominal;
+    }
+    if (variant == kINDI) {
+        *count = kDynINDICount;
+        return kDynINDINominal;
+    }
+    *count = 0;
+    return nullptr;
+}
+
+}  // namespace qr

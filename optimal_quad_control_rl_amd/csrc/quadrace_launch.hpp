@@ -133,6 +133,15 @@ hipError_t launch_eval_policy_bank(int variant, const Params& P, const half8* ba
 hipError_t launch_eval_policy_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const int2* map,
                                    bool f32class, int num_groups, int envs_per_group, int K, int32_t* rec, float* recf, hipStream_t st);
 
+// quadrace_eval_dynamics.hip: the same grid with a third axis, the coefficients of the equations of motion
+// (qr_evaluate_policy_dynamics_grid): group g flies policy map[g].x under condition map[g].y as the vehicle of dynamics slot map[g].z
+// (map[g].w is not read); dyns = slot 0 of [capacity][kDynSlotFloats].  dynamics_nominal: the variant's nominal table and its length
+// (nullptr, 0 for an unknown variant)
+hipError_t launch_eval_policy_dynamics_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
+                                            const int4* map, bool f32class, int num_groups, int envs_per_group, int K, int32_t* rec, float* recf,
+                                            hipStream_t st);
+const float* dynamics_nominal(int variant, int* count);
+
 // quadrace_rollout_cond.hip: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions): the workgroups of
 // group g fly under condition map[g].y (map[g].x is not read); conds = slot 0 of [capacity][kCondSlotFloats]
 hipError_t launch_rollout_policy_cond(int variant, const Params& P, const PolicyArgs& A, const float* conds, const int2* map, int num_groups,

@@ -1,0 +1,191 @@
+"""Vehicles for the dynamics-grid evaluator (`qr_dynamics_*`, `qr_evaluate_policy_dynamics_grid`, csrc/quadrace_eval_dynamics.hip).
+
+The reference identifies the parameters of its equations of motion from flight logs (R:72-93, I:58-74); every kernel of this project is
+compiled from their pre-folded form, the coefficient TABLE of csrc/quadrace_device.hpp (layout: include/quadrace.h).  A DynamicsParams
+is one such table, so "how far may the real vehicle differ before lap time or crash rate moves?" becomes a sweep:
+
+    from optimal_quad_control_rl_amd import physical_sweep, evaluate_dynamics_grid, Condition
+    vehicles = physical_sweep(env.VARIANT, "k_w", [0.7, 0.85, 1.0, 1.15, 1.3])     # thrust coefficient -30 % ... +30 %
+    results = evaluate_dynamics_grid([model], [Condition.from_env(env)], vehicles, env)   # results[p][c][d]
+
+A sweep works on PHYSICAL parameters, not on table entries: one parameter moves several entries (Izz the seven that hold it, tau three).
+Importing this module needs neither torch nor a GPU; DynamicsBank does.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+E2E, INDI = 0, 1
+E2E_ENTRIES = ("motor_gain", "motor_offset", "neg_k_x", "neg_k_y", "neg_k_w", "neg_k_z", "neg_k_h", "g",
+               "p_moment", "p_qr", "p_vby", "p_rotor", "q_moment", "q_pr", "q_vbx", "q_rotor",
+               "r_moment", "r_pq", "r_rate", "r_command", "r_motor", "motor_lag")
+INDI_ENTRIES = ("neg_k_x", "neg_k_y", "thrust_gain", "thrust_offset", "g", "p_lag", "p_command", "q_lag", "q_command", "r_lag", "r_command",
+                "thrust_lag")
+ENTRIES = {E2E: E2E_ENTRIES, INDI: INDI_ENTRIES}
+# the reference's identified values (R:72-93 / I:58-74)
+E2E_PHYSICAL = dict(Ixx=0.000906, Iyy=0.001242, Izz=0.002054, k_x=1.07933887e-05, k_y=9.65250793e-06, k_z=2.7862899e-05, k_w=4.36301076e-08,
+                    k_h=0.0625501332, k_p=1.4119331e-09, k_pv=-0.00797101848, k_q=1.21601884e-09, k_qv=0.0129263739, k_r1=2.57035545e-06,
+                    k_r2=4.10923364e-07, k_rr=0.000812932607, tau=0.06, w_min=3000.0, w_max=11000.0, g=9.81)
+INDI_PHYSICAL = dict(k_x=0.33915248, k_y=0.4314916, T_max=16.0, tau_p=0.03, tau_q=0.03, tau_r=0.03, tau_T=0.03, p_max=3.0, q_max=3.0, r_max=2.0,
+                     g=9.81)
+PHYSICAL = {E2E: E2E_PHYSICAL, INDI: INDI_PHYSICAL}
+
+
+def _variant(variant):
+    v = int(variant)
+    if v not in (E2E, INDI):
+        raise ValueError("variant must be 0 (E2E) or 1 (INDI)")
+    return v
+
+
+def fold_physical(variant, **phys):
+    """The coefficient table (float64, in table order) of the physical parameters `phys`: every name of PHYSICAL[variant], nothing else.
+    E2E folds as R:106-146 does (W = (w + 1)/2 (w_max - w_min) + w_min; the rotor acceleration term of R:117-121, 131 splits into a
+    command and a motor-speed part); INDI as I:94-104 with T_min = 0 and symmetric rate ranges, the only form the table can hold."""
+    v = _variant(variant)
+    names = PHYSICAL[v]
+    unknown, missing = sorted(set(phys) - set(names)), sorted(set(names) - set(phys))
+    if unknown or missing:
+        raise ValueError("physical parameters of variant %d: unknown %s, missing %s (the table holds T_min = 0 and symmetric rate ranges only)"
+                         % (v, unknown, missing))
+    p = {k: float(x) for k, x in phys.items()}
+    for k in ("Ixx", "Iyy", "Izz", "tau") if v == E2E else ("tau_p", "tau_q", "tau_r", "tau_T"):
+        if not p[k] > 0.0:
+            raise ValueError("%s must be positive" % k)
+    if v == E2E:
+        half = (p["w_max"] - p["w_min"]) / 2.0
+        return np.array([half, half + p["w_min"],
+                         -p["k_x"], -p["k_y"], -p["k_w"], -p["k_z"], -p["k_h"], p["g"],
+                         1.0 / p["Ixx"], (p["Iyy"] - p["Izz"]) / p["Ixx"], p["k_pv"] / p["Ixx"], p["k_p"] / p["Ixx"],
+                         1.0 / p["Iyy"], (p["Izz"] - p["Ixx"]) / p["Iyy"], p["k_qv"] / p["Iyy"], p["k_q"] / p["Iyy"],
+                         1.0 / p["Izz"], (p["Ixx"] - p["Iyy"]) / p["Izz"], -p["k_rr"] / p["Izz"],
+                         -p["k_r2"] * half / p["tau"] / p["Izz"], (p["k_r2"] * half / p["tau"] - p["k_r1"] * half) / p["Izz"],
+                         1.0 / p["tau"]], dtype=np.float64)
+    return np.array([-p["k_x"], -p["k_y"], -p["T_max"] / 2.0, -p["T_max"] / 2.0, p["g"],
+                     -1.0 / p["tau_p"], p["p_max"] / p["tau_p"], -1.0 / p["tau_q"], p["q_max"] / p["tau_q"],
+                     -1.0 / p["tau_r"], p["r_max"] / p["tau_r"], 1.0 / p["tau_T"]], dtype=np.float64)
+
+
+@dataclass(frozen=True, eq=False)
+class DynamicsParams:
+    """One vehicle: `coeffs`, the float32 coefficient table of `variant` (22 entries for E2E, 12 for INDI; ENTRIES[variant] names them in
+    order, include/quadrace.h states the term each one multiplies), and a `name` for tables."""
+    variant: int
+    coeffs: np.ndarray
+    name: str = "vehicle"
+
+    def __post_init__(self):
+        v = _variant(self.variant)
+        c = np.array(self.coeffs, dtype=np.float32).reshape(-1)   # np.array copies
+        if c.shape[0] != len(ENTRIES[v]):
+            raise ValueError("variant %d has %d coefficients, not %d" % (v, len(ENTRIES[v]), c.shape[0]))
+        if not np.all(np.isfinite(c)):
+            raise ValueError("every coefficient must be finite")
+        c.setflags(write=False)
+        object.__setattr__(self, "variant", v)
+        object.__setattr__(self, "coeffs", c)
+        object.__setattr__(self, "name", str(self.name))
+
+    @property
+    def entries(self):
+        return ENTRIES[self.variant]
+
+    @classmethod
+    def nominal(cls, variant, name="nominal"):
+        """The table every kernel of the library is compiled from (qr_dynamics_nominal: host only, no GPU)."""
+        from . import _lib
+
+        v = _variant(variant)
+        L = _lib.load()
+        n = _lib.require(L, "qr_dynamics_count")(v)
+        out = np.empty(n, dtype=np.float32)
+        _lib.check(_lib.require(L, "qr_dynamics_nominal")(v, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return cls(v, out, name)
+
+    def scaled(self, name=None, **factors):
+        """A copy with the named TABLE entries multiplied (in float32) by their factors: scaled(neg_k_w=1.15)."""
+        unknown = sorted(set(factors) - set(self.entries))
+        if unknown:
+            raise ValueError("unknown table entries %s; variant %d has %s" % (unknown, self.variant, list(self.entries)))
+        c = self.coeffs.copy()
+        for k, f in factors.items():
+            i = self.entries.index(k)
+            c[i] = np.float32(c[i]) * np.float32(f)
+        label = name if name is not None else ",".join("%s*%g" % (k, float(f)) for k, f in factors.items()) or self.name
+        return DynamicsParams(self.variant, c, label)
+
+    @classmethod
+    def from_physical(cls, variant, name="physical", **phys):
+        """The table of the physical parameters `phys` (every name of PHYSICAL[variant]), folded in float64 and rounded to float32 once."""
+        return cls(variant, fold_physical(variant, **phys).astype(np.float32), name)
+
+
+def physical_sweep(variant, parameter, factors):
+    """One DynamicsParams per entry of `factors`: the reference's vehicle with the physical parameter `parameter` multiplied by the
+    factor, every other parameter as identified, named "<parameter>*<factor>".  A factor of 1 gives the folded reference values."""
+    v = _variant(variant)
+    if parameter not in PHYSICAL[v]:
+        raise ValueError("unknown physical parameter %r; variant %d has %s" % (parameter, v, sorted(PHYSICAL[v])))
+    out = []
+    for f in factors:
+        phys = dict(PHYSICAL[v])
+        phys[parameter] = phys[parameter] * float(f)
+        out.append(DynamicsParams.from_physical(v, name="%s*%g" % (parameter, float(f)), **phys))
+    return out
+
+
+class DynamicsBank:
+    """`capacity` vehicles of one env variant side by side on the device (`qr_dynamics_bank_*`): the argument of
+    `env.evaluate_dynamics_grid_device`.  A slot holds one coefficient table.  No CPU fallback."""
+
+    def __init__(self, variant, capacity, device=None):
+        import torch
+
+        from . import _lib
+
+        self._lib = _lib
+        self._L = _lib.load()
+        self._h = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("DynamicsBank needs a gfx950 GPU: libquadrace has no CPU fallback")
+        create = _lib.require(self._L, "qr_dynamics_bank_create")
+        self.variant, self.capacity = _variant(variant), int(capacity)
+        self.params = [None] * self.capacity   # the DynamicsParams of every slot set so far
+        self._dev_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self._dev_index)
+        h = C.c_void_p()
+        _lib.check(create(self.variant, self._dev_index, self.capacity, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._L.qr_dynamics_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, slot, params=None):
+        """Slot `slot` in [0, capacity) <- `params` (a DynamicsParams of the bank's variant); None = the nominal vehicle."""
+        f32p = C.POINTER(C.c_float)
+        n = len(ENTRIES[self.variant])
+        if params is None:
+            self._lib.check(self._L.qr_dynamics_bank_set(self._h, int(slot), None, n))
+            self.params[int(slot)] = DynamicsParams.nominal(self.variant)
+            return self
+        if params.variant != self.variant:
+            raise ValueError("DynamicsParams of another variant than the bank")
+        c = np.ascontiguousarray(params.coeffs, dtype=np.float32)
+        self._lib.check(self._L.qr_dynamics_bank_set(self._h, int(slot), c.ctypes.data_as(f32p), n))
+        self.params[int(slot)] = params
+        return self
+
+    def read(self, slot):
+        """The table slot `slot` holds on the device, as a float32 array."""
+        out = np.empty(len(ENTRIES[self.variant]), dtype=np.float32)
+        self._lib.check(self._L.qr_dynamics_bank_read(self._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_float)), out.shape[0]))
+        return out

@@ -261,6 +261,75 @@ def evaluate_grid(policies, conditions, env, envs_per_cell=256, n_eval_steps=200
     return results
 
 
+def plan_dynamics_batches(num_policies, num_conditions, num_dynamics, slots):
+    """How evaluate_dynamics_grid spreads the policies x conditions x vehicles cells over launches of `slots` groups each: cells in
+    row-major order (cell k = (k // (C D), (k // D) % C, k % D)), each batch a list of exactly `slots` (policy, condition, dynamics)
+    triples, the last batch padded by repeating its last cell; `kept` = how many leading groups of the batch are real.  Returns
+    [(cells, kept), ...]; pure arithmetic, no device."""
+    P, Cn, D, slots = int(num_policies), int(num_conditions), int(num_dynamics), int(slots)
+    if P < 1 or Cn < 1 or D < 1:
+        raise ValueError("need at least one policy, one condition and one vehicle")
+    if slots < 1:
+        raise ValueError("the env holds no complete group: num_envs < envs_per_cell")
+    total = P * Cn * D
+    plan = []
+    for first in range(0, total, slots):
+        real = [(k // (Cn * D), (k // D) % Cn, k % D) for k in range(first, min(first + slots, total))]
+        plan.append((real + [real[-1]] * (slots - len(real)), len(real)))
+    return plan
+
+
+def evaluate_dynamics_grid(policies, conditions, dynamics, env, envs_per_cell=256, n_eval_steps=2000, window_steps=1200, precision=None, seed=0):
+    """evaluate_grid with a third axis: every cell of `policies` x `conditions` x `dynamics` (dynamics.DynamicsParams: the coefficients
+    of the equations of motion), `env.num_envs // envs_per_cell` cells per launch (qr_evaluate_policy_dynamics_grid).  Starts, restarts,
+    entries of `policies`, `precision` and the summaries are evaluate_grid's: all cells see the same uniform draws, and a cell whose
+    vehicle is DynamicsParams.nominal flies what evaluate_grid's cell (p, c) flies.  The residual networks and the observation are
+    `env`'s.  Returns results[p][c][d], each a {"window", "total"} dict.  `env` keeps its own configuration."""
+    from .conditions import ConditionBank
+    from .dynamics import DynamicsBank
+    from .policy import MfmaPolicyBank
+    from .sb3 import _unwrap
+
+    core = _unwrap(env)
+    E, slots = group_size(envs_per_cell, core.num_envs, "envs_per_cell", "cell")
+    phases = _phases(n_eval_steps, window_steps)
+    conditions, policies, dynamics = list(conditions), list(policies), list(dynamics)
+    plan = plan_dynamics_batches(len(policies), len(conditions), len(dynamics), slots)
+    for d in dynamics:
+        if d.variant != core.VARIANT:
+            raise ValueError("DynamicsParams of another variant than the env")
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        precision = _model_precision([m for _, m in actors])
+    results = [[[None] * len(dynamics) for _ in conditions] for _ in actors]
+    pbank = MfmaPolicyBank(core.state_len, len(actors), core.device.index)
+    cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
+    dbank = DynamicsBank(core.VARIANT, len(dynamics), core.device.index)
+
+    def start(cells):
+        core.condition_starts(conditions, [c for _, c, _ in cells], E, seed=seed)
+
+    def launch(cells, steps, rec, recf):
+        core.evaluate_dynamics_grid_device(pbank, cbank, dbank, [p for p, _, _ in cells], [c for _, c, _ in cells], [d for _, _, d in cells], E,
+                                           steps, rec, recf, precision=precision)
+
+    def summarise(cell, rec, recf):
+        return summarize_eval(rec, recf, core.dt, conditions[cell[1]].gates_per_lap)
+
+    try:
+        for p, (actor, _) in enumerate(actors):
+            pbank.load_torch(p, actor)
+        for c, cond in enumerate(conditions):
+            cbank.set(c, cond)
+        for d, dyn in enumerate(dynamics):
+            dbank.set(d, dyn)
+        for (p, c, d), summaries in fly_batches(plan, start, launch, phases, (REC_INTS, REC_FLOATS), summarise, core.num_envs, E, core.device):
+            results[p][c][d] = _window_total(summaries)
+    finally:
+        _sync_and_close(core, pbank, cbank, dbank)
+    return results
+
+
 def robustness_table(results, names):
     """evaluate_grid's results[p][c] as one table per policy: a list (per policy) of rows (condition name, crashes per window,
     flying-lap seconds or None, gates per window), in the order of `names` (one name per condition)."""

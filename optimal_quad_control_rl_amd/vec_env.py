@@ -694,6 +694,28 @@ class Quadcopter3DGates(_Base):
         self._observe_under(condition_bank.conditions, cond, int(envs_per_group))
         return rec, recf
 
+    def evaluate_dynamics_grid_device(self, policy_bank, condition_bank, dynamics_bank, policy_of_group, condition_of_group, dynamics_of_group,
+                                      envs_per_group, num_steps, rec, recf=None, precision="f16-operands"):
+        """evaluate_grid_device with a third axis, the VEHICLE (qr_evaluate_policy_dynamics_grid): group g additionally flies the
+        coefficients of slot dynamics_of_group[g] of `dynamics_bank` (dynamics.DynamicsBank) in its equations of motion.  A group
+        whose slot holds the nominal table flies bit for bit what evaluate_grid_device flies; the residual weights and the
+        observation stay this env's.  Everything else -- groups, records, restarts, the observation buffer afterwards -- as
+        evaluate_grid_device.  Returns (rec, recf)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_evaluate_policy_dynamics_grid")
+        pol = np.ascontiguousarray(policy_of_group, dtype=np.int32).reshape(-1)
+        cond = np.ascontiguousarray(condition_of_group, dtype=np.int32).reshape(-1)
+        dyn = np.ascontiguousarray(dynamics_of_group, dtype=np.int32).reshape(-1)
+        if not (pol.shape == cond.shape == dyn.shape):
+            raise ValueError("policy_of_group, condition_of_group and dynamics_of_group must have one entry per group each")
+        self._check_eval_records(rec, recf)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy_bank._h, condition_bank._h, dynamics_bank._h, int(pol.shape[0]), int(envs_per_group),
+                      pol.ctypes.data_as(i32p), cond.ctypes.data_as(i32p), dyn.ctypes.data_as(i32p), int(num_steps), flags, _ptr(rec),
+                      _ptr(recf), self._stream()))
+        self._observe_under(condition_bank.conditions, cond, int(envs_per_group))
+        return rec, recf
+
     def _under_each_condition(self, conditions, condition_of_group, fn):
         """fn(c) with the HANDLE configured as conditions[c] (track, start, disturbances, max_steps), once per distinct entry of
         condition_of_group in ascending order; the handle's own configuration is restored afterwards, also when fn raises."""
