@@ -58,7 +58,8 @@ extern "C" {
                              qr_ppo_population_load_bank / qr_ppo_population_prepare / qr_policy_bank_read (round 16),
                              qr_ppo_population_exploit (round 18), qr_es_* (round 19),
                              qr_dynamics_* / qr_evaluate_policy_dynamics_grid (round 20),
-                             qr_rollout_policy_dynamics / qr_vehicle_physical_count / qr_vehicle_bank_sample (round 21) */
+                             qr_rollout_policy_dynamics / qr_vehicle_physical_count / qr_vehicle_bank_sample (round 21),
+                             qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22) */
 
 enum {
     QR_OK = 0,
@@ -386,7 +387,8 @@ int qr_evaluate_policy_grid(qr_env* env, qr_policy_bank* policies, qr_condition_
  * other slots of the three banks, flies bit for bit the same from the same group-local state; and K steps in one call equal K calls of one
  * step through the same record buffers.
  * NOT modelled: the residual thrust / moment MLPs and the observation are the handle's -- a perturbed vehicle adds the same learned
- * residual and is observed in the same units; there is no scale on the residual, no actuator delay and no observation noise.
+ * residual and is observed in the same units; there is no scale on the residual.  Observation noise and command delay are the fourth
+ * axis of qr_evaluate_policy_sensing_grid (below), which takes a dynamics bank too.
  * Refused before anything is launched or copied (qr_last_error set, records and state untouched): everything qr_evaluate_policy_grid
  * refuses, in its order; and next to the condition bank's refusals the dynamics bank's -- QR_E_INVALID: NULL dynamics bank or map, a
  * dynamics bank of another variant or device, an index outside the bank; QR_E_STATE: a referenced slot that was never set. */
@@ -402,6 +404,67 @@ int qr_evaluate_policy_dynamics_grid(qr_env* env, qr_policy_bank* policies, qr_c
                                      int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
                                      const int32_t* condition_of_group, const int32_t* dynamics_of_group, int32_t num_steps, int32_t flags,
                                      int32_t* rec_dev, float* recf_dev, void* stream);
+
+/* Evaluation of a grid of policies x flight conditions x vehicles x SENSING in one launch: "which sensing error breaks this policy first,
+ * and how many control periods of latency can it fly with?"  Every other closed-loop entry point feeds the policy the exact state of the
+ * step and applies its command in the same step; on a real vehicle the state comes from an estimator with noise and the command reaches
+ * the motors some control periods late.
+ * A SENSING SLOT is 32 floats (128 bytes, 16-byte aligned, like a dynamics slot): sigma[0..7], then the command delay as an int32 bit
+ * pattern, then zeros.  sigma is indexed by a GROUP of observation entries (S = 16 for E2E, 13 for INDI; GA = gates ahead; L = the
+ * observation length), in the units of the observation the policy sees:
+ *    0  o[0..2]                    position in the gate frame
+ *    1  o[3..5]                    velocity in the gate frame
+ *    2  o[6..8]                    roll, pitch, yaw relative to the gate
+ *    3  o[9..11]                   body rates
+ *    4  o[12..S-1]                 actuator state (motor speeds / T_norm)
+ *    5  o[S+4a+0..2], a < GA       relative position of gate a ahead
+ *    6  o[S+4a+3]                  relative yaw of gate a ahead
+ *    7  o[S+4GA..L-1] (E2E only)   disturbance columns
+ * OBSERVATION NOISE: at step t the policy is evaluated on o~[j] = add_rn(o[j], mul_rn(sigma[group(j)], eps[j])) -- two roundings, no
+ * FMA.  The env's own observation and state are untouched.  eps[4q..4q+3] is one Philox4x32-10 block with the uniforms and the Box-Muller
+ * arithmetic of the action noise (qr_rollout_policy); counter (gid lo, gid hi, step lo, (step hi & 0xFFFFFF) | (q << 24)) with
+ * gid = env_id_base + the index of the env WITHIN ITS GROUP (the id of the group-local reset stream: every cell of a grid draws the same
+ * eps), step = first_step + t, q < 9; key (noise_seed lo ^ 0x6A09E667, noise_seed hi ^ 0x3C6EF372), distinct from the reset, action-noise
+ * and ES keys.  The noise costs ceil(L / 4) Philox blocks per step when it is on; a slot whose eight sigmas are all zero draws nothing and
+ * adds nothing (a workgroup-uniform branch): the policy then sees o itself, bit for bit.
+ * COMMAND DELAY: d = delay in [0, 4].  a_t = clip(mean_t) is computed from o~_t.  With d = 0 the env steps with a_t; otherwise with the
+ * command computed d steps earlier, and with (0, 0, 0, 0) for the first d steps of an episode: the queue of an env is cleared to zeros by
+ * the step that ends its episode (auto-reset, crash and time limit alike).  The queue lives across launches in the caller's pending_dev,
+ * float [n][16], 16-byte aligned: pending[i][4j..4j+3] is the command computed j + 1 steps ago; entries with j >= d are written as zeros.
+ * Zero it when the envs are (re)started.
+ * NOT modelled: bias or drift, correlated noise, an estimator that runs slower than the control loop, quantisation.
+ * A sensing bank owns one device array [capacity][32 floats] and belongs to no variant.  qr_sensing_bank_set fills slot `slot` from the
+ * HOST array sigma8 [8] (NULL = the ideal sensor: all zeros) and `delay`, after synchronising the device like the other setters;
+ * QR_E_INVALID: NULL bank, slot outside the bank, a sigma that is negative or not finite, delay outside [0, 4].  qr_sensing_bank_read
+ * copies a slot back (QR_E_STATE: slot never set).
+ * qr_evaluate_policy_sensing_grid is qr_evaluate_policy_dynamics_grid with the fourth bank and the fourth HOST map: group g flies through
+ * the sensor of slot sensing_of_group[g].  A 256-env workgroup loads its slot once, ahead of the step loop, through uniform-address loads
+ * and keeps sigma and d in scalar registers; inside the step loop there is no load of a slot value, no atomic and no global store, and no
+ * workgroup waits for another.  Records, restarts, continue-a-call behaviour are qr_evaluate_policy_grid's: K steps in one call equal K
+ * calls of one step with first_step advanced, through the same rec, recf and pending.
+ * CONTRACT: (1) a group whose slot is ideal (set from NULL) flies bit for bit what qr_evaluate_policy_dynamics_grid flies for the same
+ * policy, condition and vehicle from the same state -- records, float records, env state, observation -- and leaves its rows of pending
+ * zero.  (2) A group depends on its (policy, condition, dynamics, sensing) quadruple only.
+ * qr_sensing_noise writes mul_rn(sigma[group(j)], eps[j]) as rows out_dev [num_steps][envs_per_group][L] for the group-local envs
+ * 0..envs_per_group-1 of `env` (its variant, gates_ahead and env_id_base) under slot `slot`: what the evaluator adds to the observations,
+ * from the same device function.  An all-zero slot writes +0.0f.  num_steps <= 65535.
+ * Refused before anything is launched or copied (qr_last_error set; records, pending, state and output untouched): everything
+ * qr_evaluate_policy_dynamics_grid refuses, in its order; then QR_E_INVALID: a NULL sensing bank, map or pending_dev, a misaligned
+ * pending_dev, a sensing bank of another device, an index outside the bank, first_step + num_steps > 2^56; QR_E_STATE: a referenced slot
+ * that was never set. */
+typedef struct qr_sensing_bank qr_sensing_bank;
+int qr_sensing_bank_create(int32_t device, int32_t capacity, qr_sensing_bank** out);
+int qr_sensing_bank_destroy(qr_sensing_bank* bank);
+int qr_sensing_bank_capacity(const qr_sensing_bank* bank);
+int qr_sensing_bank_set(qr_sensing_bank* bank, int32_t slot, const float* sigma8, int32_t delay);
+int qr_sensing_bank_read(const qr_sensing_bank* bank, int32_t slot, float* sigma8, int32_t* delay);
+int qr_evaluate_policy_sensing_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group,
+                                    int32_t num_steps, int32_t flags, uint64_t noise_seed, uint64_t first_step, float* pending_dev,
+                                    int32_t* rec_dev, float* recf_dev, void* stream);
+int qr_sensing_noise(qr_env* env, qr_sensing_bank* sensing, int32_t slot, int32_t envs_per_group, int32_t num_steps, uint64_t noise_seed,
+                     uint64_t first_step, float* out_dev, void* stream);
 
 /* Closed-loop rollout across a MIX of flight conditions in one launch: PPO's collect phase (qr_rollout_policy: same policy forward, same
  * action noise, same rows, terminal-observation rows, last_obs and state write-back) with the group map and the condition bank of

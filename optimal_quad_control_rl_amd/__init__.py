@@ -11,7 +11,8 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "evaluate_policy", "summarize_eval", "record_policy", "FlightRecord", "evaluate_policies", "rank_policies", "MfmaPolicyBank",
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
            "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy",
-           "evaluate_dynamics_grid", "DynamicsParams", "DynamicsBank", "physical_sweep", "VehicleRanges"]
+           "evaluate_dynamics_grid", "DynamicsParams", "DynamicsBank", "physical_sweep", "VehicleRanges",
+           "evaluate_sensing_grid", "SensingParams", "SensingBank", "noise_sweep", "delay_sweep"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -27,7 +28,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import sb3
 
         return getattr(sb3, name)
-    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid", "evaluate_dynamics_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
+    if name in ("evaluate_policy", "summarize_eval", "evaluate_policies", "rank_policies", "evaluate_grid", "evaluate_dynamics_grid", "evaluate_sensing_grid"):  # on-device lap times / crash rate of a policy (qr_evaluate_policy)
         from . import evaluation
 
         return getattr(evaluation, name)
@@ -51,6 +52,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import dynamics
 
         return getattr(dynamics, name)
+    if name in ("SensingParams", "SensingBank", "noise_sweep", "delay_sweep"):  # sensors of the sensing-grid evaluator (qr_sensing_*)
+        from . import sensing
+
+        return getattr(sensing, name)
     if name == "MfmaPolicyBank":  # a bank of policies for one-launch evaluation (qr_policy_bank_*, qr_evaluate_policy_bank)
         from . import policy
 

@@ -51,6 +51,7 @@ struct qr_env {
     DeviceTable<int2> group_map;                  // qr_evaluate_policy_grid and the group rollouts: (policy or dynamics, condition) per group
     DeviceTable<qr::PopulationEntry> pop_table;   // qr_rollout_policy_population: the sampling values per group
     DeviceTable<int4> dyn_map;                    // qr_evaluate_policy_dynamics_grid: (policy, condition, dynamics, 0) per group
+    DeviceTable<int4> sen_map;                    // qr_evaluate_policy_sensing_grid: (policy, condition, dynamics, sensing) per group
 };
 
 // A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
@@ -68,6 +69,14 @@ struct qr_dynamics_bank {
     int variant = 0, device = 0, capacity = 0;
     float* d_slots = nullptr;
     std::vector<uint8_t> is_set;   // per slot: qr_dynamics_bank_set has succeeded, or qr_vehicle_bank_sample has enqueued its draw
+};
+
+// A bank of sensors for qr_evaluate_policy_sensing_grid: [capacity][qr::kSensingSlotFloats] floats on the device, slot s = sigma[0..7],
+// the command delay as an int32 bit pattern, zeros.
+struct qr_sensing_bank {
+    int device = 0, capacity = 0;
+    float* d_slots = nullptr;
+    std::vector<uint8_t> is_set;   // per slot: qr_sensing_bank_set has succeeded
 };
 
 namespace {
@@ -426,6 +435,7 @@ int qr_destroy(qr_env* e) {
     if (e->group_map.d) (void)hipFree(e->group_map.d);
     if (e->pop_table.d) (void)hipFree(e->pop_table.d);
     if (e->dyn_map.d) (void)hipFree(e->dyn_map.d);
+    if (e->sen_map.d) (void)hipFree(e->sen_map.d);
     delete e;
     return QR_OK;
 }
@@ -911,6 +921,144 @@ int qr_evaluate_policy_dynamics_grid(qr_env* e, qr_policy_bank* policies, qr_con
     return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_dynamics_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
                                        conditions->d_slots, dynamics->d_slots, e->dyn_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups,
                                        envs_per_group, K, rec_dev, recf_dev, st));
+}
+
+// ---- bank of sensors (qr_evaluate_policy_sensing_grid) ----
+int qr_sensing_bank_create(int32_t device, int32_t capacity, qr_sensing_bank** out) {
+    if (!out) return fail(QR_E_INVALID, "qr_sensing_bank_create: null output");
+    *out = nullptr;
+    if (capacity < 1) return fail(QR_E_INVALID, "qr_sensing_bank_create: capacity must be >= 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(QR_E_NO_DEVICE, "qr_sensing_bank_create: no HIP device visible (no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(QR_E_INVALID, "qr_sensing_bank_create: bad device ordinal");
+    QR_HIP(hipSetDevice(device));
+    qr_sensing_bank* b = new qr_sensing_bank();
+    b->device = device;
+    b->capacity = capacity;
+    b->is_set.assign((size_t)capacity, 0);
+    const size_t bytes = (size_t)capacity * qr::kSensingSlotFloats * sizeof(float);
+    if (hipMalloc((void**)&b->d_slots, bytes) != hipSuccess) {
+        delete b;
+        return fail(QR_E_HIP, "qr_sensing_bank_create: hipMalloc failed");
+    }
+    (void)hipMemset(b->d_slots, 0, bytes);
+    *out = b;
+    return QR_OK;
+}
+
+int qr_sensing_bank_destroy(qr_sensing_bank* b) {
+    if (!b) return QR_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    if (b->d_slots) (void)hipFree(b->d_slots);
+    delete b;
+    return QR_OK;
+}
+
+int qr_sensing_bank_capacity(const qr_sensing_bank* b) { return b ? b->capacity : fail(QR_E_INVALID, "qr_sensing_bank_capacity: null bank"); }
+
+int qr_sensing_bank_set(qr_sensing_bank* b, int32_t slot, const float* sigma8, int32_t delay) {
+    if (!b) return fail(QR_E_INVALID, "qr_sensing_bank_set: null bank");
+    if (slot < 0 || slot >= b->capacity) return fail(QR_E_INVALID, "qr_sensing_bank_set: slot must be in [0, capacity)");
+    float host[qr::kSensingSlotFloats] = {};   // NULL = the ideal sensor: no noise
+    for (int k = 0; k < 8 && sigma8; ++k) {
+        if (!std::isfinite(sigma8[k]) || sigma8[k] < 0.0f)
+            return fail(QR_E_INVALID, "qr_sensing_bank_set: sigma " + std::to_string(k) + " must be finite and >= 0");
+        host[k] = sigma8[k] == 0.0f ? 0.0f : sigma8[k];   // (-0.0f -> +0.0f)
+    }
+    if (delay < 0 || delay > qr::kMaxDelay) return fail(QR_E_INVALID, "qr_sensing_bank_set: delay must be in [0, 4]");
+    std::memcpy(&host[8], &delay, sizeof(delay));
+    QR_HIP(hipSetDevice(b->device));
+    QR_HIP(hipDeviceSynchronize());   // a launch may still read the slot
+    if (hipMemcpy(b->d_slots + (size_t)slot * qr::kSensingSlotFloats, host, sizeof(host), hipMemcpyHostToDevice) != hipSuccess) {
+        b->is_set[(size_t)slot] = 0;
+        return fail(QR_E_HIP, "qr_sensing_bank_set: upload failed");
+    }
+    b->is_set[(size_t)slot] = 1;
+    return QR_OK;
+}
+
+int qr_sensing_bank_read(const qr_sensing_bank* b, int32_t slot, float* sigma8, int32_t* delay) {
+    if (!b) return fail(QR_E_INVALID, "qr_sensing_bank_read: null bank");
+    if (!sigma8 || !delay) return fail(QR_E_INVALID, "qr_sensing_bank_read: null output");
+    if (slot < 0 || slot >= b->capacity) return fail(QR_E_INVALID, "qr_sensing_bank_read: slot must be in [0, capacity)");
+    if (!b->is_set[(size_t)slot]) return fail(QR_E_STATE, "qr_sensing_bank_read: slot " + std::to_string(slot) + " of the sensing bank was never set");
+    float host[9];
+    QR_HIP(hipSetDevice(b->device));
+    QR_HIP(hipDeviceSynchronize());
+    QR_HIP(hipMemcpy(host, b->d_slots + (size_t)slot * qr::kSensingSlotFloats, sizeof(host), hipMemcpyDeviceToHost));
+    std::memcpy(sigma8, host, 8 * sizeof(float));
+    std::memcpy(delay, &host[8], sizeof(int32_t));
+    return QR_OK;
+}
+
+// the Philox counter of the observation noise keeps 56 bits of the step: its top byte carries the block number
+static bool sensing_steps_fit(uint64_t first_step, int K) {
+    const uint64_t limit = (uint64_t)1 << 56;
+    return first_step <= limit && (uint64_t)K <= limit - first_step;
+}
+
+// qr_evaluate_policy_dynamics_grid with a fourth bank and a fourth map: its refusals in its order, then the sensing bank's.  Nothing is
+// enqueued or copied unless every argument is valid.
+int qr_evaluate_policy_sensing_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t K,
+                                    int32_t flags, uint64_t noise_seed, uint64_t first_step, float* pending_dev, int32_t* rec_dev, float* recf_dev,
+                                    void* stream) {
+    const char* who = "qr_evaluate_policy_sensing_grid";
+    const std::string w = std::string(who) + ": ";
+    if (int rc = check_ready(e)) return rc;
+    if (!policies) return fail(QR_E_INVALID, w + "null policy bank handle");
+    if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
+    if (!dynamics) return fail(QR_E_INVALID, w + "null dynamics bank handle");
+    if (!policy_of_group || !condition_of_group || !dynamics_of_group) return fail(QR_E_INVALID, w + "the three group maps are required");
+    if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, who)) return rc;
+    if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (int rc = check_dynamics_bank(e, dynamics, who)) return rc;
+    if (int rc = check_group_indices(policies, policy_of_group, conditions, condition_of_group, num_groups, who)) return rc;
+    if (int rc = check_dynamics_indices(dynamics, dynamics_of_group, num_groups, who)) return rc;
+    // the sensing bank's own
+    if (!sensing) return fail(QR_E_INVALID, w + "null sensing bank handle");
+    if (!sensing_of_group) return fail(QR_E_INVALID, w + "sensing_of_group is required");
+    if (!pending_dev) return fail(QR_E_INVALID, w + "pending_dev is required");
+    if ((uintptr_t)pending_dev & 15) return fail(QR_E_INVALID, w + "pending_dev must be 16-byte aligned");
+    if (sensing->device != e->cfg.device) return fail(QR_E_INVALID, w + "sensing bank on another GPU");
+    for (int g = 0; g < num_groups; ++g)
+        if (sensing_of_group[g] < 0 || sensing_of_group[g] >= sensing->capacity)
+            return fail(QR_E_INVALID, w + "sensing_of_group[" + std::to_string(g) + "] is outside the sensing bank");
+    if (!sensing_steps_fit(first_step, K)) return fail(QR_E_INVALID, w + "first_step + num_steps must not exceed 2^56");
+    for (int g = 0; g < num_groups; ++g)
+        if (!sensing->is_set[(size_t)sensing_of_group[g]])
+            return fail(QR_E_STATE, w + "slot " + std::to_string(sensing_of_group[g]) + " of the sensing bank was never set");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int4> map((size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g)
+        map[(size_t)g] = make_int4(policy_of_group[g], condition_of_group[g], dynamics_of_group[g], sensing_of_group[g]);
+    if (int rc = upload_table(e->sen_map, map, st, who, "group map", "this map")) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_sensing_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
+                                       conditions->d_slots, dynamics->d_slots, sensing->d_slots, e->sen_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0,
+                                       num_groups, envs_per_group, K, noise_seed, first_step, pending_dev, rec_dev, recf_dev, st));
+}
+
+// the rows the evaluator adds to the observations of one group under one slot: refusals first, then one launch
+int qr_sensing_noise(qr_env* e, qr_sensing_bank* sensing, int32_t slot, int32_t envs_per_group, int32_t K, uint64_t noise_seed, uint64_t first_step,
+                     float* out_dev, void* stream) {
+    const std::string w = "qr_sensing_noise: ";
+    if (int rc = bind_device(e)) return rc;
+    if (!sensing) return fail(QR_E_INVALID, w + "null sensing bank handle");
+    if (!out_dev) return fail(QR_E_INVALID, w + "out_dev is required");
+    if (envs_per_group < 1) return fail(QR_E_INVALID, w + "envs_per_group must be >= 1");
+    if (K < 1 || K > 65535) return fail(QR_E_INVALID, w + "num_steps must be in [1, 65535]");
+    if (sensing->device != e->cfg.device) return fail(QR_E_INVALID, w + "sensing bank on another GPU");
+    if (slot < 0 || slot >= sensing->capacity) return fail(QR_E_INVALID, w + "slot is outside the sensing bank");
+    if (!sensing_steps_fit(first_step, K)) return fail(QR_E_INVALID, w + "first_step + num_steps must not exceed 2^56");
+    if (!sensing->is_set[(size_t)slot]) return fail(QR_E_STATE, w + "slot " + std::to_string(slot) + " of the sensing bank was never set");
+    if (hipError_t err = qr::launch_sensing_noise(e->cfg.variant, e->P, sensing->d_slots + (size_t)slot * qr::kSensingSlotFloats, envs_per_group, K,
+                                                  noise_seed, first_step, out_dev, (hipStream_t)stream))
+        return fail(QR_E_HIP, w + hipGetErrorString(err));
+    return QR_OK;
 }
 
 // The refusals come first and in full, as in qr_evaluate_policy_grid; the map travels in that call's (policy, condition) array with

@@ -835,6 +835,9 @@ __device__ __forceinline__ float fast_sqrt(float x) {
 // reproduces NominalDyn bit for bit.  The kPk packed forms belong to the one-wave fused rollout and are nominal-only: their packed
 // instructions keep their own literals (eom_e2e refuses kPk with any other source).
 constexpr int kDynE2ECount = 22, kDynINDICount = 12, kDynSlotFloats = 32;   // a bank slot: 128 bytes, entries past the count are zero
+// a slot of a sensing bank (quadrace_eval_sensing.hip): 128 bytes, sigma[0..7], the command delay as an int32 bit pattern, zeros; and the
+// command queue of an env: kMaxDelay commands of 4 floats
+constexpr int kSensingSlotFloats = 32, kMaxDelay = 4, kSensingQueueFloats = 4 * kMaxDelay;
 enum : int {   // E2E
     kEMotorGain = 0, kEMotorOffset,                 // W = gain w + offset: (w_max - w_min) / 2, (w_max + w_min) / 2          R:106-109
     kENegKx, kENegKy,                               // -k_x, -k_y                                                            R:125-126

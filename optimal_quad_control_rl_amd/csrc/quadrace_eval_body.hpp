@@ -36,12 +36,22 @@ constexpr size_t eval_lds_bytes() {
 //   gates_per_lap  passes that make a lap
 //   C, dyn         the coefficients of the equations of motion: NominalDyn<V> (the literals; the default, dyn a dummy) or RuntimeDyn<V> with
 //                  dyn = the set the kernel has loaded into workgroup-uniform registers (quadrace_eval_dynamics.hip)
+//   Sn, sen        what lies between the env and the policy: IdealSensing (the default, sen a dummy: the policy sees the observation of
+//                  the step and its command flies in the step; no code) or a class with kOn (quadrace_eval_sensing.hip), which supplies
+//                  three hooks -- perturb<V, GA>(sen, gid, k, o) in front of the forward, delay(sen) / pending(sen) for the command queue
+//                  between clip_action and step_env -- and kSensingQueueFloats more floats of dynamic LDS per lane behind the lap sums
 // kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
 // for every lane, every lane is an env and every lane stores.
-template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>>
+struct IdealSensing {
+    using Arg = int;
+    static constexpr bool kOn = false;
+};
+
+template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing>
 __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
                                                  const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,
-                                                 int4* __restrict__ rec, float4* __restrict__ recf, typename C::Arg dyn = typename C::Arg()) {
+                                                 int4* __restrict__ rec, float4* __restrict__ recf, typename C::Arg dyn = typename C::Arg(),
+                                                 typename Sn::Arg sen = typename Sn::Arg()) {
     constexpr int L = obs_len<V, GA>();
     using D = PolicyDims<L>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -89,17 +99,50 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
     __syncthreads();
     const uint32_t gid_lo = P.gid_lo + (uint32_t)(active ? rid : 0);
     const uint32_t gid_hi = P.gid_hi + (gid_lo < P.gid_lo ? 1u : 0u);
+    // the command queue (Sn::kOn only): a ring of d = delay commands in the lane's own LDS column behind the lap sums.  The command of
+    // call-step k sits in ring slot k mod d, the same slot for every lane -- a cleared queue is all zeros, so an episode end moves nothing.
+    // The caller's buffer holds it in canonical order (entry j = the command computed j + 1 steps ago), so slot d - 1 - j <- entry j.
+    if constexpr (Sn::kOn) {
+        const int d = Sn::delay(sen);
+        if (d > 0) {
+            float* ring = reinterpret_cast<float*>(laps + 2 * QR_EVAL_MAX_LAPS * kBlock);
+            const float4* pend = reinterpret_cast<const float4*>(Sn::pending(sen)) + (size_t)ii * kMaxDelay;
+#pragma unroll
+            for (int j = 0; j < kMaxDelay; ++j) {
+                if (j < d) {
+                    const float4 c = pend[j];
+                    float* slot = ring + (d - 1 - j) * 4 * kBlock;
+                    slot[0] = c.x; slot[kBlock] = c.y; slot[2 * kBlock] = c.z; slot[3 * kBlock] = c.w;
+                }
+            }
+        }
+    }
+    int ring_pos = 0;   // (Sn::kOn only) k mod d
     bool any_reset = false;
     float stash[reset_value_count<V>()];   // the lane's own next reset draws (reset_from_stash)
     bool stash_ok = false;
     float o[L];
     observe<V, GA>(P, gates, e, o);
     for (int k = 0; k < K; ++k) {
+        if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen, gid_lo, gid_hi, k, o);   // o is rebuilt from the state behind the step
         float mean[4];
         if constexpr (kF32) policy_forward_f32class<L>(W, img_lo, lane, o, mean);
         else policy_forward<L>(W, lane, o, mean);
         float u[4];
         clip_action(mean, u);
+        if constexpr (Sn::kOn) {   // the env flies the command computed d steps ago; this step's command takes its ring slot
+            const int d = Sn::delay(sen);
+            if (d > 0) {
+                float* slot = reinterpret_cast<float*>(laps + 2 * QR_EVAL_MAX_LAPS * kBlock) + ring_pos * 4 * kBlock;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float old = slot[c * kBlock];
+                    slot[c * kBlock] = u[c];
+                    u[c] = old;
+                }
+                ring_pos = ring_pos + 1 == d ? 0 : ring_pos + 1;
+            }
+        }
         const int target_before = e.target;
         bool done, trunc, did_reset;
         const float reward = step_env<V, 0, C>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,
@@ -131,6 +174,13 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
             ret_sum = add_rn(ret_sum, ep_ret);
             ret_sq = add_rn(ret_sq, mul_rn(ep_ret, ep_ret));
             ep_ret = 0.0f;
+            if constexpr (Sn::kOn) {   // the step that ends an episode clears the queue: the next d steps fly (0, 0, 0, 0)
+                if (Sn::delay(sen) > 0) {
+                    float* ring = reinterpret_cast<float*>(laps + 2 * QR_EVAL_MAX_LAPS * kBlock);
+#pragma unroll
+                    for (int q = 0; q < kSensingQueueFloats; ++q) ring[q * kBlock] = 0.0f;
+                }
+            }
         }
         observe<V, GA>(P, gates, e, o);
     }
@@ -149,6 +199,22 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
     row[4] = make_int4(lap_cnt[2], lap_cnt[3], lap_cnt[4], lap_cnt[5]);
     row[5] = make_int4(lap_cnt[6], lap_cnt[7], 0, 0);
     if (recf) recf[i] = make_float4(ep_ret, ret_sum, ret_sq, 0.0f);
+    if constexpr (Sn::kOn) {   // the queue in canonical order: entry j = slot (K - 1 - j) mod d for j < d, zeros behind
+        const int d = Sn::delay(sen);
+        const float* ring = reinterpret_cast<const float*>(laps + 2 * QR_EVAL_MAX_LAPS * kBlock);
+        float4* pend = reinterpret_cast<float4*>(Sn::pending(sen)) + (size_t)i * kMaxDelay;
+#pragma unroll
+        for (int j = 0; j < kMaxDelay; ++j) {
+            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (j < d) {
+                int p = ring_pos - 1 - j;
+                p += p < 0 ? d : 0;
+                const float* slot = ring + p * 4 * kBlock;
+                c = make_float4(slot[0], slot[kBlock], slot[2 * kBlock], slot[3 * kBlock]);
+            }
+            pend[j] = c;
+        }
+    }
     define_exit_values<V>(e);
     P.ts[i] = pack_ts<V>(e);
     store_world<V>(P, i, e);

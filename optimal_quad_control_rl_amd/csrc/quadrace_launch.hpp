@@ -142,6 +142,17 @@ hipError_t launch_eval_policy_dynamics_grid(int variant, const Params& P, const 
                                             hipStream_t st);
 const float* dynamics_nominal(int variant, int* count);
 
+// quadrace_eval_sensing.hip: the same grid with a fourth axis, observation noise and command delay (qr_evaluate_policy_sensing_grid):
+// group g flies policy map[g].x under condition map[g].y as vehicle map[g].z through the sensor of slot map[g].w; sens = slot 0 of
+// [capacity][kSensingSlotFloats]; pending = the command queues [n][kSensingQueueFloats].  launch_sensing_noise (qr_sensing_noise): what
+// the evaluator adds to the observations of the group-local envs 0..envs_per_group-1 under `slot` (a pointer to the slot itself), rows
+// out [K][envs_per_group][obs_len]; K <= 65535
+hipError_t launch_eval_policy_sensing_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
+                                           const float* sens, const int4* map, bool f32class, int num_groups, int envs_per_group, int K,
+                                           uint64_t noise_seed, uint64_t first_step, float* pending, int32_t* rec, float* recf, hipStream_t st);
+hipError_t launch_sensing_noise(int variant, const Params& P, const float* slot, int envs_per_group, int K, uint64_t noise_seed, uint64_t first_step,
+                                float* out, hipStream_t st);
+
 // quadrace_rollout_cond.hip: the closed-loop rollout across a mix of flight conditions (qr_rollout_policy_conditions): the workgroups of
 // group g fly under condition map[g].y (map[g].x is not read); conds = slot 0 of [capacity][kCondSlotFloats]
 hipError_t launch_rollout_policy_cond(int variant, const Params& P, const PolicyArgs& A, const float* conds, const int2* map, int num_groups,

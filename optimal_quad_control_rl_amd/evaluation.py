@@ -330,6 +330,70 @@ def evaluate_dynamics_grid(policies, conditions, dynamics, env, envs_per_cell=25
     return results
 
 
+def evaluate_sensing_grid(policies, conditions, sensing, env, dynamics=None, envs_per_cell=256, n_eval_steps=2000, window_steps=1200, precision=None,
+                          seed=0, noise_seed=0):
+    """evaluate_grid with the sensor as third axis: every cell of `policies` x `conditions` x `sensing` (sensing.SensingParams: noise on
+    the observation the policy sees, a command delay of 0..4 steps), `env.num_envs // envs_per_cell` cells per launch
+    (qr_evaluate_policy_sensing_grid), all flown as ONE vehicle, `dynamics` (a dynamics.DynamicsParams; default: the nominal one).
+    Starts, restarts, entries of `policies`, `precision` and the summaries are evaluate_grid's; all cells see the same uniform draws and,
+    keyed by `noise_seed`, the same normal draws, so two columns differ by their sensor alone.  The command queues are zeroed with each
+    start and the noise stream's step counter runs on across the phases.  The column of SensingParams.ideal() equals
+    evaluate_dynamics_grid's cell for that vehicle.  Returns results[p][c][s], each a {"window", "total"} dict."""
+    import torch
+
+    from .conditions import ConditionBank
+    from .dynamics import DynamicsBank
+    from .policy import MfmaPolicyBank
+    from .sb3 import _unwrap
+    from .sensing import QUEUE_FLOATS, SensingBank
+
+    core = _unwrap(env)
+    E, slots = group_size(envs_per_cell, core.num_envs, "envs_per_cell", "cell")
+    phases = _phases(n_eval_steps, window_steps)
+    conditions, policies, sensing = list(conditions), list(policies), list(sensing)
+    plan = plan_dynamics_batches(len(policies), len(conditions), len(sensing), slots)   # cells (policy, condition, sensor)
+    if dynamics is not None and dynamics.variant != core.VARIANT:
+        raise ValueError("DynamicsParams of another variant than the env")
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        precision = _model_precision([m for _, m in actors])
+    results = [[[None] * len(sensing) for _ in conditions] for _ in actors]
+    pbank = MfmaPolicyBank(core.state_len, len(actors), core.device.index)
+    cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
+    dbank = DynamicsBank(core.VARIANT, 1, core.device.index)
+    sbank = SensingBank(len(sensing), core.device.index)
+    pending = torch.zeros((core.num_envs, QUEUE_FLOATS), dtype=torch.float32, device=core.device)
+    flown = [0]   # steps since the start of the batch: the next launch's first_step
+
+    def start(cells):
+        core.condition_starts(conditions, [c for _, c, _ in cells], E, seed=seed)
+        pending.zero_()
+        flown[0] = 0
+
+    def launch(cells, steps, rec, recf):
+        core.evaluate_sensing_grid_device(pbank, cbank, dbank, sbank, [p for p, _, _ in cells], [c for _, c, _ in cells], [0] * len(cells),
+                                          [s for _, _, s in cells], E, steps, pending, rec, recf, precision=precision, noise_seed=noise_seed,
+                                          first_step=flown[0])
+        flown[0] += int(steps)
+
+    def summarise(cell, rec, recf):
+        return summarize_eval(rec, recf, core.dt, conditions[cell[1]].gates_per_lap)
+
+    try:
+        for p, (actor, _) in enumerate(actors):
+            pbank.load_torch(p, actor)
+        for c, cond in enumerate(conditions):
+            cbank.set(c, cond)
+        dbank.set(0, dynamics)
+        for s, sen in enumerate(sensing):
+            sbank.set(s, sen)
+        for (p, c, s), summaries in fly_batches(plan, start, launch, phases, (REC_INTS, REC_FLOATS), summarise, core.num_envs, E, core.device):
+            results[p][c][s] = _window_total(summaries)
+    finally:
+        _sync_and_close(core, pbank, cbank, dbank, sbank)
+    return results
+
+
 def robustness_table(results, names):
     """evaluate_grid's results[p][c] as one table per policy: a list (per policy) of rows (condition name, crashes per window,
     flying-lap seconds or None, gates per window), in the order of `names` (one name per condition)."""

@@ -716,6 +716,44 @@ class Quadcopter3DGates(_Base):
         self._observe_under(condition_bank.conditions, cond, int(envs_per_group))
         return rec, recf
 
+    def evaluate_sensing_grid_device(self, policy_bank, condition_bank, dynamics_bank, sensing_bank, policy_of_group, condition_of_group,
+                                     dynamics_of_group, sensing_of_group, envs_per_group, num_steps, pending, rec, recf=None,
+                                     precision="f16-operands", noise_seed=0, first_step=0):
+        """evaluate_dynamics_grid_device with a fourth axis, the SENSOR (qr_evaluate_policy_sensing_grid): group g additionally flies
+        through slot sensing_of_group[g] of `sensing_bank` (sensing.SensingBank) -- Gaussian noise on the observation the policy sees,
+        keyed by (`noise_seed`, env_id_base + the env's index within its group, `first_step` + t), and a command delay of 0..4 steps
+        whose queue lives in `pending`, float32 CUDA [N, 16]: zero it with every (re)start, pass it again -- with `first_step` advanced
+        by the steps flown -- to continue.  A group with an ideal slot flies bit for bit what evaluate_dynamics_grid_device flies.
+        Returns (rec, recf)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_evaluate_policy_sensing_grid")
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("policy_of_group, condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        self._check_eval_records(rec, recf)
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy_bank._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, int(maps[0].shape[0]), int(envs_per_group),
+                      *[m.ctypes.data_as(i32p) for m in maps], int(num_steps), flags, int(noise_seed) & (2 ** 64 - 1), int(first_step), _ptr(pending),
+                      _ptr(rec), _ptr(recf), self._stream()))
+        self._observe_under(condition_bank.conditions, maps[1], int(envs_per_group))
+        return rec, recf
+
+    def sensing_noise_device(self, sensing_bank, slot, envs_per_group, num_steps, noise_seed=0, first_step=0, out=None):
+        """What evaluate_sensing_grid_device adds to the observations of a group under slot `slot` (qr_sensing_noise): float32 CUDA
+        [num_steps, envs_per_group, obs_len], row [t, e] = sigma[group(j)] * eps[j] of the group-local env e at step first_step + t, from
+        the device function the evaluator calls.  An all-zero slot gives +0.0."""
+        fn = _lib.require(self._L, "qr_sensing_noise")
+        shape = (int(num_steps), int(envs_per_group), self.state_len)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise AssertionError("out must be a contiguous float32 CUDA tensor [num_steps, envs_per_group, obs_len]")
+        _lib.check(fn(self._h, sensing_bank._h, int(slot), shape[1], shape[0], int(noise_seed) & (2 ** 64 - 1), int(first_step), _ptr(out),
+                      self._stream()))
+        return out
+
     def _under_each_condition(self, conditions, condition_of_group, fn):
         """fn(c) with the HANDLE configured as conditions[c] (track, start, disturbances, max_steps), once per distinct entry of
         condition_of_group in ascending order; the handle's own configuration is restored afterwards, also when fn raises."""
