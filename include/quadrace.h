@@ -59,7 +59,8 @@ extern "C" {
                              qr_ppo_population_exploit (round 18), qr_es_* (round 19),
                              qr_dynamics_* / qr_evaluate_policy_dynamics_grid (round 20),
                              qr_rollout_policy_dynamics / qr_vehicle_physical_count / qr_vehicle_bank_sample (round 21),
-                             qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22) */
+                             qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22),
+                             qr_rollout_policy_sensing (round 23) */
 
 enum {
     QR_OK = 0,
@@ -523,6 +524,43 @@ int qr_rollout_policy_dynamics(qr_env* env, qr_policy* policy, qr_condition_bank
                                uint64_t first_step, int32_t flags, float* obs_out_dev, float* act_out_dev, float* logp_out_dev,
                                float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
                                float* last_obs_dev, void* stream);
+
+/* Closed-loop rollout under OBSERVATION NOISE and COMMAND DELAY in one launch: qr_rollout_policy_dynamics with a sensing bank, a third
+ * HOST map and the command queues, so that a policy trains under the sensor qr_evaluate_policy_sensing_grid measures it with (sensor
+ * randomisation: a sensor per group of envs).  Group g additionally flies through slot sensing_of_group[g] of `sensing`; the slot, the
+ * sigma groups, the Philox stream and the queue are the ones described at qr_sensing_bank above, from the same device functions.  A
+ * 256-env workgroup loads its slot once, ahead of the step loop, and keeps sigma and d in scalar registers; inside the loop there is no
+ * load of a slot value and no atomic, and no workgroup waits for another.
+ * OBSERVATION NOISE: at call-step k the policy is evaluated on o~[j] = add_rn(o[j], mul_rn(sigma[group(j)], eps[j])), and obs_out[k] holds
+ * that NOISY row -- the one act_out[k] and logp_out[k] belong to.  The env's state is untouched.  Counter and key as in the evaluator
+ * with step = first_step + k and ONE deliberate difference: gid is the ORDINARY env id env_id_base + i that the reset stream and the
+ * action noise of this call use, not the group-local id -- training wants independent envs, not common random numbers across groups.
+ * noise_seed keys both streams (each under its own tweak); the action noise is bit for bit qr_rollout_policy_dynamics' for the same
+ * noise_seed and first_step.  last_obs_dev carries the noise of call-step num_steps.
+ * TERMINAL-OBSERVATION ROWS ARE CLEAN: a registered buffer receives the observation of the terminal state without noise, as in every
+ * other entry point.  They feed the time-limit bootstrap only.
+ * COMMAND DELAY: the env flies the clipped command computed d steps earlier, (0, 0, 0, 0) for the first d steps of an episode; act_out[k]
+ * and logp_out[k] remain this step's unclipped sample and its log-prob, rew_out[k] is the reward of the step flown.  pending_dev is the
+ * evaluator's float [n][16], 16-byte aligned, read and written in its canonical order: a buffer passes between the two calls.  Zero it
+ * when the envs are (re)started.
+ * CONTRACT: (1) a group whose slot is ideal (all sigma 0, d = 0) produces bit for bit what qr_rollout_policy_dynamics produces for that
+ * group -- every output, the terminal-observation rows, last_obs and the env state afterwards -- and its rows of pending are written as
+ * zeros.  (2) Group g of a G-group call equals the one-group call on an E-env handle that has env_id_base = this handle's + g E, is
+ * configured with the group's condition and is given the same slots, seed, policy, first_step and rows of pending.  (3) K steps in one
+ * call equal K calls of one step with first_step advanced and pending carried.  (4) last_obs of a call is, bit for bit, row 0 of obs_out
+ * of the next call when that call is given first_step + num_steps.  (5) Terminal-observation rows are clean.
+ * Refused before anything is launched or copied (qr_last_error set; outputs, pending and state untouched): everything
+ * qr_rollout_policy_dynamics refuses, in its order; then the sensing bank's refusals as qr_evaluate_policy_sensing_grid words them --
+ * QR_E_INVALID: NULL sensing bank or map, a sensing bank of another device, an index outside the bank, first_step + num_steps >= 2^56;
+ * QR_E_STATE: a referenced slot that was never set; then QR_E_INVALID: a NULL or misaligned pending_dev; and last QR_E_STATE for new maps
+ * while `stream` is being captured.  The host maps are copied to device arrays the handle owns under the rule of qr_evaluate_policy_grid.
+ * flags: QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS.  qr_last_step_many_ms() reports this launch too. */
+int qr_rollout_policy_sensing(qr_env* env, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                              qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group,
+                              const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t num_steps, const float* log_std,
+                              uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev, float* obs_out_dev,
+                              float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                              float* last_obs_dev, void* stream);
 
 /* Fresh vehicles drawn ON THE DEVICE (the qr_vehicle_* pair works on a qr_dynamics_bank; the qr_dynamics_* names stay the eight entry
  * points of the bank and its table, which work on coefficient tables, while these two work on PHYSICAL parameters): qr_vehicle_bank_sample fills slots [first_slot, first_slot + num_slots) of `bank` with one launch

@@ -12,7 +12,7 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
            "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy",
            "evaluate_dynamics_grid", "DynamicsParams", "DynamicsBank", "physical_sweep", "VehicleRanges",
-           "evaluate_sensing_grid", "SensingParams", "SensingBank", "noise_sweep", "delay_sweep"]
+           "evaluate_sensing_grid", "SensingParams", "SensingBank", "noise_sweep", "delay_sweep", "plan_sensor_mix"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -52,7 +52,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import dynamics
 
         return getattr(dynamics, name)
-    if name in ("SensingParams", "SensingBank", "noise_sweep", "delay_sweep"):  # sensors of the sensing-grid evaluator (qr_sensing_*)
+    if name in ("SensingParams", "SensingBank", "noise_sweep", "delay_sweep", "plan_sensor_mix"):  # sensors of the sensing-grid evaluator (qr_sensing_*) and of PPO(sensing=...)
         from . import sensing
 
         return getattr(sensing, name)

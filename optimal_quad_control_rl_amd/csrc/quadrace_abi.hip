@@ -52,6 +52,7 @@ struct qr_env {
     DeviceTable<qr::PopulationEntry> pop_table;   // qr_rollout_policy_population: the sampling values per group
     DeviceTable<int4> dyn_map;                    // qr_evaluate_policy_dynamics_grid: (policy, condition, dynamics, 0) per group
     DeviceTable<int4> sen_map;                    // qr_evaluate_policy_sensing_grid: (policy, condition, dynamics, sensing) per group
+    DeviceTable<int> rollout_sen_map;             // qr_rollout_policy_sensing: the sensing slot per group (the pair travels in group_map)
 };
 
 // A bank of flight conditions for qr_evaluate_policy_grid: [capacity][qr::kCondSlotFloats] floats on the device, slot s =
@@ -283,9 +284,13 @@ int check_dynamics_indices(const qr_dynamics_bank* dynamics, const int32_t* dyna
 // pad is zero) is already there; another one is copied after a device synchronisation, like the tables (an earlier launch may still
 // read the array), which a stream under capture does not allow.  `noun` / `these`: what the capture refusal calls the table.
 template <typename T>
+bool table_is_current(const qr_env::DeviceTable<T>& t, const std::vector<T>& table) {
+    return t.d && table.size() == t.host.size() && std::memcmp(table.data(), t.host.data(), table.size() * sizeof(T)) == 0;
+}
+template <typename T>
 int upload_table(qr_env::DeviceTable<T>& t, const std::vector<T>& table, hipStream_t st, const char* who, const char* noun, const char* these) {
     const size_t bytes = table.size() * sizeof(T);
-    if (t.d && table.size() == t.host.size() && std::memcmp(table.data(), t.host.data(), bytes) == 0) return QR_OK;
+    if (table_is_current(t, table)) return QR_OK;
     if (qr::stream_is_capturing(st))
         return fail(QR_E_STATE, std::string(who) + ": a new " + noun + " is uploaded after a device synchronisation, which a stream under "
                                                    "capture does not allow; call once with " + these + " outside the capture");
@@ -436,6 +441,7 @@ int qr_destroy(qr_env* e) {
     if (e->pop_table.d) (void)hipFree(e->pop_table.d);
     if (e->dyn_map.d) (void)hipFree(e->dyn_map.d);
     if (e->sen_map.d) (void)hipFree(e->sen_map.d);
+    if (e->rollout_sen_map.d) (void)hipFree(e->rollout_sen_map.d);
     delete e;
     return QR_OK;
 }
@@ -1111,6 +1117,63 @@ int qr_rollout_policy_dynamics(qr_env* e, qr_policy* policy, qr_condition_bank* 
     return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_dynamics(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, e->group_map.d, num_groups,
                                        envs_per_group, K, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev,
                                        last_obs_dev, st));
+}
+
+// qr_rollout_policy_dynamics with the sensing bank, its map and the command queues: that entry point's refusals in its order, then the
+// sensing bank's in the words of qr_evaluate_policy_sensing_grid, then pending_dev, then the copy of the maps.  The (dynamics, condition)
+// pair travels in the handle's group map as in qr_rollout_policy_dynamics, the sensing slots in an array of their own; under capture
+// BOTH must already be on the device, and the test comes before either copy.
+int qr_rollout_policy_sensing(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
+                              int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
+                              const int32_t* sensing_of_group, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags,
+                              float* pending_dev, float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
+                              uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, void* stream) {
+    const char* who = "qr_rollout_policy_sensing";
+    const std::string w = std::string(who) + ": ";
+    if (!e) return fail(QR_E_INVALID, w + "null env handle");
+    if (int rc = check_ready(e)) return rc;
+    qr::PolicyArgs A{};
+    if (int rc = rollout_policy_args(e, policy, K, log_std, noise_seed, first_step, flags, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
+                                     done_out_dev, who, A))
+        return rc;
+    if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
+    if (!condition_of_group) return fail(QR_E_INVALID, w + "the condition map is required");
+    if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
+    if (int rc = check_group_indices(nullptr, nullptr, conditions, condition_of_group, num_groups, who)) return rc;
+    if (!dynamics) return fail(QR_E_INVALID, w + "null dynamics bank handle");
+    if (!dynamics_of_group) return fail(QR_E_INVALID, w + "the dynamics map is required");
+    if (int rc = check_dynamics_bank(e, dynamics, who)) return rc;
+    if (int rc = check_dynamics_indices(dynamics, dynamics_of_group, num_groups, who)) return rc;
+    // the sensing bank's own
+    if (!sensing) return fail(QR_E_INVALID, w + "null sensing bank handle");
+    if (!sensing_of_group) return fail(QR_E_INVALID, w + "sensing_of_group is required");
+    if (sensing->device != e->cfg.device) return fail(QR_E_INVALID, w + "sensing bank on another GPU");
+    for (int g = 0; g < num_groups; ++g)
+        if (sensing_of_group[g] < 0 || sensing_of_group[g] >= sensing->capacity)
+            return fail(QR_E_INVALID, w + "sensing_of_group[" + std::to_string(g) + "] is outside the sensing bank");
+    // last_obs carries the noise of step first_step + num_steps: that step, too, must fit the counter's 56 bits
+    if (!sensing_steps_fit(first_step, K) || first_step + (uint64_t)K == (uint64_t)1 << 56)
+        return fail(QR_E_INVALID, w + "first_step + num_steps must stay below 2^56");
+    for (int g = 0; g < num_groups; ++g)
+        if (!sensing->is_set[(size_t)sensing_of_group[g]])
+            return fail(QR_E_STATE, w + "slot " + std::to_string(sensing_of_group[g]) + " of the sensing bank was never set");
+    if (!pending_dev) return fail(QR_E_INVALID, w + "pending_dev is required");
+    if ((uintptr_t)pending_dev & 15) return fail(QR_E_INVALID, w + "pending_dev must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int2> map((size_t)num_groups);
+    std::vector<int> smap((size_t)num_groups);
+    for (int g = 0; g < num_groups; ++g) {
+        map[(size_t)g] = make_int2(dynamics_of_group[g], condition_of_group[g]);
+        smap[(size_t)g] = sensing_of_group[g];
+    }
+    if (qr::stream_is_capturing(st) && !(table_is_current(e->group_map, map) && table_is_current(e->rollout_sen_map, smap)))
+        return fail(QR_E_STATE, w + "new group maps are uploaded after a device synchronisation, which a stream under capture does not allow; "
+                                    "call once with these maps outside the capture");
+    if (int rc = upload_table(e->group_map, map, st, who, "group map", "this map")) return rc;
+    if (int rc = upload_table(e->rollout_sen_map, smap, st, who, "sensing map", "this map")) return rc;
+    return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_sensing(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, sensing->d_slots,
+                                       e->group_map.d, e->rollout_sen_map.d, num_groups, envs_per_group, K, noise_seed, first_step, pending_dev,
+                                       obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
 }
 
 int qr_vehicle_physical_count(int32_t variant) {

@@ -15,6 +15,7 @@
 #pragma once
 #include "../../include/quadrace.h"
 #include "quadrace_env_kernels.hpp"
+#include "quadrace_sensing.hpp"
 
 namespace qr {
 
@@ -36,17 +37,12 @@ constexpr size_t eval_lds_bytes() {
 //   gates_per_lap  passes that make a lap
 //   C, dyn         the coefficients of the equations of motion: NominalDyn<V> (the literals; the default, dyn a dummy) or RuntimeDyn<V> with
 //                  dyn = the set the kernel has loaded into workgroup-uniform registers (quadrace_eval_dynamics.hip)
-//   Sn, sen        what lies between the env and the policy: IdealSensing (the default, sen a dummy: the policy sees the observation of
-//                  the step and its command flies in the step; no code) or a class with kOn (quadrace_eval_sensing.hip), which supplies
+//   Sn, sen        what lies between the env and the policy (quadrace_sensing.hpp): IdealSensing (the default, sen a dummy: the policy sees
+//                  the observation of the step and its command flies in the step; no code) or RuntimeSensing, which supplies
 //                  three hooks -- perturb<V, GA>(sen, gid, k, o) in front of the forward, delay(sen) / pending(sen) for the command queue
 //                  between clip_action and step_env -- and kSensingQueueFloats more floats of dynamic LDS per lane behind the lap sums
 // kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
 // for every lane, every lane is an env and every lane stores.
-struct IdealSensing {
-    using Arg = int;
-    static constexpr bool kOn = false;
-};
-
 template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing>
 __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
                                                  const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,

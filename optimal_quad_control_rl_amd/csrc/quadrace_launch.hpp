@@ -171,6 +171,14 @@ hipError_t launch_dynamics_sample(int variant, float* slots, int first_slot, int
                                   uint64_t draw, hipStream_t st);
 const char* const* dynamics_physical_names(int variant, int* count);
 
+// quadrace_rollout_sensing.hip: the vehicle-mix rollout under observation noise and command delay (qr_rollout_policy_sensing): group g
+// additionally flies through the sensor of slot sen_map[g]; sens = slot 0 of [capacity][kSensingSlotFloats]; pending = the command
+// queues [n][kSensingQueueFloats], read and written; the observation noise is keyed by (noise_seed, ordinary env id, first_step + k)
+hipError_t launch_rollout_policy_sensing(int variant, const Params& P, const PolicyArgs& A, const float* conds, const float* dyns, const float* sens,
+                                         const int2* map, const int* sen_map, int num_groups, int envs_per_group, int K, uint64_t noise_seed,
+                                         uint64_t first_step, float* pending, float* obs, float* act, float* logp, float* rew, uint8_t* done,
+                                         uint8_t* trunc, float* last_obs, hipStream_t st);
+
 // quadrace_rollout_population.hip: the closed-loop rollout for a population of policies (qr_rollout_policy_population): the workgroups of
 // group g fly policy map[g].x under condition map[g].y and sample with table[g]; A carries the launch-wide step counter, deterministic
 // and f32class only.  One entry = the sampling values of one (log_std, noise seed): 32 bytes, read by one scalar load.

@@ -1,7 +1,8 @@
-// quadrace_rollout_group.hpp -- the ONE kernel behind the three grouped closed-loop rollouts: qr_rollout_policy_conditions
-// (quadrace_rollout_cond.hip, kPop = false), qr_rollout_policy_population (quadrace_rollout_population.hip, kPop = true) and
-// qr_rollout_policy_dynamics (quadrace_rollout_dynamics.hip, kPop = false, kDyn = true).  Included by those three units and by nothing
-// else; each keeps its launch function, its checks and its instantiations.
+// quadrace_rollout_group.hpp -- the ONE kernel behind the four grouped closed-loop rollouts: qr_rollout_policy_conditions
+// (quadrace_rollout_cond.hip, kPop = false), qr_rollout_policy_population (quadrace_rollout_population.hip, kPop = true),
+// qr_rollout_policy_dynamics (quadrace_rollout_dynamics.hip, kPop = false, kDyn = true) and qr_rollout_policy_sensing
+// (quadrace_rollout_sensing.hip, kDyn = true, Sn = RuntimeSensing).  Included by those four units and by nothing else; each keeps its
+// launch function, its checks and its instantiations.
 //
 // K x [obs -> MFMA policy -> a = mean + std * eps -> env.step(clip(a))] with the rollout rows, the terminal-observation rows, last_obs
 // and the end-of-kernel state write-back of rollout_policy_kernel (quadrace_env_kernels.hpp), and the inputs of eval_policy_grid_kernel
@@ -34,6 +35,28 @@
 //                  the table).  `dyns` is the LAST parameter: the arguments of the two older modes keep their offsets and neighbours,
 //                  and those modes pass it as null.  The residual networks and the observation stay the env's: the vehicle is not
 //                  observed.
+//   Sn = RuntimeSensing   (with kDyn = true only; qr_rollout_policy_sensing) the vehicle mode with a SENSOR per group (quadrace_sensing.hpp:
+//                  the slot, the stream and the device functions are the sensing-grid evaluator's).  The workgroup loads slot
+//                  sen_map[grp] of the sensing bank once, in the prologue (load_sensing): sigma and the delay d stay in scalar registers,
+//                  no load of a slot value in the step loop.
+//                  OBSERVATION NOISE: at call-step k the row o is perturbed in place BEFORE the forward, o~[j] = add_rn(o[j],
+//                  mul_rn(sigma[group(j)], eps[j])), so obs_slice stores the NOISY row to obs_out[k] -- the row the action and its
+//                  log-prob belong to -- and observe() rebuilds o from the untouched state behind the step.  The Philox counter's env
+//                  id is the ORDINARY id gid this kernel already uses (not the evaluator's group-local one: training wants
+//                  independent envs), step = first_step + k, the key the sensing tweak of the seed: the action-noise stream (its own
+//                  tweak) does not move.  A slot with all sigmas zero draws nothing (workgroup-uniform branch).  last_obs is
+//                  perturbed with k = K before it is stored: bit for bit row 0 of the next launch called with first_step + K.
+//                  TERMINAL-OBSERVATION ROWS STAY CLEAN, by decision: store_terminal_obs writes the observation of the terminal
+//                  state as in every other mode.  These rows feed the time-limit bootstrap only, and a second noise draw on divergent
+//                  lanes (a few lanes per thousand steps) is not worth its instructions in every step.
+//                  COMMAND DELAY: the env flies the clipped command computed d steps earlier, (0, 0, 0, 0) for the first d steps of an
+//                  episode; act_out[k] / logp_out[k] stay this step's unclipped sample and its log-prob, rew_out[k] is the reward of
+//                  the step flown.  The queue is eval_policy_body's: a ring of clipped commands in the lane's own LDS column behind
+//                  the observation tiles (kSensingQueueFloats * kBlock more floats of dynamic LDS), slot k mod d, cleared by the step
+//                  that ends an episode, read from and written back to `pending` [n][16] in canonical order (entry j = the command
+//                  computed j + 1 steps ago, zeros behind d), so a buffer passes between the evaluator and this kernel.
+//                  sens, sen_map, pending and stream come AFTER dyns: every older mode keeps its argument offsets and passes nulls.
+//                  No atomics, no workgroup that waits for another.
 // Unlike the grid evaluator the reset stream and the action noise are keyed by the handle's ORDINARY env ids (P.gid + i): training
 // wants independent envs, not common random numbers across groups.  Group g therefore computes what an E-env handle with
 // env_id_base + g E, configured with the group's condition, computes under qr_rollout_policy with the group's weights, log_std and seed
@@ -49,19 +72,23 @@
 #pragma once
 #include "quadrace_env_kernels.hpp"
 #include "quadrace_launch.hpp"
+#include "quadrace_sensing.hpp"
 
 namespace qr {
 
 // conds: slot 0 of the condition bank; map[g] = (policy, condition) of group g; wgs_per_group = E / kBlock; kPop: bank / bank_lo = image 0
-// of the two policy arrays, table[g] = sampling arguments of group g; kDyn: dyns = slot 0 of the dynamics bank, map[g] = (dynamics, condition)
-template <int V, int GA, bool kF32, bool kPop, bool kDyn = false>
+// of the two policy arrays, table[g] = sampling arguments of group g; kDyn: dyns = slot 0 of the dynamics bank, map[g] = (dynamics, condition);
+// Sn::kOn: sens = slot 0 of the sensing bank, sen_map[g] = the sensing slot of group g, pending = the command queues [n][kSensingQueueFloats]
+template <int V, int GA, bool kF32, bool kPop, bool kDyn = false, class Sn = IdealSensing>
 __global__ void __launch_bounds__(kBlock, 1)
 rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ bank, const half8* __restrict__ bank_lo,
                             const float* __restrict__ conds, const int2* __restrict__ map, const PopulationEntry* __restrict__ table,
                             int wgs_per_group, int K, float* __restrict__ obs_out, float4* __restrict__ act_out,
                             float* __restrict__ logp_out, float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
-                            uint8_t* __restrict__ trunc_out, float* __restrict__ last_obs_out, const float* __restrict__ dyns) {
+                            uint8_t* __restrict__ trunc_out, float* __restrict__ last_obs_out, const float* __restrict__ dyns,
+                            const float* __restrict__ sens, const int* __restrict__ sen_map, float* __restrict__ pending, SensingStream stream) {
     static_assert(!(kPop && kDyn), "the vehicle mode is a single-policy mode");
+    static_assert(!Sn::kOn || kDyn, "the sensing mode is a mode of the vehicle mode");
     constexpr int L = obs_len<V, GA>();
     using D = PolicyDims<L>;
     using C = std::conditional_t<kDyn, RuntimeDyn<V>, NominalDyn<V>>;   // where the step takes the coefficients of the equations of motion from
@@ -99,6 +126,14 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         S.seed_lo = A.seed_lo;
         S.seed_hi = A.seed_hi;
     }
+    std::conditional_t<Sn::kOn, SensingRegs, int> sen{};   // Sn::kOn: the group's sensor, sigma and delay in scalar registers; else a dummy
+    typename Sn::Arg sen_arg;
+    if constexpr (Sn::kOn) {
+        load_sensing(sens + (size_t)sen_map[grp] * kSensingSlotFloats, stream, pending, sen);
+        sen_arg = &sen;
+    } else {
+        sen_arg = 0;
+    }
     typename C::Arg dyn_arg;   // NominalDyn: a dummy int, nothing travels; RuntimeDyn: the kernel's own set (everything that takes it is inlined)
     if constexpr (kDyn) dyn_arg = &dyn; else dyn_arg = 0;
     const CondHeader* __restrict__ hdr = reinterpret_cast<const CondHeader*>(cond);
@@ -134,12 +169,34 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
     const size_t n = (size_t)P.n;
     const int wave_first = i - lane;
     float* tile = gates + kMaxGates * kGateStride + (threadIdx.x >> 6) * 64 * L;
+    // the command queue (Sn::kOn only), as eval_policy_body keeps it: a ring of d = delay commands in the lane's own LDS column behind the
+    // observation tiles.  The command of call-step k sits in ring slot k mod d, the same slot for every lane -- a cleared queue is all
+    // zeros, so an episode end moves nothing.  The caller's buffer holds it in canonical order (entry j = the command computed j + 1 steps
+    // ago), so slot d - 1 - j <- entry j.  Own column only: no barrier.
+    float* ring = gates + kMaxGates * kGateStride + kBlock * L + threadIdx.x;
+    if constexpr (Sn::kOn) {
+        const int d = Sn::delay(sen_arg);
+        if (d > 0) {
+            const float4* pend = reinterpret_cast<const float4*>(Sn::pending(sen_arg)) + (size_t)i * kMaxDelay;
+#pragma unroll
+            for (int j = 0; j < kMaxDelay; ++j) {
+                if (j < d) {
+                    const float4 c = pend[j];
+                    float* slot = ring + (d - 1 - j) * 4 * kBlock;
+                    slot[0] = c.x; slot[kBlock] = c.y; slot[2 * kBlock] = c.z; slot[3 * kBlock] = c.w;
+                }
+            }
+        }
+    }
+    int ring_pos = 0;   // (Sn::kOn only) k mod d
     bool any_reset = false;
     float stash[reset_value_count<V>()];   // the lane's own next reset draws (reset_from_stash)
     bool stash_ok = false;
     float o[L];
     observe<V, GA>(P, gates, e, o);
     for (int k = 0; k < K; ++k) {
+        // the policy's input is the noisy row (and obs_slice stores it); o is rebuilt from the state behind the step
+        if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen_arg, gid_lo, gid_hi, k, o);
         // ---- action noise: rollout_policy_kernel's slices, verbatim (drawn in deterministic mode too and then multiplied out); the
         // Philox key is the group's
         float mean[4];
@@ -203,18 +260,56 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         stream_store(logp_out + (size_t)k * n + i, logp);
         float u[4];
         clip_action(a, u);
+        if constexpr (Sn::kOn) {   // the env flies the command computed d steps ago; this step's command takes its ring slot
+            const int d = Sn::delay(sen_arg);
+            if (d > 0) {
+                float* slot = ring + ring_pos * 4 * kBlock;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float old = slot[c * kBlock];
+                    slot[c * kBlock] = u[c];
+                    u[c] = old;
+                }
+                ring_pos = ring_pos + 1 == d ? 0 : ring_pos + 1;
+            }
+        }
         bool done, trunc, did_reset;
         const float reward = step_env<V, 0, C>(P, gates, rtab, tile, mlp, lane, true, e, u, gid_lo, gid_hi, done, trunc, did_reset,
                                                [&](bool fin) { store_terminal_obs<V, GA>(P, gates, e, (size_t)k * n, i, fin); },
                                                [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); },
                                                dyn_arg);
         any_reset |= did_reset;
+        if constexpr (Sn::kOn) {   // the step that ends an episode clears the queue: the next d steps fly (0, 0, 0, 0)
+            if (done && Sn::delay(sen_arg) > 0) {
+#pragma unroll
+                for (int q = 0; q < kSensingQueueFloats; ++q) ring[q * kBlock] = 0.0f;
+            }
+        }
         stream_store(rew_out + (size_t)k * n + i, reward);
         stream_store(done_out + (size_t)k * n + i, (uint8_t)(done ? 1 : 0));
         if (trunc_out) stream_store(trunc_out + (size_t)k * n + i, (uint8_t)(trunc ? 1 : 0));
         observe<V, GA>(P, gates, e, o);
     }
+    if constexpr (Sn::kOn) {
+        // last_obs is what the policy sees next: the noise of call-step K, row 0 of a launch with first_step + K
+        if (last_obs_out) Sn::template perturb<V, GA>(sen_arg, gid_lo, gid_hi, K, o);
+    }
     if (last_obs_out) store_obs_coalesced<V, GA>(tile, last_obs_out, (size_t)wave_first, lane, o);
+    if constexpr (Sn::kOn) {   // the queue in canonical order: entry j = slot (K - 1 - j) mod d for j < d, zeros behind
+        const int d = Sn::delay(sen_arg);
+        float4* pend = reinterpret_cast<float4*>(Sn::pending(sen_arg)) + (size_t)i * kMaxDelay;
+#pragma unroll
+        for (int j = 0; j < kMaxDelay; ++j) {
+            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (j < d) {
+                int p = ring_pos - 1 - j;
+                p += p < 0 ? d : 0;
+                const float* slot = ring + p * 4 * kBlock;
+                c = make_float4(slot[0], slot[kBlock], slot[2 * kBlock], slot[3 * kBlock]);
+            }
+            pend[j] = c;
+        }
+    }
     define_exit_values<V>(e);
     P.ts[i] = pack_ts<V>(e);
     store_world<V>(P, i, e);

@@ -419,7 +419,8 @@ class PPO:
                  learning_rate=3e-4, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, net_arch=(120, 120, 120),
                  log_std_init=0.0, seed=0, target_kl=None, lr_final_frac=1.0, total_timesteps_hint=None,
                  fused_collect=False, native_update=False, truncation_bootstrap=True, policy_forward="torch", update_precision="f16-operands",
-                 conditions=None, envs_per_group=256, condition_weights=None, dynamics=None, dynamics_of_group=None, resample_every=None):
+                 conditions=None, envs_per_group=256, condition_weights=None, dynamics=None, dynamics_of_group=None, resample_every=None,
+                 sensing=None, sensing_of_group=None):
         self.env = env
         self.n_envs, self.dev = env.num_envs, env.device
         self.n_steps, self.n_epochs = n_steps, n_epochs
@@ -474,6 +475,14 @@ class PPO:
             plan_vehicle_ensemble(env.VARIANT, self.n_envs, self.envs_per_group, dynamics, dynamics_of_group, resample_every)
         elif dynamics_of_group is not None or resample_every is not None:
             raise ValueError("dynamics_of_group and resample_every belong to `dynamics`")
+        if sensing is not None:   # (likewise: described below, where the bank is built)
+            if not fused_collect or self._q3:
+                raise ValueError("sensing needs fused_collect=True on a race env: the sensor exists in the closed-loop kernel only")
+            from .sensing import plan_sensor_mix
+
+            plan_sensor_mix(self.n_envs, self.envs_per_group, sensing, sensing_of_group)
+        elif sensing_of_group is not None:
+            raise ValueError("sensing_of_group belongs to `sensing`")
         if conditions is not None:
             if not fused_collect:
                 raise ValueError("conditions need fused_collect=True: the mix of conditions exists in the closed-loop kernel only")
@@ -497,6 +506,20 @@ class PPO:
         self._vehicle_seed = int(seed)
         if dynamics is not None:
             self._set_dynamics(dynamics, dynamics_of_group, resample_every)
+        # sensing (a list of sensing.SensingParams): the collect phase flies under OBSERVATION NOISE and COMMAND DELAY in one launch
+        # (qr_rollout_policy_sensing), a sensor per group of envs_per_group envs, group g through sensor sensing_of_group[g] (default
+        # g % S) -- sensor randomisation with the sensors evaluate_sensing_grid measures a checkpoint under.  Composes with `conditions`
+        # and `dynamics`; without `dynamics` every group flies the nominal vehicle (a one-slot bank built here).  The trainer owns the
+        # command queues (`_pending`, [N, 16]): carried from rollout to rollout, zeroed wherever the env is reset, checkpointed.
+        # THE VALUE NETWORK SEES WHAT THE POLICY SEES: buf_obs holds the noisy rows the actions were sampled from, so V(s_t) and the
+        # update's log-probs are functions of the same input; last_obs -- the bootstrap of the last row -- carries the noise of the next
+        # step, bit for bit the first row of the next rollout; the terminal-observation rows of time-limit ends are CLEAN (the kernel
+        # draws no second noise row on the few lanes that end an episode), so that one bootstrap term is evaluated on the exact state.
+        # The delay is not observed: rewards arrive for the command of d steps ago, which PPO treats as part of the environment.
+        self.sensing = self.sensing_of_group = self._sen_bank = self._pending = None
+        if sensing is not None:
+            self._set_sensing(list(sensing), sensing_of_group)
+            self._pending = env.new_sensing_queue()   # the env was reset above
         # on-device episode statistics (what VecMonitor provides in the reference, R:769)
         self.ep_ret = torch.zeros(N, **f32)
         self.ep_len = torch.zeros(N, **f32)
@@ -582,6 +605,41 @@ class PPO:
         self._veh_ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)   # running episodes, carried between rollouts
         self._veh_len = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)
 
+    def _set_sensing(self, sensing, sensing_of_group):
+        """The mix of sensors of collect_fused: the list, the group map, the device bank, and -- without `dynamics` -- a one-slot
+        dynamics bank that holds the nominal vehicle (and, without `conditions`, the one-slot condition bank of the env's own
+        configuration, as _set_dynamics builds it)."""
+        from .conditions import Condition, ConditionBank
+        from .dynamics import DynamicsBank
+        from .sensing import SensingBank, plan_sensor_mix
+
+        self.sensing_of_group, self._sensor_names = plan_sensor_mix(self.n_envs, self.envs_per_group, sensing, sensing_of_group)
+        self.sensing = sensing
+        self._sen_bank = SensingBank(len(sensing), self.dev.index)
+        for slot, s in enumerate(sensing):
+            self._sen_bank.set(slot, s)
+        self._own_dyn_bank = None
+        if self._dyn_bank is None:
+            self._own_dyn_bank = DynamicsBank(int(self.env.VARIANT), 1, self.dev.index)
+            self._own_dyn_bank.set(0)   # the nominal table
+        if self.conditions is None and self._own_cond_bank is None:
+            self._own_cond_bank = ConditionBank(int(self.env.VARIANT), 1, self.dev.index)
+            self._own_cond_bank.set(0, Condition.from_env(self.env))
+        self._sen_ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)   # running episodes, carried between rollouts
+        self._sen_len = torch.zeros(self.n_envs, dtype=torch.float32, device=self.dev)
+
+    def reset_sensing_queue(self):
+        """Zero the command queues: call wherever the env is reset behind the trainer's back (`reset`, `condition_reset`)."""
+        if self._pending is not None:
+            self._pending.zero_()
+
+    @torch.no_grad()
+    def _sensor_stats(self, rew, done, trunc):
+        """stats["per_sensor"]: _group_stats over the sensors"""
+        carry = [self._sen_ret, self._sen_len]
+        self.stats["per_sensor"] = self._group_stats(rew, done, trunc, carry, self.sensing_of_group, self._sensor_names)
+        self._sen_ret, self._sen_len = carry
+
     @torch.no_grad()
     def _condition_stats(self, rew, done, trunc):
         """stats["per_condition"] (see _group_stats)"""
@@ -658,6 +716,13 @@ class PPO:
             self.stats.update({"ep_rew_mean": f[0] / f[3], "ep_len_mean": f[1] / f[3], self._gates_key: f[2] / f[3], "episodes": f[3]})
         self.stats["reward_per_step"] = float(rew.mean())
 
+    def _resample_vehicles(self):
+        """Ahead of a rollout over the dynamics bank: count it, and draw the ensemble again when its period has come."""
+        if self.vehicle_ranges is not None and self.resample_every and self._dyn_rollouts and self._dyn_rollouts % self.resample_every == 0:
+            self._resamples += 1   # one launch, stream-ordered before the rollout; envs mid-episode change vehicle (see __init__)
+            self._dyn_bank.sample(self.vehicle_ranges, 0, len(self.dynamics_of_group), seed=self._vehicle_seed, draw=self._resamples)
+        self._dyn_rollouts += 1
+
     @torch.no_grad()
     def collect_fused(self):
         self._mfma.load_torch(self.policy.pi)
@@ -666,12 +731,24 @@ class PPO:
         kw = dict(noise_seed=self.noise_seed, first_step=first_step,
                   out=(self.buf_obs, self.buf_act, self.buf_lp, self.buf_rew, self._done_u8, self._trunc_u8),
                   precision="f32" if self.policy_forward == "f32class" else "f16-operands")
-        if self._dyn_bank is not None:
+        if self._sen_bank is not None:
+            # a mix of sensors, under the mix of conditions / vehicles or the env's own configuration and the nominal vehicle in every group
+            groups = len(self.sensing_of_group)
+            mixed, vehicles = self.conditions is not None, self._dyn_bank is not None
+            if vehicles:
+                self._resample_vehicles()
+            obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_sensing_device(
+                self._mfma, self._cond_bank if mixed else self._own_cond_bank, self.condition_of_group if mixed else [0] * groups,
+                self._dyn_bank if vehicles else self._own_dyn_bank, self.dynamics_of_group if vehicles else [0] * groups,
+                self._sen_bank, self.sensing_of_group, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
+            if mixed:
+                self._condition_stats(rew, done, trunc)
+            if vehicles:
+                self._vehicle_stats(rew, done, trunc)
+            self._sensor_stats(rew, done, trunc)
+        elif self._dyn_bank is not None:
             # a mix of vehicles, under the mix of conditions or under the env's own configuration in every group
-            if self.vehicle_ranges is not None and self.resample_every and self._dyn_rollouts and self._dyn_rollouts % self.resample_every == 0:
-                self._resamples += 1   # one launch, stream-ordered before the rollout; envs mid-episode change vehicle (see __init__)
-                self._dyn_bank.sample(self.vehicle_ranges, 0, len(self.dynamics_of_group), seed=self._vehicle_seed, draw=self._resamples)
-            self._dyn_rollouts += 1
+            self._resample_vehicles()
             mixed = self.conditions is not None
             obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_dynamics_device(
                 self._mfma, self._cond_bank if mixed else self._own_cond_bank,
@@ -1010,6 +1087,10 @@ class PPO:
                   conditions=self._conditions_state())
         if self._dyn_bank is not None:   # without `dynamics` the keys are what they always were
             sd["dynamics"] = self._dynamics_state()
+        if self._sen_bank is not None:   # likewise: a key of its own, present with `sensing` only
+            sd["sensing"] = dict(slots=[s.pack() for s in self.sensing], names=list(self._sensor_names),
+                                 sensing_of_group=list(self.sensing_of_group), envs_per_group=int(self.envs_per_group),
+                                 pending=self._pending.cpu(), ep_ret=self._sen_ret.cpu(), ep_len=self._sen_len.cpu())
         return sd
 
     def _dynamics_state(self):
@@ -1093,5 +1174,18 @@ class PPO:
             self._veh_ret.copy_(ds["ep_ret"]); self._veh_len.copy_(ds["ep_len"])
         else:
             self.dynamics = self.dynamics_of_group = self.vehicle_ranges = self._dyn_bank = self._own_cond_bank = None
+        ss = sd.get("sensing")
+        if ss is not None:
+            from .sensing import SensingParams
+
+            if not self.fused_collect:
+                raise ValueError("the checkpoint flies a mix of sensors: construct the PPO with fused_collect=True")
+            self.envs_per_group = int(ss["envs_per_group"])
+            self._set_sensing([SensingParams.unpack(s, n) for s, n in zip(ss["slots"], ss["names"])], ss["sensing_of_group"])
+            self._pending = self.env.new_sensing_queue()
+            self._pending.copy_(ss["pending"])
+            self._sen_ret.copy_(ss["ep_ret"]); self._sen_len.copy_(ss["ep_len"])
+        else:
+            self.sensing = self.sensing_of_group = self._sen_bank = self._pending = None
         self.obs = self.env.states_tensor.clone()
         self._gen.set_state(sd["rng"])

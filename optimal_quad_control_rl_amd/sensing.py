@@ -1,9 +1,10 @@
-"""Sensors for the sensing-grid evaluator (`qr_sensing_*`, `qr_evaluate_policy_sensing_grid`, csrc/quadrace_eval_sensing.hip).
+"""Sensors for the sensing-grid evaluator (`qr_sensing_*`, `qr_evaluate_policy_sensing_grid`, csrc/quadrace_eval_sensing.hip) and for
+training under them (`qr_rollout_policy_sensing`, csrc/quadrace_rollout_sensing.hip, `PPO(sensing=...)`).
 
 A *sensor* is what lies between the env and the policy: white Gaussian noise on the observation the policy sees, one sigma per group of
 observation entries, and a command delay of 0..4 control steps (layout, stream and queue rule: include/quadrace.h).  `SensingParams`
 holds one, `noise_sweep` / `delay_sweep` build the two curves a user asks for first, `SensingBank` is the device bank.  Everything but
-`SensingBank` needs neither torch nor a GPU."""
+`SensingBank` needs neither torch nor a GPU; `plan_sensor_mix` is what `PPO(sensing=...)` decides on the host."""
 import ctypes as C
 
 import numpy as np
@@ -88,6 +89,32 @@ def noise_sweep(base, scales):
 def delay_sweep(base, delays):
     """[base.with_delay(d) for d in delays]: one sensor per command delay, the sigmas of `base` in all."""
     return [base.with_delay(d) for d in delays]
+
+
+def plan_sensor_mix(n_envs, envs_per_group, sensing, sensing_of_group=None):
+    """Everything `PPO(sensing=...)` decides on the host, checked before a device is touched: (the group map, one name per bank slot).
+    `sensing` is a non-empty list of SensingParams, one bank slot each; group g of `envs_per_group` envs flies through sensor
+    sensing_of_group[g] (default g % S: round-robin; fewer groups than sensors is an error, as for a fixed ensemble of vehicles)."""
+    n, e = int(n_envs), int(envs_per_group)
+    if e < 256 or e % 256 != 0:
+        raise ValueError("envs_per_group must be a multiple of 256, at least 256 (one workgroup serves one group)")
+    if n < e or n % e != 0:
+        raise ValueError("num_envs must be a whole number of groups of envs_per_group envs")
+    groups = n // e
+    if isinstance(sensing, SensingParams):
+        raise ValueError("sensing must be a non-empty list of SensingParams (one sensor: [sensor])")
+    sensors = list(sensing)
+    if not sensors or not all(isinstance(s, SensingParams) for s in sensors):
+        raise ValueError("sensing must be a non-empty list of SensingParams")
+    if sensing_of_group is None:
+        if groups < len(sensors):
+            raise ValueError("%d groups cannot fly %d sensors: lower envs_per_group or pass fewer sensors" % (groups, len(sensors)))
+        sog = [g % len(sensors) for g in range(groups)]
+    else:
+        sog = [int(s) for s in sensing_of_group]
+    if len(sog) != groups or any(s < 0 or s >= len(sensors) for s in sog):
+        raise ValueError("sensing_of_group must name one of the %d sensors for each of the %d groups" % (len(sensors), groups))
+    return sog, [s.name for s in sensors]
 
 
 class SensingBank:

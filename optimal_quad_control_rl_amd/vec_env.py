@@ -888,6 +888,43 @@ class Quadcopter3DGates(_Base):
         self._last_obs = self._obs
         return obs, act, logp, rew, done, trunc, self._obs
 
+    def new_sensing_queue(self):
+        """The command queues of rollout_policy_sensing_device / evaluate_sensing_grid_device for a freshly (re)started env: a zeroed
+        float32 CUDA tensor [num_envs, 16]."""
+        return torch.zeros((self.num_envs, 16), dtype=torch.float32, device=self.device)
+
+    def rollout_policy_sensing_device(self, policy, condition_bank, condition_of_group, dynamics_bank, dynamics_of_group, sensing_bank,
+                                      sensing_of_group, envs_per_group, num_steps, log_std, pending, noise_seed=0, first_step=0,
+                                      deterministic=False, out=None, precision="f16-operands"):
+        """rollout_policy_dynamics_device under OBSERVATION NOISE and COMMAND DELAY in ONE kernel (qr_rollout_policy_sensing): group g
+        additionally flies through slot sensing_of_group[g] of `sensing_bank` (sensing.SensingBank), the sensor of
+        evaluate_sensing_grid_device -- but keyed by the env's ORDINARY ids (`noise_seed`, env_id_base + i, `first_step` + k).  The
+        returned obs rows and last_obs are the NOISY rows the policy saw; the terminal-observation rows stay clean; actions and
+        log-probs are this step's sample, the reward is that of the step flown (with the command of d steps ago).  `pending`, float32
+        CUDA [num_envs, 16] (new_sensing_queue), carries the command queues from call to call: zero it with every (re)start, pass it
+        again with `first_step` advanced by the steps flown to continue.  A group with an ideal slot computes bit for bit what
+        rollout_policy_dynamics_device computes.  Everything else -- groups, return tuple, terminal-observation buffer -- as
+        rollout_policy_dynamics_device."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_rollout_policy_sensing")
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        if out is None:
+            out = rollout_outputs(K, n, self.state_len, dev)
+        obs, act, logp, rew, done, trunc = out
+        ls = log_std_array(log_std)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, int(maps[0].shape[0]), int(envs_per_group),
+                      *[m.ctypes.data_as(i32p) for m in maps], K, _f32p(ls), int(noise_seed) & (2 ** 64 - 1), int(first_step),
+                      int(bool(deterministic)) | flags, _ptr(pending), _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew), _ptr(done), _ptr(trunc),
+                      _ptr(self._obs), self._stream()))
+        self._last_obs = self._obs
+        return obs, act, logp, rew, done, trunc, self._obs
+
     def rollout_policy_population_device(self, bank, policy_of_group, condition_bank, condition_of_group, envs_per_group, num_steps, log_stds,
                                          noise_seeds, first_step=0, deterministic=False, out=None, precision="f16-operands"):
         """rollout_policy_conditions_device for a POPULATION of policies in ONE kernel (qr_rollout_policy_population): group g = envs

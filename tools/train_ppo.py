@@ -11,6 +11,10 @@ final policy's robustness table over the same conditions (evaluate_grid).
 --vehicle-spread S [--resample-every R] (with --fused): the collect phase flies an ENSEMBLE of vehicles, one per group of envs, drawn on
 the device within 1 +- S of the identified parameters (PPO(dynamics=VehicleRanges(...)) -> qr_rollout_policy_dynamics); --eval-final then
 prints the final policy's reality-gap table (evaluate_dynamics_grid over a physical_sweep of three parameters across 1 +- S).
+--obs-noise SIGMA[,...8] [--delay D[,D...]] (with --fused): the collect phase flies under observation noise and command delay
+(PPO(sensing=...) -> qr_rollout_policy_sensing): one sensor per delay value (default 0), round-robin over the groups, every sensor with
+the given sigmas (one value for all eight groups of observation entries, or eight; default none).  The log then carries one line per
+sensor, and --eval-final prints the final policy's table over the training sensors plus the ideal one (evaluate_sensing_grid).
 
 Prints training progress and a final deterministic evaluation on the 4-gate square track: gates per 12 s from a standing
 start, and lap times the way the reference tabulates them (FP:3474-3488: lap 1 from the start, then the flying laps; its
@@ -19,6 +23,7 @@ import argparse, os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from robustness_sweep import condition_name, format_table, parse_scales, parse_tracks   # the sweep tool's argument forms and table
+from sensing_sweep import parse_delays, parse_sigma                                      # likewise: --obs-noise is its --base-sigma
 
 
 def train_conditions(env, variant, scales=None, tracks=None):
@@ -40,6 +45,18 @@ def train_conditions(env, variant, scales=None, tracks=None):
         base = Condition.from_env(env, name=t, gate_pos=gate_pos, gate_yaw=gate_yaw, start_pos=start_pos)
         conds += [base] if scales is None else [base.replace(name=condition_name(t, s), disturbance_scale=s) for s in scales]
     return conds
+
+
+def train_sensors(obs_noise="", delay=""):
+    """The sensors of --obs-noise / --delay (their texts, "" = not given): None without either; otherwise one SensingParams per delay
+    value (default: 0), each with the sigmas of --obs-noise (default: none), named "d=<delay>"."""
+    from optimal_quad_control_rl_amd.sensing import SensingParams
+
+    if not obs_noise and not delay:
+        return None
+    sigma = parse_sigma(obs_noise) if obs_noise else [0.0] * 8
+    delays = parse_delays(delay) if delay else [0]
+    return [SensingParams("d=%d" % d, *sigma, delay_steps=d) for d in delays]
 
 
 def format_condition_stats(per_condition):
@@ -87,6 +104,12 @@ def main():
                          "identified value (PPO(dynamics=VehicleRanges(variant, S)) -> qr_rollout_policy_dynamics)")
     ap.add_argument("--resample-every", type=int, default=0,
                     help="with --vehicle-spread: draw the ensemble again before every R-th rollout (envs mid-episode change vehicle); 0: drawn once")
+    ap.add_argument("--obs-noise", default="", metavar="SIGMA[,...8]",
+                    help="with --fused: train under white Gaussian noise on the observation the policy sees, one sigma for all eight groups of "
+                         "entries or eight (position, velocity, attitude, body rates, actuator state, gate position, gate yaw, disturbances)")
+    ap.add_argument("--delay", default="", metavar="D[,D...]",
+                    help="with --fused: train under a command delay of D control steps (0..4); a list gives one sensor per value, round-robin "
+                         "over the groups (PPO(sensing=...) -> qr_rollout_policy_sensing)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
 
@@ -119,11 +142,14 @@ def main():
         ranges = VehicleRanges(env.VARIANT, a.vehicle_spread)
     elif a.resample_every:
         raise SystemExit("--resample-every belongs to --vehicle-spread")
+    sensors = train_sensors(a.obs_noise, a.delay)
+    if sensors is not None and not a.fused:
+        raise SystemExit("--obs-noise / --delay need --fused: the sensor exists in the closed-loop kernel only")
     model = PPO(env, seed=a.seed, ent_coef=a.ent_coef, gamma=a.gamma, n_steps=a.n_steps, n_epochs=a.epochs, batch_size=a.envs * a.n_steps // a.minibatches, learning_rate=a.lr,
                 target_kl=a.target_kl, lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps) // world, fused_collect=a.fused,
                 native_update=a.native_update, truncation_bootstrap=not a.no_trunc_bootstrap,
                 policy_forward="f32class" if a.precision != "f16-operands" else "torch", update_precision="f32" if a.precision == "f32" else "f16-operands",
-                conditions=conds, envs_per_group=a.envs_per_group, dynamics=ranges, resample_every=a.resample_every or None)
+                conditions=conds, envs_per_group=a.envs_per_group, dynamics=ranges, resample_every=a.resample_every or None, sensing=sensors)
     if "RANK" in os.environ:
         model._updater.broadcast_parameters(0)   # identical start on every rank (the seed already makes it so; this guarantees it)
         model.noise_seed = a.seed                 # same key, different global env ids -> independent action noise per rank
@@ -200,6 +226,8 @@ def main():
         it_no[0] += 1
         if conds is not None and it_no[0] % 20 == 0:   # under the trainer's own log line (log_every=20 below)
             print(format_condition_stats(m.stats["per_condition"]), flush=True)
+        if sensors is not None and it_no[0] % 20 == 0:
+            print(format_condition_stats(m.stats["per_sensor"]), flush=True)
         if a.curve and it_no[0] % a.curve == 0 and rank == 0:
             torch.cuda.synchronize()
             e0 = time.perf_counter()
@@ -255,6 +283,18 @@ def main():
                                                  float(r["window"]["gates_per_window"])), flush=True)
             res["reality_gap"].append(dict(vehicle=v.name, crashes_per_window=float(r["window"]["crashes_per_window"]), flying_lap_seconds=lap,
                                            gates_per_window=float(r["window"]["gates_per_window"])))
+    if sensors is not None:
+        print(format_condition_stats(model.stats["per_sensor"]), flush=True)
+        if a.eval_final and rank == 0:
+            # the FINAL policy through each training sensor and the ideal one, on the evaluation env (nominal vehicle, its own configuration)
+            from optimal_quad_control_rl_amd import Condition, SensingParams, evaluate_sensing_grid
+            ev_sensors = sensors + ([] if any(s.is_ideal for s in sensors) else [SensingParams.ideal()])
+            cells = evaluate_sensing_grid([model], [Condition.from_env(ev)], ev_sensors, ev, envs_per_cell=256, n_eval_steps=2000, window_steps=1200,
+                                          seed=99, noise_seed=a.seed)[0][0]
+            rows = [(s.name, float(r["window"]["crashes_per_window"]), r["total"]["flying_lap_seconds"], float(r["window"]["gates_per_window"]))
+                    for s, r in zip(ev_sensors, cells)]
+            print(format_table("final policy, by sensor", rows).replace("condition", "sensor   ", 1), flush=True)
+            res["sensing"] = [dict(sensor=n, crashes_per_window=cr, flying_lap_seconds=fl, gates_per_window=g) for n, cr, fl, g in rows]
     sk, up_n = res.get("skipped_nonfinite", 0), res.get("updates", 0)
     if sk > 0.002 * max(1, sk + up_n):   # a handful of skips = diverged sims in a minibatch; more means something is wrong
         print(f"WARNING: {sk} of {sk + up_n} minibatch updates were skipped for a non-finite gradient norm", file=sys.stderr, flush=True)
