@@ -60,7 +60,8 @@ extern "C" {
                              qr_dynamics_* / qr_evaluate_policy_dynamics_grid (round 20),
                              qr_rollout_policy_dynamics / qr_vehicle_physical_count / qr_vehicle_bank_sample (round 21),
                              qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22),
-                             qr_rollout_policy_sensing (round 23) */
+                             qr_rollout_policy_sensing (round 23),
+                             qr_rollout_policy_history / qr_evaluate_policy_history_grid (round 24) */
 
 enum {
     QR_OK = 0,
@@ -433,7 +434,8 @@ int qr_evaluate_policy_dynamics_grid(qr_env* env, qr_policy_bank* policies, qr_c
  * the step that ends its episode (auto-reset, crash and time limit alike).  The queue lives across launches in the caller's pending_dev,
  * float [n][16], 16-byte aligned: pending[i][4j..4j+3] is the command computed j + 1 steps ago; entries with j >= d are written as zeros.
  * Zero it when the envs are (re)started.
- * NOT modelled: bias or drift, correlated noise, an estimator that runs slower than the control loop, quantisation.
+ * NOT modelled: bias or drift, correlated noise, an estimator that runs slower than the control loop, quantisation; noise on the entries
+ * of a command history (qr_rollout_policy_history below: the controller knows its own commands).
  * A sensing bank owns one device array [capacity][32 floats] and belongs to no variant.  qr_sensing_bank_set fills slot `slot` from the
  * HOST array sigma8 [8] (NULL = the ideal sensor: all zeros) and `delay`, after synchronising the device like the other setters;
  * QR_E_INVALID: NULL bank, slot outside the bank, a sigma that is negative or not finite, delay outside [0, 4].  qr_sensing_bank_read
@@ -561,6 +563,49 @@ int qr_rollout_policy_sensing(qr_env* env, qr_policy* policy, qr_condition_bank*
                               uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev, float* obs_out_dev,
                               float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
                               float* last_obs_dev, void* stream);
+
+/* COMMAND HISTORY: the two sensing calls for a policy that OBSERVES ITS LAST COMMANDS.  Under a command delay of d control steps the env
+ * flies the command computed d steps ago while the policy sees only the observation of the step: that observation is no Markov state of
+ * the delayed system -- the commands computed and not yet flown are hidden from the network that computed them.  The remedy, for delay
+ * and for unknown actuator lag alike, is to append the last few commands to the policy's input; an onboard controller can do the same,
+ * because it always knows what it sent.
+ * qr_rollout_policy_history is qr_rollout_policy_sensing, and qr_evaluate_policy_history_grid is qr_evaluate_policy_sensing_grid, with
+ * `history` = H directly behind sensing_of_group.  DEFINITION (both calls):
+ *   RANGE     H in [1, 4 - gates_ahead].  The policy's row at call-step k is [ o~_k | h_k ] of L' = L + 4 H floats, L = qr_obs_len(env).
+ *             L + 4 H is the observation length of an env with gates_ahead + H gates ahead, and for gates_ahead + H <= 4 that is a
+ *             length every network kernel of the library exists for: `policy` (the bank) is created with obs_len = L', and the policy
+ *             forward, the PPO update, the bank loader and ES run on it unchanged.  That is the reason for the bound.
+ *   SENSOR    o~_k is exactly what the sensing call feeds: the env's observation with the slot's noise -- stream, key, counter and sigma
+ *             groups unchanged.  The noise touches the first L entries only; the history part is exact.
+ *   HISTORY   h_k = (u_{k-1}, u_{k-2}, ..., u_{k-H}), newest first, four floats each: the clipped commands COMPUTED at those steps of the
+ *             current episode -- the computed ones, not the flown ones -- and zeros for steps before the episode's start.
+ *   END       the step that ends an episode clears the history together with the queue: one event.
+ *   TERMINAL  rows are L' wide: [ clean observation of the terminal state | u_k, u_{k-1}, ..., u_{k-H+1} ], what the policy would have seen
+ *             next had the episode gone on (the first part clean, as in the sensing call).  In qr_rollout_policy_history the buffer
+ *             registered with qr_set_terminal_obs is read as [rows][N][L'].  obs_out_dev is [num_steps][N][L'], last_obs_dev [N][L'].
+ *   PENDING   pending_dev [n][16] keeps its canonical layout and carries max(d, H) entries: entry j < max(d, H) is the clipped command
+ *             computed j + 1 steps ago in this episode, everything behind is zero.  The delay still flies entry d - 1.  d (per group,
+ *             from the sensing slot) and H (per launch) are independent.  The buffer passes between all four sensing / history calls.
+ * Noise on the history entries is NOT modelled (the list at qr_sensing_bank above).
+ * CONTRACT: (1) K steps in one call equal K calls of one step with first_step advanced through the same pending (and rec / recf).
+ * (2) A group depends only on its (policy,) condition, dynamics and sensing entries and on H.  (3) The action-noise and observation-noise
+ * streams are bit for bit the sensing call's for the same noise_seed and first_step.  (4) The definition above.
+ * A 256-env workgroup keeps the slot values in scalar registers; no load of a slot value in the step loop, no atomics, no workgroup that
+ * waits for another; LDS within the footprint of the sensing call at gates_ahead = 4.
+ * Refused before anything is launched or copied (qr_last_error set; outputs, records, pending and state untouched): everything the sensing
+ * twin refuses, in its order, with two changes: QR_E_INVALID for `history` outside [1, 4 - gates_ahead], directly before the
+ * observation-length comparison; and that comparison requires the policy's (bank's) obs_len == qr_obs_len(env) + 4 * history. */
+int qr_rollout_policy_history(qr_env* env, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                              qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group,
+                              const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t history, int32_t num_steps,
+                              const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev,
+                              float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev,
+                              uint8_t* trunc_out_dev, float* last_obs_dev, void* stream);
+int qr_evaluate_policy_history_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group,
+                                    int32_t history, int32_t num_steps, int32_t flags, uint64_t noise_seed, uint64_t first_step,
+                                    float* pending_dev, int32_t* rec_dev, float* recf_dev, void* stream);
 
 /* Fresh vehicles drawn ON THE DEVICE (the qr_vehicle_* pair works on a qr_dynamics_bank; the qr_dynamics_* names stay the eight entry
  * points of the bank and its table, which work on coefficient tables, while these two work on PHYSICAL parameters): qr_vehicle_bank_sample fills slots [first_slot, first_slot + num_slots) of `bank` with one launch

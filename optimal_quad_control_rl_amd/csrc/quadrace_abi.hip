@@ -657,14 +657,27 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
 }
 
 // What qr_rollout_policy and qr_rollout_policy_conditions refuse about their shared arguments and the handle's mode, in one order; on
-// success A holds the weights and the sampling arguments of the launch.
+// success A holds the weights and the sampling arguments of the launch.  history: null, or the command history of
+// qr_rollout_policy_history -- its range is refused directly before the observation length, which is then the env's + 4 * history.
+static int check_history(const qr_env* e, int history, const char* who) {
+    if (history < 1 || history > 4 - e->cfg.gates_ahead)
+        return fail(QR_E_INVALID, std::string(who) + ": history must be in [1, 4 - gates_ahead] (the row of obs_len + 4 * history floats must be a "
+                                                     "length the policy kernels have: gates_ahead + history <= 4)");
+    return QR_OK;
+}
 static int rollout_policy_args(const qr_env* e, qr_policy* policy, int K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
                                int flags, const float* obs_out_dev, const float* act_out_dev, const float* logp_out_dev,
-                               const float* rew_out_dev, const uint8_t* done_out_dev, const char* who, qr::PolicyArgs& A) {
+                               const float* rew_out_dev, const uint8_t* done_out_dev, const char* who, qr::PolicyArgs& A,
+                               const int32_t* history = nullptr) {
     if (int rc = check_rollout_common(e, K, policy && log_std, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, who)) return rc;
     A = qr::PolicyArgs{};
     if (int rc = qr::fetch_policy_weights(policy, who, A.weights)) return rc;
-    if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, who)) return rc;
+    if (history) {
+        if (int rc = check_history(e, *history, who)) return rc;
+        if (int rc = qr::check_policy_handle(policy, e->L + 4 * *history, e->cfg.device, who, "!= env obs_len + 4 * history")) return rc;
+    } else if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, who)) {
+        return rc;
+    }
     if (flags < 0 || flags > (QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS))
         return fail(QR_E_INVALID, std::string(who) + ": `deterministic` takes QR_ROLLOUT_DETERMINISTIC | QR_ROLLOUT_F32CLASS");
     A.weights_lo = qr::policy_weights_lo(policy);
@@ -1006,13 +1019,13 @@ static bool sensing_steps_fit(uint64_t first_step, int K) {
 }
 
 // qr_evaluate_policy_dynamics_grid with a fourth bank and a fourth map: its refusals in its order, then the sensing bank's.  Nothing is
-// enqueued or copied unless every argument is valid.
-int qr_evaluate_policy_sensing_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
-                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
-                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t K,
-                                    int32_t flags, uint64_t noise_seed, uint64_t first_step, float* pending_dev, int32_t* rec_dev, float* recf_dev,
-                                    void* stream) {
-    const char* who = "qr_evaluate_policy_sensing_grid";
+// enqueued or copied unless every argument is valid.  history: null (qr_evaluate_policy_sensing_grid), or the command history of
+// qr_evaluate_policy_history_grid: its range is refused directly before the bank's observation length, which is then the env's + 4 * history.
+static int evaluate_policy_sensing_grid(const char* who, const int32_t* history, qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions,
+                                        qr_dynamics_bank* dynamics, qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group,
+                                        const int32_t* policy_of_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
+                                        const int32_t* sensing_of_group, int32_t K, int32_t flags, uint64_t noise_seed, uint64_t first_step,
+                                        float* pending_dev, int32_t* rec_dev, float* recf_dev, void* stream) {
     const std::string w = std::string(who) + ": ";
     if (int rc = check_ready(e)) return rc;
     if (!policies) return fail(QR_E_INVALID, w + "null policy bank handle");
@@ -1020,7 +1033,12 @@ int qr_evaluate_policy_sensing_grid(qr_env* e, qr_policy_bank* policies, qr_cond
     if (!dynamics) return fail(QR_E_INVALID, w + "null dynamics bank handle");
     if (!policy_of_group || !condition_of_group || !dynamics_of_group) return fail(QR_E_INVALID, w + "the three group maps are required");
     if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, who)) return rc;
-    if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
+    if (history) {
+        if (int rc = check_history(e, *history, who)) return rc;
+        if (int rc = qr::check_policy_bank(policies, e->L + 4 * *history, e->cfg.device, who, "policy bank", "!= env obs_len + 4 * history")) return rc;
+    } else if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) {
+        return rc;
+    }
     if (int rc = check_condition_groups(e, conditions, num_groups, envs_per_group, who)) return rc;
     if (int rc = check_dynamics_bank(e, dynamics, who)) return rc;
     if (int rc = check_group_indices(policies, policy_of_group, conditions, condition_of_group, num_groups, who)) return rc;
@@ -1043,9 +1061,35 @@ int qr_evaluate_policy_sensing_grid(qr_env* e, qr_policy_bank* policies, qr_cond
     for (int g = 0; g < num_groups; ++g)
         map[(size_t)g] = make_int4(policy_of_group[g], condition_of_group[g], dynamics_of_group[g], sensing_of_group[g]);
     if (int rc = upload_table(e->sen_map, map, st, who, "group map", "this map")) return rc;
+    if (history)
+        return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_history_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
+                                           conditions->d_slots, dynamics->d_slots, sensing->d_slots, e->sen_map.d, *history,
+                                           (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, noise_seed, first_step, pending_dev, rec_dev,
+                                           recf_dev, st));
     return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_sensing_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
                                        conditions->d_slots, dynamics->d_slots, sensing->d_slots, e->sen_map.d, (flags & QR_ROLLOUT_F32CLASS) != 0,
                                        num_groups, envs_per_group, K, noise_seed, first_step, pending_dev, rec_dev, recf_dev, st));
+}
+
+int qr_evaluate_policy_sensing_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t K,
+                                    int32_t flags, uint64_t noise_seed, uint64_t first_step, float* pending_dev, int32_t* rec_dev, float* recf_dev,
+                                    void* stream) {
+    return evaluate_policy_sensing_grid("qr_evaluate_policy_sensing_grid", nullptr, e, policies, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                        policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group, K, flags, noise_seed, first_step,
+                                        pending_dev, rec_dev, recf_dev, stream);
+}
+
+// qr_evaluate_policy_sensing_grid for a bank of policies that observe their last `history` commands
+int qr_evaluate_policy_history_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                    qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                                    const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t history,
+                                    int32_t K, int32_t flags, uint64_t noise_seed, uint64_t first_step, float* pending_dev, int32_t* rec_dev,
+                                    float* recf_dev, void* stream) {
+    return evaluate_policy_sensing_grid("qr_evaluate_policy_history_grid", &history, e, policies, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                        policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group, K, flags, noise_seed, first_step,
+                                        pending_dev, rec_dev, recf_dev, stream);
 }
 
 // the rows the evaluator adds to the observations of one group under one slot: refusals first, then one launch
@@ -1122,19 +1166,20 @@ int qr_rollout_policy_dynamics(qr_env* e, qr_policy* policy, qr_condition_bank* 
 // qr_rollout_policy_dynamics with the sensing bank, its map and the command queues: that entry point's refusals in its order, then the
 // sensing bank's in the words of qr_evaluate_policy_sensing_grid, then pending_dev, then the copy of the maps.  The (dynamics, condition)
 // pair travels in the handle's group map as in qr_rollout_policy_dynamics, the sensing slots in an array of their own; under capture
-// BOTH must already be on the device, and the test comes before either copy.
-int qr_rollout_policy_sensing(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
-                              int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
-                              const int32_t* sensing_of_group, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags,
-                              float* pending_dev, float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
-                              uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, void* stream) {
-    const char* who = "qr_rollout_policy_sensing";
+// BOTH must already be on the device, and the test comes before either copy.  history: null (qr_rollout_policy_sensing), or the command
+// history of qr_rollout_policy_history (rollout_policy_args refuses its range and compares the policy's length with the longer row).
+static int rollout_policy_sensing(const char* who, const int32_t* history, qr_env* e, qr_policy* policy, qr_condition_bank* conditions,
+                                  qr_dynamics_bank* dynamics, qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group,
+                                  const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t K,
+                                  const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev, float* obs_out_dev,
+                                  float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                                  float* last_obs_dev, void* stream) {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(QR_E_INVALID, w + "null env handle");
     if (int rc = check_ready(e)) return rc;
     qr::PolicyArgs A{};
     if (int rc = rollout_policy_args(e, policy, K, log_std, noise_seed, first_step, flags, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
-                                     done_out_dev, who, A))
+                                     done_out_dev, who, A, history))
         return rc;
     if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
     if (!condition_of_group) return fail(QR_E_INVALID, w + "the condition map is required");
@@ -1171,9 +1216,35 @@ int qr_rollout_policy_sensing(qr_env* e, qr_policy* policy, qr_condition_bank* c
                                     "call once with these maps outside the capture");
     if (int rc = upload_table(e->group_map, map, st, who, "group map", "this map")) return rc;
     if (int rc = upload_table(e->rollout_sen_map, smap, st, who, "sensing map", "this map")) return rc;
+    if (history)
+        return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_history(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, sensing->d_slots,
+                                           e->group_map.d, e->rollout_sen_map.d, *history, num_groups, envs_per_group, K, noise_seed, first_step,
+                                           pending_dev, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev,
+                                           st));
     return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_sensing(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, sensing->d_slots,
                                        e->group_map.d, e->rollout_sen_map.d, num_groups, envs_per_group, K, noise_seed, first_step, pending_dev,
                                        obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, st));
+}
+
+int qr_rollout_policy_sensing(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
+                              int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
+                              const int32_t* sensing_of_group, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags,
+                              float* pending_dev, float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
+                              uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, void* stream) {
+    return rollout_policy_sensing("qr_rollout_policy_sensing", nullptr, e, policy, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                  condition_of_group, dynamics_of_group, sensing_of_group, K, log_std, noise_seed, first_step, flags, pending_dev,
+                                  obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, stream);
+}
+
+// qr_rollout_policy_sensing for a policy that observes its last `history` commands: rows of obs_len + 4 * history floats
+int qr_rollout_policy_history(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
+                              int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
+                              const int32_t* sensing_of_group, int32_t history, int32_t K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
+                              int32_t flags, float* pending_dev, float* obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
+                              uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, void* stream) {
+    return rollout_policy_sensing("qr_rollout_policy_history", &history, e, policy, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                  condition_of_group, dynamics_of_group, sensing_of_group, K, log_std, noise_seed, first_step, flags, pending_dev,
+                                  obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, stream);
 }
 
 int qr_vehicle_physical_count(int32_t variant) {

@@ -41,14 +41,20 @@ constexpr size_t eval_lds_bytes() {
 //                  the observation of the step and its command flies in the step; no code) or RuntimeSensing, which supplies
 //                  three hooks -- perturb<V, GA>(sen, gid, k, o) in front of the forward, delay(sen) / pending(sen) for the command queue
 //                  between clip_action and step_env -- and kSensingQueueFloats more floats of dynamic LDS per lane behind the lap sums
+//   H              (RuntimeSensing only; quadrace_eval_history.hip) the policy's row carries the last H clipped commands COMPUTED in the
+//                  current episode behind the noisy observation, [o~_k | u_{k-1}, ..., u_{k-H}]: img / img_lo are images of a policy of
+//                  obs_len<V, GA + H>() inputs and the kernel supplies eval_lds_bytes of THAT length; the tail is read from and written back
+//                  to entries 0 .. H - 1 of `pending`, cleared with the queue (rollout_policy_group_kernel carries the same statements)
 // kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
 // for every lane, every lane is an env and every lane stores.
-template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing>
+template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing, int H = 0>
 __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
                                                  const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,
                                                  int4* __restrict__ rec, float4* __restrict__ recf, typename C::Arg dyn = typename C::Arg(),
                                                  typename Sn::Arg sen = typename Sn::Arg()) {
-    constexpr int L = obs_len<V, GA>();
+    static_assert(H == 0 || (Sn::kOn && H >= 1 && GA + H <= 4), "the command history needs the sensing hooks, 1 <= H <= 4 - GA");
+    constexpr int LE = obs_len<V, GA>();       // the env's row: observe, the sensor's noise
+    constexpr int L = obs_len<V, GA + H>();    // the policy's row [o~ | h] = LE + 4 H floats (H = 0: LE)
     using D = PolicyDims<L>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     half8* W = reinterpret_cast<half8*>(smem);                                   // policy weights (f16) of THIS workgroup's policy
@@ -119,6 +125,14 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
     bool stash_ok = false;
     float o[L];
     observe<V, GA>(P, gates, e, o);
+    if constexpr (H > 0) {   // h_0 = the caller's queue, entries 0 .. H - 1 (whatever d is)
+        const float4* pend = reinterpret_cast<const float4*>(Sn::pending(sen)) + (size_t)ii * kMaxDelay;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float4 c = pend[j];
+            o[LE + 4 * j] = c.x; o[LE + 4 * j + 1] = c.y; o[LE + 4 * j + 2] = c.z; o[LE + 4 * j + 3] = c.w;
+        }
+    }
     for (int k = 0; k < K; ++k) {
         if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen, gid_lo, gid_hi, k, o);   // o is rebuilt from the state behind the step
         float mean[4];
@@ -126,6 +140,11 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
         else policy_forward<L>(W, lane, o, mean);
         float u[4];
         clip_action(mean, u);
+        [[maybe_unused]] float uc[4];   // (H > 0 only) the command COMPUTED in this step: what enters the history, whatever flies
+        if constexpr (H > 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) uc[c] = u[c];
+        }
         if constexpr (Sn::kOn) {   // the env flies the command computed d steps ago; this step's command takes its ring slot
             const int d = Sn::delay(sen);
             if (d > 0) {
@@ -179,6 +198,12 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
             }
         }
         observe<V, GA>(P, gates, e, o);
+        if constexpr (H > 0) {   // h_{k+1}: the tail moves on by one command, this step's enters in front; an episode end clears it
+#pragma unroll
+            for (int j = 4 * H - 1; j >= 4; --j) o[LE + j] = done ? 0.0f : o[LE + j - 4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[LE + c] = done ? 0.0f : uc[c];
+        }
     }
     if (!active) return;
     int4* row = rec + (size_t)i * 6;
@@ -207,6 +232,9 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
                 p += p < 0 ? d : 0;
                 const float* slot = ring + p * 4 * kBlock;
                 c = make_float4(slot[0], slot[kBlock], slot[2 * kBlock], slot[3 * kBlock]);
+            }
+            if constexpr (H > 0) {   // max(d, H) entries: the tail holds entries 0 .. H - 1 (equal to the ring's where both hold one)
+                if (j < H) c = make_float4(o[LE + 4 * j], o[LE + 4 * j + 1], o[LE + 4 * j + 2], o[LE + 4 * j + 3]);
             }
             pend[j] = c;
         }

@@ -47,6 +47,17 @@ hipError_t dispatch_vg(int variant, int gates_ahead, F&& f) {
         return variant == kE2E ? f(std::integral_constant<int, kE2E>{}, ga) : f(std::integral_constant<int, kINDI>{}, ga);
     });
 }
+// command history -> f(integral_constant<int, H>) for 1 <= H <= 4 - GA (quadrace_rollout_history.hip, quadrace_eval_history.hip): the row
+// of an env with GA gates ahead and H commands is as long as the row of GA + H gates ahead, a length the network kernels have up to 4;
+// hipErrorInvalidValue outside
+template <int GA, typename F>
+hipError_t dispatch_history(int history, F&& f) {
+    if constexpr (GA + 1 <= 4) if (history == 1) return f(std::integral_constant<int, 1>{});
+    if constexpr (GA + 2 <= 4) if (history == 2) return f(std::integral_constant<int, 2>{});
+    if constexpr (GA + 3 <= 4) if (history == 3) return f(std::integral_constant<int, 3>{});
+    if constexpr (GA + 4 <= 4) if (history == 4) return f(std::integral_constant<int, 4>{});
+    return hipErrorInvalidValue;
+}
 // observation length -> f(integral_constant<int, L>): every length the two env variants can produce (gates_ahead 0..4: 13 + 4g, 20 + 4g)
 // and 16, the raw-state observation of the predecessor envs (include/quad3d.h).  The caller
 // supplies what an illegal length yields: `invalid()` runs only then (it may record an error message).
@@ -178,6 +189,18 @@ hipError_t launch_rollout_policy_sensing(int variant, const Params& P, const Pol
                                          const int2* map, const int* sen_map, int num_groups, int envs_per_group, int K, uint64_t noise_seed,
                                          uint64_t first_step, float* pending, float* obs, float* act, float* logp, float* rew, uint8_t* done,
                                          uint8_t* trunc, float* last_obs, hipStream_t st);
+
+// quadrace_rollout_history.hip / quadrace_eval_history.hip: the two sensing calls for a policy whose row carries its last `history`
+// clipped commands behind the observation (qr_rollout_policy_history, qr_evaluate_policy_history_grid): the sensing call's arguments and
+// history in [1, 4 - gates_ahead]; the policy / the bank has obs_len + 4 history inputs, obs / last_obs / the terminal buffer rows of that
+// length; pending carries max(delay, history) entries
+hipError_t launch_rollout_policy_history(int variant, const Params& P, const PolicyArgs& A, const float* conds, const float* dyns, const float* sens,
+                                         const int2* map, const int* sen_map, int history, int num_groups, int envs_per_group, int K,
+                                         uint64_t noise_seed, uint64_t first_step, float* pending, float* obs, float* act, float* logp, float* rew,
+                                         uint8_t* done, uint8_t* trunc, float* last_obs, hipStream_t st);
+hipError_t launch_eval_policy_history_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
+                                           const float* sens, const int4* map, int history, bool f32class, int num_groups, int envs_per_group, int K,
+                                           uint64_t noise_seed, uint64_t first_step, float* pending, int32_t* rec, float* recf, hipStream_t st);
 
 // quadrace_rollout_population.hip: the closed-loop rollout for a population of policies (qr_rollout_policy_population): the workgroups of
 // group g fly policy map[g].x under condition map[g].y and sample with table[g]; A carries the launch-wide step counter, deterministic

@@ -1,8 +1,9 @@
-// quadrace_rollout_group.hpp -- the ONE kernel behind the four grouped closed-loop rollouts: qr_rollout_policy_conditions
+// quadrace_rollout_group.hpp -- the ONE kernel behind the grouped closed-loop rollouts: qr_rollout_policy_conditions
 // (quadrace_rollout_cond.hip, kPop = false), qr_rollout_policy_population (quadrace_rollout_population.hip, kPop = true),
 // qr_rollout_policy_dynamics (quadrace_rollout_dynamics.hip, kPop = false, kDyn = true) and qr_rollout_policy_sensing
-// (quadrace_rollout_sensing.hip, kDyn = true, Sn = RuntimeSensing).  Included by those four units and by nothing else; each keeps its
-// launch function, its checks and its instantiations.
+// (quadrace_rollout_sensing.hip, kDyn = true, Sn = RuntimeSensing), and behind qr_rollout_policy_history (quadrace_rollout_history.hip: the
+// sensing mode with H > 0).  Included by those five units and by nothing else; each keeps its launch function, its checks and its
+// instantiations.
 //
 // K x [obs -> MFMA policy -> a = mean + std * eps -> env.step(clip(a))] with the rollout rows, the terminal-observation rows, last_obs
 // and the end-of-kernel state write-back of rollout_policy_kernel (quadrace_env_kernels.hpp), and the inputs of eval_policy_grid_kernel
@@ -57,6 +58,16 @@
 //                  computed j + 1 steps ago, zeros behind d), so a buffer passes between the evaluator and this kernel.
 //                  sens, sen_map, pending and stream come AFTER dyns: every older mode keeps its argument offsets and passes nulls.
 //                  No atomics, no workgroup that waits for another.
+//   H > 0          (with Sn = RuntimeSensing only; qr_rollout_policy_history, quadrace_rollout_history.hip) the sensing mode with a COMMAND
+//                  HISTORY in the policy's row: at call-step k the row is [o~_k | u_{k-1}, ..., u_{k-H}], L = obs_len<V, GA + H>() = LE + 4 H
+//                  floats, u_j the clipped command COMPUTED (not flown) at step j of the current episode, zeros before the episode's start.
+//                  The network side (PolicyDims, the forward, the LDS tile, the row stores) is instantiated at L, an observation length every
+//                  network kernel already has because GA + H <= 4; the env side (observe, step_env, the sensor's noise) stays at GA and touches
+//                  o[0 .. LE) only: the history is exact.  The tail lives in o[LE .. L): loaded from entries 0 .. H - 1 of `pending` in the
+//                  prologue, moved on by one command behind each step (cleared by the step that ends an episode, with the ring), stored to
+//                  `pending` in the epilogue, which then carries max(d, H) entries.  The delay ring is untouched: d and H are independent.
+//                  Terminal rows are L wide, [clean observation | u_k, ..., u_{k-H+1}] (store_terminal_obs_history below): P.term_obs is read
+//                  as [rows][N][L] in this mode.
 // Unlike the grid evaluator the reset stream and the action noise are keyed by the handle's ORDINARY env ids (P.gid + i): training
 // wants independent envs, not common random numbers across groups.  Group g therefore computes what an E-env handle with
 // env_id_base + g E, configured with the group's condition, computes under qr_rollout_policy with the group's weights, log_std and seed
@@ -76,10 +87,27 @@
 
 namespace qr {
 
+// store_terminal_obs (quadrace_env_kernels.hpp) for a row with a command history: [clean observation of the terminal state | u_k,
+// u_{k-1}, ..., u_{k-H+1}] -- `uc` the command computed in the step that ended the episode, `tail` the history that step's row carried
+// (its first 4 (H - 1) floats move back by one command) -- to row [row_base + i] of P.term_obs read as rows of obs_len<V, GA + H>() floats.
+template <int V, int GA, int H>
+__device__ __forceinline__ void store_terminal_obs_history(const Params& P, const float* __restrict__ gates, const Env<V>& e, size_t row_base, int i,
+                                                           bool write, const float* uc, const float* tail) {
+    if (P.term_obs == nullptr || !write) return;
+    constexpr int LE = obs_len<V, GA>(), L = obs_len<V, GA + H>();
+    float to[L];
+    observe<V, GA>(P, gates, e, to);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) to[LE + c] = uc[c];
+#pragma unroll
+    for (int j = 4; j < 4 * H; ++j) to[LE + j] = tail[j - 4];
+    store_obs<V, GA + H>(P.term_obs + row_base * L, i, to);
+}
+
 // conds: slot 0 of the condition bank; map[g] = (policy, condition) of group g; wgs_per_group = E / kBlock; kPop: bank / bank_lo = image 0
 // of the two policy arrays, table[g] = sampling arguments of group g; kDyn: dyns = slot 0 of the dynamics bank, map[g] = (dynamics, condition);
 // Sn::kOn: sens = slot 0 of the sensing bank, sen_map[g] = the sensing slot of group g, pending = the command queues [n][kSensingQueueFloats]
-template <int V, int GA, bool kF32, bool kPop, bool kDyn = false, class Sn = IdealSensing>
+template <int V, int GA, bool kF32, bool kPop, bool kDyn = false, class Sn = IdealSensing, int H = 0>
 __global__ void __launch_bounds__(kBlock, 1)
 rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ bank, const half8* __restrict__ bank_lo,
                             const float* __restrict__ conds, const int2* __restrict__ map, const PopulationEntry* __restrict__ table,
@@ -89,7 +117,9 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
                             const float* __restrict__ sens, const int* __restrict__ sen_map, float* __restrict__ pending, SensingStream stream) {
     static_assert(!(kPop && kDyn), "the vehicle mode is a single-policy mode");
     static_assert(!Sn::kOn || kDyn, "the sensing mode is a mode of the vehicle mode");
-    constexpr int L = obs_len<V, GA>();
+    static_assert(H == 0 || (Sn::kOn && H >= 1 && GA + H <= 4), "the command history is a mode of the sensing mode, 1 <= H <= 4 - GA");
+    constexpr int LE = obs_len<V, GA>();       // the env's row: observe, the sensor's noise
+    constexpr int L = obs_len<V, GA + H>();    // the policy's row [o~ | h] = LE + 4 H floats: the network, the tiles, the row stores (H = 0: LE)
     using D = PolicyDims<L>;
     using C = std::conditional_t<kDyn, RuntimeDyn<V>, NominalDyn<V>>;   // where the step takes the coefficients of the equations of motion from
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -194,6 +224,14 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
     bool stash_ok = false;
     float o[L];
     observe<V, GA>(P, gates, e, o);
+    if constexpr (H > 0) {   // h_0 = the caller's queue, entries 0 .. H - 1 (whatever d is)
+        const float4* pend = reinterpret_cast<const float4*>(Sn::pending(sen_arg)) + (size_t)i * kMaxDelay;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float4 c = pend[j];
+            o[LE + 4 * j] = c.x; o[LE + 4 * j + 1] = c.y; o[LE + 4 * j + 2] = c.z; o[LE + 4 * j + 3] = c.w;
+        }
+    }
     for (int k = 0; k < K; ++k) {
         // the policy's input is the noisy row (and obs_slice stores it); o is rebuilt from the state behind the step
         if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen_arg, gid_lo, gid_hi, k, o);
@@ -235,8 +273,8 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         // The observation row of this step (the policy's input) is stored under the third layer's MFMAs: LDS transpose in slot 0,
         // coalesced block store in slot 2 (every wave is full).
         auto obs_slice = [&](int slot) {
-            if (slot == 0) obs_tile_write<V, GA>(tile, lane, o);
-            if (slot == 2) obs_tile_flush<V, GA>(tile, obs_out + (size_t)k * n * L, (size_t)wave_first, lane);
+            if (slot == 0) obs_tile_write<V, GA + H>(tile, lane, o);
+            if (slot == 2) obs_tile_flush<V, GA + H>(tile, obs_out + (size_t)k * n * L, (size_t)wave_first, lane);
         };
         if constexpr (kF32) {
 #pragma unroll
@@ -260,6 +298,11 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         stream_store(logp_out + (size_t)k * n + i, logp);
         float u[4];
         clip_action(a, u);
+        [[maybe_unused]] float uc[4];   // (H > 0 only) the command COMPUTED in this step: what enters the history, whatever flies
+        if constexpr (H > 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) uc[c] = u[c];
+        }
         if constexpr (Sn::kOn) {   // the env flies the command computed d steps ago; this step's command takes its ring slot
             const int d = Sn::delay(sen_arg);
             if (d > 0) {
@@ -275,7 +318,10 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         }
         bool done, trunc, did_reset;
         const float reward = step_env<V, 0, C>(P, gates, rtab, tile, mlp, lane, true, e, u, gid_lo, gid_hi, done, trunc, did_reset,
-                                               [&](bool fin) { store_terminal_obs<V, GA>(P, gates, e, (size_t)k * n, i, fin); },
+                                               [&](bool fin) {
+                                                   if constexpr (H > 0) store_terminal_obs_history<V, GA, H>(P, gates, e, (size_t)k * n, i, fin, uc, o + LE);
+                                                   else store_terminal_obs<V, GA>(P, gates, e, (size_t)k * n, i, fin);
+                                               },
                                                [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); },
                                                dyn_arg);
         any_reset |= did_reset;
@@ -289,12 +335,18 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         stream_store(done_out + (size_t)k * n + i, (uint8_t)(done ? 1 : 0));
         if (trunc_out) stream_store(trunc_out + (size_t)k * n + i, (uint8_t)(trunc ? 1 : 0));
         observe<V, GA>(P, gates, e, o);
+        if constexpr (H > 0) {   // h_{k+1}: the tail moves on by one command, this step's enters in front; an episode end clears it
+#pragma unroll
+            for (int j = 4 * H - 1; j >= 4; --j) o[LE + j] = done ? 0.0f : o[LE + j - 4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[LE + c] = done ? 0.0f : uc[c];
+        }
     }
     if constexpr (Sn::kOn) {
         // last_obs is what the policy sees next: the noise of call-step K, row 0 of a launch with first_step + K
         if (last_obs_out) Sn::template perturb<V, GA>(sen_arg, gid_lo, gid_hi, K, o);
     }
-    if (last_obs_out) store_obs_coalesced<V, GA>(tile, last_obs_out, (size_t)wave_first, lane, o);
+    if (last_obs_out) store_obs_coalesced<V, GA + H>(tile, last_obs_out, (size_t)wave_first, lane, o);
     if constexpr (Sn::kOn) {   // the queue in canonical order: entry j = slot (K - 1 - j) mod d for j < d, zeros behind
         const int d = Sn::delay(sen_arg);
         float4* pend = reinterpret_cast<float4*>(Sn::pending(sen_arg)) + (size_t)i * kMaxDelay;
@@ -306,6 +358,9 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
                 p += p < 0 ? d : 0;
                 const float* slot = ring + p * 4 * kBlock;
                 c = make_float4(slot[0], slot[kBlock], slot[2 * kBlock], slot[3 * kBlock]);
+            }
+            if constexpr (H > 0) {   // max(d, H) entries: the tail holds entries 0 .. H - 1 (equal to the ring's where both hold one)
+                if (j < H) c = make_float4(o[LE + 4 * j], o[LE + 4 * j + 1], o[LE + 4 * j + 2], o[LE + 4 * j + 3]);
             }
             pend[j] = c;
         }

@@ -330,15 +330,28 @@ def evaluate_dynamics_grid(policies, conditions, dynamics, env, envs_per_cell=25
     return results
 
 
+def check_command_history(command_history, gates_ahead):
+    """command_history as an int: 0 (none), or H in 1 .. 4 - gates_ahead -- the row of obs_len + 4 H floats is as long as the observation
+    of an env with gates_ahead + H gates ahead, and the policy kernels exist for up to 4."""
+    H = int(command_history)
+    if H != command_history or H < 0 or (H > 0 and int(gates_ahead) + H > 4):
+        raise ValueError("command_history must be 0 or an integer in 1 .. 4 - gates_ahead (gates_ahead=%d: at most %d); got %r"
+                         % (int(gates_ahead), 4 - int(gates_ahead), command_history))
+    return H
+
+
 def evaluate_sensing_grid(policies, conditions, sensing, env, dynamics=None, envs_per_cell=256, n_eval_steps=2000, window_steps=1200, precision=None,
-                          seed=0, noise_seed=0):
+                          seed=0, noise_seed=0, command_history=0):
     """evaluate_grid with the sensor as third axis: every cell of `policies` x `conditions` x `sensing` (sensing.SensingParams: noise on
     the observation the policy sees, a command delay of 0..4 steps), `env.num_envs // envs_per_cell` cells per launch
     (qr_evaluate_policy_sensing_grid), all flown as ONE vehicle, `dynamics` (a dynamics.DynamicsParams; default: the nominal one).
     Starts, restarts, entries of `policies`, `precision` and the summaries are evaluate_grid's; all cells see the same uniform draws and,
     keyed by `noise_seed`, the same normal draws, so two columns differ by their sensor alone.  The command queues are zeroed with each
     start and the noise stream's step counter runs on across the phases.  The column of SensingParams.ideal() equals
-    evaluate_dynamics_grid's cell for that vehicle.  Returns results[p][c][s], each a {"window", "total"} dict."""
+    evaluate_dynamics_grid's cell for that vehicle.  Returns results[p][c][s], each a {"window", "total"} dict.
+    command_history = H > 0 (1 .. 4 - gates_ahead): the policies OBSERVE THEIR LAST H COMMANDS (qr_evaluate_policy_history_grid) -- they have
+    obs_len + 4 H inputs and are fed [noisy observation | the last H clipped commands computed in the episode], as
+    PPO(command_history=H) trains them.  0 (the default) is the call without it, unchanged."""
     import torch
 
     from .conditions import ConditionBank
@@ -348,6 +361,7 @@ def evaluate_sensing_grid(policies, conditions, sensing, env, dynamics=None, env
     from .sensing import QUEUE_FLOATS, SensingBank
 
     core = _unwrap(env)
+    H = check_command_history(command_history, core.gates_ahead)
     E, slots = group_size(envs_per_cell, core.num_envs, "envs_per_cell", "cell")
     phases = _phases(n_eval_steps, window_steps)
     conditions, policies, sensing = list(conditions), list(policies), list(sensing)
@@ -358,7 +372,7 @@ def evaluate_sensing_grid(policies, conditions, sensing, env, dynamics=None, env
     if precision is None:
         precision = _model_precision([m for _, m in actors])
     results = [[[None] * len(sensing) for _ in conditions] for _ in actors]
-    pbank = MfmaPolicyBank(core.state_len, len(actors), core.device.index)
+    pbank = MfmaPolicyBank(core.state_len + 4 * H, len(actors), core.device.index)
     cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
     dbank = DynamicsBank(core.VARIANT, 1, core.device.index)
     sbank = SensingBank(len(sensing), core.device.index)
@@ -371,9 +385,13 @@ def evaluate_sensing_grid(policies, conditions, sensing, env, dynamics=None, env
         flown[0] = 0
 
     def launch(cells, steps, rec, recf):
-        core.evaluate_sensing_grid_device(pbank, cbank, dbank, sbank, [p for p, _, _ in cells], [c for _, c, _ in cells], [0] * len(cells),
-                                          [s for _, _, s in cells], E, steps, pending, rec, recf, precision=precision, noise_seed=noise_seed,
-                                          first_step=flown[0])
+        maps = ([p for p, _, _ in cells], [c for _, c, _ in cells], [0] * len(cells), [s for _, _, s in cells])
+        if H > 0:
+            core.evaluate_history_grid_device(pbank, cbank, dbank, sbank, *maps, H, E, steps, pending, rec, recf, precision=precision,
+                                              noise_seed=noise_seed, first_step=flown[0])
+        else:
+            core.evaluate_sensing_grid_device(pbank, cbank, dbank, sbank, *maps, E, steps, pending, rec, recf, precision=precision,
+                                              noise_seed=noise_seed, first_step=flown[0])
         flown[0] += int(steps)
 
     def summarise(cell, rec, recf):

@@ -420,7 +420,7 @@ class PPO:
                  log_std_init=0.0, seed=0, target_kl=None, lr_final_frac=1.0, total_timesteps_hint=None,
                  fused_collect=False, native_update=False, truncation_bootstrap=True, policy_forward="torch", update_precision="f16-operands",
                  conditions=None, envs_per_group=256, condition_weights=None, dynamics=None, dynamics_of_group=None, resample_every=None,
-                 sensing=None, sensing_of_group=None):
+                 sensing=None, sensing_of_group=None, command_history=0):
         self.env = env
         self.n_envs, self.dev = env.num_envs, env.device
         self.n_steps, self.n_epochs = n_steps, n_epochs
@@ -438,12 +438,28 @@ class PPO:
         # goal (+100) and the final gate (+10) pay that much -- an intermediate gate earns the ordinary progress reward -- so there the same
         # count is successes per episode, and the statistic is named for what it is
         self._gates_key = "successes_per_episode" if self._q3 else "gates_per_episode"
+        # command_history = H > 0: the policy (and the value network) OBSERVE THE LAST H COMMANDS -- their row is [observation | the last
+        # H clipped commands computed in the episode], obs_len + 4 H floats, assembled inside the collect launch (qr_rollout_policy_history).
+        # Under a command delay the observation alone is no Markov state of what is flown; the commands computed and not yet flown are.
+        # H <= 4 - gates_ahead: the longer row is as long as the observation of gates_ahead + H gates ahead, a length every network kernel
+        # (forward, PPO update) already has.  Fused collect on a race env only; without `sensing` the run flies under one ideal sensor.
+        # The history travels in the command queues (`_pending`), so a checkpoint carries it.  0: nothing about the trainer changes.
+        from .evaluation import check_command_history
+
+        self.command_history = check_command_history(command_history, 0 if self._q3 else env.gates_ahead) if command_history else 0
+        if self.command_history:
+            if not fused_collect or self._q3:
+                raise ValueError("command_history needs fused_collect=True on a race env: the row is assembled in the closed-loop kernel only")
+            if sensing is None:
+                from .sensing import SensingParams
+
+                sensing = [SensingParams.ideal()]
         torch.manual_seed(seed)
         # minibatch permutations come from the trainer's OWN generator (checkpointed; independent of whatever else draws from
         # torch's global generators in the process)
         self._gen = torch.Generator(device=self.dev)
         self._gen.manual_seed(int(seed))
-        obs_dim = env.state_len
+        obs_dim = env.state_len + 4 * self.command_history
         self.policy = ActorCritic(obs_dim, 4, net_arch, log_std_init).to(self.dev)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=learning_rate, eps=1e-5)
         T, N = n_steps, self.n_envs
@@ -565,7 +581,10 @@ class PPO:
                              if (self.policy_forward == "f32class" and fused_collect and self._updater is not None and self._updater.precision == "f32") else None)
         if self.truncation_bootstrap:  # the kernels write the pre-reset observation of finished envs here
             self._term_obs = torch.zeros((T, N, obs_dim) if fused_collect else (N, obs_dim), **f32)
-            env.set_terminal_obs_buffer(self._term_obs)
+            if self.command_history:   # rows [terminal observation | the commands the next row would have carried]
+                env.set_terminal_obs_buffer(self._term_obs, obs_len=obs_dim)
+            else:
+                env.set_terminal_obs_buffer(self._term_obs)
 
     def _set_conditions(self, conditions, condition_of_group):
         """The mix of flight conditions of collect_fused: the list, the group map and the device bank built from them."""
@@ -737,10 +756,15 @@ class PPO:
             mixed, vehicles = self.conditions is not None, self._dyn_bank is not None
             if vehicles:
                 self._resample_vehicles()
-            obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_sensing_device(
-                self._mfma, self._cond_bank if mixed else self._own_cond_bank, self.condition_of_group if mixed else [0] * groups,
-                self._dyn_bank if vehicles else self._own_dyn_bank, self.dynamics_of_group if vehicles else [0] * groups,
-                self._sen_bank, self.sensing_of_group, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
+            banks = (self._mfma, self._cond_bank if mixed else self._own_cond_bank, self.condition_of_group if mixed else [0] * groups,
+                     self._dyn_bank if vehicles else self._own_dyn_bank, self.dynamics_of_group if vehicles else [0] * groups,
+                     self._sen_bank, self.sensing_of_group)
+            if self.command_history:
+                obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_history_device(
+                    *banks, self.command_history, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
+            else:
+                obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_sensing_device(
+                    *banks, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
             if mixed:
                 self._condition_stats(rew, done, trunc)
             if vehicles:
@@ -1091,6 +1115,8 @@ class PPO:
             sd["sensing"] = dict(slots=[s.pack() for s in self.sensing], names=list(self._sensor_names),
                                  sensing_of_group=list(self.sensing_of_group), envs_per_group=int(self.envs_per_group),
                                  pending=self._pending.cpu(), ep_ret=self._sen_ret.cpu(), ep_len=self._sen_len.cpu())
+        if self.command_history:   # likewise; the history itself is the first rows of `pending` above
+            sd["command_history"] = int(self.command_history)
         return sd
 
     def _dynamics_state(self):
@@ -1114,6 +1140,9 @@ class PPO:
 
     @torch.no_grad()
     def load_state_dict(self, sd):
+        if int(sd.get("command_history", 0)) != self.command_history:   # the networks differ in their input length: nothing is loaded
+            raise ValueError("the checkpoint was trained with command_history=%d, this PPO was constructed with command_history=%d: "
+                             "construct it with the checkpoint's value" % (int(sd.get("command_history", 0)), self.command_history))
         opt = sd["optimizer"]
         if self._updater is not None:
             assert opt["kind"] == "mfma_adam", "checkpoint was written by the torch optimiser path"

@@ -526,16 +526,19 @@ class Quadcopter3DGates(_Base):
         return {**state_dict, **action_dict}
 
     # ------------------------------------------------------------------ device fast path (no host sync)
-    def set_terminal_obs_buffer(self, buf):
+    def set_terminal_obs_buffer(self, buf, obs_len=None):
         """Register (or, with None, remove) a float32 CUDA tensor that receives the TRUE terminal observation -- the
         gate-frame observation of an episode's final state, taken before the auto-reset -- of every env that finishes
         at a step: shape [N, L] for step_device, [K, N, L] for rollout_device / step_sequence_device /
         rollout_policy_device (row [k, env]).  Rows of envs that did not finish are left untouched.  This is what SB3
         bootstraps time-limit truncations from; the reference itself fills `terminal_observation` after reset_()
-        (R:589-594), i.e. with the first observation of the NEXT episode."""
+        (R:589-594), i.e. with the first observation of the NEXT episode.
+        obs_len (default: the env's own): the row length of `buf` -- obs_len + 4 H for rollout_policy_history_device with
+        command_history = H, which writes [terminal observation | last H commands] rows and refuses a buffer of any other width."""
         rows = 0
         if buf is not None:
-            assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.shape[-1] == self.state_len
+            width = self.state_len if obs_len is None else int(obs_len)
+            assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.shape[-1] == width
             assert buf.dim() in (2, 3) and buf.shape[-2] == self.num_envs
             rows = int(buf.shape[0]) if buf.dim() == 3 else 1   # K-step calls with K > rows are refused by the library
         self._term_obs_buf = buf   # keep it alive while the library holds the pointer
@@ -924,6 +927,71 @@ class Quadcopter3DGates(_Base):
                       _ptr(self._obs), self._stream()))
         self._last_obs = self._obs
         return obs, act, logp, rew, done, trunc, self._obs
+
+    def rollout_policy_history_device(self, policy, condition_bank, condition_of_group, dynamics_bank, dynamics_of_group, sensing_bank,
+                                      sensing_of_group, command_history, envs_per_group, num_steps, log_std, pending, noise_seed=0, first_step=0,
+                                      deterministic=False, out=None, precision="f16-operands"):
+        """rollout_policy_sensing_device for a policy that OBSERVES ITS LAST COMMANDS (qr_rollout_policy_history): with
+        H = command_history in 1 .. 4 - gates_ahead the policy's row at call-step k is [noisy observation | u_{k-1}, ..., u_{k-H}], the
+        last H clipped commands COMPUTED (not flown) in the current episode, newest first, zeros before the episode's start and after
+        the step that ends it; the history part carries no noise.  `policy` is an MfmaPolicy of obs_len + 4 H inputs -- the length of an
+        env with gates_ahead + H gates ahead, which is why gates_ahead + H <= 4.  obs rows are [K, N, obs_len + 4 H], last_obs
+        [N, obs_len + 4 H] (a buffer of this call's own; the env's observation buffer takes its first obs_len columns on the next read);
+        a registered terminal-observation buffer must have rows of obs_len + 4 H floats (set_terminal_obs_buffer(buf, obs_len=...)) and
+        receives [clean terminal observation | u_k, ..., u_{k-H+1}].  `pending` carries max(delay, H) commands per env and passes
+        between this call, rollout_policy_sensing_device and the two evaluators.  Everything else as rollout_policy_sensing_device."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_rollout_policy_history")
+        H = int(command_history)
+        width = self.state_len + 4 * H
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        term = getattr(self, "_term_obs_buf", None)
+        if term is not None and H >= 1 and int(term.shape[-1]) != width:   # the kernel would write rows of `width` floats into it
+            raise ValueError("the registered terminal-observation buffer has rows of %d floats; command_history=%d writes rows of %d: "
+                             "register it with set_terminal_obs_buffer(buf, obs_len=%d)" % (int(term.shape[-1]), H, width, width))
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        if out is None:
+            out = rollout_outputs(K, n, width, dev)
+        obs, act, logp, rew, done, trunc = out
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and obs.numel() >= K * n * max(width, self.state_len)):
+            raise AssertionError("the obs rows must be a contiguous float32 CUDA tensor [num_steps, num_envs, obs_len + 4 * command_history]")
+        last = getattr(self, "_obs_history", None)
+        if last is None or int(last.shape[1]) != max(width, self.state_len):
+            last = self._obs_history = torch.zeros((n, max(width, self.state_len)), dtype=torch.float32, device=dev)
+        ls = log_std_array(log_std)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, int(maps[0].shape[0]), int(envs_per_group),
+                      *[m.ctypes.data_as(i32p) for m in maps], H, K, _f32p(ls), int(noise_seed) & (2 ** 64 - 1), int(first_step),
+                      int(bool(deterministic)) | flags, _ptr(pending), _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew), _ptr(done), _ptr(trunc),
+                      _ptr(last), self._stream()))
+        self._last_obs = last[:, :self.state_len]
+        return obs, act, logp, rew, done, trunc, last
+
+    def evaluate_history_grid_device(self, policy_bank, condition_bank, dynamics_bank, sensing_bank, policy_of_group, condition_of_group,
+                                     dynamics_of_group, sensing_of_group, command_history, envs_per_group, num_steps, pending, rec, recf=None,
+                                     precision="f16-operands", noise_seed=0, first_step=0):
+        """evaluate_sensing_grid_device for policies that OBSERVE THEIR LAST COMMANDS (qr_evaluate_policy_history_grid): `policy_bank`
+        holds policies of obs_len + 4 * command_history inputs, fed [noisy observation | the last command_history clipped commands
+        computed in the episode] as rollout_policy_history_device feeds them; `pending` carries max(delay, command_history) commands
+        per env.  Everything else as evaluate_sensing_grid_device.  Returns (rec, recf)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_evaluate_policy_history_grid")
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("policy_of_group, condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        self._check_eval_records(rec, recf)
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy_bank._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, int(maps[0].shape[0]), int(envs_per_group),
+                      *[m.ctypes.data_as(i32p) for m in maps], int(command_history), int(num_steps), flags, int(noise_seed) & (2 ** 64 - 1),
+                      int(first_step), _ptr(pending), _ptr(rec), _ptr(recf), self._stream()))
+        self._observe_under(condition_bank.conditions, maps[1], int(envs_per_group))
+        return rec, recf
 
     def rollout_policy_population_device(self, bank, policy_of_group, condition_bank, condition_of_group, envs_per_group, num_steps, log_stds,
                                          noise_seeds, first_step=0, deterministic=False, out=None, precision="f16-operands"):

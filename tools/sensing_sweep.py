@@ -100,12 +100,20 @@ def main():
         env = Quadcopter3DGatesINDI(n, *track, gates_ahead=a.gates_ahead, infos_mode="none", seed=a.seed)
     env.max_steps = 10 ** 6
     cond = Condition.from_env(env, name=a.track)
+    # a checkpoint trained with PPO(command_history=H) has obs_len + 4 H inputs: H is read off the checkpoint's input length, and every
+    # checkpoint of one sweep must agree (one bank, one launch per batch of cells)
+    from optimal_quad_control_rl_amd.evaluation import _as_actor, check_command_history
+    extra = sorted({int(_as_actor(p)[0][0].in_features) - env.state_len for p in paths})
+    if len(extra) != 1 or extra[0] < 0 or extra[0] % 4:
+        raise SystemExit("the checkpoints have %s inputs beyond the env's observation (gates_ahead %d): one command history, a multiple of 4, is needed"
+                         % (extra, a.gates_ahead))
+    history = check_command_history(extra[0] // 4, a.gates_ahead)
     results = evaluate_sensing_grid(paths, [cond], sensors, env, envs_per_cell=E, n_eval_steps=a.steps, window_steps=a.window, precision=a.precision,
-                                    seed=a.seed, noise_seed=a.noise_seed)
+                                    seed=a.seed, noise_seed=a.noise_seed, command_history=history)
     env.close()
     print("# %d checkpoints x %d noise scales x %d delays, base sigma %s, %s track, %d envs per cell, %d steps (window %d), seed %d, noise seed %d, "
-          "%d cells per launch" % (len(paths), len(scales), len(delays), ",".join("%g" % s for s in sigma), a.track, E, a.steps, a.window, a.seed,
-                                   a.noise_seed, n // E))
+          "%d cells per launch%s" % (len(paths), len(scales), len(delays), ",".join("%g" % s for s in sigma), a.track, E, a.steps, a.window, a.seed,
+                                     a.noise_seed, n // E, ", command history %d" % history if history else ""))
     D = len(delays)
     tables = [[per_policy[0][i * D:(i + 1) * D] for i in range(len(scales))] for per_policy in results]
     for path, cells in zip(paths, tables):
