@@ -61,7 +61,8 @@ extern "C" {
                              qr_rollout_policy_dynamics / qr_vehicle_physical_count / qr_vehicle_bank_sample (round 21),
                              qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22),
                              qr_rollout_policy_sensing (round 23),
-                             qr_rollout_policy_history / qr_evaluate_policy_history_grid (round 24) */
+                             qr_rollout_policy_history / qr_evaluate_policy_history_grid (round 24),
+                             qr_blackbox_policy_grid (round 25) */
 
 enum {
     QR_OK = 0,
@@ -716,6 +717,44 @@ enum { QR_BLACKBOX_ON_CRASH = 1, QR_BLACKBOX_ON_TIME_LIMIT = 2 };
 int qr_blackbox_policy(qr_env* env, qr_policy* policy, int32_t num_steps, const float* log_std, uint64_t noise_seed,
                        uint64_t first_step, int32_t flags, int32_t trigger, int32_t window, int32_t rec_envs, float* ring_dev,
                        int32_t* st_dev, float* term_dev, void* stream);
+
+/* BLACK BOX AND FLIGHT RECORDER OF THE SENSING-GRID EVALUATOR: the launch of qr_evaluate_policy_history_grid with the black box of
+ * qr_blackbox_policy riding in its step loop, so that the crash log of a cell belongs to the numbers the evaluator reports for that cell:
+ * per group the policy slot, condition, vehicle and sensor, the optional command history, the group-local reset and noise streams and
+ * deterministic clip(mean) actions.  A black box that never freezes (trigger 0) with window = num_steps is the flight recorder of a cell.
+ * Every argument up to and including recf_dev has the meaning, the order and the refusals of qr_evaluate_policy_history_grid, with one
+ * extension: `history` may be 0, the call is then the twin of qr_evaluate_policy_sensing_grid and the bank's obs_len is the env's.
+ * CONTRACT (1), the evaluator half: rec_dev, recf_dev, pending_dev and the env state after the call are bit for bit what the evaluator twin
+ * produces for the same arguments, whatever trigger, window, rec_per_group and the three black-box buffers are.
+ * The black-box half follows qr_blackbox_policy -- row layout R = qr_record_row_len(), status [.][QR_BLACKBOX_ST_INTS], cause bits, trigger
+ * bits, armed / frozen rule, continuation rule (consecutive first_step, same window, same buffers and the same pending / rec / recf) --
+ * and differs in this:
+ *   WHICH ENVS   M = rec_per_group, 1 <= M <= envs_per_group: the first M envs of every group are recorded; env g E + j, j < M, owns column
+ *                c = g M + j of ring_dev [W][G M][R], st_dev [G M][4] and term_dev [G M][S] (or NULL), G = num_groups, E = envs_per_group.
+ *                All envs fly, and nothing beyond these extents is ever written.
+ *   RING SLOT    the row of call-step k goes to slot (first_step + k) mod W; the same first_step advances the sensor's noise stream.
+ *   THE ROW UNDER A SENSOR
+ *                [0, S)       the TRUE world state before the step (what qr_get_state would return), not the noisy observation
+ *                [S, S + 4)   the command the env RECEIVED, the command flown: under a delay d the clipped command computed d steps earlier
+ *                             in the episode, zeros for the episode's first d steps
+ *                [S + 4 ..)   unchanged: reward of the step flown, end code, target gate before the step, the episode's step count before it
+ *                Not recorded: the noisy row the policy saw, the commands computed and not yet flown (they are in pending_dev after the
+ *                call), and any stochastic or training-keyed form (ordinary env ids, action noise).
+ *   TRIGGER STEP the terminal world state and the cause bits are taken where qr_blackbox_policy takes them, after the integration and before
+ *                the auto-reset; the step that freezes an env is also the step that clears its queue and history (the evaluator's one event).
+ * A wave's 64 rows leave as one contiguous block iff all its envs lie below M and the block is 16-byte aligned in every group (R % 4 == 0 or
+ * M % 4 == 0); otherwise per lane.  No atomics, no workgroup that waits for another, no load of a slot value in the step loop.
+ * Refused before anything is launched or copied (qr_last_error set; every buffer and the state untouched): everything
+ * qr_evaluate_policy_history_grid refuses, in its order, with `history` checked against [0, 4 - gates_ahead]; then, in qr_blackbox_policy's
+ * order and wording, NULL or misaligned ring_dev / st_dev, misaligned term_dev, rec_per_group outside 1..envs_per_group, trigger outside
+ * 0..3, window < 1.  qr_last_step_many_ms() reports this launch too. */
+int qr_blackbox_policy_grid(qr_env* env, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                            qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group,
+                            const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group,
+                            int32_t history, int32_t num_steps, int32_t flags, uint64_t noise_seed, uint64_t first_step,
+                            float* pending_dev, int32_t* rec_dev, float* recf_dev,
+                            int32_t trigger, int32_t window, int32_t rec_per_group, float* ring_dev, int32_t* st_dev, float* term_dev,
+                            void* stream);
 
 /* ---- PPO minibatch update on the matrix cores (replaces SB3's PPO.train inner loop, R:783-795 / R:820) -------------
  * Networks: policy obs -> 120 -> 120 -> 120 -> 4 and value obs -> 120 -> 120 -> 120 -> 1 (ReLU), log_std[4].

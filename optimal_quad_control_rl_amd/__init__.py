@@ -12,7 +12,8 @@ __all__ = ["Quadcopter3DGates", "Quadcopter3DGatesINDI", "zigzag_track", "square
            "evaluate_grid", "Condition", "ConditionBank", "disturbance_sweep", "plan_condition_groups", "blackbox_policy", "CrashLog",
            "evaluate_q3_policy", "evaluate_q3_policies", "summarize_q3_eval", "PopulationPPO", "PBT", "EvolutionStrategy",
            "evaluate_dynamics_grid", "DynamicsParams", "DynamicsBank", "physical_sweep", "VehicleRanges",
-           "evaluate_sensing_grid", "SensingParams", "SensingBank", "noise_sweep", "delay_sweep", "plan_sensor_mix"]
+           "evaluate_sensing_grid", "SensingParams", "SensingBank", "noise_sweep", "delay_sweep", "plan_sensor_mix",
+           "blackbox_grid", "record_grid"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch / a GPU
@@ -36,11 +37,11 @@ def __getattr__(name):  # lazy: importing the package must not require torch / a
         from . import evaluation
 
         return getattr(evaluation, name)
-    if name in ("record_policy", "FlightRecord"):  # on-device flight recorder: the trajectory a policy flew (qr_record_policy)
+    if name in ("record_policy", "FlightRecord", "record_grid"):  # on-device flight recorder: the trajectory a policy flew (qr_record_policy; per grid cell: qr_blackbox_policy_grid)
         from . import recording
 
         return getattr(recording, name)
-    if name in ("blackbox_policy", "CrashLog"):  # on-device black box: the last steps before each crash (qr_blackbox_policy)
+    if name in ("blackbox_policy", "CrashLog", "blackbox_grid"):  # on-device black box: the last steps before each crash (qr_blackbox_policy; per grid cell: qr_blackbox_policy_grid)
         from . import blackbox
 
         return getattr(blackbox, name)

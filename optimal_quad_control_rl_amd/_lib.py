@@ -129,6 +129,9 @@ SIGNATURES = {
     "qr_evaluate_policy_history_grid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                                   _vp, _vp, _vp, _vp]),
+    "qr_blackbox_policy_grid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                                          _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "qr_vehicle_physical_count": (C.c_int, [C.c_int32]),
     "qr_vehicle_bank_sample": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_uint64, C.c_uint64,
                                           _vp]),
@@ -207,7 +210,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_evaluate_policy_dynamics_grid", "qr_rollout_policy_dynamics", "qr_vehicle_physical_count",
                     "qr_vehicle_bank_sample", "qr_sensing_bank_create", "qr_sensing_bank_destroy", "qr_sensing_bank_capacity", "qr_sensing_bank_set",
                     "qr_sensing_bank_read", "qr_evaluate_policy_sensing_grid", "qr_sensing_noise",
-                    "qr_rollout_policy_sensing", "qr_rollout_policy_history", "qr_evaluate_policy_history_grid")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_rollout_policy_sensing", "qr_rollout_policy_history", "qr_evaluate_policy_history_grid",
+                    "qr_blackbox_policy_grid")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

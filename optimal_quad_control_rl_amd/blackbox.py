@@ -29,7 +29,9 @@ class CrashLog:
     """Host view of a black-box ring [W][M][R] (float32, recorder rows), its status [M][4] (int32) and the terminal states [M][S] or None,
     after calls that covered steps first_step .. last_step (the absolute step index of the last call's last step)."""
 
-    def __init__(self, ring, status, terminal, last_step, dt):
+    def __init__(self, ring, status, terminal, last_step, dt, evaluation=None):
+        """evaluation (optional; blackbox_grid): summarize_eval's dict of the flight the log was taken from"""
+        self.evaluation = evaluation
         ring, status = _host(ring), _host(status)
         if ring.dtype != np.float32 or ring.ndim != 3 or ring.shape[2] - RECORD_EXTRA not in (13, 16):
             raise ValueError("ring must be float32 [W][M][S + %d] with S = 13 or 16, got %s %s" % (RECORD_EXTRA, ring.dtype, ring.shape))
@@ -144,3 +146,103 @@ def blackbox_policy(model, env, n_steps, window=64, trigger="crash", rec_envs=No
                                                      rec_envs=rec_envs, precision=precision)
         ring, st, term = ring.cpu().numpy(), st.cpu().numpy(), term.cpu().numpy()
     return CrashLog(ring, st, term, int(n_steps) - 1, core.dt)
+
+
+def cell_columns(ring, status, terminal, group, rec_per_group):
+    """The columns of group `group` in the buffers of qr_blackbox_policy_grid: env g E + j, j < M = rec_per_group, owns column g M + j of
+    ring [W][G M][R], status [G M][4] and terminal [G M][S] (or None).  Returns contiguous copies (ring [W][M][R], status [M][4],
+    terminal [M][S] or None) of host arrays."""
+    g, m = int(group), int(rec_per_group)
+    ring, status = _host(ring), _host(status)
+    if m < 1 or g < 0 or (g + 1) * m > ring.shape[1] or status.shape[0] != ring.shape[1]:
+        raise ValueError("group %d of %d columns each lies outside ring %s / status %s" % (g, m, ring.shape, status.shape))
+    cols = slice(g * m, (g + 1) * m)
+    term = None if terminal is None else np.ascontiguousarray(_host(terminal)[cols])
+    return np.ascontiguousarray(ring[:, cols]), np.ascontiguousarray(status[cols]), term
+
+
+def fly_grid_cells(policies, conditions, sensing, env, dynamics, envs_per_cell, n_steps, window, trigger, rec_per_cell, precision, seed, noise_seed,
+                   command_history, make):
+    """The launches of blackbox_grid / record_grid: evaluate_sensing_grid's banks, starts and batching with ONE phase of n_steps through
+    env.blackbox_grid_device; make(ring, status, terminal, evaluation) [one cell's columns, host arrays] -> logs[p][c][s]."""
+    import torch
+
+    from ._closed_loop import fly_batches, group_size
+    from .conditions import ConditionBank
+    from .dynamics import DynamicsBank
+    from .evaluation import REC_FLOATS, REC_INTS, _as_actor, _model_precision, _sync_and_close, check_command_history, plan_dynamics_batches, summarize_eval
+    from .policy import MfmaPolicyBank
+    from .sb3 import _unwrap
+    from .sensing import QUEUE_FLOATS, SensingBank
+
+    core = _unwrap(env)
+    H = check_command_history(command_history, core.gates_ahead)
+    E, slots = group_size(envs_per_cell, core.num_envs, "envs_per_cell", "cell")
+    n_steps, window = int(n_steps), int(window)
+    M = E if rec_per_cell is None else int(rec_per_cell)
+    if n_steps < 1 or window < 1 or not 1 <= M <= E:
+        raise ValueError("need n_steps >= 1, window >= 1 and 1 <= rec_per_cell <= envs_per_cell")
+    conditions, policies, sensing = list(conditions), list(policies), list(sensing)
+    plan = plan_dynamics_batches(len(policies), len(conditions), len(sensing), slots)   # cells (policy, condition, sensor)
+    if dynamics is not None and dynamics.variant != core.VARIANT:
+        raise ValueError("DynamicsParams of another variant than the env")
+    actors = [_as_actor(p) for p in policies]
+    if precision is None:
+        precision = _model_precision([m for _, m in actors])
+    logs = [[[None] * len(sensing) for _ in conditions] for _ in actors]
+    pbank = MfmaPolicyBank(core.state_len + 4 * H, len(actors), core.device.index)
+    cbank = ConditionBank(core.VARIANT, len(conditions), core.device.index)
+    dbank = DynamicsBank(core.VARIANT, 1, core.device.index)
+    sbank = SensingBank(len(sensing), core.device.index)
+    pending = torch.zeros((core.num_envs, QUEUE_FLOATS), dtype=torch.float32, device=core.device)
+    box = [None]   # the batch's (ring, status, terminal) on the host
+
+    def start(cells):
+        core.condition_starts(conditions, [c for _, c, _ in cells], E, seed=seed)
+        pending.zero_()
+
+    def launch(cells, steps, rec, recf):
+        maps = ([p for p, _, _ in cells], [c for _, c, _ in cells], [0] * len(cells), [s for _, _, s in cells])
+        out = core.blackbox_grid_device(pbank, cbank, dbank, sbank, *maps, H, E, steps, pending, rec, recf, precision=precision,
+                                        noise_seed=noise_seed, first_step=0, window=window, trigger=trigger, rec_per_group=M)
+        box[0] = tuple(t.cpu().numpy() for t in out[2:])
+
+    def summarise(cell, rec, recf):
+        return summarize_eval(rec, recf, core.dt, conditions[cell[1]].gates_per_lap)
+
+    try:
+        for p, (actor, _) in enumerate(actors):
+            pbank.load_torch(p, actor)
+        for c, cond in enumerate(conditions):
+            cbank.set(c, cond)
+        dbank.set(0, dynamics)
+        for s, sen in enumerate(sensing):
+            sbank.set(s, sen)
+        # one batch at a time: the batch's buffers are split into its cells before the next batch overwrites them
+        for members, kept in plan:
+            flown = fly_batches([(members, kept)], start, launch, [n_steps], (REC_INTS, REC_FLOATS), summarise, core.num_envs, E, core.device)
+            for g, ((p, c, s), summaries) in enumerate(flown):
+                logs[p][c][s] = make(*cell_columns(*box[0], g, M), summaries[0], core.dt)
+    finally:
+        _sync_and_close(core, pbank, cbank, dbank, sbank)
+    return logs
+
+
+def blackbox_grid(policies, conditions, sensing, env, dynamics=None, envs_per_cell=256, n_steps=2000, window=64, trigger="crash", rec_per_cell=None,
+                  precision=None, seed=0, noise_seed=0, command_history=0):
+    """The black box of evaluate_sensing_grid (qr_blackbox_policy_grid): every cell of `policies` x `conditions` x `sensing` flies exactly
+    what that evaluator flies -- its starts, restarts and noise draws, deterministic actions, the vehicle `dynamics`, the optional
+    `command_history` -- for `n_steps` in one launch per `env.num_envs // envs_per_cell` cells, and the first `rec_per_cell` envs of each
+    cell (None: all) keep their last `window` rows, frozen by `trigger` as in blackbox_policy.  A row holds the TRUE state before the step
+    and the command FLOWN (under a delay, the one computed that many steps earlier; zeros at an episode's start).  Returns logs[p][c][s],
+    each a CrashLog of that cell's columns whose `.evaluation` is summarize_eval of the cell over the same n_steps: the dict
+    evaluate_sensing_grid(..., n_eval_steps=n_steps, window_steps=n_steps) returns as "total"."""
+    if trigger not in TRIGGERS:
+        raise ValueError("trigger must be one of %s, got %r" % (sorted(TRIGGERS), trigger))
+    last = int(n_steps) - 1
+
+    def make(ring, status, terminal, evaluation, dt):
+        return CrashLog(ring, status, terminal, last, dt, evaluation=evaluation)
+
+    return fly_grid_cells(policies, conditions, sensing, env, dynamics, envs_per_cell, n_steps, window, TRIGGERS[trigger], rec_per_cell, precision,
+                          seed, noise_seed, command_history, make)

@@ -659,9 +659,9 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
 // What qr_rollout_policy and qr_rollout_policy_conditions refuse about their shared arguments and the handle's mode, in one order; on
 // success A holds the weights and the sampling arguments of the launch.  history: null, or the command history of
 // qr_rollout_policy_history -- its range is refused directly before the observation length, which is then the env's + 4 * history.
-static int check_history(const qr_env* e, int history, const char* who) {
-    if (history < 1 || history > 4 - e->cfg.gates_ahead)
-        return fail(QR_E_INVALID, std::string(who) + ": history must be in [1, 4 - gates_ahead] (the row of obs_len + 4 * history floats must be a "
+static int check_history(const qr_env* e, int history, const char* who, int lowest = 1) {
+    if (history < lowest || history > 4 - e->cfg.gates_ahead)
+        return fail(QR_E_INVALID, std::string(who) + ": history must be in [" + std::to_string(lowest) + ", 4 - gates_ahead] (the row of obs_len + 4 * history floats must be a "
                                                      "length the policy kernels have: gates_ahead + history <= 4)");
     return QR_OK;
 }
@@ -1021,11 +1021,20 @@ static bool sensing_steps_fit(uint64_t first_step, int K) {
 // qr_evaluate_policy_dynamics_grid with a fourth bank and a fourth map: its refusals in its order, then the sensing bank's.  Nothing is
 // enqueued or copied unless every argument is valid.  history: null (qr_evaluate_policy_sensing_grid), or the command history of
 // qr_evaluate_policy_history_grid: its range is refused directly before the bank's observation length, which is then the env's + 4 * history.
+// bb: null, or the black box of qr_blackbox_policy_grid: history may then be 0, and the black box's own refusals (qr_blackbox_policy's, in
+// its order and wording) follow everything the evaluator refuses.
+struct BlackboxGridCall {
+    int32_t trigger, window, rec_per_group;
+    float* ring_dev;
+    int32_t* st_dev;
+    float* term_dev;
+};
 static int evaluate_policy_sensing_grid(const char* who, const int32_t* history, qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions,
                                         qr_dynamics_bank* dynamics, qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group,
                                         const int32_t* policy_of_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
                                         const int32_t* sensing_of_group, int32_t K, int32_t flags, uint64_t noise_seed, uint64_t first_step,
-                                        float* pending_dev, int32_t* rec_dev, float* recf_dev, void* stream) {
+                                        float* pending_dev, int32_t* rec_dev, float* recf_dev, void* stream,
+                                        const BlackboxGridCall* bb = nullptr) {
     const std::string w = std::string(who) + ": ";
     if (int rc = check_ready(e)) return rc;
     if (!policies) return fail(QR_E_INVALID, w + "null policy bank handle");
@@ -1033,8 +1042,10 @@ static int evaluate_policy_sensing_grid(const char* who, const int32_t* history,
     if (!dynamics) return fail(QR_E_INVALID, w + "null dynamics bank handle");
     if (!policy_of_group || !condition_of_group || !dynamics_of_group) return fail(QR_E_INVALID, w + "the three group maps are required");
     if (int rc = check_eval_args(e, K, nullptr, flags, rec_dev, recf_dev, who)) return rc;
-    if (history) {
-        if (int rc = check_history(e, *history, who)) return rc;
+    if (history && bb && *history == 0) {
+        if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) return rc;
+    } else if (history) {
+        if (int rc = check_history(e, *history, who, bb ? 0 : 1)) return rc;
         if (int rc = qr::check_policy_bank(policies, e->L + 4 * *history, e->cfg.device, who, "policy bank", "!= env obs_len + 4 * history")) return rc;
     } else if (int rc = qr::check_policy_bank(policies, e->L, e->cfg.device, who)) {
         return rc;
@@ -1056,11 +1067,27 @@ static int evaluate_policy_sensing_grid(const char* who, const int32_t* history,
     for (int g = 0; g < num_groups; ++g)
         if (!sensing->is_set[(size_t)sensing_of_group[g]])
             return fail(QR_E_STATE, w + "slot " + std::to_string(sensing_of_group[g]) + " of the sensing bank was never set");
+    if (bb) {   // the black box's own, as qr_blackbox_policy words them (num_steps and the flags are the evaluator's, above)
+        if (!bb->ring_dev || !bb->st_dev) return fail(QR_E_INVALID, w + "ring_dev and st_dev are required");
+        if (((uintptr_t)bb->ring_dev | (uintptr_t)bb->st_dev) & 15) return fail(QR_E_INVALID, w + "ring_dev and st_dev must be 16-byte aligned");
+        if ((uintptr_t)bb->term_dev & 3) return fail(QR_E_INVALID, w + "term_dev must be 4-byte aligned");
+        if (bb->rec_per_group < 1 || bb->rec_per_group > envs_per_group) return fail(QR_E_INVALID, w + "rec_per_group must be in 1..envs_per_group");
+        if (bb->trigger < 0 || bb->trigger > (QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT))
+            return fail(QR_E_INVALID, w + "`trigger` takes QR_BLACKBOX_ON_CRASH | QR_BLACKBOX_ON_TIME_LIMIT");
+        if (bb->window < 1) return fail(QR_E_INVALID, w + "window must be >= 1");
+    }
     hipStream_t st = (hipStream_t)stream;
     std::vector<int4> map((size_t)num_groups);
     for (int g = 0; g < num_groups; ++g)
         map[(size_t)g] = make_int4(policy_of_group[g], condition_of_group[g], dynamics_of_group[g], sensing_of_group[g]);
     if (int rc = upload_table(e->sen_map, map, st, who, "group map", "this map")) return rc;
+    if (bb) {
+        const int slot0 = (int)(first_step % (uint64_t)bb->window);   // the ring slot of the call's first step
+        return QR_TIMED_LAUNCH(e, st, qr::launch_blackbox_policy_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
+                                           conditions->d_slots, dynamics->d_slots, sensing->d_slots, e->sen_map.d, *history,
+                                           (flags & QR_ROLLOUT_F32CLASS) != 0, num_groups, envs_per_group, K, noise_seed, first_step, pending_dev, rec_dev,
+                                           recf_dev, bb->trigger, bb->window, bb->rec_per_group, slot0, bb->ring_dev, bb->st_dev, bb->term_dev, st));
+    }
     if (history)
         return QR_TIMED_LAUNCH(e, st, qr::launch_eval_policy_history_grid(e->cfg.variant, e->P, qr::bank_weights(policies), qr::bank_weights_lo(policies),
                                            conditions->d_slots, dynamics->d_slots, sensing->d_slots, e->sen_map.d, *history,
@@ -1090,6 +1117,18 @@ int qr_evaluate_policy_history_grid(qr_env* e, qr_policy_bank* policies, qr_cond
     return evaluate_policy_sensing_grid("qr_evaluate_policy_history_grid", &history, e, policies, conditions, dynamics, sensing, num_groups, envs_per_group,
                                         policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group, K, flags, noise_seed, first_step,
                                         pending_dev, rec_dev, recf_dev, stream);
+}
+
+// the evaluator's launch (history 0: the sensing grid's) with the black box riding in the step loop
+int qr_blackbox_policy_grid(qr_env* e, qr_policy_bank* policies, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
+                            int32_t num_groups, int32_t envs_per_group, const int32_t* policy_of_group, const int32_t* condition_of_group,
+                            const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t history, int32_t K, int32_t flags,
+                            uint64_t noise_seed, uint64_t first_step, float* pending_dev, int32_t* rec_dev, float* recf_dev, int32_t trigger,
+                            int32_t window, int32_t rec_per_group, float* ring_dev, int32_t* st_dev, float* term_dev, void* stream) {
+    const BlackboxGridCall bb = {trigger, window, rec_per_group, ring_dev, st_dev, term_dev};
+    return evaluate_policy_sensing_grid("qr_blackbox_policy_grid", &history, e, policies, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                        policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group, K, flags, noise_seed, first_step,
+                                        pending_dev, rec_dev, recf_dev, stream, &bb);
 }
 
 // the rows the evaluator adds to the observations of one group under one slot: refusals first, then one launch

@@ -2,7 +2,8 @@
 // env.step] with the lap / crash accounting a user reads after training (gate passes, crashes, time-limit ends, lap durations by lap
 // number, episode returns) kept in registers next to the env state.  eval_policy_kernel (quadrace_eval.hip), eval_policy_bank_kernel
 // (quadrace_eval_bank.hip) and eval_policy_grid_kernel (quadrace_eval_grid.hip) each derive their inputs and call it; the record and
-// its accounting exist here and in tests/eval_spec.py, nowhere else.
+// its accounting exist here and in tests/eval_spec.py, nowhere else.  The dynamics-, sensing- and history-grid kernels call it with their
+// classes, and blackbox_policy_grid_kernel (quadrace_blackbox_grid.hip) with a recording class on top: the one form with a per-step output.
 //
 // The step loop is rollout_policy_kernel's (quadrace_env_kernels.hpp) without everything an evaluation throws away: no action noise
 // (no Philox / Box-Muller slices between the matrix instructions), no observation tile, no observation / action / log-prob / reward /
@@ -45,13 +46,27 @@ constexpr size_t eval_lds_bytes() {
 //                  current episode behind the noisy observation, [o~_k | u_{k-1}, ..., u_{k-H}]: img / img_lo are images of a policy of
 //                  obs_len<V, GA + H>() inputs and the kernel supplies eval_lds_bytes of THAT length; the tail is read from and written back
 //                  to entries 0 .. H - 1 of `pending`, cleared with the queue (rollout_policy_group_kernel carries the same statements)
+//   Rec, rc        what leaves the kernel PER STEP: NoRecording (the default, rc a dummy: nothing -- no global store inside the step loop; no
+//                  code) or a recording class (quadrace_blackbox_grid.hip; RuntimeSensing only) whose State<V> carries the black box of
+//                  quadrace_blackbox.hip through the loop: begin ahead of it, flush_lanes at its top, slice(s, e.s) in the matrix-instruction
+//                  shadow of the third layer, advance behind the forward, on_end inside step_env's before_reset hook (e.s is the terminal
+//                  state), row_tail behind the step, finish / store_status behind the loop -- and kBlock rows of R floats of dynamic LDS
+//                  behind the command queue.  The row's command is the one FLOWN (u behind the queue), its state the true e.s.
 // kTail: lanes with i >= P.n exist (MFMA / permlane are wave-wide: they shadow env 0 and store nothing); without it i < P.n holds
 // for every lane, every lane is an env and every lane stores.
-template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing, int H = 0>
+struct NoRecording {
+    using Arg = int;
+    static constexpr bool kOn = false;
+    template <int V>
+    struct State {};
+};
+
+template <int V, int GA, bool kF32, bool kTail, class C = NominalDyn<V>, class Sn = IdealSensing, int H = 0, class Rec = NoRecording>
 __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* __restrict__ img, const half8* __restrict__ img_lo,
                                                  const float* __restrict__ tab, int i, int rid, int K, int gates_per_lap,
                                                  int4* __restrict__ rec, float4* __restrict__ recf, typename C::Arg dyn = typename C::Arg(),
-                                                 typename Sn::Arg sen = typename Sn::Arg()) {
+                                                 typename Sn::Arg sen = typename Sn::Arg(), typename Rec::Arg rc = typename Rec::Arg()) {
+    static_assert(!Rec::kOn || (Sn::kOn && !kTail), "a recording class rides on the sensing-grid form: every lane an env, the tile behind the queue");
     static_assert(H == 0 || (Sn::kOn && H >= 1 && GA + H <= 4), "the command history needs the sensing hooks, 1 <= H <= 4 - GA");
     constexpr int LE = obs_len<V, GA>();       // the env's row: observe, the sensor's noise
     constexpr int L = obs_len<V, GA + H>();    // the policy's row [o~ | h] = LE + 4 H floats (H = 0: LE)
@@ -123,6 +138,9 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
     bool any_reset = false;
     float stash[reset_value_count<V>()];   // the lane's own next reset draws (reset_from_stash)
     bool stash_ok = false;
+    [[maybe_unused]] typename Rec::template State<V> rs;
+    if constexpr (Rec::kOn)   // the record tile: kBlock rows behind the command queue
+        rs.begin(rc, reinterpret_cast<float*>(laps - threadIdx.x + 2 * QR_EVAL_MAX_LAPS * kBlock) + kSensingQueueFloats * kBlock, rid, lane);
     float o[L];
     observe<V, GA>(P, gates, e, o);
     if constexpr (H > 0) {   // h_0 = the caller's queue, entries 0 .. H - 1 (whatever d is)
@@ -136,8 +154,22 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
     for (int k = 0; k < K; ++k) {
         if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen, gid_lo, gid_hi, k, o);   // o is rebuilt from the state behind the step
         float mean[4];
-        if constexpr (kF32) policy_forward_f32class<L>(W, img_lo, lane, o, mean);
-        else policy_forward<L>(W, lane, o, mean);
+        if constexpr (Rec::kOn) {   // the rows of step k - 1 leave and the state of step k enters the tile under the third layer
+            rs.flush_lanes();
+            auto rec_slice = [&](int s) { rs.slice(s, e.s); };
+            if constexpr (kF32) {
+                rec_slice(0);
+                rec_slice(2);
+                policy_forward_f32class<L>(W, img_lo, lane, o, mean);
+            } else {
+                policy_forward<L>(W, lane, o, mean, NoFiller(), rec_slice);
+            }
+            rs.advance();
+        } else if constexpr (kF32) {
+            policy_forward_f32class<L>(W, img_lo, lane, o, mean);
+        } else {
+            policy_forward<L>(W, lane, o, mean);
+        }
         float u[4];
         clip_action(mean, u);
         [[maybe_unused]] float uc[4];   // (H > 0 only) the command COMPUTED in this step: what enters the history, whatever flies
@@ -159,10 +191,15 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
             }
         }
         const int target_before = e.target;
+        [[maybe_unused]] const int steps_before = e.steps;
         bool done, trunc, did_reset;
         const float reward = step_env<V, 0, C>(P, gates, rtab, nullptr, mlp, lane, active, e, u, gid_lo, gid_hi, done, trunc, did_reset,
-                                               [](bool) {}, [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); }, dyn);
+                                               [&](bool d) {
+                                                   if constexpr (Rec::kOn) rs.on_end(d, trunc, e.s);
+                                               },
+                                               [&](bool need) { reset_from_stash<V>(P, rtab, need, e, gid_lo, gid_hi, stash, stash_ok); }, dyn);
         any_reset |= did_reset;
+        if constexpr (Rec::kOn) rs.row_tail(u, reward, done, trunc, target_before, steps_before);
         // ---- accounting (tests/eval_spec.py, same order).  A pass on the step that ends the episode is not counted: the reset has
         // replaced the target, and that episode's lap count is void anyway.
         now += 1;
@@ -205,7 +242,9 @@ __device__ __forceinline__ void eval_policy_body(const Params& P, const half8* _
             for (int c = 0; c < 4; ++c) o[LE + c] = done ? 0.0f : uc[c];
         }
     }
+    if constexpr (Rec::kOn) rs.finish();   // the rows of the last step
     if (!active) return;
+    if constexpr (Rec::kOn) rs.store_status();
     int4* row = rec + (size_t)i * 6;
     int lap_sum[QR_EVAL_MAX_LAPS], lap_cnt[QR_EVAL_MAX_LAPS];
 #pragma unroll

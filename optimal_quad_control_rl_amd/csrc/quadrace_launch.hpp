@@ -253,6 +253,14 @@ hipError_t launch_record_policy(int variant, const Params& P, const PolicyArgs& 
 hipError_t launch_blackbox_policy(int variant, const Params& P, const PolicyArgs& A, int K, int rec_envs, int trigger, int window, int slot0,
                                   float* ring, int32_t* st_rec, float* term, hipStream_t st);
 
+// quadrace_blackbox_grid.hip: the black box of the sensing-grid evaluator (qr_blackbox_policy_grid): launch_eval_policy_history_grid's
+// arguments with history in [0, 4 - gates_ahead] (0: the sensing grid's launch), then the black box's -- the first rec_per_group envs of every
+// group own columns of ring [window][num_groups * rec_per_group][S + 8], st_rec [..][4], term [..][S] or null; slot0 = first_step mod window
+hipError_t launch_blackbox_policy_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
+                                       const float* sens, const int4* map, int history, bool f32class, int num_groups, int envs_per_group, int K,
+                                       uint64_t noise_seed, uint64_t first_step, float* pending, int32_t* rec, float* recf, int trigger, int window,
+                                       int rec_per_group, int slot0, float* ring, int32_t* st_rec, float* term, hipStream_t st);
+
 // quadrace_policy.hip
 hipError_t launch_policy(int L, const half8* w, int n, const float* obs, float* mean, hipStream_t st);
 hipError_t launch_policy_f32class(int L, const half8* w0, const half8* w1, int n, const float* obs, float* mean, hipStream_t st);

@@ -1,6 +1,7 @@
 // quadrace_record_tiles.hpp -- the wave-private LDS tile through which the flight recorder (quadrace_record.hip) and the black box
 // (quadrace_blackbox.hip) assemble their packed rows [R = S + QR_RECORD_EXTRA floats per env and step] and stream them out; the write
-// shape and its LDS traffic are described at the top of quadrace_record.hip.  Included by those two units and by nothing else.
+// shape and its LDS traffic are described at the top of quadrace_record.hip.  Included by those two units and by the black box of the
+// sensing-grid evaluator (quadrace_blackbox_grid.hip), and by nothing else.
 #pragma once
 #include "quadrace_env_kernels.hpp"
 

@@ -118,3 +118,20 @@ def record_policy(model, env, n_steps, envs=None, deterministic=True, seed=None,
         host = rows.cpu().numpy()
         final_target = core.get_state_tensors()[2][:host.shape[1]].cpu().numpy()
     return FlightRecord(host, core.dt, final_target)
+
+
+def record_grid(policies, conditions, sensing, env, dynamics=None, envs_per_cell=256, n_steps=2000, rec_per_cell=None, precision=None, seed=0,
+                noise_seed=0, command_history=0):
+    """The flight recorder of evaluate_sensing_grid: blackbox_grid's launch with a black box that never freezes and a ring as long as the
+    call (trigger 0, window = n_steps), so slot k holds the row of step k.  Returns records[p][c][s], each the FlightRecord [n_steps][M][R]
+    of the first `rec_per_cell` envs of that cell (None: all), with `.evaluation` = summarize_eval of the cell over the same steps.  Rows
+    hold the TRUE state before the step and the command FLOWN, as blackbox_grid's."""
+    from .blackbox import fly_grid_cells
+
+    def make(ring, status, terminal, evaluation, dt):
+        record = FlightRecord(ring, dt)
+        record.evaluation = evaluation
+        return record
+
+    return fly_grid_cells(policies, conditions, sensing, env, dynamics, envs_per_cell, n_steps, int(n_steps), 0, rec_per_cell, precision, seed,
+                          noise_seed, command_history, make)

@@ -1112,6 +1112,52 @@ class Quadcopter3DGates(_Base):
         self.update_states()   # the kernel stores no observation: refresh the env's own buffer from the state it left
         return ring, status, terminal
 
+    def blackbox_grid_device(self, policy_bank, condition_bank, dynamics_bank, sensing_bank, policy_of_group, condition_of_group,
+                             dynamics_of_group, sensing_of_group, command_history, envs_per_group, num_steps, pending, rec, recf=None,
+                             precision="f16-operands", noise_seed=0, first_step=0, window=64, trigger=1, rec_per_group=None, ring=None,
+                             status=None, terminal=None):
+        """The black box of the sensing-grid evaluator (qr_blackbox_policy_grid): the launch of evaluate_history_grid_device
+        (command_history = 0: of evaluate_sensing_grid_device) -- rec, recf, pending and the env state afterwards are bit for bit that
+        call's -- which also keeps, for the first M = rec_per_group envs of every group (None: all of them), the last `window` recorder
+        rows in a ring frozen the way `trigger` selects, as blackbox_policy_device does.  Env g E + j, j < M, owns column g M + j of
+        ring [W, G M, R], status [G M, 4] and terminal [G M, S]; the row of call-step k sits in slot (first_step + k) % W and holds the
+        TRUE world state before the step and the command FLOWN (under a delay, the one computed that many steps earlier).  window =
+        num_steps with trigger 0 is the flight recorder of every cell.  Pass the returned tensors back, with first_step advanced by
+        num_steps and the same pending / rec / recf, to continue; fresh ones are NaN / zero filled.
+        Returns (rec, recf, ring, status, terminal)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_blackbox_policy_grid")
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (policy_of_group, condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("policy_of_group, condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        self._check_eval_records(rec, recf)
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        g, e, w, dev = int(maps[0].shape[0]), int(envs_per_group), int(window), self.device
+        m = e if rec_per_group is None else int(rec_per_group)
+        cols, r = max(g, 1) * min(max(m, 1), max(e, 1)), self.STATE_LEN + self.RECORD_EXTRA   # (never empty: the library names a bad argument)
+        if ring is None:
+            ring = torch.full((max(w, 1), cols, r), float("nan"), dtype=torch.float32, device=dev)
+        else:
+            assert ring.is_cuda and ring.dtype == torch.float32 and ring.is_contiguous() and tuple(ring.shape) == (w, g * m, r), (ring.dtype, ring.shape)
+        if status is None:
+            status = torch.zeros((cols, self.BLACKBOX_ST_INTS), dtype=torch.int32, device=dev)
+        else:
+            assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and \
+                tuple(status.shape) == (g * m, self.BLACKBOX_ST_INTS), (status.dtype, status.shape)
+        if terminal is None:
+            terminal = torch.full((cols, self.STATE_LEN), float("nan"), dtype=torch.float32, device=dev)
+        else:
+            assert terminal.is_cuda and terminal.dtype == torch.float32 and terminal.is_contiguous() and \
+                tuple(terminal.shape) == (g * m, self.STATE_LEN), (terminal.dtype, terminal.shape)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy_bank._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, g, e,
+                      *[mp.ctypes.data_as(i32p) for mp in maps], int(command_history), int(num_steps), flags, int(noise_seed) & (2 ** 64 - 1),
+                      int(first_step), _ptr(pending), _ptr(rec), _ptr(recf), int(trigger), w, m, _ptr(ring), _ptr(status), _ptr(terminal),
+                      self._stream()))
+        self._observe_under(condition_bank.conditions, maps[1], e)
+        return rec, recf, ring, status, terminal
+
     def profile_rollout(self, actions, out):
         """Like rollout_device but every step kernel is bracketed by its own hipEvent pair on the launch stream.
         Returns (mean single-kernel duration in ms, whole-region ms).  Blocks."""

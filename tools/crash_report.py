@@ -5,11 +5,20 @@ one kernel launch, every env keeps its last --window rows and freezes them at it
     python tools/crash_report.py CHECKPOINT [--variant e2e|indi] [--track square|zigzag] [--gates-ahead 1] [--scale 1.0] [--num-envs 65536]
                                  [--steps 2000] [--window 64] [--trigger crash|time_limit|any] [--max-steps N] [--stochastic] [--seed 0]
                                  [--precision f16-operands|f32] [--out crashes.npz]
+                                 [--obs-noise SIGMA[,...8]] [--delay D] [--vehicle PARAM=SCALE]
 
 CHECKPOINT is what sb3.PPO.save or tools/train_ppo.py --save wrote; the env options are those of tools/robustness_sweep.py (E2E flies
 with the training disturbance ranges times --scale).  Prints the cause x target-gate table of the frozen envs, the median time into
 the episode and the median speed at the trigger row, and writes the log (CrashLog.save_npz: ring, status, terminal states and the
-unrolled flights of the frozen envs, oldest row first, NaN-padded) to --out."""
+unrolled flights of the frozen envs, oldest row first, NaN-padded) to --out.
+
+--obs-noise / --delay / --vehicle, or a checkpoint trained with --command-history H (H is read off its input length, as
+tools/sensing_sweep.py --load does): the flight is ONE CELL of the sensing-grid evaluator (blackbox_grid -> qr_blackbox_policy_grid) -- that
+sensor, that vehicle (one physical parameter scaled, through physical_sweep), the command history, deterministic actions, the evaluator's
+starts and noise draws -- so the log belongs to the numbers tools/sensing_sweep.py / tools/reality_gap_sweep.py print for that cell; the
+cell's own evaluation summary is printed with it.  Rows then hold the TRUE state and the command FLOWN.  --num-envs must be a multiple of
+256 there and --stochastic is refused.  Without any of these, and with a checkpoint without a command history, the call is blackbox_policy's
+as before."""
 import argparse
 import os
 import sys
@@ -42,6 +51,52 @@ def report(log, num_gates):
     return lines
 
 
+def add_cell_options(ap):
+    """the options that make the flight one cell of the sensing-grid evaluator (shared with tools/record_flight.py)"""
+    ap.add_argument("--obs-noise", default="", metavar="SIGMA[,...8]", help="observation noise: one sigma for all eight groups, or eight")
+    ap.add_argument("--delay", type=int, default=None, metavar="D", help="command delay in control steps, 0..4")
+    ap.add_argument("--vehicle", default="", metavar="PARAM=SCALE", help="one physical parameter of the vehicle times SCALE (physical_sweep), e.g. Izz=1.25")
+
+
+def grid_cell(a, env, model):
+    """None if the tool's call stays the one-policy call of before; otherwise the cell to fly: dict(condition, sensor, dynamics,
+    command_history).  `a`: the parsed options of add_cell_options and --track / --gates-ahead; `model`: the loaded checkpoint."""
+    from sensing_sweep import parse_sigma
+    from optimal_quad_control_rl_amd import Condition, SensingParams, physical_sweep
+    from optimal_quad_control_rl_amd.evaluation import _as_actor, check_command_history
+
+    extra = int(_as_actor(model)[0][0].in_features) - env.state_len
+    if extra < 0 or extra % 4:
+        raise SystemExit("the checkpoint has %d inputs beyond the env's observation: a command history, a multiple of 4, is needed" % extra)
+    history = check_command_history(extra // 4, env.gates_ahead)
+    if not (a.obs_noise or a.delay is not None or a.vehicle or history):
+        return None
+    if getattr(a, "stochastic", False):
+        raise SystemExit("--stochastic: a cell of the sensing-grid evaluator flies deterministic actions")
+    delay = 0 if a.delay is None else a.delay
+    if not 0 <= delay <= 4:
+        raise SystemExit("--delay needs an integer in [0, 4], got %r" % a.delay)
+    sigma = parse_sigma(a.obs_noise) if a.obs_noise else [0.0] * 8
+    dynamics = None
+    if a.vehicle:
+        name, _, scale = a.vehicle.partition("=")
+        try:
+            dynamics = physical_sweep(env.VARIANT, name.strip(), [float(scale)])[0]
+        except ValueError as err:
+            raise SystemExit("--vehicle takes PARAM=SCALE: %s" % err)
+    sensor = SensingParams.from_sigma(sigma, delay, "sigma %s d=%d" % (",".join("%g" % x for x in sigma), delay))
+    return dict(condition=Condition.from_env(env, name=a.track), sensor=sensor, dynamics=dynamics, command_history=history)
+
+
+def cell_lines(cell, evaluation):
+    """what was flown, and the evaluator's own numbers for it"""
+    fly = evaluation["flying_lap_seconds"]
+    return ["cell: sensor %s, vehicle %s, command history %d" % (cell["sensor"].name, cell["dynamics"].name if cell["dynamics"] is not None else "nominal",
+                                                                 cell["command_history"]),
+            "evaluation of the same flight: %.4f crashes per env, %.2f gates per env, flying lap %s s"
+            % (float(evaluation["crashes_per_env"]), float(evaluation["gates_per_env"]), "none" if fly is None else "%.3f" % fly)]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("checkpoint")
@@ -58,6 +113,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=("f16-operands", "f32"), default=None, help="default: f32 if the checkpoint was trained in f32")
     ap.add_argument("--out", default="crashes.npz", help="'' = write nothing")
+    add_cell_options(ap)
     a = ap.parse_args()
 
     trk = square_track() if a.track == "square" else zigzag_track()
@@ -68,10 +124,20 @@ def main():
         env.disturbance_scale = a.scale
     env.max_steps = a.max_steps
     model = PPO.load(a.checkpoint)
-    log = blackbox_policy(model, env, a.steps, window=a.window, trigger=a.trigger, deterministic=not a.stochastic, seed=a.seed, precision=a.precision)
+    cell = grid_cell(a, env, model)
+    if cell is None:
+        log = blackbox_policy(model, env, a.steps, window=a.window, trigger=a.trigger, deterministic=not a.stochastic, seed=a.seed, precision=a.precision)
+    else:
+        from optimal_quad_control_rl_amd import blackbox_grid
+
+        if a.num_envs % 256:
+            raise SystemExit("--num-envs must be a multiple of 256 for a cell of the sensing-grid evaluator")
+        log = blackbox_grid([model], [cell["condition"]], [cell["sensor"]], env, dynamics=cell["dynamics"], envs_per_cell=a.num_envs, n_steps=a.steps,
+                            window=a.window, trigger=a.trigger, precision=a.precision, seed=a.seed, noise_seed=a.seed,
+                            command_history=cell["command_history"])[0][0][0]
     print("# %s: %s %s track, %d envs x %d steps (%.1f s), trigger %s, seed %d"
           % (a.checkpoint, a.variant, a.track, a.num_envs, a.steps, a.steps * float(log.dt), a.trigger, a.seed))
-    for line in report(log, len(trk[0])):
+    for line in ([] if cell is None else cell_lines(cell, log.evaluation)) + report(log, len(trk[0])):
         print(line)
     if a.out:
         print("wrote", log.save_npz(a.out))
