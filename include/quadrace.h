@@ -62,7 +62,9 @@ extern "C" {
                              qr_sensing_* / qr_evaluate_policy_sensing_grid (round 22),
                              qr_rollout_policy_sensing (round 23),
                              qr_rollout_policy_history / qr_evaluate_policy_history_grid (round 24),
-                             qr_blackbox_policy_grid (round 25) */
+                             qr_blackbox_policy_grid (round 25),
+                             qr_rollout_policy_privileged / qr_ppo_grad_privileged / qr_ppo_minibatch_privileged /
+                             qr_ppo_epoch_privileged (round 26) */
 
 enum {
     QR_OK = 0,
@@ -608,6 +610,37 @@ int qr_evaluate_policy_history_grid(qr_env* env, qr_policy_bank* policies, qr_co
                                     int32_t history, int32_t num_steps, int32_t flags, uint64_t noise_seed, uint64_t first_step,
                                     float* pending_dev, int32_t* rec_dev, float* recf_dev, void* stream);
 
+/* PRIVILEGED CRITIC, the collect half: the sensing / history rollout that ALSO stores the row before the sensor's noise.  Under
+ * observation noise the policy must read the noisy row, because that is what it will fly on; the value network is never flown -- it is
+ * a training device and may read what the simulator knows (asymmetric actor-critic).  Nothing that is evaluated, recorded or exported
+ * changes: those paths use the actor only.
+ * qr_rollout_policy_privileged is qr_rollout_policy_history with two more device pointers: critic_obs_out_dev directly behind
+ * obs_out_dev, critic_last_obs_dev directly behind last_obs_dev.  DEFINITION:
+ *   RANGE     `history` = H in [0, 4 - gates_ahead].  H = 0 is the form of qr_rollout_policy_sensing (the TWIN for H = 0), H >= 1 the form of
+ *             qr_rollout_policy_history (the twin for H >= 1).  L' = qr_obs_len(env) + 4 H; `policy` has obs_len = L'.
+ *   CLEAN ROW critic_obs_out_dev [num_steps][N][L'], 16-byte aligned: row k is c_k = [ o_k | h_k ].  o_k is the env's observation at
+ *             call-step k BEFORE the sensor's noise, with the condition's scaling of the disturbance columns as the kernel forms it:
+ *             obs_out_dev[k] = [ o~_k | h_k ] is the slot's noise added to exactly this o_k.  h_k is the history tail of the policy's row;
+ *             it is exact in both rows.
+ *   LAST ROW  critic_last_obs_dev [N][L'] or NULL, 16-byte aligned: [ o_K | h_K ], bit for bit row 0 of critic_obs_out_dev of the next
+ *             launch called with first_step + num_steps through the same pending_dev.
+ *   IDEAL     a slot with all sigmas zero still gets its clean rows written; they then equal obs_out_dev bit for bit.
+ *   TERMINAL  rows are unchanged: they are clean already and serve both networks.
+ * CONTRACT: every other output, pending_dev and the env state are bit for bit those of the twin launch with the same arguments, whatever
+ * the two new pointers are; the action-noise, observation-noise and reset streams do not move.  K steps in one call equal K calls of one
+ * step with first_step advanced through the same pending_dev, the clean rows included.
+ * The clean row leaves through the wave's observation tile in LDS in front of the noise: no new LDS, no atomics, no workgroup that waits
+ * for another, no load of a slot value in the step loop.
+ * Refused before anything is launched or copied (qr_last_error set; outputs, pending and state untouched): everything the twin refuses, in
+ * its order; QR_E_INVALID for a NULL or misaligned critic_obs_out_dev (or a misaligned critic_last_obs_dev), directly behind the check of
+ * obs_out_dev / act / logp / rew / done; QR_E_INVALID for `history` outside [0, 4 - gates_ahead] where the history call refuses its range. */
+int qr_rollout_policy_privileged(qr_env* env, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics,
+                                 qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group,
+                                 const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t history, int32_t num_steps,
+                                 const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev,
+                                 float* obs_out_dev, float* critic_obs_out_dev, float* act_out_dev, float* logp_out_dev, float* rew_out_dev,
+                                 uint8_t* done_out_dev, uint8_t* trunc_out_dev, float* last_obs_dev, float* critic_last_obs_dev, void* stream);
+
 /* Fresh vehicles drawn ON THE DEVICE (the qr_vehicle_* pair works on a qr_dynamics_bank; the qr_dynamics_* names stay the eight entry
  * points of the bank and its table, which work on coefficient tables, while these two work on PHYSICAL parameters): qr_vehicle_bank_sample fills slots [first_slot, first_slot + num_slots) of `bank` with one launch
  * (one thread per slot), so that resampling an ensemble between rollouts makes no qr_dynamics_bank_set calls and reads nothing back.
@@ -864,6 +897,35 @@ int qr_ppo_gae(qr_ppo* ppo, int32_t T, int32_t N, const float* rew_dev, const fl
 int qr_ppo_apply(qr_ppo* ppo, float* theta_dev, float* adam_m_dev, float* adam_v_dev, float* grad_dev, int32_t B,
                  float max_grad_norm, float lr, float beta1, float beta2, float eps, int32_t adam_step, float* stats_dev,
                  void* stream);
+
+/* PRIVILEGED CRITIC, the update half: the three update calls whose VALUE network reads rows of its own.  Each is its twin -- qr_ppo_grad,
+ * qr_ppo_minibatch, qr_ppo_epoch -- with `const float* critic_obs_dev` directly behind obs_dev.  DEFINITION:
+ *   ROWS      critic_obs_dev [rows][obs_len], indexed by the same idx_dev / perm_dev as obs_dev.  The policy network's workgroups gather
+ *             their rows from obs_dev, the value network's workgroups from critic_obs_dev.  Everything else is the twin's: advantage
+ *             statistics, loss, clip, partials (bf16 or QR_PPO_PARTIAL_F32), apply kernel, Adam, re-pack, early stop, non-finite guard,
+ *             device shuffle, epoch graph (QR_PPO_NO_EPOCH_GRAPH honoured; critic_obs_dev is part of the graph's key).
+ *   SPLIT     qr_ppo_grad_privileged(obs = A, critic_obs = C): the policy network's entries of grad_out_dev (the four log_std entries
+ *             included) and statistics [0], [2], [3] are bit for bit those of qr_ppo_grad(obs = A); the value network's entries and
+ *             statistic [1] are bit for bit those of qr_ppo_grad(obs = C).
+ *   TWIN      with critic_obs_dev a different buffer of the same content as obs_dev, each call leaves grad_out, theta, both Adam moments,
+ *             both operand images, the status quadruple, stats, the Adam step count and the shuffle state bit for bit where its twin does.
+ *   COMPOSE   qr_ppo_minibatch_privileged = qr_ppo_grad_privileged + qr_ppo_apply; qr_ppo_epoch_privileged = the per-minibatch calls on
+ *             the permutation the buffer holds, replayed graph or plain launches.
+ * Refused (QR_E_INVALID, nothing launched): a NULL critic_obs_dev, then everything the twin refuses, in its order.  The f32-class gradient
+ * (qr_ppo_grad_f32class) and the population update have no privileged form. */
+int qr_ppo_grad_privileged(qr_ppo* ppo, const float* theta_dev, const float* obs_dev, const float* critic_obs_dev, const float* act_dev,
+                           const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B,
+                           float clip, float vf_coef, float ent_coef, float* grad_out_dev, float* stats_dev, void* stream);
+int qr_ppo_minibatch_privileged(qr_ppo* ppo, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev,
+                                const float* critic_obs_dev, const float* act_dev, const float* old_logp_dev, const float* adv_dev,
+                                const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip, float vf_coef, float ent_coef,
+                                float max_grad_norm, float lr, float beta1, float beta2, float eps, int32_t adam_step, float* stats_dev,
+                                void* stream);
+int qr_ppo_epoch_privileged(qr_ppo* ppo, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev,
+                            const float* critic_obs_dev, const float* act_dev, const float* old_logp_dev, const float* adv_dev,
+                            const float* ret_dev, int32_t* perm_dev, int32_t B, int32_t num_minibatches, int32_t num_epochs,
+                            int32_t device_shuffle, float clip, float vf_coef, float ent_coef, float max_grad_norm, float lr, float beta1,
+                            float beta2, float eps, float* stats_dev, void* stream);
 
 /* ---- the update of a POPULATION of learners: one minibatch of all members in three launches -------------------------------------
  * A population object BORROWS num_members existing qr_ppo handles (1..256; it does not own them: destroy it before them) that share

@@ -129,6 +129,10 @@ SIGNATURES = {
     "qr_evaluate_policy_history_grid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                                   _vp, _vp, _vp, _vp]),
+    # qr_rollout_policy_history with critic_obs_out_dev behind obs_out_dev and critic_last_obs_dev behind last_obs_dev
+    "qr_rollout_policy_privileged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.c_int32, C.c_int32, _f32p, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qr_blackbox_policy_grid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                           _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
@@ -155,6 +159,10 @@ SIGNATURES = {
     "qr_ppo_apply": (C.c_int, [_vp] * 5 + [C.c_int32] + [C.c_float] * 5 + [C.c_int32, _vp, _vp]),
     "qr_ppo_epoch_begin": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "qr_ppo_epoch": (C.c_int, [_vp] * 10 + [C.c_int32] * 4 + [C.c_float] * 8 + [_vp, _vp]),
+    # the three update calls with critic_obs_dev directly behind obs_dev (the privileged critic)
+    "qr_ppo_grad_privileged": (C.c_int, [_vp] * 9 + [C.c_int32, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "qr_ppo_minibatch_privileged": (C.c_int, [_vp] * 11 + [C.c_int32] + [C.c_float] * 8 + [C.c_int32, _vp, _vp]),
+    "qr_ppo_epoch_privileged": (C.c_int, [_vp] * 11 + [C.c_int32] * 4 + [C.c_float] * 8 + [_vp, _vp]),
     "qr_ppo_shuffle_state": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
     "qr_ppo_adam_step": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32, _vp]),
     "qr_ppo_control": (C.c_int, [_vp, C.c_float, C.c_int32, _vp]),
@@ -211,7 +219,8 @@ OPTIONAL_SYMBOLS = ("qr_set_rollout_form", "qr_ppo_create_ex", "q3_rollout", "qr
                     "qr_vehicle_bank_sample", "qr_sensing_bank_create", "qr_sensing_bank_destroy", "qr_sensing_bank_capacity", "qr_sensing_bank_set",
                     "qr_sensing_bank_read", "qr_evaluate_policy_sensing_grid", "qr_sensing_noise",
                     "qr_rollout_policy_sensing", "qr_rollout_policy_history", "qr_evaluate_policy_history_grid",
-                    "qr_blackbox_policy_grid")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
+                    "qr_blackbox_policy_grid", "qr_rollout_policy_privileged", "qr_ppo_grad_privileged", "qr_ppo_minibatch_privileged",
+                    "qr_ppo_epoch_privileged")   # added in rounds 5-14 and after: a QR_PROBE_LIB build of older sources may lack them
 
 
 def require(L, name):

@@ -18,12 +18,12 @@ SOURCES = ["quadrace_kernels.hip", "quadrace_kernels_mlp.hip", "quadrace_abi.hip
            "quadrace_rollout_cond.hip", "quadrace_blackbox.hip", "quadrace_rollout_population.hip", "quadrace_ppo_population.hip",
            "quadrace_population_prepare.hip", "quadrace_es.hip", "quadrace_eval_dynamics.hip", "quadrace_rollout_dynamics.hip",
            "quadrace_eval_sensing.hip", "quadrace_rollout_sensing.hip", "quadrace_eval_history.hip", "quadrace_rollout_history.hip",
-           "quadrace_blackbox_grid.hip"]
+           "quadrace_blackbox_grid.hip", "quadrace_rollout_privileged.hip"]
 HEADERS = ["quadrace_device.hpp", "quadrace_policy.hpp", "quadrace_env_kernels.hpp", "quadrace_eval_body.hpp", "quadrace_launch.hpp", "quadrace_ppo_device.hpp",
            "quadrace_rollout_group.hpp", "quadrace_sensing.hpp", "quadrace_record_tiles.hpp", "quadrace_host.hpp", os.path.join("..", "..", "include", "quadrace.h"), os.path.join("..", "..", "include", "quad3d.h")]
 # quadrace_kernels_mlp.hip = the launcher, and with it the instantiations, of the two fused E2E + residual-MLP rollout kernels: compiled
 # without the SLP vectoriser (reasons and measurements at the top of that file); every other kernel keeps it
-# (quadrace_rollout_cond.hip, quadrace_rollout_dynamics.hip, quadrace_rollout_sensing.hip, quadrace_rollout_history.hip and quadrace_rollout_population.hip inline the same residual-MLP step but take the flags of quadrace_kernels.hip, where their twin
+# (quadrace_rollout_cond.hip, quadrace_rollout_dynamics.hip, quadrace_rollout_sensing.hip, quadrace_rollout_history.hip, quadrace_rollout_privileged.hip and quadrace_rollout_population.hip inline the same residual-MLP step but take the flags of quadrace_kernels.hip, where their twin
 # rollout_policy_kernel is instantiated: one workgroup per CU, and the two closed-loop kernels stay comparable)
 PER_SOURCE_FLAGS = {"quadrace_kernels_mlp.hip": ["-fno-slp-vectorize"]}
 # -ffp-contract=off: FMAs are written explicitly (fmaf) in the kernels, so the arithmetic is fixed by the source and

@@ -659,6 +659,9 @@ int qr_step_launches(qr_env* e, int32_t K, const float* actions_dev, float* obs_
 // What qr_rollout_policy and qr_rollout_policy_conditions refuse about their shared arguments and the handle's mode, in one order; on
 // success A holds the weights and the sampling arguments of the launch.  history: null, or the command history of
 // qr_rollout_policy_history -- its range is refused directly before the observation length, which is then the env's + 4 * history.
+// critic: null, or the two buffers of qr_rollout_policy_privileged -- its range of history starts at 0, and a NULL or misaligned
+// critic_obs_out_dev is refused directly behind the buffers of check_rollout_common.
+struct CriticRows { float* obs; float* last_obs; };
 static int check_history(const qr_env* e, int history, const char* who, int lowest = 1) {
     if (history < lowest || history > 4 - e->cfg.gates_ahead)
         return fail(QR_E_INVALID, std::string(who) + ": history must be in [" + std::to_string(lowest) + ", 4 - gates_ahead] (the row of obs_len + 4 * history floats must be a "
@@ -668,12 +671,17 @@ static int check_history(const qr_env* e, int history, const char* who, int lowe
 static int rollout_policy_args(const qr_env* e, qr_policy* policy, int K, const float* log_std, uint64_t noise_seed, uint64_t first_step,
                                int flags, const float* obs_out_dev, const float* act_out_dev, const float* logp_out_dev,
                                const float* rew_out_dev, const uint8_t* done_out_dev, const char* who, qr::PolicyArgs& A,
-                               const int32_t* history = nullptr) {
+                               const int32_t* history = nullptr, const CriticRows* critic = nullptr) {
     if (int rc = check_rollout_common(e, K, policy && log_std, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, who)) return rc;
+    if (critic) {
+        if (!critic->obs) return fail(QR_E_INVALID, std::string(who) + ": critic_obs_out_dev is required");
+        if (((uintptr_t)critic->obs & 15) || ((uintptr_t)critic->last_obs & 15))
+            return fail(QR_E_INVALID, std::string(who) + ": critic_obs_out_dev and critic_last_obs_dev must be 16-byte aligned");
+    }
     A = qr::PolicyArgs{};
     if (int rc = qr::fetch_policy_weights(policy, who, A.weights)) return rc;
     if (history) {
-        if (int rc = check_history(e, *history, who)) return rc;
+        if (int rc = check_history(e, *history, who, critic ? 0 : 1)) return rc;
         if (int rc = qr::check_policy_handle(policy, e->L + 4 * *history, e->cfg.device, who, "!= env obs_len + 4 * history")) return rc;
     } else if (int rc = qr::check_policy_handle(policy, e->L, e->cfg.device, who)) {
         return rc;
@@ -1207,18 +1215,19 @@ int qr_rollout_policy_dynamics(qr_env* e, qr_policy* policy, qr_condition_bank* 
 // pair travels in the handle's group map as in qr_rollout_policy_dynamics, the sensing slots in an array of their own; under capture
 // BOTH must already be on the device, and the test comes before either copy.  history: null (qr_rollout_policy_sensing), or the command
 // history of qr_rollout_policy_history (rollout_policy_args refuses its range and compares the policy's length with the longer row).
+// critic: null, or the two buffers of qr_rollout_policy_privileged (with history, which may then be 0).
 static int rollout_policy_sensing(const char* who, const int32_t* history, qr_env* e, qr_policy* policy, qr_condition_bank* conditions,
                                   qr_dynamics_bank* dynamics, qr_sensing_bank* sensing, int32_t num_groups, int32_t envs_per_group,
                                   const int32_t* condition_of_group, const int32_t* dynamics_of_group, const int32_t* sensing_of_group, int32_t K,
                                   const float* log_std, uint64_t noise_seed, uint64_t first_step, int32_t flags, float* pending_dev, float* obs_out_dev,
                                   float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
-                                  float* last_obs_dev, void* stream) {
+                                  float* last_obs_dev, void* stream, const CriticRows* critic = nullptr) {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(QR_E_INVALID, w + "null env handle");
     if (int rc = check_ready(e)) return rc;
     qr::PolicyArgs A{};
     if (int rc = rollout_policy_args(e, policy, K, log_std, noise_seed, first_step, flags, obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev,
-                                     done_out_dev, who, A, history))
+                                     done_out_dev, who, A, history, critic))
         return rc;
     if (!conditions) return fail(QR_E_INVALID, w + "null condition bank handle");
     if (!condition_of_group) return fail(QR_E_INVALID, w + "the condition map is required");
@@ -1255,6 +1264,11 @@ static int rollout_policy_sensing(const char* who, const int32_t* history, qr_en
                                     "call once with these maps outside the capture");
     if (int rc = upload_table(e->group_map, map, st, who, "group map", "this map")) return rc;
     if (int rc = upload_table(e->rollout_sen_map, smap, st, who, "sensing map", "this map")) return rc;
+    if (critic)
+        return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_privileged(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, sensing->d_slots,
+                                           e->group_map.d, e->rollout_sen_map.d, *history, num_groups, envs_per_group, K, noise_seed, first_step,
+                                           pending_dev, obs_out_dev, critic->obs, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev,
+                                           last_obs_dev, critic->last_obs, st));
     if (history)
         return QR_TIMED_LAUNCH(e, st, qr::launch_rollout_policy_history(e->cfg.variant, e->P, A, conditions->d_slots, dynamics->d_slots, sensing->d_slots,
                                            e->group_map.d, e->rollout_sen_map.d, *history, num_groups, envs_per_group, K, noise_seed, first_step,
@@ -1284,6 +1298,19 @@ int qr_rollout_policy_history(qr_env* e, qr_policy* policy, qr_condition_bank* c
     return rollout_policy_sensing("qr_rollout_policy_history", &history, e, policy, conditions, dynamics, sensing, num_groups, envs_per_group,
                                   condition_of_group, dynamics_of_group, sensing_of_group, K, log_std, noise_seed, first_step, flags, pending_dev,
                                   obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, stream);
+}
+
+// qr_rollout_policy_history (history >= 1) / qr_rollout_policy_sensing (history == 0) that also stores the rows before the sensor's noise
+int qr_rollout_policy_privileged(qr_env* e, qr_policy* policy, qr_condition_bank* conditions, qr_dynamics_bank* dynamics, qr_sensing_bank* sensing,
+                                 int32_t num_groups, int32_t envs_per_group, const int32_t* condition_of_group, const int32_t* dynamics_of_group,
+                                 const int32_t* sensing_of_group, int32_t history, int32_t K, const float* log_std, uint64_t noise_seed,
+                                 uint64_t first_step, int32_t flags, float* pending_dev, float* obs_out_dev, float* critic_obs_out_dev,
+                                 float* act_out_dev, float* logp_out_dev, float* rew_out_dev, uint8_t* done_out_dev, uint8_t* trunc_out_dev,
+                                 float* last_obs_dev, float* critic_last_obs_dev, void* stream) {
+    const CriticRows critic{critic_obs_out_dev, critic_last_obs_dev};
+    return rollout_policy_sensing("qr_rollout_policy_privileged", &history, e, policy, conditions, dynamics, sensing, num_groups, envs_per_group,
+                                  condition_of_group, dynamics_of_group, sensing_of_group, K, log_std, noise_seed, first_step, flags, pending_dev,
+                                  obs_out_dev, act_out_dev, logp_out_dev, rew_out_dev, done_out_dev, trunc_out_dev, last_obs_dev, stream, &critic);
 }
 
 int qr_vehicle_physical_count(int32_t variant) {

@@ -198,6 +198,14 @@ hipError_t launch_rollout_policy_history(int variant, const Params& P, const Pol
                                          const int2* map, const int* sen_map, int history, int num_groups, int envs_per_group, int K,
                                          uint64_t noise_seed, uint64_t first_step, float* pending, float* obs, float* act, float* logp, float* rew,
                                          uint8_t* done, uint8_t* trunc, float* last_obs, hipStream_t st);
+// quadrace_rollout_privileged.hip: launch_rollout_policy_history with history in [0, 4 - gates_ahead] (0: the sensing call's launch) that
+// also stores the rows a privileged critic reads (qr_rollout_policy_privileged): critic_obs [K][n][obs_len + 4 history] = the row before
+// the sensor's noise with the same history tail, 16-byte aligned, required; critic_last_obs [n][obs_len + 4 history] or null
+hipError_t launch_rollout_policy_privileged(int variant, const Params& P, const PolicyArgs& A, const float* conds, const float* dyns, const float* sens,
+                                            const int2* map, const int* sen_map, int history, int num_groups, int envs_per_group, int K,
+                                            uint64_t noise_seed, uint64_t first_step, float* pending, float* obs, float* critic_obs, float* act,
+                                            float* logp, float* rew, uint8_t* done, uint8_t* trunc, float* last_obs, float* critic_last_obs,
+                                            hipStream_t st);
 hipError_t launch_eval_policy_history_grid(int variant, const Params& P, const half8* bank, const half8* bank_lo, const float* conds, const float* dyns,
                                            const float* sens, const int4* map, int history, bool f32class, int num_groups, int envs_per_group, int K,
                                            uint64_t noise_seed, uint64_t first_step, float* pending, int32_t* rec, float* recf, hipStream_t st);

@@ -370,7 +370,12 @@ struct PpoOps {
     static constexpr size_t kLdsFused = ((size_t)D::kImage + qr::kExHalf8) * 16 + 7 * qr::kStashRows * sizeof(float);
     // dynamic-LDS limit of the gradient kernel on the CURRENT device (idempotent; not a stream operation, so it also runs
     // before a graph capture instead of inside it)
-    static int configure(qr_ppo* p) {
+    static int configure(qr_ppo* p, bool privileged = false) {
+        if (privileged) {   // the privileged-critic form of the same kernel (qr_ppo_grad_privileged): an instantiation of its own
+            if (p->partial_bf16) QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, false, true>>(kLdsFused)));
+            else QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, float, false, true>>(kLdsFused)));
+            return QR_OK;
+        }
         if (p->partial_bf16) {
             QR_HIP((qr::configure_dynamic_lds<qr::ppo_grad_kernel<L, __bf16, false>>(kLdsFused)));
         } else {
@@ -379,19 +384,27 @@ struct PpoOps {
         return QR_OK;
     }
     // one kernel: forward, backward and the weight gradients of 128 samples per workgroup and pass; partial gradients of every workgroup
-    // in d_partial, per-wave sums in d_wave; returns the number of partials per network
-    static int grad(qr_ppo* p, qr::PpoBatch b, hipStream_t st, int* chunks_out) {
+    // in d_partial, per-wave sums in d_wave; returns the number of partials per network.  critic_obs: null, or the rows the value network's
+    // workgroups gather instead of b.obs (the privileged critic: the same launch of the kernel's kPriv form)
+    static int grad(qr_ppo* p, qr::PpoBatch b, hipStream_t st, int* chunks_out, const float* critic_obs = nullptr) {
         constexpr size_t lds_f = kLdsFused;
-        if (int rc = configure(p)) return rc;
+        if (int rc = configure(p, critic_obs != nullptr)) return rc;
         if (int rc = adv_stats(p, b, st)) return rc;
         const int pairs = (b.G + 1) / 2;
         const int wgs = pairs < qr_ppo::kFusedChunks ? pairs : qr_ppo::kFusedChunks;
         const qr::PopMember* no_table = nullptr;   // direct mode: the minibatch and its partial are the arguments
-        if (p->partial_bf16)
+        const float* no_critic = nullptr;
+        if (critic_obs && p->partial_bf16)
+            hipLaunchKernelGGL((qr::ppo_grad_kernel<L, __bf16, false, true>), dim3(wgs, 2), dim3(512), lds_f, st, b,
+                               reinterpret_cast<__bf16*>(p->d_partial), no_table, 0, critic_obs);
+        else if (critic_obs)
+            hipLaunchKernelGGL((qr::ppo_grad_kernel<L, float, false, true>), dim3(wgs, 2), dim3(512), lds_f, st, b, p->d_partial, no_table, 0,
+                               critic_obs);
+        else if (p->partial_bf16)
             hipLaunchKernelGGL((qr::ppo_grad_kernel<L, __bf16, false>), dim3(wgs, 2), dim3(512), lds_f, st, b,
-                               reinterpret_cast<__bf16*>(p->d_partial), no_table, 0);
+                               reinterpret_cast<__bf16*>(p->d_partial), no_table, 0, no_critic);
         else
-            hipLaunchKernelGGL((qr::ppo_grad_kernel<L, float, false>), dim3(wgs, 2), dim3(512), lds_f, st, b, p->d_partial, no_table, 0);
+            hipLaunchKernelGGL((qr::ppo_grad_kernel<L, float, false>), dim3(wgs, 2), dim3(512), lds_f, st, b, p->d_partial, no_table, 0, no_critic);
         QR_HIP(hipGetLastError());
         *chunks_out = wgs;
         return QR_OK;
@@ -581,9 +594,10 @@ static int epoch_begin_impl(qr_ppo* p, const float* adv_dev, const int32_t* idx_
     return QR_OK;
 }
 
-int qr_ppo_grad(qr_ppo* p, const float* theta_dev, const float* obs_dev, const float* act_dev, const float* old_logp_dev,
-                const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip, float vf_coef,
-                float ent_coef, float* grad_out_dev, float* stats_dev, void* stream) {
+// critic_obs_dev: null (qr_ppo_grad), or the value network's rows (qr_ppo_grad_privileged, which has refused a null one)
+static int ppo_grad_impl(qr_ppo* p, const float* theta_dev, const float* obs_dev, const float* critic_obs_dev, const float* act_dev,
+                         const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip,
+                         float vf_coef, float ent_coef, float* grad_out_dev, float* stats_dev, void* stream) {
     qr::PpoBatch b;
     if (int rc = fill_batch(p, b, theta_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, stats_dev))
         return rc;
@@ -599,7 +613,7 @@ int qr_ppo_grad(qr_ppo* p, const float* theta_dev, const float* obs_dev, const f
             p->packed_theta = theta_dev;
         }
         int chunks = 0;
-        if (int r = PpoOps<L>::grad(p, b, st, &chunks)) return r;
+        if (int r = PpoOps<L>::grad(p, b, st, &chunks, critic_obs_dev)) return r;
         qr::ApplyArgs a{};
         a.grad_out = grad_out_dev;
         a.chunks = chunks;
@@ -611,10 +625,27 @@ int qr_ppo_grad(qr_ppo* p, const float* theta_dev, const float* obs_dev, const f
     });
 }
 
+int qr_ppo_grad(qr_ppo* p, const float* theta_dev, const float* obs_dev, const float* act_dev, const float* old_logp_dev,
+                const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip, float vf_coef,
+                float ent_coef, float* grad_out_dev, float* stats_dev, void* stream) {
+    return ppo_grad_impl(p, theta_dev, obs_dev, nullptr, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, grad_out_dev,
+                         stats_dev, stream);
+}
+
+// qr_ppo_grad whose value network reads its own rows: net 1's workgroups gather from critic_obs_dev [rows][obs_len] by the same idx_dev
+int qr_ppo_grad_privileged(qr_ppo* p, const float* theta_dev, const float* obs_dev, const float* critic_obs_dev, const float* act_dev,
+                           const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B, float clip,
+                           float vf_coef, float ent_coef, float* grad_out_dev, float* stats_dev, void* stream) {
+    if (p && !critic_obs_dev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_grad_privileged: null critic_obs_dev (qr_ppo_grad is the call without one)");
+    return ppo_grad_impl(p, theta_dev, obs_dev, critic_obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef,
+                         grad_out_dev, stats_dev, stream);
+}
+
+// critic_obs_dev (last): null, or the value network's rows (the privileged forms)
 static int ppo_minibatch_impl(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* act_dev,
                               const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev, int32_t B,
                               float clip, float vf_coef, float ent_coef, float max_grad_norm, float lr, bool device_lr, float beta1,
-                              float beta2, float eps, int32_t adam_step, float* stats_dev, void* stream) {
+                              float beta2, float eps, int32_t adam_step, float* stats_dev, void* stream, const float* critic_obs_dev = nullptr) {
     qr::PpoBatch b;
     if (int rc = fill_batch(p, b, theta_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip, vf_coef, ent_coef, stats_dev))
         return rc;
@@ -625,7 +656,7 @@ static int ppo_minibatch_impl(qr_ppo* p, float* theta_dev, float* adam_m_dev, fl
     return dispatch_L(p->L, [&](auto Lc) {
         constexpr int L = decltype(Lc)::value;
         int chunks = 0;
-        if (int r = PpoOps<L>::grad(p, b, st, &chunks)) return r;  // images were packed by the previous call (or qr_ppo_pack)
+        if (int r = PpoOps<L>::grad(p, b, st, &chunks, critic_obs_dev)) return r;  // images were packed by the previous call (or qr_ppo_pack)
         qr::ApplyArgs a{};
         a.theta = theta_dev; a.m = adam_m_dev; a.v = adam_v_dev;
         a.chunks = chunks;
@@ -646,6 +677,18 @@ int qr_ppo_minibatch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam
     if (!(lr >= 0.0f)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_minibatch: the learning rate must be >= 0");
     return ppo_minibatch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip,
                               vf_coef, ent_coef, max_grad_norm, lr, false, beta1, beta2, eps, adam_step, stats_dev, stream);
+}
+
+// qr_ppo_minibatch whose value network reads its own rows (qr_ppo_grad_privileged + qr_ppo_apply in the same two launches)
+int qr_ppo_minibatch_privileged(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* critic_obs_dev,
+                                const float* act_dev, const float* old_logp_dev, const float* adv_dev, const float* ret_dev, const int32_t* idx_dev,
+                                int32_t B, float clip, float vf_coef, float ent_coef, float max_grad_norm, float lr, float beta1, float beta2,
+                                float eps, int32_t adam_step, float* stats_dev, void* stream) {
+    if (p && !critic_obs_dev)
+        return qr::set_last_error(QR_E_INVALID, "qr_ppo_minibatch_privileged: null critic_obs_dev (qr_ppo_minibatch is the call without one)");
+    if (!(lr >= 0.0f)) return qr::set_last_error(QR_E_INVALID, "qr_ppo_minibatch: the learning rate must be >= 0");
+    return ppo_minibatch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, idx_dev, B, clip,
+                              vf_coef, ent_coef, max_grad_norm, lr, false, beta1, beta2, eps, adam_step, stats_dev, stream, critic_obs_dev);
 }
 
 // Data-parallel training: every rank calls qr_ppo_grad on its shard of the minibatch, the caller averages the [n + 4] vector
@@ -706,10 +749,12 @@ int qr_ppo_shuffle_state(qr_ppo* p, uint64_t* state2, int32_t set, void* stream)
 // epoch at the config-5 shape; the host issues one graph launch instead of 257 kernel launches.  Replays are valid because nothing a
 // node's arguments name changes: the permutation is rewritten IN PLACE by the caller, the Adam step count and the learning rate
 // are read from device memory, the early-stop flag is sticky on the device.  The graph is re-captured when any argument changes.
-int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* act_dev,
-                 const float* old_logp_dev, const float* adv_dev, const float* ret_dev, int32_t* perm_dev, int32_t B,
-                 int32_t num_minibatches, int32_t num_epochs, int32_t device_shuffle, float clip, float vf_coef, float ent_coef,
-                 float max_grad_norm, float lr, float beta1, float beta2, float eps, float* stats_dev, void* stream) {
+// critic_obs_dev: null (qr_ppo_epoch), or the value network's rows (qr_ppo_epoch_privileged, which has refused a null one); part of the
+// graph's key: the same handle may serve both calls
+static int ppo_epoch_impl(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* critic_obs_dev,
+                          const float* act_dev, const float* old_logp_dev, const float* adv_dev, const float* ret_dev, int32_t* perm_dev, int32_t B,
+                          int32_t num_minibatches, int32_t num_epochs, int32_t device_shuffle, float clip, float vf_coef, float ent_coef,
+                          float max_grad_norm, float lr, float beta1, float beta2, float eps, float* stats_dev, void* stream) {
     if (!p || !theta_dev || !adam_m_dev || !adam_v_dev || !obs_dev || !act_dev || !old_logp_dev || !adv_dev || !ret_dev || !perm_dev)
         return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch: null argument");
     if (B < 64 || B > p->max_B || num_minibatches < 1 || num_minibatches > qr_ppo::kMaxEpochMinibatches || !(lr >= 0.0f))
@@ -726,7 +771,7 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
     QR_HIP(hipGetLastError());
     p->packed_theta = theta_dev;
     // per-device kernel attributes are set outside the capture (not a stream operation)
-    if (int rc = dispatch_L(p->L, [&](auto Lc) { return PpoOps<decltype(Lc)::value>::configure(p); })) return rc;
+    if (int rc = dispatch_L(p->L, [&](auto Lc) { return PpoOps<decltype(Lc)::value>::configure(p, critic_obs_dev != nullptr); })) return rc;
     const unsigned int rows = (unsigned int)B * (unsigned int)num_minibatches;
     auto enqueue = [&](hipStream_t s) -> int {
         for (int e = 0; e < num_epochs; ++e) {
@@ -740,14 +785,15 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
             for (int k = 0; k < num_minibatches; ++k)
                 if (int rc = ppo_minibatch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev,
                                                 perm_dev + (size_t)k * B, B, clip, vf_coef, ent_coef, max_grad_norm, 0.0f, true, beta1,
-                                                beta2, eps, 0, stats_dev, s))
+                                                beta2, eps, 0, stats_dev, s, critic_obs_dev))
                     return rc;
         }
         return QR_OK;
     };
     if (caller_captures || !p->epoch_graph) return enqueue(st);   // a graph launch cannot be captured: plain nodes into the caller's graph
     qr_ppo::EpochGraph& g = p->eg;
-    const bool hit = g.exec && g.theta == theta_dev && g.m == adam_m_dev && g.v == adam_v_dev && g.obs == obs_dev && g.act == act_dev &&
+    const bool hit = g.exec && g.theta == theta_dev && g.m == adam_m_dev && g.v == adam_v_dev && g.obs == obs_dev && g.critic == critic_obs_dev &&
+                     g.act == act_dev &&
                      g.old_logp == old_logp_dev && g.adv == adv_dev && g.ret == ret_dev && g.perm == perm_dev && g.stats == stats_dev &&
                      g.B == B && g.M == num_minibatches && g.E == num_epochs && g.shuffle == device_shuffle && g.seed == p->shuffle_seed &&
                      g.clip == clip && g.vf_coef == vf_coef && g.ent_coef == ent_coef &&
@@ -769,7 +815,7 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
             g.exec = nullptr;
             return qr::set_last_error(QR_E_HIP, std::string("qr_ppo_epoch: hipGraphInstantiate: ") + hipGetErrorString(inst));
         }
-        g.theta = theta_dev; g.m = adam_m_dev; g.v = adam_v_dev; g.obs = obs_dev; g.act = act_dev; g.old_logp = old_logp_dev;
+        g.theta = theta_dev; g.m = adam_m_dev; g.v = adam_v_dev; g.obs = obs_dev; g.critic = critic_obs_dev; g.act = act_dev; g.old_logp = old_logp_dev;
         g.adv = adv_dev; g.ret = ret_dev; g.perm = perm_dev; g.stats = stats_dev; g.B = B; g.M = num_minibatches;
         g.E = num_epochs; g.shuffle = device_shuffle; g.seed = p->shuffle_seed;
         g.clip = clip; g.vf_coef = vf_coef; g.ent_coef = ent_coef; g.max_grad_norm = max_grad_norm; g.beta1 = beta1; g.beta2 = beta2;
@@ -779,6 +825,24 @@ int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_d
     p->epoch_idx = nullptr;
     QR_HIP(hipGraphLaunch(g.exec, st));
     return QR_OK;
+}
+
+int qr_ppo_epoch(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* act_dev,
+                 const float* old_logp_dev, const float* adv_dev, const float* ret_dev, int32_t* perm_dev, int32_t B,
+                 int32_t num_minibatches, int32_t num_epochs, int32_t device_shuffle, float clip, float vf_coef, float ent_coef,
+                 float max_grad_norm, float lr, float beta1, float beta2, float eps, float* stats_dev, void* stream) {
+    return ppo_epoch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, nullptr, act_dev, old_logp_dev, adv_dev, ret_dev, perm_dev, B, num_minibatches,
+                          num_epochs, device_shuffle, clip, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, eps, stats_dev, stream);
+}
+
+// qr_ppo_epoch whose value network reads its own rows: every minibatch of the epoch is qr_ppo_minibatch_privileged
+int qr_ppo_epoch_privileged(qr_ppo* p, float* theta_dev, float* adam_m_dev, float* adam_v_dev, const float* obs_dev, const float* critic_obs_dev,
+                            const float* act_dev, const float* old_logp_dev, const float* adv_dev, const float* ret_dev, int32_t* perm_dev, int32_t B,
+                            int32_t num_minibatches, int32_t num_epochs, int32_t device_shuffle, float clip, float vf_coef, float ent_coef,
+                            float max_grad_norm, float lr, float beta1, float beta2, float eps, float* stats_dev, void* stream) {
+    if (p && !critic_obs_dev) return qr::set_last_error(QR_E_INVALID, "qr_ppo_epoch_privileged: null critic_obs_dev (qr_ppo_epoch is the call without one)");
+    return ppo_epoch_impl(p, theta_dev, adam_m_dev, adam_v_dev, obs_dev, critic_obs_dev, act_dev, old_logp_dev, adv_dev, ret_dev, perm_dev, B,
+                          num_minibatches, num_epochs, device_shuffle, clip, vf_coef, ent_coef, max_grad_norm, lr, beta1, beta2, eps, stats_dev, stream);
 }
 
 // Forward pass of one of the two networks with the operand images of the last pack (0 = policy means, 1 = value in column 0):

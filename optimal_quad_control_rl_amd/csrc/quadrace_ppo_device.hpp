@@ -716,9 +716,14 @@ struct PopMember {
 // host sets its fields, so a profiling build stamps nothing in this mode (a.ticks == nullptr).
 // ONE template with real __restrict__ parameters and the mode's prologue under `if constexpr`: both modes' code objects are the ones the
 // two separate kernels had, up to kernel-argument offsets ("A variant of a pinned kernel without a copy").
-template <int L, typename PT, bool kMember>
+// kPriv = true (with kMember = false only; qr_ppo_grad_privileged and its minibatch / epoch forms): the PRIVILEGED CRITIC.  The value
+// network's workgroups (net = blockIdx.y = 1) gather their rows from critic_obs [rows][L] instead of a.obs, by the same idx; the policy
+// network's workgroups read a.obs as ever.  Its only effect is the base pointer of the row gather, selected by the workgroup-uniform
+// `net`.  critic_obs is the LAST parameter: the other instantiations keep their argument offsets and pass null.
+template <int L, typename PT, bool kMember, bool kPriv = false>
 __global__ void __launch_bounds__(512, 1)
-ppo_grad_kernel(PpoBatch a, PT* __restrict__ partial, const PopMember* __restrict__ table, int k) {
+ppo_grad_kernel(PpoBatch a, PT* __restrict__ partial, const PopMember* __restrict__ table, int k, const float* __restrict__ critic_obs) {
+    static_assert(!(kPriv && kMember), "the privileged critic has no population form");
     using D = PpoDims<L>;
     using P = PolicyDims<L>;
     constexpr int KS1 = P::kSteps1;
@@ -778,7 +783,9 @@ ppo_grad_kernel(PpoBatch a, PT* __restrict__ partial, const PopMember* __restric
             const int b = a.idx[row_ok ? pos : a.B - 1];
             float xin[KS1][8];
             {
-                const float* row = a.obs + (size_t)b * L;
+                const float* row;
+                if constexpr (kPriv) row = (net == 1 ? critic_obs : a.obs) + (size_t)b * L;
+                else row = a.obs + (size_t)b * L;
 #pragma unroll
                 for (int s = 0; s < KS1; ++s)
 #pragma unroll
@@ -1360,7 +1367,7 @@ struct qr_ppo {
     struct EpochGraph {
         hipGraphExec_t exec = nullptr;
         const void *theta = nullptr, *m = nullptr, *v = nullptr, *obs = nullptr, *act = nullptr, *old_logp = nullptr, *adv = nullptr,
-                   *ret = nullptr, *perm = nullptr, *stats = nullptr;
+                   *ret = nullptr, *perm = nullptr, *stats = nullptr, *critic = nullptr;   // critic: null for qr_ppo_epoch
         int B = 0, M = 0, E = 0, shuffle = 0;
         unsigned long long seed = 0;
         float clip = 0, vf_coef = 0, ent_coef = 0, max_grad_norm = 0, beta1 = 0, beta2 = 0, eps = 0, target_kl = 0;

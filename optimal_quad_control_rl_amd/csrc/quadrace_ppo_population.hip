@@ -248,10 +248,10 @@ struct PopOps {
         const qr::PopMember* table = pop->d_table;   // member mode: the minibatch and the partial argument are passed empty
         if (pop->partial_bf16)
             hipLaunchKernelGGL((qr::ppo_grad_kernel<L, __bf16, true>), dim3(wgs, 2, P), dim3(512), kLdsFused, st, qr::PpoBatch{},
-                               static_cast<__bf16*>(nullptr), table, k);
+                               static_cast<__bf16*>(nullptr), table, k, static_cast<const float*>(nullptr));
         else
             hipLaunchKernelGGL((qr::ppo_grad_kernel<L, float, true>), dim3(wgs, 2, P), dim3(512), kLdsFused, st, qr::PpoBatch{},
-                               static_cast<float*>(nullptr), table, k);
+                               static_cast<float*>(nullptr), table, k, static_cast<const float*>(nullptr));
         hipLaunchKernelGGL(qr::ppo_population_reduce_kernel<L>, dim3(kWorkgroups, P), dim3(qr::kApplyThreads), 0, st, pop->d_table, wgs, 2 * G,
                            pop->partial_bf16 ? 1 : 0);
         hipLaunchKernelGGL(qr::ppo_population_step_kernel<L>, dim3(kWorkgroups, P), dim3(qr::kApplyThreads), 0, st, pop->d_table);

@@ -28,15 +28,16 @@ hipError_t launch_rollout_policy_cond(int variant, const Params& P, const Policy
         const float* no_sens = nullptr;   // no sensor either: the four arguments behind dyns are not read
         const int* no_sen_map = nullptr;
         float* no_pending = nullptr;
+        float* no_critic = nullptr;    // no privileged-critic rows: the two last arguments are not read
         const half8* no_bank = nullptr;   // one policy per launch: A.weights / A.weights_lo and A's sampling arguments
         const PopulationEntry* no_table = nullptr;
         if (A.f32class)
             return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, true, false>>(grid, dim3(kBlock), lds, st, P, A, no_bank, no_bank, conds, map,
                                                                                        no_table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, no_dyns,
-                                                                                       no_sens, no_sen_map, no_pending, SensingStream{});
+                                                                                       no_sens, no_sen_map, no_pending, SensingStream{}, no_critic, no_critic);
         return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, false, false>>(grid, dim3(kBlock), lds, st, P, A, no_bank, no_bank, conds, map,
                                                                                     no_table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, no_dyns,
-                                                                                    no_sens, no_sen_map, no_pending, SensingStream{});
+                                                                                    no_sens, no_sen_map, no_pending, SensingStream{}, no_critic, no_critic);
     });
 }
 

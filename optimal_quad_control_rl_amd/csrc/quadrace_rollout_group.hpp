@@ -2,8 +2,8 @@
 // (quadrace_rollout_cond.hip, kPop = false), qr_rollout_policy_population (quadrace_rollout_population.hip, kPop = true),
 // qr_rollout_policy_dynamics (quadrace_rollout_dynamics.hip, kPop = false, kDyn = true) and qr_rollout_policy_sensing
 // (quadrace_rollout_sensing.hip, kDyn = true, Sn = RuntimeSensing), and behind qr_rollout_policy_history (quadrace_rollout_history.hip: the
-// sensing mode with H > 0).  Included by those five units and by nothing else; each keeps its launch function, its checks and its
-// instantiations.
+// sensing mode with H > 0) and qr_rollout_policy_privileged (quadrace_rollout_privileged.hip: the sensing / history mode with kPriv = true).
+// Included by those six units and by nothing else; each keeps its launch function, its checks and its instantiations.
 //
 // K x [obs -> MFMA policy -> a = mean + std * eps -> env.step(clip(a))] with the rollout rows, the terminal-observation rows, last_obs
 // and the end-of-kernel state write-back of rollout_policy_kernel (quadrace_env_kernels.hpp), and the inputs of eval_policy_grid_kernel
@@ -68,6 +68,14 @@
 //                  `pending` in the epilogue, which then carries max(d, H) entries.  The delay ring is untouched: d and H are independent.
 //                  Terminal rows are L wide, [clean observation | u_k, ..., u_{k-H+1}] (store_terminal_obs_history below): P.term_obs is read
 //                  as [rows][N][L] in this mode.
+//   kPriv = true   (with Sn = RuntimeSensing only, H >= 0; qr_rollout_policy_privileged, quadrace_rollout_privileged.hip) the sensing / history mode
+//                  that ALSO stores the row a privileged critic reads: c_k = [o_k | h_k], the observation BEFORE the sensor's noise (with the
+//                  condition's scaling, as observe() forms it) and the same exact history tail, to critic_obs_out[k], rows of L floats.  The
+//                  clean row leaves through the wave's observation tile in front of perturb (store_obs_coalesced); the noisy row reuses the
+//                  tile behind it (one wave's LDS operations stay in order: no barrier, no new LDS), so the forward and its pinned schedule
+//                  see what they see in the other modes.  critic_last_obs_out (may be null) = [o_K | h_K], stored in front of the noise of
+//                  call-step K.  Nothing else is computed differently: every other output, `pending` and the env state are those of the
+//                  kPriv = false launch.  The two pointers are the LAST parameters; every older mode passes nulls.
 // Unlike the grid evaluator the reset stream and the action noise are keyed by the handle's ORDINARY env ids (P.gid + i): training
 // wants independent envs, not common random numbers across groups.  Group g therefore computes what an E-env handle with
 // env_id_base + g E, configured with the group's condition, computes under qr_rollout_policy with the group's weights, log_std and seed
@@ -107,17 +115,19 @@ __device__ __forceinline__ void store_terminal_obs_history(const Params& P, cons
 // conds: slot 0 of the condition bank; map[g] = (policy, condition) of group g; wgs_per_group = E / kBlock; kPop: bank / bank_lo = image 0
 // of the two policy arrays, table[g] = sampling arguments of group g; kDyn: dyns = slot 0 of the dynamics bank, map[g] = (dynamics, condition);
 // Sn::kOn: sens = slot 0 of the sensing bank, sen_map[g] = the sensing slot of group g, pending = the command queues [n][kSensingQueueFloats]
-template <int V, int GA, bool kF32, bool kPop, bool kDyn = false, class Sn = IdealSensing, int H = 0>
+template <int V, int GA, bool kF32, bool kPop, bool kDyn = false, class Sn = IdealSensing, int H = 0, bool kPriv = false>
 __global__ void __launch_bounds__(kBlock, 1)
 rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ bank, const half8* __restrict__ bank_lo,
                             const float* __restrict__ conds, const int2* __restrict__ map, const PopulationEntry* __restrict__ table,
                             int wgs_per_group, int K, float* __restrict__ obs_out, float4* __restrict__ act_out,
                             float* __restrict__ logp_out, float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
                             uint8_t* __restrict__ trunc_out, float* __restrict__ last_obs_out, const float* __restrict__ dyns,
-                            const float* __restrict__ sens, const int* __restrict__ sen_map, float* __restrict__ pending, SensingStream stream) {
+                            const float* __restrict__ sens, const int* __restrict__ sen_map, float* __restrict__ pending, SensingStream stream,
+                            float* __restrict__ critic_obs_out, float* __restrict__ critic_last_obs_out) {
     static_assert(!(kPop && kDyn), "the vehicle mode is a single-policy mode");
     static_assert(!Sn::kOn || kDyn, "the sensing mode is a mode of the vehicle mode");
     static_assert(H == 0 || (Sn::kOn && H >= 1 && GA + H <= 4), "the command history is a mode of the sensing mode, 1 <= H <= 4 - GA");
+    static_assert(!kPriv || Sn::kOn, "the privileged-critic rows are a mode of the sensing mode");
     constexpr int LE = obs_len<V, GA>();       // the env's row: observe, the sensor's noise
     constexpr int L = obs_len<V, GA + H>();    // the policy's row [o~ | h] = LE + 4 H floats: the network, the tiles, the row stores (H = 0: LE)
     using D = PolicyDims<L>;
@@ -233,6 +243,8 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
         }
     }
     for (int k = 0; k < K; ++k) {
+        // (kPriv) the critic's row [o_k | h_k] leaves before the noise exists; the tile is free again when obs_slice writes the noisy row
+        if constexpr (kPriv) store_obs_coalesced<V, GA + H>(tile, critic_obs_out + (size_t)k * n * L, (size_t)wave_first, lane, o);
         // the policy's input is the noisy row (and obs_slice stores it); o is rebuilt from the state behind the step
         if constexpr (Sn::kOn) Sn::template perturb<V, GA>(sen_arg, gid_lo, gid_hi, k, o);
         // ---- action noise: rollout_policy_kernel's slices, verbatim (drawn in deterministic mode too and then multiplied out); the
@@ -341,6 +353,9 @@ rollout_policy_group_kernel(Params P0, PolicyArgs A, const half8* __restrict__ b
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[LE + c] = done ? 0.0f : uc[c];
         }
+    }
+    if constexpr (kPriv) {   // [o_K | h_K]: row 0 of critic_obs_out of a launch with first_step + K
+        if (critic_last_obs_out) store_obs_coalesced<V, GA + H>(tile, critic_last_obs_out, (size_t)wave_first, lane, o);
     }
     if constexpr (Sn::kOn) {
         // last_obs is what the policy sees next: the noise of call-step K, row 0 of a launch with first_step + K

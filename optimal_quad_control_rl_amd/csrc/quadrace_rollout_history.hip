@@ -48,13 +48,14 @@ hipError_t launch_rollout_policy_history(int variant, const Params& P, const Pol
             const int wgs = envs_per_group / kBlock;
             const half8* no_bank = nullptr;   // one policy per launch: A.weights / A.weights_lo and A's sampling arguments
             const PopulationEntry* no_table = nullptr;
+            float* no_critic = nullptr;   // no privileged-critic rows: the two last arguments are not read
             if (A.f32class)
                 return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, true, false, true, RuntimeSensing, H>>(
                     grid, dim3(kBlock), lds, st, P, A, no_bank, no_bank, conds, map, no_table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, dyns,
-                    sens, sen_map, pending, stream);
+                    sens, sen_map, pending, stream, no_critic, no_critic);
             return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, false, false, true, RuntimeSensing, H>>(
                 grid, dim3(kBlock), lds, st, P, A, no_bank, no_bank, conds, map, no_table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, dyns, sens,
-                sen_map, pending, stream);
+                sen_map, pending, stream, no_critic, no_critic);
         });
     });
 }

@@ -29,13 +29,14 @@ hipError_t launch_rollout_policy_population(int variant, const Params& P, const 
         const float* no_sens = nullptr;   // no sensor either: the four arguments behind dyns are not read
         const int* no_sen_map = nullptr;
         float* no_pending = nullptr;
+        float* no_critic = nullptr;    // no privileged-critic rows: the two last arguments are not read
         if (A.f32class)
             return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, true, true>>(grid, dim3(kBlock), lds, st, P, A, bank, bank_lo, conds, map,
                                                                                       table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, no_dyns,
-                                                                                      no_sens, no_sen_map, no_pending, SensingStream{});
+                                                                                      no_sens, no_sen_map, no_pending, SensingStream{}, no_critic, no_critic);
         return launch_dynamic_lds<rollout_policy_group_kernel<V, GA, false, true>>(grid, dim3(kBlock), lds, st, P, A, bank, bank_lo, conds, map,
                                                                                    table, wgs, K, obs, act4, logp, rew, done, trunc, last_obs, no_dyns,
-                                                                                   no_sens, no_sen_map, no_pending, SensingStream{});
+                                                                                   no_sens, no_sen_map, no_pending, SensingStream{}, no_critic, no_critic);
     });
 }
 

@@ -168,12 +168,31 @@ class MfmaPpoUpdater:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()
 
-    def grad(self, obs, act, old_lp, adv, ret, idx, clip=0.2, vf_coef=0.5, ent_coef=0.0, stats=False, precision=None, out=None):
+    def _critic_rows(self, obs, critic_obs, what, precision=None):
+        """`critic_obs` checked for a privileged-critic call (qr_ppo_*_privileged): rows like `obs`, f16-operand kernels, one rank."""
+        if (precision or self.precision) == "f32":
+            raise ValueError("%s(critic_obs=...): the f32-class gradient kernels (qr_ppo_grad_f32class) have no privileged-critic form" % what)
+        if what != "grad" and self.data_parallel():
+            raise ValueError("%s(critic_obs=...): the privileged critic has no data-parallel form" % what)
+        assert critic_obs.is_cuda and critic_obs.dtype == torch.float32 and critic_obs.is_contiguous() and critic_obs.shape == obs.shape
+        return self._p(critic_obs)
+
+    def grad(self, obs, act, old_lp, adv, ret, idx, clip=0.2, vf_coef=0.5, ent_coef=0.0, stats=False, precision=None, out=None,
+             critic_obs=None):
         """Flat gradient of the PPO loss on the rows `idx` (no clipping, no optimiser step).  precision="f32": the reference-precision
         kernels (qr_ppo_grad_f32class: every GEMM operand as three bf16 pieces, replayed as one cached graph per distinct argument
-        set -- pass the same `out` buffer from call to call to hit it); default = this updater's `precision`."""
+        set -- pass the same `out` buffer from call to call to hit it); default = this updater's `precision`.
+        critic_obs (rows like `obs`): the PRIVILEGED CRITIC -- the value network gathers its rows from it, the policy network from `obs`
+        (qr_ppo_grad_privileged); None: the plain call."""
         self._check(obs, act, old_lp, adv, ret, idx)
         g = out if out is not None else torch.empty(self.theta.numel() + 4, dtype=torch.float32, device=self.device)  # gradient + minibatch statistics
+        if critic_obs is not None:
+            rows = self._critic_rows(obs, critic_obs, "grad", precision)
+            fn = self._lib.require(self._L, "qr_ppo_grad_privileged")
+            self._lib.check(fn(self._h, self._p(self.theta), self._p(obs), rows, self._p(act), self._p(old_lp), self._p(adv), self._p(ret),
+                               self._p(idx), int(idx.numel()), clip, vf_coef, ent_coef, self._p(g), self._p(self.stats) if stats else None,
+                               self._stream()))
+            return g
         fn = self._L.qr_ppo_grad_f32class if (precision or self.precision) == "f32" else self._L.qr_ppo_grad
         self._lib.check(fn(self._h, self._p(self.theta), self._p(obs), self._p(act), self._p(old_lp), self._p(adv),
                                             self._p(ret), self._p(idx), int(idx.numel()), clip, vf_coef, ent_coef, self._p(g),
@@ -241,7 +260,15 @@ class MfmaPpoUpdater:
                                              max_grad_norm, lr, self.betas[0], self.betas[1], self.eps, 0,   # 0: device step count
                                              self._p(self.stats) if stats else None, self._stream()))
 
-    def minibatch(self, obs, act, old_lp, adv, ret, idx, lr, clip=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5):
+    def minibatch(self, obs, act, old_lp, adv, ret, idx, lr, clip=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, critic_obs=None):
+        """One complete minibatch update.  critic_obs: as in grad() (qr_ppo_minibatch_privileged); None: the plain call."""
+        if critic_obs is not None:
+            self._check(obs, act, old_lp, adv, ret, idx)
+            rows = self._critic_rows(obs, critic_obs, "minibatch")
+            fn = self._lib.require(self._L, "qr_ppo_minibatch_privileged")
+            return self._lib.check(fn(self._h, self._p(self.theta), self._p(self.m), self._p(self.v), self._p(obs), rows, self._p(act),
+                                      self._p(old_lp), self._p(adv), self._p(ret), self._p(idx), int(idx.numel()), clip, vf_coef, ent_coef,
+                                      max_grad_norm, lr, self.betas[0], self.betas[1], self.eps, 0, self._p(self.stats), self._stream()))
         if self.precision == "f32":   # reference-precision gradient kernels, then the (f32) apply kernel; averaged across ranks when data parallel
             if getattr(self, "_g32", None) is None:
                 self._g32 = torch.empty(self.theta.numel() + 4, dtype=torch.float32, device=self.device)
@@ -258,13 +285,21 @@ class MfmaPpoUpdater:
                                                  self.betas[1], self.eps, 0, self._p(self.stats), self._stream()))
 
     def epoch(self, obs, act, old_lp, adv, ret, perm, B, lr, clip=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, num_epochs=1,
-              device_shuffle=False):
+              device_shuffle=False, critic_obs=None):
         """`num_epochs` whole epochs -- every minibatch perm[k B:(k + 1) B] in order -- as ONE replayed graph launch
         (qr_ppo_epoch).  `perm` must be the SAME int32 CUDA tensor from call to call: the graph's nodes address it.  Without
         `device_shuffle` the caller rewrites its content in place with a new permutation per epoch (num_epochs = 1); with it the
-        library fills it with a fresh keyed permutation at the start of every epoch (set_shuffle / shuffle_state)."""
+        library fills it with a fresh keyed permutation at the start of every epoch (set_shuffle / shuffle_state).
+        critic_obs: as in grad() (qr_ppo_epoch_privileged; the buffer is part of the graph's key); None: the plain call."""
         self._check(obs, act, old_lp, adv, ret, perm)
         assert perm.numel() % int(B) == 0
+        if critic_obs is not None:
+            rows = self._critic_rows(obs, critic_obs, "epoch")
+            fn = self._lib.require(self._L, "qr_ppo_epoch_privileged")
+            return self._lib.check(fn(self._h, self._p(self.theta), self._p(self.m), self._p(self.v), self._p(obs), rows, self._p(act),
+                                      self._p(old_lp), self._p(adv), self._p(ret), self._p(perm), int(B), perm.numel() // int(B),
+                                      int(num_epochs), int(bool(device_shuffle)), clip, vf_coef, ent_coef, max_grad_norm, float(lr),
+                                      self.betas[0], self.betas[1], self.eps, self._p(self.stats), self._stream()))
         self._lib.check(self._L.qr_ppo_epoch(self._h, self._p(self.theta), self._p(self.m), self._p(self.v), self._p(obs), self._p(act),
                                              self._p(old_lp), self._p(adv), self._p(ret), self._p(perm), int(B), perm.numel() // int(B),
                                              int(num_epochs), int(bool(device_shuffle)), clip, vf_coef, ent_coef, max_grad_norm,
@@ -420,7 +455,7 @@ class PPO:
                  log_std_init=0.0, seed=0, target_kl=None, lr_final_frac=1.0, total_timesteps_hint=None,
                  fused_collect=False, native_update=False, truncation_bootstrap=True, policy_forward="torch", update_precision="f16-operands",
                  conditions=None, envs_per_group=256, condition_weights=None, dynamics=None, dynamics_of_group=None, resample_every=None,
-                 sensing=None, sensing_of_group=None, command_history=0):
+                 sensing=None, sensing_of_group=None, command_history=0, privileged_critic=False):
         self.env = env
         self.n_envs, self.dev = env.num_envs, env.device
         self.n_steps, self.n_epochs = n_steps, n_epochs
@@ -454,6 +489,27 @@ class PPO:
                 from .sensing import SensingParams
 
                 sensing = [SensingParams.ideal()]
+        # privileged_critic: the VALUE network reads the observation BEFORE the sensor's noise (asymmetric actor-critic).  The critic is a
+        # training device and is never flown, so it may see what the simulator knows; the policy keeps reading the noisy row.  The collect
+        # launch stores both rows (qr_rollout_policy_privileged): buf_critic_obs [T, N, obs_dim] = [clean observation | the same command
+        # history]; buf_val, last_val and -- as ever -- the time-limit bootstrap come from the clean rows, and the update's value network
+        # gathers them (qr_ppo_epoch_privileged).  Nothing that is evaluated, recorded or exported changes: those paths use the actor.
+        # Needs the fused collect on a race env and the native f16-operand update on one rank; composes with conditions, dynamics, sensing
+        # and command_history; without `sensing` the run flies under one ideal sensor (both rows are then equal).
+        self.privileged_critic = bool(privileged_critic)
+        if self.privileged_critic:
+            if not fused_collect or self._q3:
+                raise ValueError("privileged_critic needs fused_collect=True on a race env: the clean row exists in the closed-loop kernel only")
+            if not native_update:
+                raise ValueError("privileged_critic needs native_update=True: the torch update reads one observation array for both networks")
+            if update_precision == "f32":
+                raise ValueError("privileged_critic needs update_precision='f16-operands': the f32-class gradient kernels have no privileged-critic form")
+            if MfmaPpoUpdater.data_parallel():
+                raise ValueError("privileged_critic has no data-parallel form: the all-reduce path updates through qr_ppo_grad / qr_ppo_apply")
+            if sensing is None:
+                from .sensing import SensingParams
+
+                sensing = [SensingParams.ideal()]
         torch.manual_seed(seed)
         # minibatch permutations come from the trainer's OWN generator (checkpointed; independent of whatever else draws from
         # torch's global generators in the process)
@@ -465,6 +521,7 @@ class PPO:
         T, N = n_steps, self.n_envs
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.buf_obs = torch.empty((T, N, obs_dim), **f32)
+        self.buf_critic_obs = torch.empty((T, N, obs_dim), **f32) if self.privileged_critic else None
         self.buf_act = torch.empty((T, N, 4), **f32)
         self.buf_lp = torch.empty((T, N), **f32)
         self.buf_val = torch.empty((T, N), **f32)
@@ -540,7 +597,7 @@ class PPO:
         self.ep_ret = torch.zeros(N, **f32)
         self.ep_len = torch.zeros(N, **f32)
         self.ep_gates = torch.zeros(N, **f32)
-        self.stats = {}
+        self.stats = {"critic_input": "clean" if self.privileged_critic else "policy"}   # what the value network reads
         # fused_collect: the whole collect phase is ONE kernel (qr_rollout_policy): MFMA policy (f16 operands) +
         # Gaussian sampling + env step; values (and nothing else) are evaluated by torch afterwards in one batch.
         # native_update: every minibatch update (forward, loss, backward, grad-norm clip, Adam) runs in the hand-written
@@ -759,7 +816,12 @@ class PPO:
             banks = (self._mfma, self._cond_bank if mixed else self._own_cond_bank, self.condition_of_group if mixed else [0] * groups,
                      self._dyn_bank if vehicles else self._own_dyn_bank, self.dynamics_of_group if vehicles else [0] * groups,
                      self._sen_bank, self.sensing_of_group)
-            if self.command_history:
+            critic_last_obs = None
+            if self.privileged_critic:   # the twin launch (history or sensing) that also stores the rows before the noise
+                kw["out"] = (self.buf_obs, self.buf_critic_obs) + kw["out"][1:]
+                obs, _, act, logp, rew, done, trunc, last_obs, critic_last_obs = self.env.rollout_policy_privileged_device(
+                    *banks, self.command_history, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
+            elif self.command_history:
                 obs, act, logp, rew, done, trunc, last_obs = self.env.rollout_policy_history_device(
                     *banks, self.command_history, self.envs_per_group, self.n_steps, self.policy.log_std, self._pending, **kw)
             else:
@@ -805,8 +867,9 @@ class PPO:
             if rows.numel():
                 self.buf_term_val.view(-1)[rows] = value(self._term_obs.view(T * N, -1)[rows])
         if self._updater is not None:   # values on the matrix cores too; GAE and episode statistics follow in train()
-            self.buf_val.copy_(value(self.buf_obs.view(T * N, -1)).view(T, N))
-            self.last_val = value(last_obs)
+            # (privileged critic: V of the clean rows; the terminal rows above are clean in every mode)
+            self.buf_val.copy_(value((self.buf_critic_obs if self.privileged_critic else self.buf_obs).view(T * N, -1)).view(T, N))
+            self.last_val = value(critic_last_obs if self.privileged_critic else last_obs)
             if self.policy_forward == "f32class" and self._updater.precision != "f32":
                 # f32-class collect + f16-operand update: the update's forward (the f16 operand images) gives means up to ~7e-4 away
                 # from the collect kernel's, an offset of z dmu / sigma in every log-ratio.  Store the OLD log-probs from the update's
@@ -885,10 +948,14 @@ class PPO:
         poison a minibatch: zero them (their advantage is zeroed in train())."""
         bad = ~(torch.isfinite(self.buf_obs).all(-1) & torch.isfinite(self.buf_act).all(-1) &
                 torch.isfinite(self.buf_lp) & torch.isfinite(self.buf_rew) & torch.isfinite(self.buf_val))
+        if self.buf_critic_obs is not None:   # a non-finite clean row is a non-finite observation row
+            bad |= ~torch.isfinite(self.buf_critic_obs).all(-1)
         self._bad = bad
         self.stats["non_finite_rows"] = int(bad.sum())
         if self.stats["non_finite_rows"]:
             self.buf_obs[bad] = 0.0
+            if self.buf_critic_obs is not None:
+                self.buf_critic_obs[bad] = 0.0
             self.buf_act[bad] = 0.0
             self.buf_lp[bad] = 0.0
             self.buf_rew[bad] = 0.0
@@ -1015,15 +1082,17 @@ class PPO:
     def _train_native(self, obs, act, old_lp, adv, ret, B):
         up = self._updater
         lr, kl_stop, perm = self._native_begin(B)
+        # (privileged critic: the value network's rows; the updater refuses the two paths that have no such form)
+        critic = dict(critic_obs=self.buf_critic_obs.view(B, -1)) if self.privileged_critic else {}
         if not up.data_parallel() and up.precision != "f32":
             # the permutations are drawn on the device too (a keyed bijection per epoch, no sort); without the early stop ALL
             # epochs of this train() are one graph launch, with it one launch per epoch and one status read in between
             hp = (self.batch_size, lr, self.clip, self.vf_coef, self.ent_coef, self.max_grad_norm)
             if not kl_stop:
-                up.epoch(obs, act, old_lp, adv, ret, perm, *hp, num_epochs=self.n_epochs, device_shuffle=True)
+                up.epoch(obs, act, old_lp, adv, ret, perm, *hp, num_epochs=self.n_epochs, device_shuffle=True, **critic)
             else:
                 for _ in range(self.n_epochs):
-                    up.epoch(obs, act, old_lp, adv, ret, perm, *hp, num_epochs=1, device_shuffle=True)
+                    up.epoch(obs, act, old_lp, adv, ret, perm, *hp, num_epochs=1, device_shuffle=True, **critic)
                     if up.status()[0]:   # after the stop every further launch is a no-op: one ~50 us read per epoch saves them
                         break
         else:
@@ -1033,7 +1102,7 @@ class PPO:
                     up.begin_epoch(adv, perm, self.batch_size)
                 for s in range(0, B, self.batch_size):
                     up.minibatch(obs, act, old_lp, adv, ret, perm[s:s + self.batch_size], lr, self.clip, self.vf_coef, self.ent_coef,
-                                 self.max_grad_norm)
+                                 self.max_grad_norm, **critic)
                 if kl_stop and up.status()[0]:   # identical on every rank: the KL sum travels with the all-reduced gradient
                     break
         self._native_finish(kl_stop)
@@ -1117,6 +1186,8 @@ class PPO:
                                  pending=self._pending.cpu(), ep_ret=self._sen_ret.cpu(), ep_len=self._sen_len.cpu())
         if self.command_history:   # likewise; the history itself is the first rows of `pending` above
             sd["command_history"] = int(self.command_history)
+        if self.privileged_critic:   # likewise: the value network of such a run was fitted to the clean rows
+            sd["privileged_critic"] = True
         return sd
 
     def _dynamics_state(self):
@@ -1143,6 +1214,9 @@ class PPO:
         if int(sd.get("command_history", 0)) != self.command_history:   # the networks differ in their input length: nothing is loaded
             raise ValueError("the checkpoint was trained with command_history=%d, this PPO was constructed with command_history=%d: "
                              "construct it with the checkpoint's value" % (int(sd.get("command_history", 0)), self.command_history))
+        if bool(sd.get("privileged_critic", False)) != self.privileged_critic:   # the value networks were fitted to different inputs
+            raise ValueError("the checkpoint was trained with privileged_critic=%s, this PPO was constructed with privileged_critic=%s: "
+                             "construct it with the checkpoint's value" % (bool(sd.get("privileged_critic", False)), self.privileged_critic))
         opt = sd["optimizer"]
         if self._updater is not None:
             assert opt["kind"] == "mfma_adam", "checkpoint was written by the torch optimiser path"
@@ -1159,7 +1233,7 @@ class PPO:
             self.opt.load_state_dict(opt["state"])
         self.num_timesteps = int(sd["num_timesteps"])
         self.ep_ret.copy_(sd["ep_ret"]); self.ep_len.copy_(sd["ep_len"]); self.ep_gates.copy_(sd["ep_gates"])
-        self.stats = dict(sd["stats"])
+        self.stats = dict(sd["stats"], critic_input="clean" if self.privileged_critic else "policy")
         if self._q3 and "gates_per_episode" in self.stats:   # a checkpoint from before the statistic was named for what it counts
             self.stats["successes_per_episode"] = self.stats.pop("gates_per_episode")
         self.noise_seed = int(sd["noise_seed"])

@@ -971,6 +971,53 @@ class Quadcopter3DGates(_Base):
         self._last_obs = last[:, :self.state_len]
         return obs, act, logp, rew, done, trunc, last
 
+    def rollout_policy_privileged_device(self, policy, condition_bank, condition_of_group, dynamics_bank, dynamics_of_group, sensing_bank,
+                                         sensing_of_group, command_history, envs_per_group, num_steps, log_std, pending, noise_seed=0,
+                                         first_step=0, deterministic=False, out=None, precision="f16-operands"):
+        """rollout_policy_history_device that ALSO stores the rows a PRIVILEGED CRITIC reads (qr_rollout_policy_privileged):
+        critic_obs [K, N, obs_len + 4 H] holds, at call-step k, [the observation BEFORE the sensor's noise | the same history tail] -- the
+        row obs[k] is the slot's noise added to -- and critic_last_obs [N, obs_len + 4 H] the clean row behind the last step, bit for bit
+        row 0 of critic_obs of the next call with first_step advanced through the same `pending`.  command_history = H may be 0 (the
+        form of rollout_policy_sensing_device) up to 4 - gates_ahead.  Every other output, `pending` and the env state are bit for bit
+        those of the twin call (rollout_policy_sensing_device for H = 0, rollout_policy_history_device otherwise); terminal rows are
+        clean already and unchanged.  out = (obs, critic_obs, act, logp, rew, done, trunc).
+        Returns (obs, critic_obs, act, logp, rew, done, trunc, last_obs, critic_last_obs)."""
+        flags = _precision_flags(precision)
+        fn = _lib.require(self._L, "qr_rollout_policy_privileged")
+        H = int(command_history)
+        width = self.state_len + 4 * H
+        maps = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (condition_of_group, dynamics_of_group, sensing_of_group)]
+        if len({m.shape for m in maps}) != 1:
+            raise ValueError("condition_of_group, dynamics_of_group and sensing_of_group must have one entry per group each")
+        if not (pending.is_cuda and pending.dtype == torch.float32 and pending.is_contiguous() and tuple(pending.shape) == (self.num_envs, 16)):
+            raise AssertionError("pending must be a contiguous float32 CUDA tensor [num_envs, 16]")
+        term = getattr(self, "_term_obs_buf", None)
+        if term is not None and H >= 1 and int(term.shape[-1]) != width:   # the kernel would write rows of `width` floats into it
+            raise ValueError("the registered terminal-observation buffer has rows of %d floats; command_history=%d writes rows of %d: "
+                             "register it with set_terminal_obs_buffer(buf, obs_len=%d)" % (int(term.shape[-1]), H, width, width))
+        K, n, dev = int(num_steps), self.num_envs, self.device
+        if out is None:
+            obs, act, logp, rew, done, trunc = rollout_outputs(K, n, width, dev)
+            out = (obs, torch.empty_like(obs), act, logp, rew, done, trunc)
+        obs, critic_obs, act, logp, rew, done, trunc = out
+        for rows in (obs, critic_obs):
+            if not (rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() >= K * n * max(width, self.state_len)):
+                raise AssertionError("the obs and critic_obs rows must be contiguous float32 CUDA tensors [num_steps, num_envs, obs_len + 4 * command_history]")
+        last = getattr(self, "_obs_history", None)
+        if last is None or int(last.shape[1]) != max(width, self.state_len):
+            last = self._obs_history = torch.zeros((n, max(width, self.state_len)), dtype=torch.float32, device=dev)
+        critic_last = getattr(self, "_obs_critic", None)
+        if critic_last is None or int(critic_last.shape[1]) != int(last.shape[1]):
+            critic_last = self._obs_critic = torch.zeros_like(last)
+        ls = log_std_array(log_std)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(fn(self._h, policy._h, condition_bank._h, dynamics_bank._h, sensing_bank._h, int(maps[0].shape[0]), int(envs_per_group),
+                      *[m.ctypes.data_as(i32p) for m in maps], H, K, _f32p(ls), int(noise_seed) & (2 ** 64 - 1), int(first_step),
+                      int(bool(deterministic)) | flags, _ptr(pending), _ptr(obs), _ptr(critic_obs), _ptr(act), _ptr(logp), _ptr(rew), _ptr(done),
+                      _ptr(trunc), _ptr(last), _ptr(critic_last), self._stream()))
+        self._last_obs = last[:, :self.state_len]
+        return obs, critic_obs, act, logp, rew, done, trunc, last, critic_last
+
     def evaluate_history_grid_device(self, policy_bank, condition_bank, dynamics_bank, sensing_bank, policy_of_group, condition_of_group,
                                      dynamics_of_group, sensing_of_group, command_history, envs_per_group, num_steps, pending, rec, recf=None,
                                      precision="f16-operands", noise_seed=0, first_step=0):

@@ -20,6 +20,9 @@ sensor, and --eval-final prints the final policy's table over the training senso
 Every evaluation of the run (the final line, --eval-final, --curve) then goes through evaluate_sensing_grid(..., command_history=H) under
 the training sensors -- the first one for the keys of the result line.  --eval-delays D[,D...]: --eval-final's table over the training
 sigmas at these delays instead of the training sensors (with or without --command-history).
+--privileged-critic (with --fused --native-update): the VALUE network reads the observation before the sensor's noise
+(PPO(privileged_critic=True) -> qr_rollout_policy_privileged + qr_ppo_epoch_privileged); the policy keeps reading the noisy row.  Nothing
+about the evaluations changes (they fly the actor); --save stores the flag in the checkpoint's metadata, which the loading tools ignore.
 
 Prints training progress and a final deterministic evaluation on the 4-gate square track: gates per 12 s from a standing
 start, and lap times the way the reference tabulates them (FP:3474-3488: lap 1 from the start, then the flying laps; its
@@ -62,6 +65,35 @@ def train_sensors(obs_noise="", delay=""):
     sigma = parse_sigma(obs_noise) if obs_noise else [0.0] * 8
     delays = parse_delays(delay) if delay else [0]
     return [SensingParams("d=%d" % d, *sigma, delay_steps=d) for d in delays]
+
+
+def save_checkpoint(model, path, a):
+    """--save: the final policy as an SB3-shaped checkpoint that sb3.PPO.load (and with it every tool that takes --load) reads: `data`
+    (the metadata, with command_history and privileged_critic of the run beside the keys of sb3.PPO.save) and `policy.pth` (both networks
+    under their SB3 names).  A policy checkpoint: no optimiser state, no env state.  Returns the path written."""
+    import io
+    import zipfile
+
+    import torch
+    from optimal_quad_control_rl_amd import sb3
+
+    path = str(path)
+    if not os.path.splitext(path)[1]:
+        path += ".zip"
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    data = dict(format_version=sb3.FORMAT_VERSION, algo="PPO", policy_class="MlpPolicy", observation_dim=int(model.policy.pi[0].in_features),
+                action_dim=4, net_arch=[120, 120, 120], activation_fn="ReLU", log_std_init=0.0, num_timesteps=int(model.num_timesteps),
+                seed=int(a.seed), precision="f32" if a.precision == "f32" else "f16-operands", learning_rate=float(a.lr), n_steps=int(a.n_steps),
+                batch_size=int(model.batch_size), n_epochs=int(a.epochs), gamma=float(a.gamma), gae_lambda=float(model.lam),
+                clip_range=float(model.clip), ent_coef=float(a.ent_coef), vf_coef=float(model.vf_coef), max_grad_norm=float(model.max_grad_norm),
+                target_kl=float(a.target_kl), command_history=int(a.command_history), privileged_critic=bool(a.privileged_critic))
+    blob = io.BytesIO()
+    torch.save({k: v.detach().cpu() for k, v in sb3.ActorCriticPolicy(model.policy).state_dict().items()}, blob)
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        z.writestr("data", json.dumps(data, indent=1))
+        z.writestr("policy.pth", blob.getvalue())
+    return path
 
 
 def format_condition_stats(per_condition):
@@ -118,6 +150,9 @@ def main():
     ap.add_argument("--command-history", type=int, default=0, metavar="H",
                     help="with --fused: the policy observes its last H clipped commands, 1 .. 4 - gates_ahead (PPO(command_history=H) -> "
                          "qr_rollout_policy_history); evaluations go through evaluate_sensing_grid(..., command_history=H)")
+    ap.add_argument("--privileged-critic", action="store_true",
+                    help="with --fused --native-update: the value network reads the observation before the sensor's noise "
+                         "(PPO(privileged_critic=True) -> qr_rollout_policy_privileged, qr_ppo_epoch_privileged); stored in --save's metadata")
     ap.add_argument("--eval-delays", default="", metavar="D[,D...]",
                     help="--eval-final's sensor table at these command delays (the training sigmas) instead of at the training sensors")
     ap.add_argument("--out", default="")
@@ -161,12 +196,19 @@ def main():
         if sensors is None:   # what PPO(command_history=H) flies under without `sensing`; named here for the tables
             from optimal_quad_control_rl_amd.sensing import SensingParams
             sensors = [SensingParams.ideal()]
+    if a.privileged_critic:
+        if not (a.fused and a.native_update) or a.precision == "f32" or world > 1:
+            raise SystemExit("--privileged-critic needs --fused --native-update at f16-operand update precision in one process: the clean row exists "
+                             "in the closed-loop kernel only, and the f32-class and data-parallel updates have no privileged-critic form")
+        if sensors is None:   # what PPO(privileged_critic=True) flies under without `sensing`; named here for the tables
+            from optimal_quad_control_rl_amd.sensing import SensingParams
+            sensors = [SensingParams.ideal()]
     model = PPO(env, seed=a.seed, ent_coef=a.ent_coef, gamma=a.gamma, n_steps=a.n_steps, n_epochs=a.epochs, batch_size=a.envs * a.n_steps // a.minibatches, learning_rate=a.lr,
                 target_kl=a.target_kl, lr_final_frac=a.lr_final, total_timesteps_hint=int(a.steps) // world, fused_collect=a.fused,
                 native_update=a.native_update, truncation_bootstrap=not a.no_trunc_bootstrap,
                 policy_forward="f32class" if a.precision != "f16-operands" else "torch", update_precision="f32" if a.precision == "f32" else "f16-operands",
                 conditions=conds, envs_per_group=a.envs_per_group, dynamics=ranges, resample_every=a.resample_every or None, sensing=sensors,
-                command_history=a.command_history)
+                command_history=a.command_history, privileged_critic=a.privileged_critic)
     if "RANK" in os.environ:
         model._updater.broadcast_parameters(0)   # identical start on every rank (the seed already makes it so; this guarantees it)
         model.noise_seed = a.seed                 # same key, different global env ids -> independent action noise per rank
@@ -347,6 +389,8 @@ def main():
         res["seconds_to_reference_lap"] = hit[0]["train_seconds"] if hit else None
         res["env_steps_to_reference_lap"] = hit[0]["env_steps"] if hit else None
         res["lap_target"] = a.lap_target
+    if a.save and rank == 0:
+        res["saved"] = save_checkpoint(model, a.save, a)
     print(json.dumps(res))
     if a.out:
         json.dump(res, open(a.out, "w"), indent=1)
